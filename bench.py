@@ -8,7 +8,7 @@ rank solves its own 8192-instance shard (weak scaling, no data-path collective) 
 multipliers and status structs are gathered over xGMI inside the step
 (mpc_trajectory_generator_amd/dist.py: the same pack / gather / unpack the gloo test exercises).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg1|cfg2|cfg3|cfg4] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg1|cfg2|cfg3|cfg4] [--batch B] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment re-launches itself under
 ``python -m torch.distributed.run`` with N ranks on 127.0.0.1 (and fails loudly when fewer than N GPUs
@@ -77,6 +77,26 @@ WORKLOADS = {   # what each BASELINE.json configuration is made of (mpc_trajecto
     "cfg4": "configs/smooth_velocity.yaml's weights/bounds overlaid on default.yaml (N_hor=20), three random moving ellipses per instance",
 }
 POINTS_PER_PASS = {"nmpc_solve_hyb_kernel": 3, "nmpc_solve_hyb2_kernel": 3}
+# status fields written by --dump-outputs: all but solve_time_ms, a clock reading that differs between two runs of one build
+DUMP_STATUS_FIELDS = ("exit_status", "num_outer_iterations", "num_inner_iterations", "num_cost_evals", "num_grad_evals", "reserved",
+                      "last_problem_norm_fpr", "delta_y_norm_over_c", "f2_norm", "penalty", "cost")
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, u, y, st):
+    """--dump-outputs: the last timed step's solutions u [B, n_u], multipliers y [B, n1] and status fields, one float64 .npy each.  Above
+    DUMP_LIMIT_BYTES the same fixed, seeded sample of instances is taken from every array and its instance indices go to sample_index.npy."""
+    arrays = {"u": u, "y": y, **{f"status_{f}": st[f] for f in DUMP_STATUS_FIELDS}}
+    B = u.shape[0]
+    row_bytes = 8 * sum(int(np.prod(a.shape[1:])) for a in arrays.values())
+    if B * row_bytes > DUMP_LIMIT_BYTES - 4096:                            # (4096: the .npy headers)
+        k = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)
+        idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(B, k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["sample_index"] = idx
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def flop_model(cfg):
@@ -212,7 +232,12 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=INT",
                     help="solver option / restatement switch (include/nmpc_solver.h), e.g. --opt akkt_gradient=1 --opt ls_failure=1; "
                          "the line then reports that variant under `solver_variant` (the headline uses the defaults)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (u, y, status fields; all ranks' shards when N > 1) as DIR/<name>.npy, "
+                         "float64, at most 64 MB in all (a fixed, seeded sample of instances beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.no_extras:
         args.no_cpu_baseline = args.no_pipelined = True
 
@@ -344,6 +369,8 @@ def main():
                          and stg[rank * B:(rank + 1) * B].tobytes() == st.tobytes())
         assert gather_ok, "gathered payload does not hold this rank's results"
         assert all((stg["num_inner_iterations"][r * B:(r + 1) * B] > 0).any() for r in range(world)), "a rank's slot is empty"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *((Ug, Yg, stg) if use_dist else (u_gpu, y_gpu, st)))
 
     # per-rank report (device, shard, kernel ms) gathered to rank 0, and the gather alone (pack + all_gather), timed
     # by events outside the timed region: a wrong rank -> device mapping or a slow link shows up in the line

@@ -21,6 +21,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 from collections import Counter, defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -218,8 +219,7 @@ def run(cmd, **kw):
 def build(which, tag):
     name = KERNELS[which]
     os.makedirs(VAR, exist_ok=True)
-    wd = os.path.join("/tmp", f"bbcount_{tag}")
-    os.makedirs(wd, exist_ok=True)
+    wd = tempfile.mkdtemp(prefix=f"bbcount_{tag}_")      # (a fixed name under /tmp may belong to another user)
     src = os.path.join(CSRC, "nmpc_kernels.hip")
     fl = base_flags()
     p0 = subprocess.Popen([HIPCC] + fl + ["-S", "--cuda-device-only", "-o", f"{wd}/plain.s", src], stderr=subprocess.DEVNULL)

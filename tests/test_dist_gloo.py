@@ -36,7 +36,7 @@ def _worker(rank, world, port, B, q):
     U, Y, st = solve_sharded(fn, P)
     if rank == 0:
         q.put((U, Y, st["num_inner_iterations"].copy(), st["exit_status"].copy()))
-    dist.barrier()
+    dist.monitored_barrier()      # (dist.barrier() asks torch for an accelerator, which opens the GPU of a GPU box in every rank)
     dist.destroy_process_group()
 
 
@@ -84,7 +84,7 @@ def _worker_big(rank, world, port, B, q):
     ok = bool(np.array_equal(U, Uo) and np.array_equal(Y, Yo) and st.tobytes() == sto.tobytes())
     lo, hi = shard_range(B, rank, world)
     q.put((rank, ok, lo, hi))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

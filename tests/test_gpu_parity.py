@@ -3,10 +3,12 @@
 The bar is bit-exact: kernels and oracle implement the same canonical f64 arithmetic (DESIGN.md
 section 4), so controls, multipliers, iteration counts and status words must be identical.  Against the
 reference-derived goldens (different summation order, libm sin/cos) the tolerance is RTOL."""
+import os
+
 import numpy as np
 import pytest
 
-from conftest import STATUS_FIELDS, VARIANTS, oracle_for
+from conftest import GOLDEN, STATUS_FIELDS, VARIANTS, oracle_for
 from mpc_trajectory_generator_amd import named_config
 from mpc_trajectory_generator_amd.harness import synthetic_batch
 
@@ -331,7 +333,7 @@ def test_closed_loop_scene1_reaches_goal():
     # clearance from the three NMPC vertices of the scene (circle radius 0.5, soft constraint)
     for vx, vy in route.vertices:
         assert np.min(np.hypot(np.array(xx) - vx, np.array(xy) - vy)) > 0.45
-    d = np.load("tests/golden/harness_scene1.npz")       # the reference's loop with the oracle as its solver
+    d = np.load(os.path.join(GOLDEN, "harness_scene1.npz"))       # the reference's loop with the oracle as its solver
     assert np.array_equal(xx, d["xx"]) and np.array_equal(xy, d["xy"])
 
 
