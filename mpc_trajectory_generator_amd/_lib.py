@@ -94,120 +94,103 @@ def source_hash() -> str:
     return h.hexdigest()[:16]
 
 
-def build_library(force: bool = False) -> str:
-    """hipcc --offload-arch=gfx950 the kernels in-tree (cross-compiles without a GPU).  Safe to call from
-    several processes at once (one rank per GPU): the build runs under a file lock into a temporary name
-    and is renamed into place, the other processes find a fresh library when they get the lock."""
-    import fcntl
-
-    def stale():
-        return (not os.path.exists(LIB_PATH)) or any(
-            os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in _sources())
-
-    if not (force or stale()):
-        return LIB_PATH
-    with open(os.path.join(_CSRC, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if force or stale():
-                tmp = f"libnmpc_hip.so.tmp{os.getpid()}"
-                r = subprocess.run(["make", "-C", _CSRC, "-B", tmp, f"OUT={tmp}"], capture_output=True, text=True)
-                if r.returncode != 0:
-                    raise RuntimeError("building libnmpc_hip.so failed:\n" + r.stdout[-2000:] + r.stderr[-4000:])
-                # the compiler's output is checked before it is accepted: ROCm 7.2 has produced silently wrong code for these kernels twice
-                # (codegen_check.py); the verdict, the flags and the kernels' resources go to build_info.json, which bench.py quotes
-                from . import codegen_check
-                res = codegen_check.verify()
-                info = {"source_hash": source_hash(), "flags": res.get("flags"), "codegen_check": {k: v for k, v in res.items() if k != "resources"},
-                        "resources": res.get("resources", {})}
-                if not res["ok"]:
-                    os.remove(os.path.join(_CSRC, tmp))
-                    with open(BUILD_INFO + ".refused", "w") as fh:      # (build_info.json keeps describing the library that is in place)
-                        json.dump(info, fh, indent=1)
-                    raise RuntimeError("libnmpc_hip.so REFUSED: the compiler generated wrong code for these flags (codegen_check): " +
-                                       json.dumps(info["codegen_check"])[:3000])
-                os.replace(os.path.join(_CSRC, tmp), LIB_PATH)
-                with open(BUILD_INFO, "w") as fh:
-                    json.dump(info, fh, indent=1)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB_PATH
-
-
-# The same sources under the other machine-scheduler strategies: not shipped, but built and run by tests/test_gpu_strategies.py -- a kernel
-# whose results depend on the schedule has a defect (or the compiler has: codegen_check.py), and the shipped strategy may only be hiding it.
-STRATEGIES = {"default": [], "max-memory-clause": ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"],
-              "max-ilp": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-# The shipped library reads no environment variable.  The knobs tests and scripts need (force the run-time-shape kernel, team modes, scheduler
-# and migration settings, culling radius) exist only in this variant: the shipped sources and scheduler flags + -DNMPC_EXPERIMENTS.
-EXPERIMENTS = "experiments"
-# Documented compile-time settings of the kernels, each with the shipped scheduler flags: tests demand the shipped library's bits from them.
-# win0: -DNMPC_WIN=0 -DNMPC_WIN2=0 (both solve kernels), the cross-track search always as the full scan (the obstacle certificate and its helper-side guard stay on).
-DEFINES = {"win0": ["-DNMPC_WIN=0", "-DNMPC_WIN2=0"]}
+# Every library built from these sources: name -> the csrc/Makefile variables it sets.  PRODUCT is the shipped csrc/libnmpc_hip.so; the others
+# go to csrc/variants/libnmpc_<name>.so: the other scheduler strategies (tests/test_gpu_strategies.py: a kernel whose results depend on the
+# schedule has a defect, or the compiler has), the experiments build (the only one with the environment knobs of tests and scripts), win0 (the
+# cross-track search always as the full scan; tests demand the shipped bits from it) and, ON_DEMAND only, the instrumented builds of scripts/.
+PRODUCT, EXPERIMENTS = "product", "experiments"
+LIBRARIES = {
+    PRODUCT: {},
+    "default": {"SCHED": ""},
+    "max-memory-clause": {"SCHED": "-mllvm -amdgpu-sched-strategy=max-memory-clause"},
+    "max-ilp": {"SCHED": "-mllvm -amdgpu-sched-strategy=max-ilp"},
+    EXPERIMENTS: {"EXTRA": "-DNMPC_EXPERIMENTS"},
+    "win0": {"EXTRA": "-DNMPC_WIN=0 -DNMPC_WIN2=0"},
+    "ws": {"EXTRA": "-DNMPC_WIN_STATS -DNMPC_EXPERIMENTS"},       # certificate fall-back shares (scripts/win_stats.py)
+    "prof2": {"EXTRA": "-DNMPC_PROF2 -DNMPC_EXPERIMENTS"},        # cycles by section of the hybrid kernel's loop (scripts/sections.py)
+    "prof2e": {"EXTRA": "-DNMPC_PROF2=2 -DNMPC_EXPERIMENTS"},     # the same, by section of the evaluation
+    "tl": {"EXTRA": "-DNMPC_TL -DNMPC_EXPERIMENTS"},              # timeline of a helped iteration (scripts/timeline.py)
+}
+ON_DEMAND = ("ws", "prof2", "prof2e", "tl")
+VARIANTS = [n for n in LIBRARIES if n != PRODUCT and n not in ON_DEMAND]      # what build() builds besides the product
+STRATEGIES = {n: v["SCHED"].split() for n, v in LIBRARIES.items() if "SCHED" in v}
 
 
 def variant_path(name: str) -> str:
-    return os.path.join(_CSRC, "variants", f"libnmpc_{name}.so")
+    return LIB_PATH if name == PRODUCT else os.path.join(_CSRC, "variants", f"libnmpc_{name}.so")
 
 
-def _variant_key() -> str:
-    """What a variant is fresh for: the kernel sources AND the Makefile (a flag change rebuilds the variants too)."""
+def _build(name: str, force: bool) -> dict:
+    """Build LIBRARIES[name] (hipcc --offload-arch=gfx950: cross-compiles without a GPU) and run the code-generation check on the same make
+    variables: ROCm 7.2 has produced silently wrong code for these kernels twice.  -> the verdict, written next to the library (the product's:
+    build_info.json, which bench.py quotes).  Fresh = built from the same content of the sources, the Makefile and the entry: not rebuilt.
+    A refused library is not put in place: the product keeps the one in place, described by build_info.json (the verdict goes to
+    build_info.json.refused); a variant's path is left empty.  Several processes may call this at once: the build runs under a file lock into
+    a temporary name and is renamed into place."""
+    import fcntl
     import hashlib
-    with open(os.path.join(_CSRC, "Makefile"), "rb") as fh:
-        return source_hash() + "+" + hashlib.sha256(fh.read()).hexdigest()[:8]
+    from . import codegen_check
+    out, make_vars = variant_path(name), LIBRARIES[name]
+    verdict = BUILD_INFO if name == PRODUCT else out[:-3] + ".json"
+    h = hashlib.sha256(json.dumps(make_vars, sort_keys=True).encode())
+    for src in _sources():
+        with open(src, "rb") as fh:
+            h.update(fh.read())
+    key = h.hexdigest()[:16]
+
+    def fresh():
+        try:
+            with open(verdict) as fh:
+                info = json.load(fh)
+        except (OSError, ValueError):
+            return None
+        ok = info.get("codegen_check", {}).get("ok")
+        return info if not force and info.get("build_key") == key and (os.path.exists(out) or ok is False) else None
+
+    info = fresh()
+    if info is not None:
+        return info
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(os.path.join(_CSRC, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            info = fresh()
+            if info is not None:
+                return info
+            tmp = os.path.relpath(out, _CSRC) + f".tmp{os.getpid()}"
+            r = subprocess.run(["make", "-C", _CSRC, "-B", tmp, f"OUT={tmp}"] + [f"{k}={v}" for k, v in make_vars.items()],
+                               capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"building {out} failed:\n" + r.stdout[-2000:] + r.stderr[-4000:])
+            res = codegen_check.verify(make_vars)
+            info = {"source_hash": source_hash(), "flags": res.get("flags"), "codegen_check": {k: v for k, v in res.items() if k != "resources"},
+                    "resources": res.get("resources", {}), "build_key": key}
+            if res["ok"]:
+                os.replace(os.path.join(_CSRC, tmp), out)
+            else:
+                os.remove(os.path.join(_CSRC, tmp))
+                if name != PRODUCT and os.path.exists(out):
+                    os.remove(out)
+            with open(verdict + (".refused" if name == PRODUCT and not res["ok"] else ""), "w") as fh:      # (under the lock: library and
+                json.dump(info, fh, indent=1)                                                               # verdict change together)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return info
+
+
+def build_library(force: bool = False) -> str:
+    """The product library, csrc/libnmpc_hip.so (_build); raises if the code-generation check refuses it."""
+    info = _build(PRODUCT, force)
+    if not info["codegen_check"]["ok"]:
+        raise RuntimeError("libnmpc_hip.so REFUSED: the compiler generated wrong code for these flags (codegen_check): " +
+                           json.dumps(info["codegen_check"])[:3000])
+    return LIB_PATH
 
 
 def build_variant(name: str, force: bool = False) -> dict:
-    """Build csrc/variants/libnmpc_<name>.so with strategy `name` and run the code-generation check on ITS flags (the experiments variant:
-    the shipped flags + -DNMPC_EXPERIMENTS); -> that check's result.  A variant whose check fails is not put in place."""
-    from . import codegen_check
-    import fcntl
-    experiments = name == EXPERIMENTS
-    defines = DEFINES.get(name)
-    flags = None if (experiments or defines) else STRATEGIES[name]
-    out, meta = variant_path(name), variant_path(name)[:-3] + ".json"
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-
-    def fresh():
-        if os.path.exists(out) and os.path.exists(meta) and not force:      # fresh = built from these very sources (content, not time stamps)
-            try:
-                with open(meta) as fh:
-                    res = json.load(fh)
-            except (OSError, ValueError):
-                return None
-            if res.get("variant_key") == _variant_key():
-                return res
-        return None
-
-    res = fresh()
-    if res is not None:
-        return res
-    with open(os.path.join(_CSRC, ".build.lock"), "w") as lock:      # (several test processes may ask for the same variant)
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            res = fresh()
-            if res is not None:
-                return res
-            tmp = os.path.relpath(out, _CSRC) + f".tmp{os.getpid()}"
-            cmd = ["make", "-C", _CSRC, "-B", tmp, f"OUT={tmp}"] + (["EXTRA=-DNMPC_EXPERIMENTS"] if experiments else
-                                                                  ["EXTRA=" + " ".join(defines)] if defines else ["SCHED=" + " ".join(flags)])
-            r = subprocess.run(cmd, capture_output=True, text=True)
-            if r.returncode != 0:
-                raise RuntimeError(f"building {out} failed:\n" + r.stdout[-2000:] + r.stderr[-4000:])
-            res = (codegen_check.verify(codegen_check.makefile_flags() + (["-DNMPC_EXPERIMENTS"] if experiments else defines))
-                   if (experiments or defines) else codegen_check.verify(flags))
-            res.pop("resources", None)
-            res["source_hash"] = source_hash()
-            res["variant_key"] = _variant_key()
-            if experiments and not res["ok"]:      # (the strategy variants are kept even when the check objects: tests/test_gpu_strategies.py reports on them)
-                os.remove(os.path.join(_CSRC, tmp))
-                raise RuntimeError(f"{out} REFUSED by the code-generation check: " + json.dumps({k: v for k, v in res.items() if k != "details"})[:2000])
-            os.replace(os.path.join(_CSRC, tmp), out)
-            with open(meta, "w") as fh:      # (under the lock: library and verdict change together)
-                json.dump(res, fh)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return res
+    """csrc/variants/libnmpc_<name>.so, LIBRARIES[name] (_build); -> its code-generation check.  A variant the check refuses is not built:
+    `ok` is False, and there is no library at variant_path(name)."""
+    return _build(name, force)["codegen_check"]
 
 
 def build_info() -> dict:
@@ -231,7 +214,9 @@ def load_library(experiments: bool = False) -> C.CDLL:
     if experiments:
         if _lib_experiments is None:
             build_library()
-            build_variant(EXPERIMENTS)
+            check = build_variant(EXPERIMENTS)
+            if not check["ok"]:
+                raise RuntimeError(f"{variant_path(EXPERIMENTS)} REFUSED by the code-generation check: " + json.dumps(check)[:2000])
             _lib_experiments = _bind(C.CDLL(variant_path(EXPERIMENTS)), variant_path(EXPERIMENTS))
             assert _lib_experiments.nmpc_experiments_build() == 1
         return _lib_experiments

@@ -1,8 +1,6 @@
 """Build-time validation of the generated gfx950 code: two classes of wrong code that ROCm 7.2's LLVM produces for these kernels and that
-neither the compiler nor its machine verifier reports.  `verify()` compiles csrc/nmpc_kernels.hip once more with the
-flags of the real build plus machine-code dumps and checks
-
-The third check reads the final assembly: every DPP read keeps its two wait states from the last vector write of its source (check_dpp_hazards).
+neither the compiler nor its machine verifier reports, and one hazard it cannot see.  `verify()` compiles
+csrc/nmpc_kernels.hip once more with the flags of the real build (`make print-flags`) plus machine-code dumps and checks
 
 1. the machine scheduler: every virtual-register lane an instruction reads must come from the same defining instruction after scheduling
    as before it.  (-amdgpu-sched-strategy=max-ilp hoisted the lane copy `%X.sub1 = COPY %X.sub3` that feeds the second operand of a
@@ -14,9 +12,13 @@ The third check reads the final assembly: every DPP read keeps its two wait stat
    when an SGPR copy already sat there: the copy saves only the lanes of the `if` side -- none when the block is reached through
    s_cbranch_execz -- and the later reload returns whatever the AGPR held before: results that depend on what ran on the SIMD earlier and
    change from run to run.  Found with tests/scrub + scripts/scrub_bisect.py.)
+3. the final assembly: every DPP read keeps its two wait states from the last vector write of its source (check_dpp_hazards; the DPP
+   arithmetic lives in asm statements, into which the compiler's hazard recognizer does not look).
 
-`build_library()` (_lib.py) calls verify() after every real compilation and refuses the library if either check fails.
-CLI:  python -m mpc_trajectory_generator_amd.codegen_check [--src file.hip] [hipcc flags ...]     (default: the library's source, the Makefile's flags)"""
+`_lib` calls verify() after every compilation of a library (_lib.LIBRARIES: the product and its variants) and refuses the library if any check
+fails.
+CLI:  python -m mpc_trajectory_generator_amd.codegen_check [--src file.hip] [hipcc flags ...]     (default: the library's source, the Makefile's
+flags; hipcc flags given here take the place of the Makefile's scheduler flags, SCHED)"""
 import os
 import re
 import subprocess
@@ -25,7 +27,6 @@ import tempfile
 
 CSRC = os.environ.get("NMPC_CSRC") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only", "-Wno-unused-result"]
 
 # ------------------------------------------------------------------------------------------------- 1. the machine scheduler
 OPERAND = re.compile(r"(undef |dead |killed |internal |early-clobber |renamable |implicit-def |implicit |def )*%(\d+)(?:\.(sub[0-9_sub]*))?(?::[A-Za-z0-9_]+)?(\(tied-def \d+\))?")
@@ -256,12 +257,20 @@ def check_dpp_hazards(asm_text):
 
 
 # ------------------------------------------------------------------------------------------------- driver
-def makefile_flags():
-    """the code-generation flags csrc/Makefile builds with (its scheduler strategy)"""
-    r = subprocess.run(["make", "-s", "-C", CSRC, "print-sched"], capture_output=True, text=True)
+def make_print(target, make_vars=None):
+    """what csrc/Makefile prints for `target` (print-flags, print-sched) with the variables `make_vars` ({"SCHED": ..., "EXTRA": ...}) set"""
+    r = subprocess.run(["make", "-s", "-C", CSRC, target] + [f"{k}={v}" for k, v in (make_vars or {}).items()], capture_output=True, text=True)
     if r.returncode != 0:
-        raise RuntimeError("make print-sched failed: " + r.stderr[-500:])
+        raise RuntimeError(f"make {target} failed: " + r.stderr[-500:])
     return r.stdout.split()
+
+
+def gate_commands(build_flags, src, outdir):
+    """the gate's two compilations: hipcc + the build's own flags (`make print-flags`) + device assembly only + the machine-code dumps that
+    checks 1 and 2 read (on stderr); the assembly goes to outdir/x.s"""
+    dev = [HIPCC] + list(build_flags) + ["-S", "--cuda-device-only"]
+    return [dev + ["-mllvm", "-print-before=machine-scheduler", "-mllvm", "-print-after=machine-scheduler", "-o", os.path.join(outdir, "x.s"), src],
+            dev + ["-mllvm", "-print-after=virtregrewriter", "-o", os.path.join(outdir, "y.s"), src]]
 
 
 def kernel_resources(asm_text):
@@ -277,14 +286,15 @@ def kernel_resources(asm_text):
     return out
 
 
-def verify(flags=None, src=None):
-    """-> dict(ok, flags, kernels, sched_changed, sched_latent, exec_hits, details, resources).  Two extra compilations side by side (about 25 s).
-    `src`: another source file than the library's (the minimal cases under tests/repro/)."""
-    flags = makefile_flags() if flags is None else list(flags)
+def verify(make_vars=None, src=None):
+    """-> dict(ok, flags, kernels, sched_changed, sched_latent, exec_hits, details, resources) for the build with the csrc/Makefile variables
+    `make_vars` ({"SCHED": ..., "EXTRA": ...}; none: the product library); `flags` = its scheduler flags + EXTRA.  Two extra compilations side
+    by side (about 25 s).  `src`: another source file than the library's (the minimal cases under tests/repro/)."""
+    make_vars = make_vars or {}
+    flags = make_print("print-sched", make_vars) + make_vars.get("EXTRA", "").split()
     src = src or os.path.join(CSRC, "nmpc_kernels.hip")
     with tempfile.TemporaryDirectory() as td:
-        cmds = [[HIPCC] + BASE + flags + ["-mllvm", "-print-before=machine-scheduler", "-mllvm", "-print-after=machine-scheduler", "-o", os.path.join(td, "x.s"), src],
-                [HIPCC] + BASE + flags + ["-mllvm", "-print-after=virtregrewriter", "-o", os.path.join(td, "y.s"), src]]
+        cmds = gate_commands(make_print("print-flags", make_vars), src, td)
         errs = [open(os.path.join(td, f"err{i}.txt"), "w+") for i in range(2)]
         procs = [subprocess.Popen(c, stdout=subprocess.DEVNULL, stderr=e) for c, e in zip(cmds, errs)]
         rcs = [p.wait() for p in procs]
@@ -317,7 +327,7 @@ def main():
     argv, src = sys.argv[1:], None
     if "--src" in argv:
         i = argv.index("--src"); src = argv[i + 1]; argv = argv[:i] + argv[i + 2:]
-    res = verify(argv or None, src)
+    res = verify({"SCHED": " ".join(argv)} if argv else None, src)
     print({k: v for k, v in res.items() if k not in ("details", "resources")})
     for d in res.get("details", []):
         print("  " + d[:400])

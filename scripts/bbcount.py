@@ -76,13 +76,10 @@ def klass(op):
 VALU = ("f64", "dpp_f64", "dpp_mov", "lane_sgpr", "permlane", "select", "compare", "move", "int_valu")
 
 
-def sched_flags():
-    return subprocess.run(["make", "-s", "-C", CSRC, "print-sched"], capture_output=True, text=True, check=True).stdout.split()
-
-
 def base_flags():
-    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"] + sched_flags() + \
-           ["-DNMPC_EXPERIMENTS", "-DNMPC_BBCOUNT"]
+    """the shipped library's code-generation flags + the experiments build and the counter symbol (csrc/Makefile print-flags)"""
+    return subprocess.run(["make", "-s", "-C", CSRC, "print-flags", "EXTRA=-DNMPC_EXPERIMENTS -DNMPC_BBCOUNT"], capture_output=True, text=True,
+                          check=True).stdout.split()
 
 
 def kernel_span(lines, name):

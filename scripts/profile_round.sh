@@ -15,11 +15,11 @@ OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT" "profiles/$TAG"
 cd /tmp && export TMPDIR=/tmp && cd "$OLDPWD"
 V=$PWD/mpc_trajectory_generator_amd/csrc/variants
-python -c "from mpc_trajectory_generator_amd import _lib; _lib.build_library(); _lib.build_variant(_lib.EXPERIMENTS)"      # (built before the call: they travel with the snapshot)
+# the experiments build and the four instrumented ones (_lib.LIBRARIES): rebuilt when made from other sources, and gated (built before the
+# call: they travel with the snapshot)
+python -c "from mpc_trajectory_generator_amd import _lib; _lib.build_library()
+for n in (_lib.EXPERIMENTS,) + _lib.ON_DEMAND: print(n, _lib.build_variant(n)['ok'])"
 XLIB=$V/libnmpc_experiments.so
-for f in ws:-DNMPC_WIN_STATS prof2:-DNMPC_PROF2 prof2e:-DNMPC_PROF2=2 tl:-DNMPC_TL; do
-    [ -f $V/libnmpc_${f%%:*}.so ] || make -s -C mpc_trajectory_generator_amd/csrc -B OUT=variants/libnmpc_${f%%:*}.so EXTRA="${f#*:} -DNMPC_EXPERIMENTS"
-done
 SQ1="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES"
 SQ2="SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES"
 for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "sq:$SQ1" "wait:$SQ2"; do

@@ -1,6 +1,7 @@
 """Timeline of a helped iteration (one instance alone in its workgroup, three helper waves): cycles from the start of a PANOC step to
-fifteen events on the owner's and the first helper's side, median over 63 consecutive steps.  Needs a library built with -DNMPC_TL:
-    make -C mpc_trajectory_generator_amd/csrc -B OUT=variants/libnmpc_tl.so EXTRA="-DNMPC_TL -DNMPC_EXPERIMENTS"
+fifteen events on the owner's and the first helper's side, median over 63 consecutive steps.  Needs a library built with -DNMPC_TL,
+_lib.LIBRARIES entry tl:
+    python -c "from mpc_trajectory_generator_amd import _lib; print(_lib.build_variant('tl'))"
     NMPC_LIB_PATH=mpc_trajectory_generator_amd/csrc/variants/libnmpc_tl.so python scripts/timeline.py [instance]
 (every event costs the wave ~100 cycles: the sum is above the plain build's iteration)."""
 import ctypes, json, os, sys

@@ -1,5 +1,6 @@
 """Windowed cross-track search: share of evaluations that fall back to the full scan, and kernel ms, for stats builds of the
-library (make -B libnmpc_ws_<tag>.so OUT=... EXTRA="-DNMPC_WIN_STATS ...").  usage: python scripts/win_stats.py cfg1 lib1.so lib2.so ..."""
+library (-DNMPC_WIN_STATS: _lib.LIBRARIES entry ws, _lib.build_variant("ws") -> csrc/variants/libnmpc_ws.so).
+usage: python scripts/win_stats.py cfg1 lib1.so lib2.so ..."""
 import ctypes, json, os, subprocess, sys
 sys.path.insert(0, ".")
 if sys.argv[1] == "child":
