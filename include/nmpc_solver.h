@@ -72,13 +72,15 @@ typedef struct nmpc_problem {
  * deterministic, so the iteration caps apply, plus -- when asked for -- max_total_inner, the
  * deterministic stand-in for max_duration. */
 typedef struct nmpc_opts {
-    double tolerance;            /* 1e-4 */
-    double initial_tolerance;    /* 1e-4 */
-    double delta_tolerance;      /* 1e-4 */
-    double initial_penalty;      /* 1.0  */
-    double penalty_update;       /* 5.0  */
-    double tolerance_update;     /* 0.1  */
-    double sufficient_decrease;  /* 0.1  */
+    /* ALM knobs: default, then the range nmpc_new accepts (anything else, NaN included, is NMPC_ERR_BAD_OPTS).
+     * The ranges are OpEn's builder assertions as recalled in SURVEY.md App. C, not checked against OpEn. */
+    double tolerance;            /* 1e-4   epsilon: finite, > 0                        */
+    double initial_tolerance;    /* 1e-4   epsilon_0: finite, >= tolerance             */
+    double delta_tolerance;      /* 1e-4   delta: finite, > 0                          */
+    double initial_penalty;      /* 1.0    c0: finite, > 0                             */
+    double penalty_update;       /* 5.0    rho: finite, > 1                            */
+    double tolerance_update;     /* 0.1    beta: in (0, 1)                             */
+    double sufficient_decrease;  /* 0.1    theta: in (0, 1)                            */
     int32_t lbfgs_memory;        /* 10 (1..10) */
     int32_t max_inner;           /* 500  */
     int32_t max_outer;           /* 10   */

@@ -1039,6 +1039,14 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
         op.max_total_inner < 0 || op.akkt_gradient < 0 || op.akkt_gradient > 2 || op.ls_failure < 0 || op.ls_failure > 1 ||
         op.inner_status < 0 || op.inner_status > 1)
         return NMPC_ERR_BAD_OPTS;
+    // the ALM knobs (ranges stated in include/nmpc_solver.h); written so that a NaN fails every test
+    auto finite_pos = [](double x) { return x > 0.0 && x <= DBL_MAX; };
+    if (!finite_pos(op.tolerance) || !finite_pos(op.initial_tolerance) || !finite_pos(op.delta_tolerance) ||
+        !(op.initial_tolerance >= op.tolerance) || !finite_pos(op.initial_penalty) ||
+        !(op.penalty_update > 1.0 && op.penalty_update <= DBL_MAX) ||
+        !(op.tolerance_update > 0.0 && op.tolerance_update < 1.0) ||
+        !(op.sufficient_decrease > 0.0 && op.sufficient_decrease < 1.0))
+        return NMPC_ERR_BAD_OPTS;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev)
         return NMPC_ERR_NO_DEVICE;

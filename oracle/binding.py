@@ -69,6 +69,9 @@ class Oracle:
             if k == "reserved" or not hasattr(self.opts, k):
                 raise TypeError(f"unknown oracle option {k!r}")
             setattr(self.opts, k, v)
+        if not self.lib.orc_opts_valid(C.byref(self.opts)):
+            raise RuntimeError("oracle options outside the ranges of include/nmpc_solver.h: "
+                               + ", ".join(f"{k}={v!r}" for k, v in opts.items()))
         for f in ("orc_n_u", "orc_n_p", "orc_n1", "orc_n2"):
             getattr(self.lib, f).restype = C.c_int
         self.lib.orc_tree_sum.restype = C.c_double

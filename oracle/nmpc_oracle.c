@@ -268,6 +268,18 @@ void orc_default_opts(orc_opts *o)
     o->reserved = 0;
 }
 
+static int finite_pos(double x) { return x > 0.0 && x <= DBL_MAX; }
+
+/* the ranges of include/nmpc_solver.h (nmpc_new applies the same); a NaN fails every comparison */
+int orc_opts_valid(const orc_opts *o)
+{
+    return finite_pos(o->tolerance) && finite_pos(o->initial_tolerance) && finite_pos(o->delta_tolerance) &&
+           o->initial_tolerance >= o->tolerance && finite_pos(o->initial_penalty) &&
+           o->penalty_update > 1.0 && o->penalty_update <= DBL_MAX &&
+           o->tolerance_update > 0.0 && o->tolerance_update < 1.0 &&
+           o->sufficient_decrease > 0.0 && o->sufficient_decrease < 1.0;
+}
+
 static int check_problem(const orc_problem *pb)
 {
     if (pb->N < 2 || pb->N > MAXN) return -1;
@@ -890,6 +902,7 @@ int orc_solve(const orc_problem *pb, const orc_opts *opts, const double *p, doub
     int rc = check_problem(pb);
     if (rc) return rc;
     if (opts->lbfgs_memory < 1 || opts->lbfgs_memory > GRAM_M) return -5;
+    if (!orc_opts_valid(opts)) return -6;
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     const int N = pb->N;
