@@ -42,6 +42,15 @@ STATUS_DTYPE = np.dtype([("exit_status", "<i4"), ("num_outer_iterations", "<u4")
                          ("solve_time_ms", "<f8")])
 assert STATUS_DTYPE.itemsize == C.sizeof(OrcStatus) == 72
 
+TRACE_NU = 80
+# orc_step (nmpc_oracle.h): one record per PANOC step() of orc_solve_trace
+STEP_DTYPE = np.dtype([("nu", "<i4"), ("k", "<i4"), ("n_back", "<i4"), ("n_trials", "<i4"), ("active", "<i4"),
+                       ("flags", "<i4"), ("c", "<f8"), ("eps_nu", "<f8"), ("gamma_in", "<f8"), ("L_in", "<f8"),
+                       ("gamma", "<f8"), ("L", "<f8"), ("psi", "<f8"), ("norm_r_in", "<f8"), ("norm_r", "<f8"),
+                       ("tau", "<f8"), ("u", "<f8", TRACE_NU), ("y", "<f8", TRACE_NU), ("u_next", "<f8", TRACE_NU)])
+assert STEP_DTYPE.itemsize == 24 + 10 * 8 + 3 * TRACE_NU * 8
+STEP_PUSHED, STEP_REJ_SY, STEP_REJ_CBFGS, STEP_FIRST, STEP_FPR, STEP_AKKT, STEP_EXHAUSTED = 1, 2, 4, 8, 16, 32, 64
+
 
 def build_oracle(force=False):
     """Compile the oracle with gcc if the .so is missing or older than its sources."""
@@ -147,3 +156,26 @@ class Oracle:
         if rc:
             raise RuntimeError(f"orc_solve_batch failed: {rc}")
         return u, y, st
+
+    def solve_traced(self, p, u0=None, y0=None, c0=None, cap=4096):
+        """One solve with every PANOC step recorded -> u[n_u], y[n1], status (a 0-d structured array), steps[n]
+        (STEP_DTYPE; u, y and u_next cut to n_u / n1).  orc_solve_trace gives orc_solve's bits."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        assert p.shape == (self.n_p,)
+        u0 = np.zeros(self.n_u) if u0 is None else np.asarray(u0, dtype=np.float64)
+        y0 = None if y0 is None else np.ascontiguousarray(y0, dtype=np.float64)
+        fn = self.lib.orc_solve_trace
+        fn.argtypes = [C.POINTER(OrcProblem), C.POINTER(OrcOpts), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                       C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int]
+        while True:
+            u = np.array(u0, dtype=np.float64, order="C")
+            y = np.zeros(self.n1)
+            st = np.zeros((), dtype=STATUS_DTYPE)
+            steps = np.zeros(cap, dtype=STEP_DTYPE)
+            n = fn(C.byref(self.pb), C.byref(self.opts), _dp(p), _dp(u), _dp(y0), 0.0 if c0 is None else float(c0),
+                   _dp(y), st.ctypes.data, steps.ctypes.data, cap)
+            if n < 0:
+                raise RuntimeError(f"orc_solve_trace failed: {n}")
+            if n <= cap:
+                return u, y, st, steps[:n]
+            cap = n

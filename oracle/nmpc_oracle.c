@@ -10,6 +10,8 @@
  *               here from its published algorithm (Stella et al., CDC 2017; Sathya et al., ECC 2018;
  *               SURVEY.md App. C).  Anchors: the reference's call sites
  *               src/mpc/mpc_generator.py:173-193,206-221 and src/path_generator.py:218-222.
+ *               Checked against the literal rules instead: the outer loop by tests/alm_reference.py, every PANOC step
+ *               (recorded by orc_solve_trace) by tests/panoc_reference.py, both in long double.
  *
  * CANONICAL ARITHMETIC
  *   Every floating-point operation below is written out explicitly (fma() where a fused
@@ -48,6 +50,7 @@
 #define MAXDYN 8    /* dynamic ellipse slots         */
 #define MAXMEM 10   /* L-BFGS memory (= GRAM_M: the ring the kernels are built for) */
 #define NZ 20       /* reference configs/default.yaml:35 ; mpc_generator.py:73-75 unpack z0[0..19] */
+_Static_assert(ORC_TRACE_NU >= 2 * MAXN, "an orc_step record holds u, y, u_next of the longest horizon");
 
 /* ------------------------------------------------------------------------------------------ */
 /* primitives                                                                                 */
@@ -645,22 +648,23 @@ static void lbfgs_push(lbfgs_t *lb, const hvec *s, const hvec *y, double ys)
     if (lb->active < lb->m) lb->active++;
 }
 
-/* lbfgs crate: update_hessian(g := gamma_fpr, s := u) with sy-epsilon and C-BFGS safeguards */
-static void lbfgs_update(const inst_t *I, lbfgs_t *lb, const hvec *r, const hvec *u, double norm_r)
+/* lbfgs crate: update_hessian(g := gamma_fpr, s := u) with sy-epsilon and C-BFGS safeguards; -> the ORC_STEP_* outcome */
+static int lbfgs_update(const inst_t *I, lbfgs_t *lb, const hvec *r, const hvec *u, double norm_r)
 {
     const int P = I->P;
-    if (lb->first_old) { lb->first_old = 0; lb->old_s = *u; lb->old_g = *r; return; }
+    if (lb->first_old) { lb->first_old = 0; lb->old_s = *u; lb->old_g = *r; return ORC_STEP_FIRST; }
     hvec s, y;
     for (int t = 0; t < P; ++t) {
         s.v[t] = u->v[t] - lb->old_s.v[t]; s.w[t] = u->w[t] - lb->old_s.w[t];
         y.v[t] = r->v[t] - lb->old_g.v[t]; y.w[t] = r->w[t] - lb->old_g.w[t];
     }
     const double ys = qdot(&s, &y, lb->gram), ss = qdot(&s, &s, lb->gram);
-    if (ss <= DBL_MIN || ys <= LBFGS_SY_EPSILON) return;
-    if (!(ys > (LBFGS_CBFGS_EPSILON * norm_r) * ss)) return;      /* C-BFGS: <y, s> / ||s||^2 > eps ||r||^alpha, alpha = 1 */
+    if (ss <= DBL_MIN || ys <= LBFGS_SY_EPSILON) return ORC_STEP_REJ_SY;
+    if (!(ys > (LBFGS_CBFGS_EPSILON * norm_r) * ss)) return ORC_STEP_REJ_CBFGS;   /* C-BFGS: <y, s> / ||s||^2 > eps ||r||^alpha, alpha = 1 */
     lb->old_s = *u;
     lb->old_g = *r;
     lbfgs_push(lb, &s, &y, ys);
+    return ORC_STEP_PUSHED;
 }
 
 /* d := H d in the Gram form (nmpc_solve_hyb.h, nmpc_solve_hyb2.h): the coefficients of the two-loop recursion,
@@ -739,11 +743,28 @@ static void do_eval(const inst_t *I, panoc_t *c, const hvec *x, double pen, cons
     if (want_grad) c->n_grad++; else c->n_cost++;
 }
 
+/* the trace of orc_solve_trace: records are written, never read back (nothing below depends on them) */
+typedef struct { orc_step *recs; int cap, n, nu; } trace_t;
+
+static orc_step *trace_next(trace_t *tr)
+{
+    if (!tr) return NULL;
+    orc_step *s = tr->n < tr->cap ? tr->recs + tr->n : NULL;
+    tr->n++;
+    return s;
+}
+
+static void trace_u(double *dst, const hvec *h, int N)
+{
+    for (int t = 0; t < N; ++t) { dst[2 * t] = h->v[t]; dst[2 * t + 1] = h->w[t]; }
+}
+
 /* returns exit status (0 converged / 1 iterations / 2 out of budget); u in/out; iters and norm_fpr reported.
- * budget_left: PANOC iterations this inner solve may still spend (0 = unlimited), opts->max_total_inner. */
+ * budget_left: PANOC iterations this inner solve may still spend (0 = unlimited), opts->max_total_inner.
+ * tr: NULL, or the trace every step is recorded into (orc_solve_trace). */
 static int panoc_solve(const inst_t *I, const orc_opts *opts, panoc_t *c, hvec *u, double pen, const hvec *y,
                        double tol, double akkt_tol, int max_iter, uint32_t budget_left, uint32_t *iters,
-                       double *cost_out)
+                       double *cost_out, trace_t *tr)
 {
     const int P = I->P, N = I->N;
     eval_out *o = &c->scratch;
@@ -782,11 +803,26 @@ static int panoc_solve(const inst_t *I, const orc_opts *opts, panoc_t *c, hvec *
     for (;;) {
         /* step(): returns "continue" */
         compute_fpr(I, c, u);
+        orc_step *rec = trace_next(tr);
+        if (rec) {
+            memset(rec, 0, sizeof(*rec));
+            rec->nu = tr->nu; rec->k = c->iteration;
+            rec->c = pen; rec->eps_nu = akkt_tol;
+            rec->gamma_in = rec->gamma = c->gamma; rec->L_in = rec->L = c->L;
+            rec->psi = c->cost;
+            rec->norm_r_in = rec->norm_r = c->norm_r;
+            rec->tau = -1.0;
+            trace_u(rec->u, u, N);
+            trace_u(rec->u_next, u, N);
+            for (int t = 0; t < N; ++t) { rec->y[t] = y->v[t]; rec->y[N + t] = y->w[t]; }
+            rec->active = c->lb.active;
+        }
         if (c->norm_r < tol) {           /* fpr test, then the AKKT test (short-circuit) */
-            if (opts->akkt_gradient == 2) break;                 /* no AKKT test */
+            if (rec) rec->flags |= ORC_STEP_FPR;
+            if (opts->akkt_gradient == 2) { if (rec) rec->flags |= ORC_STEP_AKKT; break; }   /* no AKKT test */
             if (opts->akkt_gradient == 1 && c->iteration >= 1) {
                 /* grad_prev was copied from grad at the top of this step: the difference is exactly zero and the residual is ||r|| / gamma */
-                if (c->norm_r < akkt_tol * c->gamma) break;
+                if (c->norm_r < akkt_tol * c->gamma) { if (rec) rec->flags |= ORC_STEP_AKKT; break; }
             } else {
             double t[MAXP];
             for (int j = 0; j < P; ++j) {
@@ -801,7 +837,7 @@ static int panoc_solve(const inst_t *I, const orc_opts *opts, panoc_t *c, hvec *
                 }
                 t[j] = fma(a, a, b * b);
             }
-            if (sqrt(tree_sum_p(t, P)) < akkt_tol) break;
+            if (sqrt(tree_sum_p(t, P)) < akkt_tol) { if (rec) rec->flags |= ORC_STEP_AKKT; break; }
             }
         }
         /* Lipschitz / gamma backtracking */
@@ -824,7 +860,14 @@ static int panoc_solve(const inst_t *I, const orc_opts *opts, panoc_t *c, hvec *
         }
         c->sigma = (1.0 - GAMMA_L_COEFF) / (4.0 * c->gamma);
         /* L-BFGS buffer update and direction */
-        lbfgs_update(I, &c->lb, &c->r, u, c->norm_r);
+        const int upd = lbfgs_update(I, &c->lb, &c->r, u, c->norm_r);
+        if (rec) {
+            rec->n_back = n_back;
+            rec->gamma = c->gamma; rec->L = c->L;
+            rec->norm_r = c->norm_r;
+            rec->flags |= upd;
+            rec->active = c->lb.active;
+        }
         if (c->iteration > 0) { c->d = c->r; lbfgs_apply_gram(I, &c->lb, &c->d); }
         if (c->iteration == 0) {
             /* first iteration: plain forward-backward step */
@@ -835,7 +878,7 @@ static int panoc_solve(const inst_t *I, const orc_opts *opts, panoc_t *c, hvec *
             grad_and_half_step(I, c, u);
         } else {
             const double rhs_ls = fbe(I, c) - c->sigma * c->nr2;
-            int exhausted = 0;
+            int exhausted = 0, all_failed = 0;
             c->gk = c->g;
             c->tau = 1.0;
             for (int n = 0;; ++n) {
@@ -851,8 +894,12 @@ static int panoc_solve(const inst_t *I, const orc_opts *opts, panoc_t *c, hvec *
                 c->g = o->g;
                 grad_and_half_step(I, c, &c->up);
                 if (!(fbe(I, c) > rhs_ls)) break;
-                if (n >= MAX_LINESEARCH_ITERATIONS) { exhausted = opts->ls_failure == 1; break; }
+                if (n >= MAX_LINESEARCH_ITERATIONS) { all_failed = 1; exhausted = opts->ls_failure == 1; break; }
                 c->tau /= 2.0;
+            }
+            if (rec) {
+                rec->n_trials = n_trials;
+                if (all_failed) rec->flags |= ORC_STEP_EXHAUSTED;
             }
             if (exhausted) {
                 /* tau = 0: u+ = u_bar, the forward-backward step from the current iterate */
@@ -867,6 +914,10 @@ static int panoc_solve(const inst_t *I, const orc_opts *opts, panoc_t *c, hvec *
             } else {
                 *u = c->up;
             }
+        }
+        if (rec) {
+            rec->tau = c->iteration == 0 ? -1.0 : c->tau;
+            trace_u(rec->u_next, u, N);
         }
         {   /* diagnostic pass model: the first pass of an iteration holds u_bar and the first k - 1 trials; every
              * Lipschitz back-off costs a pass of its own (and a pass for the trials that were thrown away) */
@@ -896,8 +947,8 @@ static int vec_finite(const hvec *h, int N)
     return 1;
 }
 
-int orc_solve(const orc_problem *pb, const orc_opts *opts, const double *p, double *u_io,
-              const double *y0, double c0, double *y_out, orc_status *st)
+static int solve_impl(const orc_problem *pb, const orc_opts *opts, const double *p, double *u_io,
+                      const double *y0, double c0, double *y_out, orc_status *st, trace_t *tr)
 {
     int rc = check_problem(pb);
     if (rc) return rc;
@@ -934,8 +985,9 @@ int orc_solve(const orc_problem *pb, const orc_opts *opts, const double *p, doub
         uint32_t it = 0;
         const uint32_t budget = opts->max_total_inner > 0 ? (uint32_t)opts->max_total_inner : 0u;
         if (opts->akkt_gradient == 1) memset(&pc->gprev, 0, sizeof(pc->gprev));
+        if (tr) tr->nu = nu;
         int inner_status = panoc_solve(I, opts, pc, &u, c, &y, opts->tolerance, eps_nu, opts->max_inner,
-                                       budget ? budget - inner_total : 0u, &it, &last_cost);
+                                       budget ? budget - inner_total : 0u, &it, &last_cost, tr);
         inner_total += it;
         last_fpr = pc->norm_r;
         if (!vec_finite(&u, N) || !isfinite(last_cost) || !isfinite(last_fpr)) { exit_status = 4; break; }
@@ -996,6 +1048,20 @@ int orc_solve(const orc_problem *pb, const orc_opts *opts, const double *p, doub
     }
     free(pc); free(I);
     return 0;
+}
+
+int orc_solve(const orc_problem *pb, const orc_opts *opts, const double *p, double *u_io,
+              const double *y0, double c0, double *y_out, orc_status *st)
+{
+    return solve_impl(pb, opts, p, u_io, y0, c0, y_out, st, NULL);
+}
+
+int orc_solve_trace(const orc_problem *pb, const orc_opts *opts, const double *p, double *u_io, const double *y0, double c0,
+                    double *y_out, orc_status *st, orc_step *steps, int cap)
+{
+    trace_t tr = {steps, cap > 0 && steps ? cap : 0, 0, 0};
+    const int rc = solve_impl(pb, opts, p, u_io, y0, c0, y_out, st, &tr);
+    return rc ? rc : tr.n;
 }
 
 /* ------------------------------------------------------------------------------------------ */

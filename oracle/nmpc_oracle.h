@@ -98,6 +98,36 @@ int orc_eval(const orc_problem *pb, const double *p, const double *u, double c, 
 int orc_solve(const orc_problem *pb, const orc_opts *opts, const double *p, double *u,
               const double *y0, double c0, double *y_out, orc_status *st);
 
+/* One record per call of PANOC's step(), the step that exits included (orc_solve_trace).  u, y and u_next hold the first
+ * n_u / n1 entries (u interleaved (v, w) by stage as in orc_solve; y as [acc ; omega_acc]).  Observational only: the trace
+ * changes no arithmetic, orc_solve_trace gives orc_solve's bits. */
+#define ORC_TRACE_NU 80              /* 2 * the longest horizon */
+#define ORC_STEP_PUSHED 1            /* the pair (s, y) entered the L-BFGS buffer                                  */
+#define ORC_STEP_REJ_SY 2            /* rejected: ||s||^2 <= DBL_MIN or <y, s> <= sy-epsilon                      */
+#define ORC_STEP_REJ_CBFGS 4         /* rejected by the C-BFGS test                                                */
+#define ORC_STEP_FIRST 8             /* the buffer was empty (after a reset): (u, r) stored as the old pair, no push */
+#define ORC_STEP_FPR 16              /* ||r|| < epsilon                                                            */
+#define ORC_STEP_AKKT 32             /* ... and the AKKT test passed (akkt_gradient = 2: no test, set with FPR)   */
+#define ORC_STEP_EXHAUSTED 64        /* all 11 line-search trials failed                                          */
+typedef struct orc_step {
+    int32_t nu, k;                   /* outer iteration, PANOC iteration of this inner solve                      */
+    int32_t n_back, n_trials;        /* Lipschitz back-offs, line-search trials (0 at k = 0 and on exit)          */
+    int32_t active;                  /* L-BFGS pairs in the buffer after the update                               */
+    int32_t flags;                   /* ORC_STEP_*                                                                */
+    double c, eps_nu;                /* penalty and AKKT tolerance of the inner solve                             */
+    double gamma_in, L_in;           /* entering the step                                                         */
+    double gamma, L;                 /* after the back-offs                                                       */
+    double psi;                      /* psi(u_k)                                                                  */
+    double norm_r_in, norm_r;        /* ||r|| of the exit test, and after the back-offs                           */
+    double tau;                      /* the accepted tau; 0 after an exhausted search under ls_failure = 1; -1 at k = 0 and on exit */
+    double u[ORC_TRACE_NU], y[ORC_TRACE_NU], u_next[ORC_TRACE_NU];
+} orc_step;
+
+/* orc_solve, recording every PANOC step into steps[0 .. cap - 1].  Returns the number of steps taken (> cap: the rest
+ * were not recorded), or < 0 as orc_solve. */
+int orc_solve_trace(const orc_problem *pb, const orc_opts *opts, const double *p, double *u, const double *y0, double c0,
+                    double *y_out, orc_status *st, orc_step *steps, int cap);
+
 /* B independent solves on `threads` host threads (pthreads pulling from a shared work queue). */
 int orc_solve_batch(const orc_problem *pb, const orc_opts *opts, int B, const double *p, double *u,
                     const double *y0, const double *c0, double *y_out, orc_status *st, int threads);
