@@ -17,914 +17,14 @@
 #include <string>
 #include <vector>
 
-#ifndef NMPC_WIN
-#define NMPC_WIN 1      // half width of the cross-track window of the one-stage-per-lane kernels (eval_psi); 0 = always the full scan
-#endif
-
-namespace nmpc {
-
-constexpr int NZ = 20;         // reference configs/default.yaml:35
-constexpr int MAXMEM = 10;     // L-BFGS memory the kernel is built for
-constexpr int NDYN_MAX = 3;    // Ndynobs the kernel is built for
-constexpr int GRAM_LD = 11;    // row stride of the kept inner products gsy / gyy (doubles): with 10 the ten lanes of a column read hit 8 bank pairs, with 11 ten
-constexpr int GRAM_NST = 20;   // stages the Gram-form L-BFGS of the hybrid kernel runs over (N_hor <= 20, zero padded)
-constexpr int OBS_STRIDE = 4;  // doubles per static circle in LDS: xs ys r^2 r
-constexpr int SEG_STRIDE = 5;  // doubles per reference segment in LDS (odd: the per-lane window gathers of eval_psi spread over all banks)
-// team mode of the hybrid kernel (nmpc_solve_hyb.h): four waves per workgroup; a wave without work of its own evaluates
-// line-search trials for its siblings.  Request = u, r, d by stage (3 x 24 pairs); one result area = three trials'
-// gradients by stage (3 x 24 pairs) + their psi values
-constexpr int TEAM_WAVES = 4;
-constexpr int TEAM_REQ_DOUBLES = 3 * 24 * 2;
-constexpr int TEAM_AREA_DOUBLES = 3 * 24 * 2 + 8;     // + psi[3], envelope[3]
-constexpr int TEAM_CTL_INTS = 64;
-// instances waiting for a wave (nmpc_solve_hyb.h): long = an outer criterion is still open after the outer iteration just finished, cold = all hold: the next outer iteration is the last (and short)
-constexpr int NPOOLS = 2;
-enum { POOL_LONG = 0, POOL_COLD = 1 };
-
-// PANOC constants
-constexpr double GAMMA_L_COEFF = 0.95;
-constexpr double DELTA_LIPSCHITZ = 1e-12;
-constexpr double EPSILON_LIPSCHITZ = 1e-6;
-constexpr double LIPSCHITZ_UPDATE_EPSILON = 1e-6;
-constexpr int MAX_LIPSCHITZ_UPDATE_ITERATIONS = 10;
-constexpr double MAX_LIPSCHITZ_CONSTANT = 1e9;
-constexpr double MIN_LIPSCHITZ_CONSTANT = 1e-10;
-constexpr int MAX_LINESEARCH_ITERATIONS = 10;
-constexpr double LBFGS_SY_EPSILON = 1e-10;
-constexpr double LBFGS_CBFGS_EPSILON = 1e-8;
-
-// LDS slice of one group (offsets in doubles)
-struct LdsMap {
-    int sc;      // 18 instance scalars: x0 y0 th0 vinit winit xf yf thf | q qv qth rv rw qN qthN qcte pa pw | vinit winit again, as an aligned pair
-    int cw;      // CW_NCOEF sin/cos polynomial coefficients (nmpc_device.h)
-    int par;     // up to 24 parked solver scalars (hybrid kernel)
-    int seg;     // SEG_STRIDE = 5 per reference segment (40 B): s1x s1y dx dy 1/(|d|^2 + 1e-16)
-    int obs;     // OBS_STRIDE per static circle: xs ys r^2 r
-    int f2;      // n2 penalty values
-    int dyn;     // NDYN_MAX x 6 x dyn_stride per-stage ellipse data
-    int dyn_stride;  // columns per (ellipse, field): 24 / 32 for the three- / two-point layouts, N rounded up to even for one point
-    int req;     // hybrid kernel, team mode: the line-search request of this wave's instance -- u, r, d as 3 x 24 (v, w) pairs by stage
-    int vec;     // 7 x P parked (v, w) pairs: L-BFGS old u / old r, previous gradient, y+, y, reference speed, grad at u_k
-    int rho;     // m
-    int S, Y;    // m slots x N lanes x (v, w)
-    int nv;      // hybrid kernel, Gram-form L-BFGS: the four vectors of an iteration -- s | y | r | g -- as 4 x GRAM_NST (v, w) pairs by stage
-    int gsy, gyy; // ... and the inner products it keeps, [slot][slot]: <s_a, y_b> (a older than b; zero otherwise), <y_a, y_b>
-    int total;
-};
-
-struct KArgs {
-    nmpc_problem pb;
-    nmpc_opts op;
-    LdsMap map;
-    int B;
-    int n_p, n_u, n1, n2;
-    double inv_ts;
-    const double *p;
-    double *u;
-    const double *y0;
-    const double *c0;
-    double *y_out;
-    nmpc_status *st;
-    unsigned int *queue;
-    const int *order;          // queue position -> instance (longest-expected-first), or NULL = index order
-    // migration of long-running instances to the SIMD's favoured wave slot (nmpc_solve_hyb.h), 0 = off
-    int park_min;              // passes after which an instance on an unfavoured wave is parked at an outer-iteration boundary
-    int park_depth;            // ... unless this many parked instances are already waiting for a favoured wave
-    double *park;              // [B][park_stride]: parked solver state
-    int *pool;                 // [B]: parked instance ids in arrival order (-1: not yet published)
-    unsigned int *pool_ctr;    // per pool: head, tail, count, pad (nmpc_solve_hyb.h: POOL_CTRS); after the pools: instances alive that are known to be long
-    int pool_cap;              // slots per pool ring (>= B)
-    int sched_mode;            // 0: an instance stays on its wave (but for the slot migration); 1: step-aside scheduling at outer-iteration boundaries (nmpc_solve_hyb.h)
-    int sched_long_cap;        // long instances alive beyond this many time-share the waves
-    int sched_cold_cap;        // cold instances step aside once this many long instances are alive (a batch without long instances has nobody to make room for)
-    int dbg;                   // experiments (NMPC_DEBUG_PRIO): static wave priorities + per-instance cycle counts
-    int team_owners;           // hybrid kernel: waves per workgroup that take instances from the queue (1..4); the others only help
-    int team_help;             // 0: nobody asks for help (experiments, NMPC_TEAM_HELP=0: the single-wave baseline)
-    double cull_radius;        // eval_psi's CULL path: circles whose edge is farther than this from the start position are left out of the scan
-    // eval kernel only
-    const double *ev_c;
-    const double *ev_y;
-    double *ev_psi, *ev_grad, *ev_F1, *ev_F2;
-};
-
-enum { SC_X0 = 0, SC_Y0, SC_TH0, SC_VINIT, SC_WINIT, SC_XF, SC_YF, SC_THF,
-       SC_Q, SC_QV, SC_QTH, SC_RV, SC_RW, SC_QN, SC_QTHN, SC_QCTE, SC_PA, SC_PW };
-
-// LDS pointers carry their address space: no generic-pointer casts, always ds_* instructions
-typedef __attribute__((address_space(3))) double lds_double;
-typedef double dbl2 __attribute__((ext_vector_type(2)));     // (v, w) pair, 16-byte aligned
-typedef __attribute__((address_space(3))) dbl2 lds_double2;
-
-#ifdef NMPC_NO_SCHED_BARRIER
-#define NMPC_SCHED_BARRIER() do { } while (0)
-#else
-#define NMPC_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#endif
-#define NMPC_WAVE_SYNC()                                           \
-    do {                                                           \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     \
-        __builtin_amdgcn_wave_barrier();                           \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");     \
-    } while (0)
-
-// per-stage data of the dynamic ellipses: six values per (ellipse, stage), kept in the LDS slice as
-// [ellipse][field][stage] so the stage's lane reads its column conflict-free
-enum { DY_EX = 0, DY_EY, DY_CA, DY_SA, DY_IRX2, DY_IRY2, DY_FIELDS };
-struct DynStage {
-    const lds_double *col;     // this lane's column
-    int stride;                // lanes per group (P)
-    __device__ __forceinline__ double get(int k, int f) const { return col[(k * DY_FIELDS + f) * stride]; }
-};
-
-// Problem shape known at compile time (0 / -1: taken from the arguments at run time).  The reference
-// generates one solver per configuration (mpc_generator.py:173-193); ShapeDefault is the shape of
-// configs/default.yaml (N_hor 20, Nobs 10, Ndynobs 3), for which loops unroll and LDS offsets fold.
-struct ShapeAny { static constexpr int N = 0, NOBS = -1, NDYN = -1; };
-struct ShapeDefault { static constexpr int N = 20, NOBS = 10, NDYN = 3; };
-struct ShapeNobs50 { static constexpr int N = 20, NOBS = 50, NDYN = 3; };     // BASELINE config 3
-struct ShapeN40 { static constexpr int N = 40, NOBS = 10, NDYN = 3; };        // BASELINE config 2
-template <class SH> __device__ __forceinline__ int shape_N(const KArgs &a) { if constexpr (SH::N > 0) return SH::N; else return a.pb.N; }
-template <class SH> __device__ __forceinline__ int shape_nobs(const KArgs &a) { if constexpr (SH::NOBS >= 0) return SH::NOBS; else return a.pb.nobs; }
-template <class SH> __device__ __forceinline__ int shape_ndyn(const KArgs &a) { if constexpr (SH::NDYN >= 0) return SH::NDYN; else return a.pb.ndyn; }
-
-// The LDS slice layout (offsets in doubles) as a function of the problem shape and the lane layout P (20: three query points
-// per wave, 32: two, 64: one).  constexpr: the shape-specialised kernels fold every offset into the ds_* instructions'
-// immediate fields instead of carrying a dozen kernel arguments in (spilled) SGPRs; the host computes the same map for the
-// run-time-shape kernels and for sizing the launch.  The L-BFGS ring is sized for MAXMEM slots whatever opts.lbfgs_memory is.
-__host__ __device__ constexpr LdsMap lds_layout(int N, int nobs, int ndyn, int P)
-{
-    LdsMap mp{};
-    int o = 0;
-    mp.sc = o;  o += 20;
-    mp.cw = o;  o += CW_NCOEF;
-    mp.par = o; o += 24;
-    mp.seg = o; o += SEG_STRIDE * (N + 5);
-    mp.obs = o; o += OBS_STRIDE * (nobs + 4);
-    const int points = P == 64 ? 1 : 3;               // F2 arrays: one per query point of a pass (eval kernel: per group slice)
-    // (three-point layout: only the cost-layer kernel writes F2, and it has no parked vectors -- the array shares their place)
-    mp.f2 = o;  o += P == 20 ? 0 : points * (nobs + ndyn + 1);
-    mp.rho = o; o += MAXMEM;
-    const int cols = P == 20 ? 24 : P;                // >= lay_cols (hybrid kernel: state lanes 24..31 share column 23 -- all zeros)
-    // one point per wave keeps its solver vectors in registers and needs ellipse columns for the real stages only: without
-    // the 64-column tables a 40-stage slice is 21.6 KB instead of 32.9 KB -- 7 resident waves per CU instead of 4
-    mp.dyn_stride = P == 64 ? ((N + 1) & ~1) : (P == 20 ? 24 : P);
-    mp.dyn = o; o += NDYN_MAX * 6 * mp.dyn_stride;
-    o = (o + 1) & ~1;
-    mp.req = o; o += P == 20 ? TEAM_REQ_DOUBLES : 0;
-    mp.vec = o; o += P == 64 ? 0 : 7 * 2 * cols;
-    if (P == 20) { mp.f2 = mp.vec; if (7 * 2 * cols < points * (nobs + ndyn + 1)) o = mp.vec + points * (nobs + ndyn + 1); }
-    o = (o + 1) & ~1;                                 // 16-byte alignment for the double2 arrays
-    // hybrid kernel: GRAM_NST + 1 columns per slot whatever N is -- the Gram batch reads a slot as GRAM_NST pairs, the last column is
-    // all zeros (lanes beyond the horizon read it); gsy | gyy | S | Y are contiguous (zeroed together when the buffer is reset)
-    mp.gsy = o; o += P == 20 ? MAXMEM * GRAM_LD : 0;
-    mp.gyy = o; o += P == 20 ? MAXMEM * GRAM_LD : 0;
-    const int ring = P == 20 ? GRAM_NST + 1 : N;
-    mp.S = o;   o += 2 * ring * MAXMEM;
-    mp.Y = o;   o += 2 * ring * MAXMEM;
-    mp.nv = o;  o += P == 20 ? 4 * 2 * GRAM_NST : 0;
-    mp.total = (o + 1) & ~1;
-    // team mode: a helper wave's slice holds one result area per (owner, task) from offset 0 -- twelve of them; short horizons make slices
-    // smaller than that (N_hor <= 14), and an area past the slice would land in the next wave's tables
-    if (P == 20 && mp.total < 3 * TEAM_WAVES * TEAM_AREA_DOUBLES) mp.total = 3 * TEAM_WAVES * TEAM_AREA_DOUBLES;
-    return mp;
-}
-// the map a kernel instantiation works with: compile-time for a fixed shape, the launch argument otherwise
-template <class SH, int P> __device__ __forceinline__ LdsMap the_map(const KArgs &a)
-{
-    if constexpr (SH::N > 0 && SH::NOBS >= 0 && SH::NDYN >= 0) return lds_layout(SH::N, SH::NOBS, SH::NDYN, P);
-    else return a.map;
-}
-
-// ---------------------------------------------------------------------------------------------
-// instance set-up: p -> LDS slice + per-lane registers     (reference mpc_generator.py:73-79,93-104,127-136)
-// ---------------------------------------------------------------------------------------------
-template <int P, class SH = ShapeAny>
-__device__ __forceinline__ void prepare_instance(const KArgs &a, lds_double *L, const double *p, int t,
-                                                 double &vref, DynStage &dyn)
-{
-    const int N = shape_N<SH>(a), nobs = shape_nobs<SH>(a), ndyn = shape_ndyn<SH>(a);
-    const LdsMap mp = the_map<SH, P>(a);
-    if (t < 8) L[mp.sc + t] = p[t];                      // state, last input, target (p[8:10] unused)
-    if (t >= 8 && t < 18) L[mp.sc + t] = p[t + 2];       // ten weights p[10:20]
-    if (t == 18 || t == 19) L[mp.sc + t] = p[t - 15];    // the last input once more, as a (v, w) pair: "the stage before stage 0" of the hybrid kernel's transport
-    if (t < CW_NCOEF) L[mp.cw + t] = CW_COEF_DEV[t];
-    NMPC_WAVE_SYNC();
-    vref = t < N ? p[NZ + t] : 0.0;
-    const double *ps = p + NZ + N;
-    for (int k = t; k < ((nobs + 4) & ~3); k += P) {       // padded to a multiple of 4 with inert zero circles (slot `nobs` always is one)
-        const bool real = k < nobs;
-        const double r = real ? ps[3 * k + 2] : 0.0;
-        L[mp.obs + OBS_STRIDE * k] = real ? ps[3 * k] : 0.0;
-        L[mp.obs + OBS_STRIDE * k + 1] = real ? ps[3 * k + 1] : 0.0;
-        L[mp.obs + OBS_STRIDE * k + 2] = r * r;
-        L[mp.obs + OBS_STRIDE * k + 3] = r > 0.0 ? r : -1e30;      // (obstacle certificate: an empty slot is infinitely far away)
-    }
-    const double *pd = ps + 3 * nobs;
-    {
-        lds_double *col = L + mp.dyn + t;
-        dyn.col = col;
-        // one point per wave (P = 64): only the N real stages have a column (the slice then fits 7 waves per CU, not 4)
-        const int ds = P == 64 ? mp.dyn_stride : lay_cols<P>();
-        dyn.stride = ds;
-#pragma unroll
-        for (int k = 0; k < NDYN_MAX; ++k) {
-            double ex = 0.0, ey = 0.0, ca = 0.0, sa = 0.0, irx2 = 1.0, iry2 = 1.0;
-            if (k < ndyn && t < N) {
-                const double *e = pd + (k * N + t) * 5;
-                ex = e[0];
-                ey = e[1];
-                irx2 = 1.0 / (e[2] * e[2]);
-                iry2 = 1.0 / (e[3] * e[3]);
-                sincos_cw_t(e[4], (const lds_double *)(L + mp.cw), sa, ca);
-            }
-            if (P != 64 || t < ds) {
-                col[(k * DY_FIELDS + DY_EX) * ds] = ex;
-                col[(k * DY_FIELDS + DY_EY) * ds] = ey;
-                col[(k * DY_FIELDS + DY_CA) * ds] = ca;
-                col[(k * DY_FIELDS + DY_SA) * ds] = sa;
-                col[(k * DY_FIELDS + DY_IRX2) * ds] = irx2;
-                col[(k * DY_FIELDS + DY_IRY2) * ds] = iry2;
-            }
-        }
-    }
-    const double *pr = pd + 5 * ndyn * N;
-    const int nseg4 = (N - 1 + 3) & ~3;                    // the CTE loop runs 4 segments per trip; the padding
-    if (t < nseg4) {                                       // repeats the last segment (cannot change a strict min)
-        const int i = t < N - 1 ? t : N - 2;
-        const double ax = pr[3 * i], ay = pr[3 * i + 1];
-        const double bx = pr[3 * i + 3], by = pr[3 * i + 4];
-        const double dx = bx - ax, dy = by - ay;
-        lds_double *sg = L + mp.seg + SEG_STRIDE * t;
-        sg[0] = ax;
-        sg[1] = ay;
-        sg[2] = dx;
-        sg[3] = dy;
-        sg[4] = 1.0 / (fma(dx, dx, dy * dy) + 1e-16);
-    }
-    NMPC_WAVE_SYNC();
-}
-
-// Windowed cross-track search (eval_psi / eval_psi2, WIN > 0).  What a lane remembers from its last FULL scan of the reference segments:
-// the centre of its window, where the stage was then, and the squared distance from there to the nearest segment OUTSIDE the window
-// (0 = nothing known: the next evaluation scans everything).
-struct WinState {
-    int ctr;
-    double xr, yr, mo2;
-};
-// -DNMPC_TL (scripts/timeline.py): s_memtime of fifteen events of a helped iteration -- owner 0..10, the helper of its first task 11..14 --
-// for 64 consecutive iterations of the instance that runs them (one instance solved alone)
-#ifdef NMPC_TL
-__device__ long long nmpc_tl[64 * 16];
-#ifdef NMPC_MARKS      // (with -DNMPC_MARKS: the events as markers in the ISA dump instead)
-#define NMPC_TL_EV(it, ev) do { (void)(it); __builtin_amdgcn_sched_barrier(0); asm volatile("; MARK TL_" #ev); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define NMPC_TL_EV(it, ev) do { if ((it) >= 200 && (it) < 264 && lane == 0) nmpc_tl[((it) - 200) * 16 + (ev)] = __builtin_amdgcn_s_memtime(); } while (0)
-#endif
-#define NMPC_TL_KEEP(x) do { double keep_ = (x); asm volatile("" : "+v"(keep_)); } while (0)
-#else
-#define NMPC_TL_EV(it, ev) do { } while (0)
-#define NMPC_TL_KEEP(x) do { } while (0)
-#endif
-#ifdef NMPC_BBCOUNT
-// scripts/bbcount.py: one counter per basic block of ONE solve kernel.  The increments are not in this source: bbcount.py rewrites the
-// compiler's assembly (four instructions at the head of every block, registers the kernel does not use) and links the result against this array.
-__device__ __attribute__((used)) unsigned int nmpc_bbcnt[4096];
-#endif
-#ifdef NMPC_WIN_STATS
-__device__ unsigned long long nmpc_win_stats[4];       // evaluations that tried the window | of which fell back to the full scan | that tried the obstacle certificate | of which scanned
-#endif
-// Obstacle certificate (eval_psi, oc != nullptr).  The activity scan of an evaluation only decides WHICH circles / ellipses have a stage of
-// the wave inside them (the touched ones are then summed exactly); from one evaluation to the next that set rarely changes.  So a lane
-// remembers where its stage was at the wave's last scan and how far that was -- at least -- from every obstacle the scan found
-// untouched (distance to the circle's edge; for an ellipse to the disc of its larger half axis around its centre; for the culled scan
-// also to the culling radius), and the wave remembers the scan's verdict.  While every stage has moved by less than its clearance no
-// untouched obstacle can have been entered: the old verdict is a superset of the true one, and a superfluous member contributes exactly
-// zero (its sum is +0.0, no lane is inside it) -- the scan is skipped and the result is bit for bit the scanning evaluation's.  The
-// clearances come from v_sqrt_f64 / v_rsq_f64 (approximate) with 1 % + 1e-6 taken off: they only decide whether the scan runs.
-struct ObsCert {
-    double xo, yo, m2;             // this lane: the stage's position at the wave's last scan, squared clearance there (0: scan next time).  (A reference
-                                   // point shared with the cross-track window was measured: four registers less, but either certificate's failure then
-                                   // runs both scans -- 10 % of the evaluations instead of 1 %, headline + 6 %.)
-    // the wave: circles and ellipses the last scan found touched.  Kept in VECTOR registers (every lane the same value; read back with
-    // v_readfirstlane): as scalar-register values in the select chains of the caller they crash ROCm 7.2's greedy register allocator
-    // (VirtRegAuxInfo::isRematerializable, iterative-ilp, the Nobs = 50 instantiation)
-    int act_lo, act_hi, act_dyn;
-};
-__device__ __forceinline__ int opaque_i(int x) { asm("" : "+v"(x)); return x; }
-// Is the windowed minimum `best` (squared) the global one?  With a2 = |p - p_ref|^2 and mo2 = the squared clearance of the window at
-// p_ref, every segment outside the window is at least sqrt(mo2) - |p - p_ref| away from p (distances are 1-Lipschitz), so it is if
-// sqrt(best) + |p - p_ref| < sqrt(mo2)  <=>  t = mo2 - a2 - best > 0 and t^2 > 4 a2 best.  The margins (1e-5 relative on squared
-// distances) dwarf the rounding of the distance formula (<= 2e-10 relative wherever it matters; mo2 <= 1e-8 is stored as 0).
-__device__ __forceinline__ bool window_is_global(double a2, double best, double mo2)
-{
-    const double t = mo2 - (a2 + best);
-    return t > 1e-5 * mo2 && t * t > 4.0001 * (a2 * best);
-}
-
-// the circles of an instance whose edge lies within `radius` of the start position (bit k = circle k); padding slots (r = 0) never are
-__device__ __forceinline__ unsigned long long circle_near_mask(const double *p, int N, int nobs, int lane, double radius)
-{
-    const double *ps = p + NZ + N;
-    bool keep = false;
-    if (lane < nobs) {
-        const double dx = ps[3 * lane] - p[0], dy = ps[3 * lane + 1] - p[1], r = ps[3 * lane + 2], lim = radius + r;
-        keep = r > 0.0 && fma(dx, dx, dy * dy) <= lim * lim;
-    }
-    return __ballot(keep);
-}
-
-// ---------------------------------------------------------------------------------------------
-// psi(z; c, y), grad psi, F1 (av, aw), sum_k F2_k^2 (pen); WRITE_F2: F2_k also left in the LDS slice
-// ---------------------------------------------------------------------------------------------
-#if defined(NMPC_PROF2) && NMPC_PROF2 == 2      // scripts/sections.py: cycles of the evaluation by section, accumulated in registers of the caller
-#define NMPC_EVTICK(i) do { if (nmpc_pe) { __builtin_amdgcn_sched_barrier(0); const long long t_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xc07f); nmpc_pe[i] += t_ - nmpc_pe[7]; nmpc_pe[7] = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#elif defined(NMPC_MARKS)       // scripts/isa_stats.py: section markers in the ISA dump
-#define NMPC_EVTICK(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("; MARK " #i); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define NMPC_EVTICK(i) do { } while (0)
-#endif
-// CULL: `near` is the set of static circles that can be touched at all while every stage stays within KArgs.cull_radius of the start
-// position (circle_near_mask below); the activity scan visits those only, and falls back to all of them for an evaluation in
-// which some stage is farther away -- so the result is exactly that of the full scan.
-// The handful of launch-uniform scalars an evaluation reads, as values of their own.  Read from the argument block (a.pb.*) they belong to a
-// sixteen-dword scalar load whose registers the allocator spills and reloads AS ONE (sixteen v_readlane per use of one bound); a kernel that
-// hands them over in this struct -- each passed through scalar_own() once -- pays two.
-struct EvK { double ts, inv_ts, amin, amax, awmax; };
-__device__ __forceinline__ double scalar_own(double x)
-{
-    // through a vector register and back (v_readfirstlane): a definition of its own that the coalescer cannot fold back into the loaded tuple
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    asm volatile("" : "+v"(lo), "+v"(hi));
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(hi), __builtin_amdgcn_readfirstlane(lo));
-}
-__device__ __forceinline__ int scalar_own(int x)
-{
-    asm volatile("" : "+v"(x));
-    return __builtin_amdgcn_readfirstlane(x);
-}
-// What the hybrid kernel's owner path hands over because its query points travel through LDS (nmpc_solve_hyb.h, "transport"): the control
-// pair of the stage before (the last input for stage 0) -- read from the transport area one slot down instead of fetched from the neighbour
-// lane --, this lane's slot of the area for handing (qa, qw) to the stage before, and the slot of the stage after (a zero pad behind the
-// last stage).  Two pointers that the compiler cannot tell apart: the write stays in front of the read, and LDS serves a wave in order.
-// Lanes 60..63 of such an evaluation hold zeros in zv, zw (Z60: group_prefix_ex_z60).
-struct EvX {
-    double vprev, wprev;
-    lds_double2 *mine;
-    const lds_double2 *next;
-};
-template <int P, class SH = ShapeAny, bool WRITE_F2 = false, bool CULL = false, int WIN = 0, bool Z60 = false>
-__device__ __forceinline__ void eval_psi(const KArgs &a, lds_double *L, int f2off, int lane, int t, double zv, double zw,
-                                         double c, double cbar_inv, double yv, double yw, double vref, const DynStage &dyn,
-                                         bool want_grad, double &psi, double &pen_out, double &gv,
-                                         double &gw, double &av_out, double &aw_out, unsigned long long near = ~0ull, WinState *ws = nullptr,
-                                         ObsCert *oc = nullptr, long long *nmpc_pe = nullptr, const EvK *ek = nullptr, const EvX *evx = nullptr)
-{
-    static_assert(!Z60 || P == 20, "zero pads in lanes 60..63: the tri layout only");
-    const int N = shape_N<SH>(a), nobs = shape_nobs<SH>(a), ndyn = shape_ndyn<SH>(a);
-    const LdsMap mp = the_map<SH, P>(a);
-    const double ts = ek ? ek->ts : a.pb.ts, inv_ts = ek ? ek->inv_ts : a.inv_ts;
-    const double k_amin = ek ? ek->amin : a.pb.amin, k_amax = ek ? ek->amax : a.pb.amax, k_awmax = ek ? ek->awmax : a.pb.awmax;
-    (void)nmpc_pe;
-    // every stage lane of the tri layout is inside a 20-stage horizon; lanes 60..63 then hold
-    // don't-care values that no cross-lane operation lets into the other lanes (nmpc_device.h)
-    constexpr bool FULL = P == 20 && SH::N == 20;
-    const bool in_r = t < N;                    // a real stage
-    const bool in = FULL ? true : in_r;         // arithmetic masks: compile-time true when FULL
-    const lds_double *sc = L + mp.sc;
-    const double x0 = sc[SC_X0], y0 = sc[SC_Y0], th0 = sc[SC_TH0];
-    const double xf = sc[SC_XF], yf = sc[SC_YF], thf = sc[SC_THF];
-
-    // rollout (:88-90) as three prefix sums
-    // (the pre-update state of a stage is the post-update state of the stage before: the same fma on the prefix sum of the stage before,
-    // which the scan hands over with its own carry exchange -- group_prefix_ex)
-    double ew_, ex_, ey_;
-    auto prefix_ex = [lane](double v, double &excl) {
-        if constexpr (Z60) return group_prefix_ex_z60(v, lane, excl);
-        else return group_prefix_ex<P>(v, lane, excl);
-    };
-    const double thn = fma(ts, prefix_ex(zw, ew_), th0);
-    const double th = t == 0 ? th0 : fma(ts, ew_, th0);
-    double sn, cs;
-    sincos_cw_t(th, (const lds_double *)(L + mp.cw), sn, cs);
-    const double xn = fma(ts, prefix_ex(zv * cs, ex_), x0);
-    const double yn = fma(ts, prefix_ex(zv * sn, ey_), y0);
-    const double xp = t == 0 ? x0 : fma(ts, ex_, x0);
-    const double yp = t == 0 ? y0 : fma(ts, ey_, y0);
-
-    const double half_c = 0.5 * c;
-    NMPC_EVTICK(0);     // rollout
-
-    double acc = (sc[SC_RV] * zv) * zv;                                           // (:84)
-    acc = fma(sc[SC_RW] * zw, zw, acc);
-    const double dv = zv - vref;                                                  // (:85)
-    acc = fma(sc[SC_QV] * dv, dv, acc);
-    {
-        const double ddx = xp - xf, ddy = yp - yf, dth = th - thf;                // (:86, 59-64)
-        acc = fma(sc[SC_Q], fma(ddx, ddx, ddy * ddy), acc);
-        acc = fma(sc[SC_QTH] * dth, dth, acc);
-    }
-    // cross-track error: min over the N-1 reference segments (:121-144)
-    double best = __builtin_inf();
-    int bi = 0;
-    bool full_scan = true;
-    int i0c = 0;                        // first segment of the window the full scan measures the clearance of
-    if constexpr (WIN > 0) {
-        // WINDOWED SEARCH (exact).  From one evaluation to the next a stage's nearest segment rarely moves, so only the 2 WIN + 1
-        // segments around the lane's window centre are measured -- per-lane LDS gathers instead of broadcasts -- and the result is
-        // accepted if it is PROVABLY the full scan's (window_is_global above).  If any stage of the wave fails the test, or holds no
-        // clearance yet, the full scan below runs instead and renews every lane's clearance; either way `best`, `bi` are the full scan's.
-        const int nseg = N - 1;
-        if (nseg >= 2 * WIN + 1) {
-            int cc = ws->ctr;
-            cc = cc < 0 ? 0 : (cc > nseg - 1 ? nseg - 1 : cc);
-            i0c = cc - WIN;
-            i0c = i0c < 0 ? 0 : (i0c > nseg - (2 * WIN + 1) ? nseg - (2 * WIN + 1) : i0c);
-            if (!__any(in_r & !(ws->mo2 > 0.0))) {
-                const lds_double *sg = L + mp.seg + SEG_STRIDE * i0c;
-                double wv[2 * WIN + 1][5];
-#pragma unroll
-                for (int j = 0; j <= 2 * WIN; ++j)
-#pragma unroll
-                    for (int f = 0; f < 5; ++f) wv[j][f] = sg[j * SEG_STRIDE + f];
-#pragma unroll
-                for (int j = 0; j <= 2 * WIN; ++j) {
-                    const double px = xn - wv[j][0], py = yn - wv[j][1];
-                    const double dot = fma(px, wv[j][2], py * wv[j][3]);
-                    const double that = dot * wv[j][4];
-                    const double tst = fmin(fmax(that, 0.0), 1.0);
-                    const double ex = fma(tst, wv[j][2], -px), ey = fma(tst, wv[j][3], -py);
-                    const double d2 = fma(ex, ex, ey * ey);
-                    bi = d2 < best ? i0c + j : bi;
-                    best = fmin(best, d2);
-                }
-                const double ax = xn - ws->xr, ay = yn - ws->yr;
-                const bool sure = window_is_global(fma(ax, ax, ay * ay), best, ws->mo2);
-                full_scan = __any(in_r & !sure);
-#ifdef NMPC_WIN_STATS
-                if (lane == 0) { atomicAdd(&nmpc_win_stats[0], 1ull); if (full_scan) atomicAdd(&nmpc_win_stats[1], 1ull); }
-#endif
-                if (full_scan) {
-                    // the full scan measures the clearance of the window around what the old window found nearest
-                    i0c = bi - WIN;
-                    i0c = i0c < 0 ? 0 : (i0c > nseg - (2 * WIN + 1) ? nseg - (2 * WIN + 1) : i0c);
-                    best = __builtin_inf(); bi = 0;
-                }
-            }
-        }
-    }
-    if (full_scan) {
-        const lds_double *sg = L + mp.seg;
-        const int nseg4 = (N - 1 + 3) & ~3;
-        // software pipeline: the ten LDS reads of the NEXT pair of segments are issued before the current
-        // pair is reduced (the scheduling barriers keep the compiler from sinking them to their uses)
-        double cur[2][5], nxt[2][5];
-        double mout = __builtin_inf();                      // (WIN) nearest segment outside the window [i0c, i0c + 2 WIN]
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int f = 0; f < 5; ++f) cur[j][f] = sg[j * SEG_STRIDE + f];
-#pragma unroll SH::N > 0 ? (SH::N <= 20 ? 32 : 2) : 1
-        for (int i = 0; i < nseg4; i += 2) {
-            sg += 2 * SEG_STRIDE;                           // table is padded: reading one pair past the end is safe
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int f = 0; f < 5; ++f) nxt[j][f] = sg[j * SEG_STRIDE + f];
-            NMPC_SCHED_BARRIER();
-            double d2[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double px = xn - cur[j][0], py = yn - cur[j][1];
-                const double dot = fma(px, cur[j][2], py * cur[j][3]);
-                const double that = dot * cur[j][4];
-                const double tst = fmin(fmax(that, 0.0), 1.0);
-                const double ex = fma(tst, cur[j][2], -px), ey = fma(tst, cur[j][3], -py);
-                d2[j] = fma(ex, ex, ey * ey);
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {                   // strict <: the first minimum keeps its index
-                bi = d2[j] < best ? i + j : bi;
-                best = fmin(best, d2[j]);
-                if constexpr (WIN > 0) {                    // (a padding entry repeats the last segment)
-                    const int ie = i + j < N - 1 ? i + j : N - 2;
-                    mout = (unsigned)(ie - i0c) <= 2u * WIN ? mout : fmin(mout, d2[j]);
-                }
-            }
-            NMPC_SCHED_BARRIER();
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int f = 0; f < 5; ++f) cur[j][f] = nxt[j][f];
-        }
-        if constexpr (WIN > 0) {
-            // this lane's certificate for the evaluations to come: if the nearest segment lies in the window that was measured, the
-            // window stays and its clearance is known; if not, the window moves there and the next evaluation measures it
-            const bool inw = (unsigned)(bi - i0c) <= 2u * WIN;
-            ws->ctr = inw ? i0c + WIN : bi;
-            ws->xr = xn; ws->yr = yn;
-            ws->mo2 = inw && mout > 1e-8 ? mout : 0.0;
-        }
-    }
-    NMPC_EVTICK(1);     // stage cost + CTE loop
-    acc = fma(sc[SC_QCTE], best, acc);                                            // (:144)
-    // accelerations (:160-161), their cost (:170-171) and the ALM term
-    const double vprev = evx ? evx->vprev : from_prev<P>(zv, lane, sc[SC_VINIT]);
-    const double wprev = evx ? evx->wprev : from_prev<P>(zw, lane, sc[SC_WINIT]);
-    double av = (zv - vprev) * inv_ts, aw = (zw - wprev) * inv_ts;
-    acc = fma(sc[SC_PA] * av, av, acc);
-    acc = fma(sc[SC_PW] * aw, aw, acc);
-    const double tv = fma(yv, cbar_inv, av), tw = fma(yw, cbar_inv, aw);
-    double sv = tv - clampd(tv, k_amin, k_amax);
-    double sw = tw - clampd(tw, -k_awmax, k_awmax);
-    acc = fma(half_c, fma(sv, sv, sw * sw), acc);
-    if (t == N - 1) {                                                             // terminal (:148)
-        const double tx = xn - xf, ty = yn - yf, tth = thn - thf;
-        acc = fma(sc[SC_QN], fma(tx, tx, ty * ty), acc);
-        acc = fma(sc[SC_QTHN] * tth, tth, acc);
-    }
-    if (!in) { acc = 0.0; av = aw = sv = sw = 0.0; }
-    av_out = av;
-    aw_out = aw;
-    const double fsum = group_sum<P>(acc, lane);
-    NMPC_EVTICK(2);     // accelerations, ALM term, cost sum
-
-    // obstacle penalties on the post-update state (:106-119).  F2_k = sum_t max(0, h_kt); an obstacle that no stage
-    // of any query point in this wave is inside of contributes exactly 0 to psi and to grad psi and is skipped
-    // (wave-uniform branch).  The adjoint terms of a touched obstacle, c F2_k dh_kt/d(x, y), are added right where
-    // its F2_k has just been summed -- same operations in the same order as a separate sweep would do them (cross-
-    // track term first, circles in ascending order, then ellipses), without the round trip of F2 through LDS.
-    double pen = 0.0;
-    unsigned long long act = 0ull;      // wave-uniform: circles some stage is inside of
-    unsigned act_dyn = 0u;              // wave-uniform: ellipses some stage is inside of
-    bool scan = true;
-    if (oc) {
-        const double ox = xn - oc->xo, oy = yn - oc->yo;
-        const bool sure = fma(ox, ox, oy * oy) < oc->m2;
-        if (!__any(in_r & !sure)) {
-            act = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(oc->act_hi) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(oc->act_lo);
-            act_dyn = (unsigned)__builtin_amdgcn_readfirstlane(oc->act_dyn);
-            scan = false;
-        }
-#ifdef NMPC_WIN_STATS
-        if (lane == 0) { atomicAdd(&nmpc_win_stats[2], 1ull); if (scan) atomicAdd(&nmpc_win_stats[3], 1ull); }
-#endif
-    }
-    if (scan) {
-        double mg = __builtin_inf();        // (oc) this lane's clearance from the obstacles the scan finds untouched
-        const lds_double *ob = L + mp.obs;
-        const int nobs4 = (nobs + 3) & ~3;
-        if constexpr (CULL) {
-            // only the circles of `near` -- unless a stage of this evaluation has left the radius the set was made for
-            const unsigned long long all = nobs >= 64 ? ~0ull : (1ull << nobs) - 1ull;
-            unsigned long long todo = near & all;
-            if (todo != all) {
-                const double rx = xn - x0, ry = yn - y0;
-                const double rg = 0.999 * a.cull_radius;
-                const double ro2 = fma(rx, rx, ry * ry);
-                if (__any(in_r & !(ro2 <= rg * rg))) todo = all;
-                else if (oc) mg = rg - __builtin_amdgcn_sqrt(ro2);      // the set holds while the stage stays inside the radius
-            }
-            while (todo) {                                  // four circles per trip; slot `nobs` holds an inert zero circle
-                int kk[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    kk[j] = todo ? __builtin_ctzll(todo) : nobs;
-                    todo &= todo - (todo ? 1ull : 0ull);
-                }
-                double od[16];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const lds_double *oj = ob + OBS_STRIDE * kk[j];
-                    od[4 * j] = oj[0]; od[4 * j + 1] = oj[1]; od[4 * j + 2] = oj[2]; od[4 * j + 3] = oc ? oj[3] : 0.0;
-                }
-                NMPC_SCHED_BARRIER();
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double dx = xn - od[4 * j], dy = yn - od[4 * j + 1];
-                    const double h = fma(-dy, dy, fma(-dx, dx, od[4 * j + 2]));       // (:112)
-                    if (__any(in_r & (h > 0.0))) act |= 1ull << (kk[j] & 63);          // (the inert circle never is)
-                    else if (oc) mg = fmin(mg, __builtin_amdgcn_sqrt(od[4 * j + 2] - h) - od[4 * j + 3]);
-                }
-            }
-        } else {
-#pragma unroll SH::NOBS >= 0 && SH::NOBS <= 16 ? 16 : 1
-        for (int k = 0; k < nobs4; k += 4, ob += 4 * OBS_STRIDE) {      // activity scan: four circles per trip, one ballot each
-            double od[16];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                od[4 * j] = ob[OBS_STRIDE * j]; od[4 * j + 1] = ob[OBS_STRIDE * j + 1]; od[4 * j + 2] = ob[OBS_STRIDE * j + 2];
-                od[4 * j + 3] = oc ? ob[OBS_STRIDE * j + 3] : 0.0;
-            }
-            NMPC_SCHED_BARRIER();
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double dx = xn - od[4 * j], dy = yn - od[4 * j + 1];
-                const double h = fma(-dy, dy, fma(-dx, dx, od[4 * j + 2]));       // (:112)
-                if (__any(in_r & (h > 0.0))) act |= 1ull << (k + j);
-                else if (oc) mg = fmin(mg, __builtin_amdgcn_sqrt(od[4 * j + 2] - h) - od[4 * j + 3]);
-            }
-        }
-        }
-        NMPC_EVTICK(5);     // static circle scan
-        {
-            double dv_[NDYN_MAX][DY_FIELDS];
-#pragma unroll
-            for (int k = 0; k < NDYN_MAX; ++k)
-#pragma unroll
-                for (int f = 0; f < DY_FIELDS; ++f) dv_[k][f] = k < ndyn ? dyn.get(k, f) : 0.0;
-            NMPC_SCHED_BARRIER();
-#pragma unroll
-            for (int k = 0; k < NDYN_MAX; ++k) {
-                if (k < ndyn) {
-                    const double ca = dv_[k][DY_CA], sa = dv_[k][DY_SA];
-                    const double dx = xn - dv_[k][DY_EX], dy = yn - dv_[k][DY_EY];
-                    const double ea = fma(dx, ca, dy * sa);
-                    const double eb = fma(dx, sa, -(dy * ca));
-                    const double h = fma(-(eb * eb), dv_[k][DY_IRY2], fma(-(ea * ea), dv_[k][DY_IRX2], 1.0));   // (:118)
-                    if (__any(in_r & (h > 0.0))) act_dyn |= 1u << k;
-                    else if (oc)      // the ellipse lies inside the disc of its larger half axis
-                        mg = fmin(mg, __builtin_amdgcn_sqrt(fma(dx, dx, dy * dy)) - __builtin_amdgcn_rsq(fmin(dv_[k][DY_IRX2], dv_[k][DY_IRY2])));
-                }
-            }
-        }
-        if (oc) {
-            const double m = fma(0.99, mg, -1e-6);
-            oc->xo = xn; oc->yo = yn;
-            oc->m2 = m > 0.0 ? (m < 1e100 ? m * m : 1e200) : 0.0;
-            oc->act_lo = opaque_i((int)(unsigned)act); oc->act_hi = opaque_i((int)(unsigned)(act >> 32)); oc->act_dyn = opaque_i((int)act_dyn);
-        }
-        NMPC_EVTICK(6);     // ellipse scan
-    }
-    // ---- adjoint, first term: the cross-track error through the arg-min segment of this stage ----
-    double gx = 0.0, gy = 0.0;
-    if (want_grad) {
-        const lds_double *sg = L + mp.seg + SEG_STRIDE * bi;
-        const double px = xn - sg[0], py = yn - sg[1];
-        const double dot = fma(px, sg[2], py * sg[3]);
-        const double that = dot * sg[4];
-        const double tst = fmin(fmax(that, 0.0), 1.0);
-        const double ex = fma(tst, sg[2], -px), ey = fma(tst, sg[3], -py);
-        const double ed = fma(ex, sg[2], ey * sg[3]);
-        const double m = (that > 0.0 && that < 1.0) ? ed * sg[4] : 0.0;
-        const double two_q = 2.0 * sc[SC_QCTE];
-        gx = two_q * fma(m, sg[2], -ex);
-        gy = two_q * fma(m, sg[3], -ey);
-    }
-    // ---- touched obstacles: F2_k, its square into the penalty, its adjoint terms ----
-    if ((act | act_dyn) != 0ull) {
-        for (unsigned long long rem = act; rem;) {          // two touched circles per trip: their tree sums interleave
-            const int k0 = __builtin_ctzll(rem);
-            rem &= rem - 1;
-            if (rem == 0ull) {
-                // a single circle left (the usual case of an instance that grazes an obstacle): one sum, not a pair with a dummy twin
-                const lds_double *o0 = L + mp.obs + OBS_STRIDE * k0;
-                const double ax = o0[0], ay = o0[1], ar = o0[2];
-                const double dx0 = xn - ax, dy0 = yn - ay;
-                const double h0 = fma(-dy0, dy0, fma(-dx0, dx0, ar));
-                const double f20 = group_sum<P>(in ? fmax(h0, 0.0) : 0.0, lane);
-                if (WRITE_F2 && t == 0) L[f2off + k0] = f20;
-                pen = fma(f20, f20, pen);
-                if (want_grad) {
-                    const double w0 = -2.0 * (c * f20);
-                    if (h0 > 0.0) { gx = fma(w0, dx0, gx); gy = fma(w0, dy0, gy); }
-                }
-                break;
-            }
-            const int k1 = __builtin_ctzll(rem);
-            rem &= rem - 1;
-            const lds_double *o0 = L + mp.obs + OBS_STRIDE * k0, *o1 = L + mp.obs + OBS_STRIDE * k1;
-            const double ax = o0[0], ay = o0[1], ar = o0[2], bx = o1[0], by = o1[1], br = o1[2];
-            const double dx0 = xn - ax, dy0 = yn - ay, dx1 = xn - bx, dy1 = yn - by;
-            const double h0 = fma(-dy0, dy0, fma(-dx0, dx0, ar)), h1 = fma(-dy1, dy1, fma(-dx1, dx1, br));
-            const double f20 = group_sum<P>(in ? fmax(h0, 0.0) : 0.0, lane);
-            const double f21 = group_sum<P>(in ? fmax(h1, 0.0) : 0.0, lane);
-            if (WRITE_F2 && t == 0) { L[f2off + k0] = f20; L[f2off + k1] = f21; }
-            pen = fma(f20, f20, pen);
-            pen = fma(f21, f21, pen);
-            if (want_grad) {
-                const double w0 = -2.0 * (c * f20), w1 = -2.0 * (c * f21);
-                if (h0 > 0.0) { gx = fma(w0, dx0, gx); gy = fma(w0, dy0, gy); }
-                if (h1 > 0.0) { gx = fma(w1, dx1, gx); gy = fma(w1, dy1, gy); }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NDYN_MAX; ++k) {
-            if (act_dyn & (1u << k)) {
-                const double ca = dyn.get(k, DY_CA), sa = dyn.get(k, DY_SA);
-                const double irx2 = dyn.get(k, DY_IRX2), iry2 = dyn.get(k, DY_IRY2);
-                const double dx = xn - dyn.get(k, DY_EX), dy = yn - dyn.get(k, DY_EY);
-                const double ea = fma(dx, ca, dy * sa);
-                const double eb = fma(dx, sa, -(dy * ca));
-                const double h = fma(-(eb * eb), iry2, fma(-(ea * ea), irx2, 1.0));      // (:118)
-                const double f2 = group_sum<P>(in ? fmax(h, 0.0) : 0.0, lane);
-                if (WRITE_F2 && t == 0) L[f2off + nobs + k] = f2;
-                pen = fma(f2, f2, pen);
-                if (want_grad) {
-                    const double wk = -2.0 * (c * f2);
-                    if (h > 0.0) {
-                        const double A = ea * irx2, Bq = eb * iry2;
-                        const double hx = fma(A, ca, Bq * sa);
-                        const double hy = fma(A, sa, -(Bq * ca));
-                        gx = fma(wk, hx, gx);
-                        gy = fma(wk, hy, gy);
-                    }
-                }
-            }
-        }
-    }
-    psi = fma(half_c, pen, fsum);
-    pen_out = pen;
-    NMPC_EVTICK(3);     // obstacles
-    if (!want_grad) return;
-
-    // ---- adjoint sweep, continued (what CasADi reverse AD generated for the reference) ----
-    // the post-update state of stage t is the tracked state of stage t+1 (:86) or the terminal state (:148)
-    const double wq = t < N - 1 ? sc[SC_Q] : sc[SC_QN];
-    const double wth = t < N - 1 ? sc[SC_QTH] : sc[SC_QTHN];
-    gx = fma(2.0 * wq, xn - xf, gx);
-    gy = fma(2.0 * wq, yn - yf, gy);
-    double gt = (2.0 * wth) * (thn - thf);
-    double qa = fma(c, sv, (2.0 * sc[SC_PA]) * av);
-    double qw = fma(c, sw, (2.0 * sc[SC_PW]) * aw);
-    if (!in) { gx = gy = gt = qa = qw = 0.0; }
-    const double Sx = group_suffix<P>(gx, lane);
-    const double Sy = group_suffix<P>(gy, lane);
-    const double e = fma(Sy, cs, -(Sx * sn));
-    const double Dt = in ? (ts * zv) * e : 0.0;
-    const double St = group_suffix<P>(in ? gt + from_next<P>(Dt, lane) : 0.0, lane);
-    double qan, qwn;
-    if (evx) { *evx->mine = dbl2{qa, qw}; const dbl2 n_ = *evx->next; qan = n_.x; qwn = n_.y; }
-    else { qan = from_next<P>(qa, lane); qwn = from_next<P>(qw, lane); }
-    const double dynv = fma(Sx, cs, Sy * sn);
-    double g1 = fma(2.0 * sc[SC_RV], zv, (2.0 * sc[SC_QV]) * dv);
-    g1 = fma(inv_ts, qa - qan, g1);
-    g1 = fma(ts, dynv, g1);
-    double g2 = (2.0 * sc[SC_RW]) * zw;
-    g2 = fma(inv_ts, qw - qwn, g2);
-    g2 = fma(ts, St, g2);
-    gv = in ? g1 : 0.0;
-    gw = in ? g2 : 0.0;
-    NMPC_EVTICK(4);     // adjoint sweep
-}
-
-// dot product of two horizon vectors (lane t holds the (v_t, w_t) pair)
-template <int P>
-__device__ __forceinline__ double hdot(double av, double aw, double bv, double bw, int lane)
-{
-    return group_sum<P>(fma(av, bv, aw * bw), lane);
-}
-
-// ---------------------------------------------------------------------------------------------
-// cost-layer kernel: one evaluation per instance (parity tests, F1/F2 mapping API)
-// ---------------------------------------------------------------------------------------------
-template <int P>
-__global__ __launch_bounds__(64) void nmpc_eval_kernel(KArgs a)
-{
-    extern __shared__ double lds[];
-    constexpr int K = 64 / P;
-    const int lane = threadIdx.x, g = lay_group<P>(lane), t = lay_stage<P>(lane);
-    lds_double *L = (lds_double *)lds + g * a.map.total;
-    const int N = a.pb.N;
-    const bool in = t < N;
-    const int inst = blockIdx.x * K + g;
-    const int b = inst < a.B ? inst : a.B - 1;          // surplus groups redo the last instance, write nothing
-    double vref;
-    DynStage dyn;
-    prepare_instance<P>(a, L, a.p + (size_t)b * a.n_p, t, vref, dyn);
-    const double *u = a.u + (size_t)b * a.n_u;
-    const double zv = in ? u[2 * t] : 0.0, zw = in ? u[2 * t + 1] : 0.0;
-    const double c = a.ev_c ? a.ev_c[b] : 0.0;
-    const double yv = (a.ev_y && in) ? a.ev_y[(size_t)b * a.n1 + t] : 0.0;
-    const double yw = (a.ev_y && in) ? a.ev_y[(size_t)b * a.n1 + N + t] : 0.0;
-    for (int k = t; k < a.n2; k += P) L[a.map.f2 + k] = 0.0;
-    NMPC_WAVE_SYNC();
-    double psi, pen, gv, gw, av, aw;
-    eval_psi<P, ShapeAny, true>(a, L, a.map.f2, lane, t, zv, zw, c, 1.0 / fmax(c, 1.0), yv, yw, vref, dyn, true, psi, pen, gv, gw, av, aw);
-    NMPC_WAVE_SYNC();          // F2_k written by lane 0 of the group are read by all its lanes below
-    if (inst >= a.B) return;
-    if (t == 0 && a.ev_psi) a.ev_psi[b] = psi;
-    if (in) {
-        if (a.ev_grad) { a.ev_grad[(size_t)b * a.n_u + 2 * t] = gv; a.ev_grad[(size_t)b * a.n_u + 2 * t + 1] = gw; }
-        if (a.ev_F1) { a.ev_F1[(size_t)b * a.n1 + t] = av; a.ev_F1[(size_t)b * a.n1 + N + t] = aw; }
-    }
-    if (a.ev_F2) for (int k = t; k < a.n2; k += P) a.ev_F2[(size_t)b * a.n2 + k] = L[a.map.f2 + k];
-}
-
-}  // namespace nmpc
-
-namespace nmpc {
-// doubles per parked instance: u, y, previous gradient (2N each) + 16 scalars
-__host__ __device__ inline int park_stride(int N) { return 6 * N + 16; }
-}
+#include "nmpc_layout.h"
+#include "nmpc_probe.h"
+#include "nmpc_eval.h"
 #include "nmpc_solve_common.h"
 #include "nmpc_solve_hyb.h"
 #include "nmpc_solve_hyb2.h"
 #include "nmpc_loop.h"
-
-// ---------------------------------------------------------------------------------------------
-// launch-order heuristic.  Iteration counts are heavy-tailed and a batch ends when its slowest
-// instance does, so instances that LOOK hard are handed out first (list scheduling, longest expected
-// first).  "Looks hard" uses the inputs only: the reference samples of the horizon pass within
-// SCHED_CLEARANCE of a circle / ellipse, or the reference bends by more than SCHED_BEND inside
-// the horizon.  Only the order of processing changes; every instance's result is independent of it.
-// ---------------------------------------------------------------------------------------------
-namespace nmpc {
-constexpr double SCHED_CLEARANCE = 0.6;    // m
-constexpr double SCHED_GRAZE = 0.05;       // m: the reference itself touches an obstacle's edge -- its penalty will be active
-constexpr double SCHED_BEND = 0.05;        // rad, summed |heading change| of the reference samples
-constexpr double SCHED_SPEED_GAP = 1.0;    // m/s between the last applied and the first reference speed: the
-                                           // acceleration bounds stay active for several stages (many outer iterations)
-constexpr int SCHED_LEVELS = 13;           // hardness level = 4 x (grazes) + 4 x (grazes within the first half of the horizon) + other criteria met
-
-__global__ void nmpc_classify_kernel(KArgs a, unsigned char *cls)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.B) return;
-    const int N = a.pb.N, nobs = a.pb.nobs, ndyn = a.pb.ndyn;
-    const double *p = a.p + (size_t)b * a.n_p;
-    const double *ps = p + NZ + N, *pd = ps + 3 * nobs, *pr = pd + 5 * ndyn * N;
-    bool hard = false, graze = false, early = false;
-    double bend = 0.0;
-    for (int t = 0; t < N; ++t) {
-        const double rx = pr[3 * t], ry = pr[3 * t + 1];
-        if (t > 0) {
-            double d = pr[3 * t + 2] - pr[3 * t - 1];
-            d = d - 6.283185307179586 * rint(d * 0.15915494309189535);
-            bend += fabs(d);
-        }
-        for (int k = 0; k < nobs; ++k) {
-            const double r = ps[3 * k + 2];
-            if (r > 0.0) {
-                const double dx = rx - ps[3 * k], dy = ry - ps[3 * k + 1], lim = r + SCHED_CLEARANCE, lim0 = r + SCHED_GRAZE;
-                hard |= dx * dx + dy * dy < lim * lim;
-                graze |= dx * dx + dy * dy < lim0 * lim0;
-                early |= 2 * t < N && dx * dx + dy * dy < lim0 * lim0;      // the sooner the robot meets the obstacle, the longer the solve
-            }
-        }
-        for (int k = 0; k < ndyn; ++k) {
-            const double *e = pd + (k * N + t) * 5;
-            const double dx = rx - e[0], dy = ry - e[1], lim = fmax(e[2], e[3]) + SCHED_CLEARANCE, lim0 = fmin(e[2], e[3]) + SCHED_GRAZE;
-            hard |= dx * dx + dy * dy < lim * lim;
-            graze |= dx * dx + dy * dy < lim0 * lim0;
-        }
-    }
-    const bool gap = fabs(p[NZ] - p[3]) > SCHED_SPEED_GAP;
-    // the horizon reaches the goal: the reference is padded with the end pose (degenerate segments, braking profile)
-    const bool goal = pr[3 * (N - 1)] == pr[3 * (N - 2)] && pr[3 * (N - 1) + 1] == pr[3 * (N - 2) + 1];
-    cls[b] = (unsigned char)((graze ? 4 : 0) + (early ? 4 : 0) + (hard ? 1 : 0) + (bend > SCHED_BEND ? 1 : 0) + (gap ? 1 : 0) + (goal ? 1 : 0));
-}
-
-// The same levels from what a receding-horizon loop already knows: the evaluation passes each instance's solve took one step earlier
-// (nmpc_status.reserved).  Consecutive solves of one robot are alike -- the previous count is a far better predictor of the next than anything the
-// inputs show -- so the closed loop hands out its instances longest-last-time first (nmpc_loop_step); level = position of the count's top bit.
-__global__ void nmpc_classify_prev_kernel(int B, const nmpc_status *prev, unsigned char *cls)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const unsigned n = prev[b].reserved;
-    const int lvl = n < 32u ? 0 : (31 - __clz((int)n)) - 4;      // 32..63 passes -> 1, 64..127 -> 2, ...
-    cls[b] = (unsigned char)(lvl > SCHED_LEVELS - 1 ? SCHED_LEVELS - 1 : lvl);
-}
-
-// stable partition of 0..B-1 by level (highest first); one block, deterministic
-__global__ void nmpc_order_kernel(int B, const unsigned char *cls, int *order)
-{
-    __shared__ int cnt[SCHED_LEVELS][1024];
-    const int t = threadIdx.x, nt = blockDim.x;
-    const int chunk = (B + nt - 1) / nt;
-    const int lo = t * chunk < B ? t * chunk : B, hi = lo + chunk < B ? lo + chunk : B;
-    int c[SCHED_LEVELS];
-#pragma unroll
-    for (int k = 0; k < SCHED_LEVELS; ++k) c[k] = 0;
-    for (int i = lo; i < hi; ++i) {
-#pragma unroll
-        for (int k = 0; k < SCHED_LEVELS; ++k) c[k] += cls[i] == k;
-    }
-#pragma unroll
-    for (int k = 0; k < SCHED_LEVELS; ++k) cnt[k][t] = c[k];
-    __syncthreads();
-    for (int off = 1; off < nt; off <<= 1) {            // inclusive scans, one per level
-        int v[SCHED_LEVELS];
-#pragma unroll
-        for (int k = 0; k < SCHED_LEVELS; ++k) v[k] = t >= off ? cnt[k][t - off] : 0;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < SCHED_LEVELS; ++k) cnt[k][t] += v[k];
-        __syncthreads();
-    }
-    int pos[SCHED_LEVELS], base = 0;                    // write cursor of this chunk inside each level's segment
-#pragma unroll
-    for (int k = SCHED_LEVELS - 1; k >= 0; --k) {
-        pos[k] = base + cnt[k][t] - c[k];
-        base += cnt[k][nt - 1];
-    }
-    for (int i = lo; i < hi; ++i) {
-        const int k = cls[i];
-#pragma unroll
-        for (int j = 0; j < SCHED_LEVELS; ++j) if (k == j) order[pos[j]++] = i;
-    }
-}
-}  // namespace nmpc
+#include "nmpc_order.h"
 
 // =================================================================================================
 // C ABI (include/nmpc_solver.h)
@@ -951,7 +51,9 @@ struct nmpc_handle {
     int sched_mode;            // step-aside scheduling (NMPC_SCHED=0 switches it off); long instances time-share beyond sched_theta x resident waves (NMPC_SCHED_THETA)
     double sched_theta, sched_cold;
     int team_owners_forced;    // experiments (NMPC_TEAM_OWNERS): waves per workgroup that take instances, 0 = automatic
-    int team_help;             // experiments (NMPC_TEAM_HELP=0): helpers never asked
+    bool team_help;            // experiments (NMPC_TEAM_HELP=0): helpers never asked
+    int waves_per_cu;          // experiments (NMPC_WAVES_PER_CU): resident waves per CU the launch is sized for, 0 = all that fit
+    int dbg;                   // experiments (NMPC_DEBUG_PRIO): KArgs.dbg
     double cull_radius;        // eval_psi CULL (NMPC_CULL_RADIUS)
     double *d_park;            // parked solver states, allocated on first use
     int *d_pool;
@@ -1027,6 +129,31 @@ static int fail(nmpc_handle *h, int code, const char *what, hipError_t e = hipSu
 
 static LdsMap make_map(const nmpc_problem &pb, int P) { return nmpc::lds_layout(pb.N, pb.nobs, pb.ndyn, P); }
 
+// The knobs of the experiments build (csrc/variants/libnmpc_experiments.so), read once into a new handle: tests use them to check that
+// every setting gives the same bits, scripts to measure.  The shipped library reads no environment.
+static void read_knobs([[maybe_unused]] nmpc_handle *h)
+{
+#ifdef NMPC_EXPERIMENTS
+    auto ival = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
+    auto flag = [](const char *name, bool &v) { if (const char *e = getenv(name)) v = atoi(e) != 0; };
+    auto pos = [](const char *name, double &v) { if (const char *e = getenv(name)) { const double x = atof(e); if (x > 0.0) v = x; } };
+    if (const char *e = getenv("NMPC_SHAPE"); e && !strcmp(e, "any")) h->shape_default = h->shape_nobs50 = h->shape_n40 = false;   // run-time-shape kernel
+    ival("NMPC_PARK_MIN", h->park_min);          // 0 switches the slot migration off
+    ival("NMPC_PARK_DEPTH", h->park_depth);
+    flag("NMPC_LOOP_ORDER_PREV", h->loop_order_prev);
+    ival("NMPC_SCHED", h->sched_mode);
+    pos("NMPC_SCHED_THETA", h->sched_theta);
+    pos("NMPC_SCHED_COLD", h->sched_cold);
+    pos("NMPC_CULL_RADIUS", h->cull_radius);
+    flag("NMPC_TEAM_HELP", h->team_help);
+    flag("NMPC_ORDER", h->use_order);            // 0 = instances in index order
+    int owners = 0; ival("NMPC_TEAM_OWNERS", owners);
+    if (owners >= 1 && owners <= nmpc::TEAM_WAVES) h->team_owners_forced = owners;
+    ival("NMPC_WAVES_PER_CU", h->waves_per_cu);  // (nmpc_new keeps it only if it is a whole number of teams that fit)
+    ival("NMPC_DEBUG_PRIO", h->dbg);
+#endif
+}
+
 int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int max_batch, nmpc_handle **out)
 {
     if (!pb || !out || max_batch < 1) return NMPC_ERR_BAD_ARG;
@@ -1058,11 +185,6 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
     h->shape_nobs50 = pb->N == nmpc::ShapeNobs50::N && pb->nobs == nmpc::ShapeNobs50::NOBS &&
                       pb->ndyn == nmpc::ShapeNobs50::NDYN;
     h->shape_n40 = pb->N == nmpc::ShapeN40::N && pb->nobs == nmpc::ShapeN40::NOBS && pb->ndyn == nmpc::ShapeN40::NDYN;
-#ifdef NMPC_EXPERIMENTS      // (the experiments build, csrc/variants/libnmpc_experiments.so: tests and scripts only -- the shipped library reads no environment)
-    if (const char *env = getenv("NMPC_SHAPE")) {              // force the run-time-shape kernel
-        if (!strcmp(env, "any")) h->shape_default = h->shape_nobs50 = h->shape_n40 = false;
-    }
-#endif
     h->map = make_map(*pb, h->P == 40 ? 64 : h->P);      // (P = 40: the kernels compute their own map, nmpc_solve_hyb2.h)
     h->d_queue = nullptr;
     h->d_park = nullptr; h->d_pool = nullptr; h->d_pool_ctr = nullptr;
@@ -1073,24 +195,13 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
     h->sched_mode = 1; h->sched_theta = h->P == 20 ? 0.5 : 0.8;
     h->sched_cold = 0.4;
     h->team_owners_forced = 0;
-    h->team_help = 1;
+    h->team_help = true; h->waves_per_cu = 0; h->dbg = 0;
     // culling radius: what the input bounds let the robot travel in a horizon, plus a margin (any value is exact: an evaluation
     // with a stage beyond it scans every circle); NMPC_CULL_RADIUS overrides it (tests use 0.5 m: the fall-back runs all the time)
     h->cull_radius = 1.1 * pb->N * pb->ts * fmax(fabs(pb->vmin), fabs(pb->vmax));
     h->use_order = true;
     h->order_hint = nullptr;
-#ifdef NMPC_EXPERIMENTS      // knobs of the experiments build: tests use them to check that every setting gives the same bits, scripts to measure
-    if (const char *env = getenv("NMPC_PARK_MIN")) h->park_min = atoi(env);       // 0 switches the slot migration off
-    if (const char *env = getenv("NMPC_PARK_DEPTH")) h->park_depth = atoi(env);
-    if (const char *env = getenv("NMPC_LOOP_ORDER_PREV")) h->loop_order_prev = atoi(env) != 0;
-    if (const char *env = getenv("NMPC_SCHED")) h->sched_mode = atoi(env);
-    if (const char *env = getenv("NMPC_SCHED_THETA")) { const double v = atof(env); if (v > 0.0) h->sched_theta = v; }
-    if (const char *env = getenv("NMPC_SCHED_COLD")) { const double v = atof(env); if (v > 0.0) h->sched_cold = v; }
-    if (const char *env = getenv("NMPC_CULL_RADIUS")) { const double v = atof(env); if (v > 0.0) h->cull_radius = v; }
-    if (const char *env = getenv("NMPC_TEAM_HELP")) h->team_help = atoi(env) != 0;
-    if (const char *env = getenv("NMPC_ORDER")) h->use_order = atoi(env) != 0;      // 0 = instances in index order
-    if (const char *env = getenv("NMPC_TEAM_OWNERS")) { const int v = atoi(env); if (v >= 1 && v <= nmpc::TEAM_WAVES) h->team_owners_forced = v; }
-#endif
+    read_knobs(h);
     h->d_order = nullptr;
     h->d_cls = nullptr;
     h->d_p = h->d_u = h->d_y0 = h->d_c0 = h->d_yout = h->d_psi = h->d_grad = h->d_F1 = h->d_F2 = nullptr;
@@ -1135,12 +246,7 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_eval2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) { nmpc_free(h); return NMPC_ERR_HIP; }
     }
-#ifdef NMPC_EXPERIMENTS
-    if (const char *env = getenv("NMPC_WAVES_PER_CU")) {
-        const int v = atoi(env);
-        if (v >= 1 && v <= per_cu && v % nmpc::TEAM_WAVES == 0) per_cu = v;
-    }
-#endif
+    if (h->waves_per_cu >= 1 && h->waves_per_cu <= per_cu && h->waves_per_cu % nmpc::TEAM_WAVES == 0) per_cu = h->waves_per_cu;
     if (per_cu < 1) per_cu = 1;
     h->grid_cap = prop.multiProcessorCount * per_cu;
     *out = h;
@@ -1180,9 +286,7 @@ static void fill_args(const nmpc_handle *h, KArgs &a, int B)
     a.n_p = nmpc_n_p(&h->pb); a.n_u = nmpc_n_u(&h->pb); a.n1 = nmpc_n1(&h->pb); a.n2 = nmpc_n2(&h->pb);
     a.queue = h->d_queue;
     a.inv_ts = 1.0 / h->pb.ts;
-#ifdef NMPC_EXPERIMENTS
-    if (const char *env = getenv("NMPC_DEBUG_PRIO")) a.dbg = atoi(env);
-#endif
+    a.dbg = h->dbg;
 }
 
 int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_u, const double *d_y0,
@@ -1667,28 +771,5 @@ int nmpc_test_divsqrt_host(nmpc_handle *h, int n, const double *a, const double 
     if (!b) return NMPC_ERR_BAD_ARG;
     return run_unary_test(h, n, a, b, out_div, out_sqrt, 1);
 }
-
-#ifdef NMPC_TL
-// experiments only (scripts/timeline.py)
-int nmpc_debug_timeline(long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(nmpc::nmpc_tl), 64 * 16 * sizeof(long long)) == hipSuccess ? NMPC_OK : NMPC_ERR_HIP; }
-#endif
-#ifdef NMPC_BBCOUNT
-// experiments only (scripts/bbcount.py): executions of every basic block of the instrumented kernel since the last reset
-int nmpc_debug_bbcount(unsigned int *out, int reset)
-{
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(nmpc::nmpc_bbcnt), 4096 * sizeof(unsigned int));
-    if (e == hipSuccess && reset) { static const unsigned int z[4096] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(nmpc::nmpc_bbcnt), z, sizeof z); }
-    return e == hipSuccess ? NMPC_OK : NMPC_ERR_HIP;
-}
-#endif
-#ifdef NMPC_WIN_STATS
-// experiments only (scripts/win_stats.py): windowed cross-track searches and how many of them fell back to the full scan
-int nmpc_debug_win_stats(unsigned long long *out, int reset)
-{
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(nmpc::nmpc_win_stats), 4 * sizeof(unsigned long long));      // windows: tried | fell back; obstacle certificates: tried | scanned
-    if (e == hipSuccess && reset) { const unsigned long long z[4] = {0, 0, 0, 0}; e = hipMemcpyToSymbol(HIP_SYMBOL(nmpc::nmpc_win_stats), z, sizeof z); }
-    return e == hipSuccess ? NMPC_OK : NMPC_ERR_HIP;
-}
-#endif
 
 }  // extern "C"

@@ -529,23 +529,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
         FlagBit running{fl, 1u << 14}, timed_out{fl, 1u << 15};
         f_start = true; running = true;
         FlagBit posted{fl, 1u << 16};                      // a request of the current iteration is open for the helpers
-#ifdef NMPC_TL
-        int tl_it = 0;                            // PANOC steps of this instance so far
-#endif
-        // -DNMPC_PROF2 (scripts/sections.py): cycles of this instance by section of the loop -- 0 phase handlers in front of the batch, 1 the batch
-        // of inner products, 2 exit test / L-BFGS update, 3 the recurrences and the direction, 4 envelope, trial points, request, 5 the
-        // evaluation, 6 the consumption of the trials.  Every mark drains the LDS queue, so the sum is a little above the plain build's time.
-#ifdef NMPC_PROF2
-        long long pf0 = 0, pf1 = 0, pf2 = 0, pf3 = 0, pf4 = 0, pf5 = 0, pf6 = 0, pf_last;
-        long long pe[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // NMPC_PROF2 == 2: the evaluation's own sections (eval_psi's NMPC_EVTICK marks), pe[7] = last mark
-#define NMPC_SEC_RAW(v) do { __builtin_amdgcn_sched_barrier(0); v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define NMPC_SEC(acc) do { long long t_; NMPC_SEC_RAW(t_); acc += t_ - pf_last; pf_last = t_; } while (0)
-        NMPC_SEC_RAW(pf_last);
-#elif defined(NMPC_MARKS)      // section markers in the ISA dump (scripts/isa_stats.py)
-#define NMPC_SEC(acc) do { __builtin_amdgcn_sched_barrier(0); asm volatile("; MARK S_" #acc); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define NMPC_SEC(acc) do { } while (0)
-#endif
+        NMPC_PROBE_STATE                                   // the instrumented builds' probes (nmpc_probe.h)
 
         // an iteration finished (raised by the consumption of a pass; the next pass starts the next step or returns from the inner solver).
         // Written out where it is raised: as a flag it was a test at the top of every pass and a set / clear pair per iteration.
@@ -606,10 +590,8 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
             }
             // ---------------------------------------------------------------- start of a PANOC step
             if (f_begin) lb_batch = true;
-#ifdef NMPC_TL
-            if (f_begin) { tl_it++; NMPC_TL_EV(tl_it, 0); }
-#endif
-            NMPC_SEC(pf0);
+            if (f_begin) { NMPC_TL_STEP(); NMPC_TL_EV(tl_it, 0); }
+            NMPC_SEC(0);
             // ---- the batch of inner products of this step (Gram-form L-BFGS, see the top of the file)
             double gU = 0.0, gs1 = 0.0, gs2 = 0.0, gy1 = 0.0, gy2 = 0.0;
             if (lb_batch) {
@@ -649,14 +631,10 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                 pk_gr = lane_scalar(gU, 32 + 11);                // <g, r>
                 norm_r = sqrt(nr2);
                 pk_last_fpr = norm_r;
-#ifdef NMPC_PROF2
-                { double keep = norm_r + gU; asm volatile("" : "+v"(keep)); }
-#endif
+                NMPC_SEC_KEEP(norm_r + gU);
             }
-            NMPC_SEC(pf1);
-#ifdef NMPC_TL
+            NMPC_SEC(1);
             if (lb_batch) { NMPC_TL_KEEP(norm_r + gU); NMPC_TL_EV(tl_it, 1); }
-#endif
             if (f_begin) {
                 f_begin = false;
                 bool exit_now = false;
@@ -726,10 +704,8 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                     }
                     // ---- d = H r over the tentative buffer ----
                     dv = rv; dw = rw;
-#ifdef NMPC_TL
                     NMPC_TL_EV(tl_it, 2);
-#endif
-                    NMPC_SEC(pf2);
+                    NMPC_SEC(2);
                     if (n_active > 0) {
                         // age k = lane & 15 of every row (lanes 10..15 idle along on slot 9; what they compute is never looked at)
                         const int pk_ = c16 < MAXMEM ? (n_head + c16 >= MAXMEM ? n_head + c16 - MAXMEM : n_head + c16) : MAXMEM - 1;
@@ -750,13 +726,9 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                         default: NMPC_GRAM_BOTH(9); break;
                         }
                     }
-#ifdef NMPC_PROF2
-                    { double keep = dv + dw; asm volatile("" : "+v"(keep)); }
-#endif
-#ifdef NMPC_TL
+                    NMPC_SEC_KEEP(dv + dw);
                     NMPC_TL_KEEP(dv + dw); NMPC_TL_EV(tl_it, 3);
-#endif
-                    NMPC_SEC(pf3);
+                    NMPC_SEC(3);
                     if (!fbe_ok) { pk_fbe_u = NMPC_FBE(uv, uw); fbe_ok = true; }
                     rhs_ls = pk_fbe_u - pk_sigma * nr2;
                     tau = 1.0; ls_n = 0;
@@ -769,17 +741,13 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                     if (k_help && __builtin_amdgcn_readfirstlane(ctl_load(ctl + CTL_HELPERS)) > 0) {
                         if (in && h == 0) { Lreq[t] = dbl2{uv, uw}; Lreq[24 + t] = dbl2{rv, rw}; Lreq[48 + t] = dbl2{dv, dw}; }
                         if (lane == 0) { Lpar[15] = pen_c; Lpar[16] = cbar_inv; Lpar[17] = gamma; }
-#ifdef NMPC_TL
-                        if (lane == 0) Lpar[22] = (double)tl_it;
+                        NMPC_TL_PUBLISH(Lpar);
                         NMPC_TL_EV(tl_it, 4);
-#endif
                         team_seq = team_seq >= 0xffff0u ? 1u : team_seq + 1u;
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                         __builtin_amdgcn_wave_barrier();
                         if (lane == 0) ctl_store(ctl + CTL_CLAIM + wid, (int)(team_seq << 8));
-#ifdef NMPC_TL
                         NMPC_TL_EV(tl_it, 5);
-#endif
                         posted = true;
                     }
                 }
@@ -834,13 +802,9 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                 else if (lvl == 2u) __builtin_amdgcn_s_setprio(2);
                 else if (lvl >= 3u) __builtin_amdgcn_s_setprio(3);
             }
-            NMPC_SEC(pf4);
-#ifdef NMPC_TL
+            NMPC_SEC(4);
             if (state == D_ITER) NMPC_TL_EV(tl_it, 6);
-#endif
-#ifdef NMPC_MARKS
-            asm volatile("; MARK 10");
-#endif
+            NMPC_MARK_LOOSE(10);
             const dbl2 ycur = *Ly;
             const double yv = ycur.x, yw = ycur.y;
             // query points: state layout -> evaluation layout (transport area; LDS serves the accesses of a wave in order)
@@ -849,23 +813,13 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
             const dbl2 zq_ = *zrd, zp_ = *zpv;
             const double zv = zq_.x, zw = zq_.y;
             const EvX evx = {zp_.x, zp_.y, zmine, znext};
-#if defined(NMPC_PROF2) && NMPC_PROF2 == 2
-            NMPC_SEC_RAW(pe[7]);
-            eval_psi<PE, SH, false, CULL, WIN, true>(a, L, f2off, lane, te, zv, zw, pen_c, cbar_inv, yv, yw, *Lvr, dyn, need_grad, psi, pen, egv, egw, eav, eaw, near, &ws, OBSC ? &oc : nullptr, pe, &ek, &evx);
-#else
-            eval_psi<PE, SH, false, CULL, WIN, true>(a, L, f2off, lane, te, zv, zw, pen_c, cbar_inv, yv, yw, *Lvr, dyn, need_grad, psi, pen, egv, egw, eav, eaw, near, &ws, OBSC ? &oc : nullptr, nullptr, &ek, &evx);
-#endif
+            NMPC_EVAL_START();
+            eval_psi<PE, SH, false, CULL, WIN, true>(a, L, f2off, lane, te, zv, zw, pen_c, cbar_inv, yv, yw, *Lvr, dyn, need_grad, psi, pen, egv, egw, eav, eaw, near, &ws, OBSC ? &oc : nullptr, NMPC_EVAL_PE, &ek, &evx);
             *zmine = dbl2{egv, egw};                 // gradients: evaluation layout -> state layout (NMPC_FETCH_GRAD)
-#ifdef NMPC_PROF2
-            { double keep = psi + egv; asm volatile("" : "+v"(keep)); }
-#endif
-            NMPC_SEC(pf5);
-#ifdef NMPC_TL
+            NMPC_SEC_KEEP(psi + egv);
+            NMPC_SEC(5);
             if (state == D_ITER) { NMPC_TL_KEEP(psi + egv); NMPC_TL_EV(tl_it, 7); }
-#endif
-#ifdef NMPC_MARKS
-            asm volatile("; MARK 11");
-#endif
+            NMPC_MARK_LOOSE(11);
             const double psiA = point_scalar(psi, 0), psiB = point_scalar(psi, 1), psiC = point_scalar(psi, 2);
             // one trial of the current direction: psi, grad psi were evaluated by query point K at step tau
             // (Measured and not taken: the envelopes of all three points formed in the evaluation layout right after the evaluation -- as the
@@ -939,9 +893,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                         if (k_lsf == 1) *Lgk = dbl2{gv, gw};
                         NMPC_TAKE_TRIAL(psiB, src1);                     // tau = 1
                         if (rejected) NMPC_TAKE_TRIAL(psiC, src2);       // tau = 1/2
-#ifdef NMPC_TL
                         NMPC_TL_KEEP(lhs + hv); NMPC_TL_EV(tl_it, 8);
-#endif
                         if (posted) {
                             // tasks 0..2 of the request hold trials ls_n = 2 + 3k .. 4 + 3k.  A task a helper has claimed is
                             // waited for and consumed in order; the first one nobody has claimed is closed (with everything
@@ -978,9 +930,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                                     }
                                     hid = __builtin_amdgcn_readfirstlane(hid);
                                 }
-#ifdef NMPC_TL
                                 if (k == 0) NMPC_TL_EV(tl_it, 9);
-#endif
                                 if (hid < 0) break;
                                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                                 n_pass++;                                // the pass these three trials would have cost this wave
@@ -1020,9 +970,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                             if (rejected && have_prev) {                 // going on alone: the state holds the last rejected trial's gradient
                                 gv = in ? prev_g.x : 0.0; gw = in ? prev_g.y : 0.0;
                             }
-#ifdef NMPC_TL
                             NMPC_TL_KEEP(uv + pv + gv + hv); NMPC_TL_EV(tl_it, 10);
-#endif
                             posted = false;
                             if (lane == 0) ctl_store(ctl + CTL_CLAIM + wid, 0);      // the request is over
                         }
@@ -1121,10 +1069,8 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                     }
                 }
             }
-#ifdef NMPC_PROF2
-            { double keep = uv + gv + hv + cost; asm volatile("" : "+v"(keep)); }
-#endif
-            NMPC_SEC(pf6);
+            NMPC_SEC_KEEP(uv + gv + hv + cost);
+            NMPC_SEC(6);
         }
 
         // ------------------------------------------------------------------ parked: state out, into the pool
@@ -1179,17 +1125,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
                 s.cost = (double)__builtin_amdgcn_s_memrealtime();
                 s.delta_y_norm_over_c = Lpar[13]; s.penalty = Lpar[14];
             }
-#ifdef NMPC_PROF2
-            s.last_problem_norm_fpr = (double)pf0; s.delta_y_norm_over_c = (double)pf1; s.f2_norm = (double)pf2;
-            s.penalty = (double)pf3; s.cost = (double)pf4; s.solve_time_ms = (double)pf5;
-            s.num_cost_evals = (uint32_t)(pf6 / 64);
-#if NMPC_PROF2 == 2
-            // rollout | stage cost + cross-track | accelerations, ALM term, cost sum | touched obstacles + adjoint head | adjoint sweep | circle scan | ellipse scan
-            s.last_problem_norm_fpr = (double)pe[0]; s.delta_y_norm_over_c = (double)pe[1]; s.f2_norm = (double)pe[2];
-            s.penalty = (double)pe[3]; s.cost = (double)pe[4]; s.solve_time_ms = (double)pe[5];
-            s.num_cost_evals = (uint32_t)(pe[6] / 64);
-#endif
-#endif
+            NMPC_PROBE_STATUS(s);
             a.st[inst] = s;
         }
         if (k_dbg == 0) __builtin_amdgcn_s_setprio(0);
@@ -1226,10 +1162,8 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
         got = __builtin_amdgcn_readfirstlane(got);
         if (got < 0) { __builtin_amdgcn_s_sleep(2); continue; }
         const int w = got >> 28, k = got & 0xff;
-#ifdef NMPC_TL
-        const int tl_h = k == 0 ? (int)((lds_double *)lds + w * slice)[mp.par + 22] : -1;
+        NMPC_TL_HELPER((lds_double *)lds + w * slice, k)
         NMPC_TL_EV(tl_h, 11);
-#endif
         const int seq = (got & 0x0fffffff) >> 8;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         // the owner's slice: tables of its instance, multipliers, reference speeds, the request
@@ -1253,13 +1187,9 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             if (inst_w != ws_inst || inst_w < 0) { ws_inst = inst_w; ws_h.mo2 = 0.0; oc_h.m2 = 0.0; }
         }
-#ifdef NMPC_TL
         NMPC_TL_KEEP(zv + zw); NMPC_TL_EV(tl_h, 12);
-#endif
         eval_psi<PE, SH, false, CULL, WIN>(a, Lw, f2off, lane, te, zv, zw, c_w, cbar_w, y_w.x, y_w.y, vref_w, dyn_w, true, psi, pen, egv, egw, eav, eaw, near_w, &ws_h, OBSC ? &oc_h : nullptr, nullptr, &ek);
-#ifdef NMPC_TL
         NMPC_TL_KEEP(psi + egv); NMPC_TL_EV(tl_h, 13);
-#endif
         {                                   // the owner moved on meanwhile: the scans may have seen half-rewritten tables
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             if (__builtin_amdgcn_readfirstlane(ctl_load(ctl + CTL_INST + w)) != ws_inst) { ws_inst = -1; ws_h.mo2 = 0.0; oc_h.m2 = 0.0; }
@@ -1278,9 +1208,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) ctl_store(ctl + CTL_DONE + (w * 3 + k) * TEAM_WAVES + wid, seq);
-#ifdef NMPC_TL
         NMPC_TL_EV(tl_h, 14);
-#endif
     }
 }
 #undef pk_eps_nu

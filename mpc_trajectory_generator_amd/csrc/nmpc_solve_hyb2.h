@@ -289,9 +289,7 @@ __device__ __forceinline__ void eval_psi2(const KArgs &a, lds_double *L, const L
                 NMPC2_WINDOW(b, bib, i0b, ws[1], sure_b);
 #undef NMPC2_WINDOW
                 full_scan = __any((ra & !sure_a) | (rb & !sure_b));
-#ifdef NMPC_WIN_STATS
-                if (lane == 0) { atomicAdd(&nmpc_win_stats[0], 1ull); if (full_scan) atomicAdd(&nmpc_win_stats[1], 1ull); }
-#endif
+                NMPC_WIN_COUNT(0, full_scan);
                 if (full_scan) {            // the full scan measures the clearance of the windows around what the old windows found nearest
                     i0a = NMPC2_CLAMP_WIN(bia); i0b = NMPC2_CLAMP_WIN(bib);
                     best = d2s(__builtin_inf()); bia = bib = 0;
@@ -390,9 +388,7 @@ __device__ __forceinline__ void eval_psi2(const KArgs &a, lds_double *L, const L
             act_dyn = (unsigned)__builtin_amdgcn_readfirstlane(oc->act_dyn);
             scan = false;
         }
-#ifdef NMPC_WIN_STATS
-        if (lane == 0) { atomicAdd(&nmpc_win_stats[2], 1ull); if (scan) atomicAdd(&nmpc_win_stats[3], 1ull); }
-#endif
+        NMPC_WIN_COUNT(2, scan);
     }
     if (scan) {
         D2 mg = d2s(__builtin_inf());
@@ -784,11 +780,6 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
             nu = (int)pks[8]; inner_total = (unsigned)pks[9]; n_cost = (unsigned)pks[10]; n_grad = (unsigned)pks[11]; n_pass = (unsigned)pks[12];
             t_start = (long long)pks[13]; long_counted = pks[15] != 0.0; q_pass = n_pass;
         }
-#if defined(NMPC_MARKS)     // section markers in the ISA dump (hipcc -S -DNMPC_MARKS; scripts/isa_stats.py)
-#define NMPC2_TK(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("; MARK " #i); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define NMPC2_TK(i) do { } while (0)
-#endif
 
         for (;;) {
             bool lb_batch = false;                     // this pass starts with the batch of inner products (f_back, f_begin)
@@ -1074,7 +1065,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
             double psi, pen;
             D2 egv = d2s(0.0), egw = d2s(0.0), eav, eaw;
             n_pass++;
-            NMPC2_TK(0);
+            NMPC_MARK(0);
             // query points: state layout -> LDS -> evaluation layout (X of half 0 | X of half 1 | Y)
             if (t < H2_ENT) {
                 st4<H2_ENT>(Pts + 2 * H2_ENT * (h), t, xv, xw);
@@ -1084,13 +1075,13 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
             D2 zv, zw, yv, yw;
             ld4<H2_ENT>(Pts + 2 * H2_ENT * (q), te, zv, zw);
             ld4<H2_COLS>(Cy, te, yv, yw);
-            NMPC2_TK(1);
+            NMPC_MARK(1);
             eval_psi2<SH, false, NMPC_WIN2>(a, L, mp, f2off, lane, te, zv, zw, pen_c, cbar_inv, yv, yw, need_grad, psi, pen, egv, egw, eav, eaw, ws, &oc);
-            NMPC2_TK(2);
+            NMPC_MARK(2);
             if (need_grad) st4<H2_ENT>(Grd + 2 * H2_ENT * (q), te, egv, egw);
             NMPC_WAVE_SYNC();
             const double psiA = point_scalar(psi, 0), psiB = point_scalar(psi, 1), psiC = point_scalar(psi, 2);
-            NMPC2_TK(3);
+            NMPC_MARK(3);
 #define NMPC2_TAKE_TRIAL(PSI, K) NMPC2_TAKE_TRIAL_(PSI, NMPC2_LOAD_GRAD(Grd + 2 * (K) * H2_ENT, gv, gw))
 #define NMPC2_TAKE_TRIAL_(PSI, FETCH)                                                  \
             do {                                                                       \
@@ -1418,7 +1409,6 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
     }
 }
 
-#undef NMPC2_TK
 #undef NMPC2_HALF_STEP
 #undef NMPC2_FBE
 #undef NMPC2_LOAD_GRAD

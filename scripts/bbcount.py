@@ -317,7 +317,7 @@ def report(fn, top=40, quiet=False):
     res["top_blocks"] = []
     for w, c, b in rows[:top]:
         own = sorted((k.split("|")[0] for k in b["lines"]), key=lambda s: (s.split(":")[0], int(s.split(":")[1])))
-        hyb = [s for s in own if s.startswith("nmpc_solve_hyb")] or [s for s in own if s.startswith("nmpc_kernels")] or own
+        hyb = [s for s in own if s.startswith("nmpc_solve_hyb")] or [s for s in own if s.startswith(("nmpc_eval", "nmpc_layout"))] or own
         res["top_blocks"].append({"block": b["label"], "executions_per_pass": round(c / passes, 3), "valu_per_pass": round(w / passes, 1),
                                   "static": b["classes"], "lines": (hyb[0] + " .. " + hyb[-1]) if hyb else ""})
     lines = sorted(by_line.items(), key=lambda kv: -kv[1][0])[:top]
