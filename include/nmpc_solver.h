@@ -184,8 +184,8 @@ int nmpc_eval_batch_host(nmpc_handle *h, int B, const double *p, const double *u
                          const double *y, double *psi, double *grad, double *F1, double *F2);
 
 /* ---- the receding-horizon loop on device ------------------------------------------------------
- * B robots follow one route in lock step; one step = assemble p (the body of the reference's
- * PathGenerator.run loop, src/path_generator.py:290-382), solve the batch warm-started from the
+ * B robots follow one route (or R routes, nmpc_loop_new_routes) in lock step; one step = assemble p
+ * (the body of the reference's PathGenerator.run loop, src/path_generator.py:290-382), solve the batch warm-started from the
  * previous controls and multipliers (mng.call, src/mpc/mpc_generator.py:206), advance the states
  * over num_steps_taken controls (src/mpc/mpc_generator.py:223-235) and evaluate the terminal test
  * (src/path_generator.py:397).  Nothing crosses PCIe between steps. */
@@ -214,6 +214,16 @@ typedef struct nmpc_loop nmpc_loop;
  * max_steps > 0 also records the trajectory on device. */
 int nmpc_loop_new(nmpc_handle *h, const nmpc_route *route, int B, const double *starts,
                   const int32_t *idx0, int K, const double *dyn, int max_steps, nmpc_loop **out);
+/* A fleet on R routes: robot b follows routes[route_of[b]] (route_of [B], values in [0, R); NULL only with
+ * R == 1, which is nmpc_loop_new).  Every field of nmpc_route is per route (tables, end, base_speed, radius,
+ * dyn_pad, weights), except num_steps_taken, which every route must share (the fleet moves in lock step).
+ * idx0[b] is checked against the n_ref of b's own route.  Everything else as nmpc_loop_new; the loop it
+ * returns is stepped, read and freed like one from nmpc_loop_new.  NMPC_ERR_BAD_ARG, with nothing allocated,
+ * for R < 1, route_of NULL with R > 1, a route_of[b] out of range, an invalid route, routes that differ in
+ * num_steps_taken, or an idx0[b] outside its route. */
+int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const int32_t *route_of,
+                         int B, const double *starts, const int32_t *idx0, int K, const double *dyn,
+                         int max_steps, nmpc_loop **out);
 void nmpc_loop_free(nmpc_loop *l);
 /* Enqueues assemble -> solve -> advance on `stream`; does not synchronise. */
 int nmpc_loop_step(nmpc_loop *l, void *stream);

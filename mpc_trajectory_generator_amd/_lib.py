@@ -22,7 +22,7 @@ SYMBOLS = (
     "nmpc_ping", "nmpc_last_error", "nmpc_abi_version", "nmpc_experiments_build", "nmpc_kernel_name", "nmpc_solve_batch_device",
     "nmpc_solve_batch_host", "nmpc_last_batch_ms", "nmpc_eval_batch_device", "nmpc_eval_batch_host",
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
-    "nmpc_loop_new", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
+    "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
     "nmpc_loop_trajectory",
 )
 
@@ -256,6 +256,8 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_test_divsqrt_host.argtypes = [vp, C.c_int, dp, dp, dp, dp]
     lib.nmpc_loop_new.argtypes = [vp, C.POINTER(NmpcRoute), C.c_int, dp, C.POINTER(C.c_int32), C.c_int, dp, C.c_int,
                                   C.POINTER(vp)]
+    lib.nmpc_loop_new_routes.argtypes = [vp, C.POINTER(NmpcRoute), C.c_int, C.POINTER(C.c_int32), C.c_int, dp, C.POINTER(C.c_int32),
+                                         C.c_int, dp, C.c_int, C.POINTER(vp)]
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_loop_step.argtypes = [vp, vp]

@@ -564,24 +564,41 @@ struct nmpc_loop {
     nmpc_handle *h;
     nmpc::LoopArgs a;            // device pointers and constants; t / dyn_in / dyn_out / traj_row change per step
     int steps, max_steps;
-    double *d_tab;               // route tables, one allocation
+    double *d_tab;               // every route's tables, one allocation
+    nmpc::LoopRoute *d_routes;   // [R]
+    int *d_route_of;             // [B]
     double *d_dynpar, *d_state, *d_last_u, *d_dyn[2], *d_P, *d_U, *d_Y, *d_traj;
     int *d_idx;
     unsigned char *d_done;
     nmpc_status *d_st;
 };
 
-int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *starts, const int32_t *idx0, int K,
-                  const double *dyn, int max_steps, nmpc_loop **out)
+static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
 {
-    if (!h || !r || !out || !starts) return NMPC_ERR_BAD_ARG;
+    return r->n_ref >= 1 && r->n_vert >= 0 && r->n_brake >= 1 && r->num_steps_taken >= 1 && r->num_steps_taken <= h->pb.N &&
+           r->x_ref && r->y_ref && r->theta_ref && r->brake_vel && r->brake_dist && (r->n_vert == 0 || r->vert_xy);
+}
+
+int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const int32_t *route_of, int B, const double *starts,
+                         const int32_t *idx0, int K, const double *dyn, int max_steps, nmpc_loop **out)
+{
+    if (!h || !routes || !out || !starts) return NMPC_ERR_BAD_ARG;
     if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
     if (B < 1 || B > h->max_batch || K < 0 || K > h->pb.ndyn || (K > 0 && !dyn) || max_steps < 0)
         return fail(h, NMPC_ERR_BAD_ARG, "bad loop arguments");
-    if (idx0) for (int b = 0; b < B; ++b) if (idx0[b] < 0 || idx0[b] >= r->n_ref) return fail(h, NMPC_ERR_BAD_ARG, "idx0 out of range");
-    if (r->n_ref < 1 || r->n_vert < 0 || r->n_brake < 1 || r->num_steps_taken < 1 || r->num_steps_taken > h->pb.N ||
-        !r->x_ref || !r->y_ref || !r->theta_ref || !r->brake_vel || !r->brake_dist || (r->n_vert > 0 && !r->vert_xy))
-        return fail(h, NMPC_ERR_BAD_ARG, "bad route");
+    if (R < 1) return fail(h, NMPC_ERR_BAD_ARG, "R < 1: no route");
+    if (!route_of && R > 1) return fail(h, NMPC_ERR_BAD_ARG, "route_of == NULL with R > 1");
+    if (route_of) for (int b = 0; b < B; ++b) if (route_of[b] < 0 || route_of[b] >= R) return fail(h, NMPC_ERR_BAD_ARG, "route_of out of range");
+    size_t ntab = 0;
+    for (int i = 0; i < R; ++i) {
+        const nmpc_route *r = routes + i;
+        if (!route_ok(h, r)) return fail(h, NMPC_ERR_BAD_ARG, R == 1 ? "bad route" : ("bad route " + std::to_string(i)).c_str());
+        if (r->num_steps_taken != routes[0].num_steps_taken)
+            return fail(h, NMPC_ERR_BAD_ARG, "routes differ in num_steps_taken (the fleet moves in lock step)");
+        ntab += 3 * (size_t)r->n_ref + 2 * (size_t)r->n_vert + 2 * (size_t)r->n_brake;
+    }
+    if (ntab > 0x7fffffff) return fail(h, NMPC_ERR_BAD_ARG, "route tables too large");
+    if (idx0) for (int b = 0; b < B; ++b) if (idx0[b] < 0 || idx0[b] >= routes[route_of ? route_of[b] : 0].n_ref) return fail(h, NMPC_ERR_BAD_ARG, "idx0 out of range");
     HIP_TRY(h, hipSetDevice(h->device));
     nmpc_loop *l = new nmpc_loop();
     std::memset(l, 0, sizeof(*l));
@@ -590,13 +607,12 @@ int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *star
     nmpc::LoopArgs &a = l->a;
     a.B = B; a.N = h->pb.N; a.nobs = h->pb.nobs; a.ndyn = h->pb.ndyn; a.K = K;
     a.n_p = nmpc_n_p(&h->pb); a.n_u = nmpc_n_u(&h->pb);
-    a.n_ref = r->n_ref; a.n_vert = r->n_vert; a.n_brake = r->n_brake; a.s = r->num_steps_taken; a.t = 0;
-    a.ts = h->pb.ts; a.base = r->base_speed; a.radius = r->radius; a.pad = r->dyn_pad;
-    for (int i = 0; i < 3; ++i) a.end[i] = r->end[i];
-    for (int i = 0; i < 10; ++i) a.w[i] = r->weights[i];
-    const size_t n1 = nmpc_n1(&h->pb), ntab = 3 * (size_t)r->n_ref + 2 * (size_t)r->n_vert + 2 * (size_t)r->n_brake;
-    const size_t ndynrow = (size_t)a.ndyn * a.N * 5;
+    a.s = routes[0].num_steps_taken; a.t = 0;
+    a.ts = h->pb.ts;
+    const size_t n1 = nmpc_n1(&h->pb), ndynrow = (size_t)a.ndyn * a.N * 5;
     hipError_t e = hipMalloc((void **)&l->d_tab, (ntab ? ntab : 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&l->d_routes, (size_t)R * sizeof(nmpc::LoopRoute));
+    if (e == hipSuccess) e = hipMalloc((void **)&l->d_route_of, (size_t)B * sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void **)&l->d_dynpar, ((size_t)B * (K ? K : 1)) * 10 * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&l->d_state, (size_t)B * 3 * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&l->d_last_u, (size_t)B * 2 * 8);
@@ -611,19 +627,28 @@ int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *star
     if (e == hipSuccess && max_steps > 0)
         e = hipMalloc((void **)&l->d_traj, ((size_t)max_steps * a.s + 1) * B * 3 * 8);
     if (e != hipSuccess) { nmpc_loop_free(l); return fail(h, NMPC_ERR_HIP, "nmpc_loop_new: hipMalloc", e); }
-    // route tables: x_ref | y_ref | theta_ref | vertices | brake velocities | brake distances
+    // route tables, route after route: x_ref | y_ref | theta_ref | vertices | brake velocities | brake distances
     std::vector<double> tab(ntab);
-    double *q = tab.data();
-    std::memcpy(q, r->x_ref, 8 * (size_t)r->n_ref); q += r->n_ref;
-    std::memcpy(q, r->y_ref, 8 * (size_t)r->n_ref); q += r->n_ref;
-    std::memcpy(q, r->theta_ref, 8 * (size_t)r->n_ref); q += r->n_ref;
-    if (r->n_vert) std::memcpy(q, r->vert_xy, 16 * (size_t)r->n_vert);
-    q += 2 * r->n_vert;
-    std::memcpy(q, r->brake_vel, 8 * (size_t)r->n_brake); q += r->n_brake;
-    std::memcpy(q, r->brake_dist, 8 * (size_t)r->n_brake);
-    e = hipMemcpy(l->d_tab, tab.data(), ntab * 8, hipMemcpyHostToDevice);
-    a.xr = l->d_tab; a.yr = a.xr + r->n_ref; a.thr = a.yr + r->n_ref; a.vert = a.thr + r->n_ref;
-    a.bv = a.vert + 2 * r->n_vert; a.bd = a.bv + r->n_brake;
+    std::vector<nmpc::LoopRoute> desc(R);
+    size_t off = 0;
+    for (int i = 0; i < R; ++i) {
+        const nmpc_route *r = routes + i;
+        nmpc::LoopRoute &d = desc[i];
+        std::memset(&d, 0, sizeof(d));
+        auto put = [&](const double *src, size_t n) { const int at = (int)off; if (n) std::memcpy(tab.data() + off, src, 8 * n); off += n; return at; };
+        d.xr = put(r->x_ref, r->n_ref); d.yr = put(r->y_ref, r->n_ref); d.thr = put(r->theta_ref, r->n_ref);
+        d.vert = put(r->vert_xy, 2 * (size_t)r->n_vert);
+        d.bv = put(r->brake_vel, r->n_brake); d.bd = put(r->brake_dist, r->n_brake);
+        d.n_ref = r->n_ref; d.n_vert = r->n_vert; d.n_brake = r->n_brake;
+        for (int k = 0; k < 3; ++k) d.end[k] = r->end[k];
+        d.base = r->base_speed; d.radius = r->radius; d.pad = r->dyn_pad;
+        for (int k = 0; k < 10; ++k) d.w[k] = r->weights[k];
+    }
+    std::vector<int> rof(B, 0);
+    if (route_of) for (int b = 0; b < B; ++b) rof[b] = route_of[b];
+    e = ntab ? hipMemcpy(l->d_tab, tab.data(), ntab * 8, hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(l->d_routes, desc.data(), (size_t)R * sizeof(nmpc::LoopRoute), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(l->d_route_of, rof.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess && K) e = hipMemcpy(l->d_dynpar, dyn, (size_t)B * K * 10 * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(l->d_state, starts, (size_t)B * 3 * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && l->d_traj) e = hipMemcpy(l->d_traj, starts, (size_t)B * 3 * 8, hipMemcpyHostToDevice);
@@ -640,17 +665,24 @@ int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *star
         e = hipMemcpy(l->d_dyn[0], pad.data(), pad.size() * 8, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) { nmpc_loop_free(l); return fail(h, NMPC_ERR_HIP, "nmpc_loop_new: initialisation", e); }
+    a.tab = l->d_tab; a.routes = l->d_routes; a.route_of = l->d_route_of;
     a.dynpar = l->d_dynpar; a.state = l->d_state; a.last_u = l->d_last_u; a.idx = l->d_idx;
     a.P = l->d_P; a.U = l->d_U; a.done = l->d_done; a.traj = l->d_traj; a.traj_row = 1;
     *out = l;
     return NMPC_OK;
 }
 
+int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *starts, const int32_t *idx0, int K,
+                  const double *dyn, int max_steps, nmpc_loop **out)
+{
+    return nmpc_loop_new_routes(h, r, 1, nullptr, B, starts, idx0, K, dyn, max_steps, out);
+}
+
 void nmpc_loop_free(nmpc_loop *l)
 {
     if (!l) return;
     (void)hipSetDevice(l->h->device);
-    (void)hipFree(l->d_tab); (void)hipFree(l->d_dynpar); (void)hipFree(l->d_state); (void)hipFree(l->d_last_u);
+    (void)hipFree(l->d_tab); (void)hipFree(l->d_routes); (void)hipFree(l->d_route_of); (void)hipFree(l->d_dynpar); (void)hipFree(l->d_state); (void)hipFree(l->d_last_u);
     (void)hipFree(l->d_dyn[0]); (void)hipFree(l->d_dyn[1]); (void)hipFree(l->d_P); (void)hipFree(l->d_U);
     (void)hipFree(l->d_Y); (void)hipFree(l->d_idx); (void)hipFree(l->d_done); (void)hipFree(l->d_st);
     (void)hipFree(l->d_traj);

@@ -1,4 +1,4 @@
-// nmpc_loop.h -- the receding-horizon loop on device: B robots following one route in lock step.
+// nmpc_loop.h -- the receding-horizon loop on device: B robots following R routes in lock step.
 //
 // Counterpart of the body of the reference's `PathGenerator.run` loop (src/path_generator.py:290-403:
 // closest reference sample in the sliding window :320-325, horizon padded with the end pose :326-341,
@@ -8,6 +8,9 @@
 // (src/mpc/mpc_generator.py:223-235).  One step = assemble p -> batched solve (warm start from the
 // previous controls and multipliers) -> advance; nothing crosses PCIe between steps.
 //
+// Routes: robot b follows routes[route_of[b]]; a route's tables live in one packed table at the offsets of
+// its descriptor.  One route (nmpc_loop_new) is the case R = 1 of the same kernels.
+//
 // Arithmetic: index selections (window arg-min, vertex window, braking-table filter) use the same
 // unfused IEEE operations as the host mirror (`trajectory.VectorizedRecedingHorizon`), so they are
 // bit-identical to it; sin / cos are the kernels' own sincos_cw (the mirror takes it as a hook).
@@ -15,12 +18,21 @@
 
 namespace nmpc {
 
-struct LoopArgs {
-    int B, N, nobs, ndyn, K, n_p, n_u, n_ref, n_vert, n_brake, s, t;
-    double ts, base, radius, pad;
+// one route: where its tables sit in LoopArgs::tab (in doubles) and its constants (nmpc_route)
+struct LoopRoute {
+    int xr, yr, thr, vert, bv, bd;          // x_ref | y_ref | theta_ref [n_ref], vertices [n_vert][2], brake vel / dist [n_brake]
+    int n_ref, n_vert, n_brake;
     double end[3];
+    double base, radius, pad;
     double w[10];
-    const double *xr, *yr, *thr, *vert, *bv, *bd;
+};
+
+struct LoopArgs {
+    int B, N, nobs, ndyn, K, n_p, n_u, s, t;
+    double ts;
+    const double *tab;        // every route's tables, packed
+    const LoopRoute *routes;  // [R]
+    const int *route_of;      // [B]
     const double *dynpar;     // [B][K][10]: p1x p1y p2x p2y freq rx ry angle | sinusoidal law (0 / 1) | atan2(p2 - p1)
     double *state;            // [B][3]
     double *last_u;           // [B][2]
@@ -59,7 +71,12 @@ __device__ __forceinline__ double linspace_at(double t0, double ts, int H, int i
 __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int N = a.N, n = a.n_ref, s = a.s;
+    // the robot's route: the same for the whole wave (read before any store, so that the loads can be scalar)
+    const LoopRoute &rt = a.routes[a.route_of[b]];
+    const double *xr = a.tab + rt.xr, *yr = a.tab + rt.yr, *thr = a.tab + rt.thr, *vert = a.tab + rt.vert;
+    const double *bv = a.tab + rt.bv, *bd = a.tab + rt.bd;
+    const int N = a.N, n = rt.n_ref, s = a.s, n_vert = rt.n_vert, n_brake = rt.n_brake;
+    const double base = rt.base, radius = rt.radius, pad = rt.pad, ex = rt.end[0], ey = rt.end[1], eth = rt.end[2];
     const double x = a.state[3 * b], y = a.state[3 * b + 1], th = a.state[3 * b + 2];
     double *p = a.P + (size_t)b * a.n_p;
     constexpr int NZ_ = 20;
@@ -67,13 +84,13 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
     // ---- static circles (path_generator.py:295-304 + visibility.py:141-148, look-back 0)
     {
         double *pc = p + NZ_ + N;
-        const int nv = a.n_vert;
+        const int nv = n_vert;
         int lb = 0, ub = nv;
         if (nv > a.nobs) {
             double best = __builtin_inf();
             int bj = 0x7fffffff;
             for (int j = lane; j < nv; j += 64) {
-                const double dx = a.vert[2 * j] - x, dy = a.vert[2 * j + 1] - y;
+                const double dx = vert[2 * j] - x, dy = vert[2 * j + 1] - y;
                 double d = sqrt(dx * dx + dy * dy);
                 if (d != d) d = -__builtin_inf();
                 if (d < best) { best = d; bj = j; }
@@ -86,9 +103,9 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
             const int j = lb + k;
             const bool ok = nv > 0 && j < ub;
             const int jj = j < nv ? j : (nv > 0 ? nv - 1 : 0);
-            pc[3 * k] = ok ? a.vert[2 * jj] : 0.0;
-            pc[3 * k + 1] = ok ? a.vert[2 * jj + 1] : 0.0;
-            pc[3 * k + 2] = ok ? a.radius : 0.0;
+            pc[3 * k] = ok ? vert[2 * jj] : 0.0;
+            pc[3 * k + 1] = ok ? vert[2 * jj + 1] : 0.0;
+            pc[3 * k + 2] = ok ? radius : 0.0;
         }
     }
     // ---- dynamic ellipses (path_generator.py:306-316; visibility.py:156-166,199-216)
@@ -126,7 +143,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
                         v = f == 0 ? qx + q[0] : qy + q[1];
                     }
                 } else {
-                    v = f == 2 ? q[5] + a.pad : (f == 3 ? q[6] + a.pad : q[7]);
+                    v = f == 2 ? q[5] + pad : (f == 3 ? q[6] + pad : q[7]);
                 }
             } else if (a.t == 0) {
                 v = din[e];                                    // padding block as initialised
@@ -149,7 +166,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
         double best = __builtin_inf();
         int bj = 0x7fffffff;
         for (int j = lb + lane; j < ub; j += 64) {
-            const double dx = a.xr[j] - x, dy = a.yr[j] - y;
+            const double dx = xr[j] - x, dy = yr[j] - y;
             double d = sqrt(dx * dx + dy * dy);
             if (d != d) d = -__builtin_inf();
             if (d < best) { best = d; bj = j; }
@@ -166,39 +183,39 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
         if (lane >= 3 && lane < 5) p[lane] = a.last_u[2 * b + lane - 3];
         if (lane >= 5 && lane < 8) {
             const int f = lane - 5;
-            p[lane] = far ? (f == 0 ? a.xr[jf] : (f == 1 ? a.yr[jf] : a.thr[jf])) : a.end[f];
+            p[lane] = far ? (f == 0 ? xr[jf] : (f == 1 ? yr[jf] : thr[jf])) : (f == 0 ? ex : (f == 1 ? ey : eth));
         }
         if (lane >= 8 && lane < 10) p[lane] = a.last_u[2 * b + lane - 8];
-        if (lane >= 10 && lane < 20) p[lane] = a.w[lane - 10];
+        if (lane >= 10 && lane < 20) p[lane] = rt.w[lane - 10];
     }
     // ---- horizon references (:326-341) and velocity reference with the braking profile (:343-361)
     {
         double *pv = p + NZ_, *pr = p + NZ_ + N + 3 * a.nobs + 5 * a.ndyn * N;
-        const bool brake = (double)(idx + N) >= (double)n - a.bd[0] / a.base;
+        const bool brake = (double)(idx + N) >= (double)n - bd[0] / base;
         const int nbase = n - idx - 1 < N ? n - idx - 1 : N;
-        const double ddx = x - a.end[0], ddy = y - a.end[1];
+        const double ddx = x - ex, ddy = y - ey;
         const double dist_to_goal = sqrt(ddx * ddx + ddy * ddy);
         for (int k = lane; k < N; k += 64) {
             const int j = idx + k;
             const bool ok = j < n;
             const int jj = ok ? j : n - 1;
-            pr[3 * k] = ok ? a.xr[jj] : a.end[0];
-            pr[3 * k + 1] = ok ? a.yr[jj] : a.end[1];
-            pr[3 * k + 2] = ok ? a.thr[jj] : a.end[2];
-            double v = a.base;
+            pr[3 * k] = ok ? xr[jj] : ex;
+            pr[3 * k + 1] = ok ? yr[jj] : ey;
+            pr[3 * k + 2] = ok ? thr[jj] : eth;
+            double v = base;
             if (brake) {
                 if (nbase == 0) {
                     // inside the last sample: the k-th braking entry whose distance is within reach (:347-351)
                     v = 0.0;
                     int cnt = 0;
-                    for (int i = 0; i < a.n_brake; ++i) {
-                        if (a.bd[i] <= dist_to_goal) {
-                            if (cnt == k) { v = a.bv[i]; break; }
+                    for (int i = 0; i < n_brake; ++i) {
+                        if (bd[i] <= dist_to_goal) {
+                            if (cnt == k) { v = bv[i]; break; }
                             ++cnt;
                         }
                     }
                 } else if (k >= nbase) {
-                    v = k - nbase < a.n_brake ? a.bv[k - nbase] : 0.0;
+                    v = k - nbase < n_brake ? bv[k - nbase] : 0.0;
                 }
             }
             pv[k] = v;
@@ -228,7 +245,8 @@ __global__ void nmpc_loop_advance_kernel(LoopArgs a)
     a.state[3 * b] = x; a.state[3 * b + 1] = y; a.state[3 * b + 2] = th;
     const double lv = u[2 * (a.s - 1)], lw = u[2 * (a.s - 1) + 1];
     a.last_u[2 * b] = lv; a.last_u[2 * b + 1] = lw;
-    a.done[b] = (fabs(x - a.end[0]) <= 0.05 && fabs(y - a.end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
+    const double *end = a.routes[a.route_of[b]].end;
+    a.done[b] = (fabs(x - end[0]) <= 0.05 && fabs(y - end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
 }
 
 }  // namespace nmpc

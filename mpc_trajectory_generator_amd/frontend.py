@@ -255,3 +255,22 @@ def random_routes(cfg: Config, scene: int, n: int, seed: int, min_length: float 
         th1 = math.atan2(path[-1][1] - path[-2][1], path[-1][0] - path[-2][0])
         out.append(harness.Route(cfg, (s[0], s[1], th0), (g[0], g[1], th1), path, pl.original_vertices(path)))
     return out
+
+
+def random_fleet(cfg: Config, scene: int, R: int, B: int, seed: int):
+    """A fleet of B robots on R routes of a scene, for ``DeviceRecedingHorizon`` / ``FleetRecedingHorizon``
+    -> (routes, route_of [B] int32, starts [B, 3], idx0 [B] int32).
+
+    ``random_routes(cfg, scene, R, seed)`` plans the routes; the robots are dealt to them as evenly as B allows
+    (every route gets a robot when B >= R), in an order drawn from the seed.  Robot b starts at a reference
+    sample idx0[b] of its own route (at least 25 samples before the end where the route is that long), with
+    N(0, 0.05^2) m noise in x and y and N(0, 0.1^2) in the heading."""
+    routes = random_routes(cfg, scene, R, seed)
+    rng = np.random.Generator(np.random.PCG64([seed, 1]))
+    route_of = rng.permutation(np.arange(B) % R).astype(np.int32)
+    n = np.array([len(r.x_ref) for r in routes])[route_of]
+    idx0 = rng.integers(0, np.maximum(1, n - 25)).astype(np.int32)
+    ref = [np.stack([r.x_ref, r.y_ref, r.theta_ref], axis=1) for r in routes]
+    base = np.stack([ref[r][i] for r, i in zip(route_of, idx0)]) if B else np.zeros((0, 3))
+    starts = base + np.stack([rng.normal(0, 0.05, B), rng.normal(0, 0.05, B), rng.normal(0, 0.1, B)], axis=1)
+    return routes, route_of, starts, idx0

@@ -10,6 +10,8 @@ what ``run`` starts from.
 
 ``BatchedRecedingHorizon`` is the batched counterpart for BASELINE config 4: B independent robots
 advance in lock step, one batched solve per step, controls and multipliers carried as warm starts.
+``FleetRecedingHorizon`` (host) and ``DeviceRecedingHorizon`` given a list of routes run a fleet whose
+robots follow routes of their own.
 """
 from __future__ import annotations
 
@@ -374,6 +376,112 @@ class VectorizedRecedingHorizon:
         return P, st
 
 
+class FleetRecedingHorizon:
+    """``VectorizedRecedingHorizon`` for a fleet on R routes: robot b follows ``routes[route_of[b]]``.
+
+    One ``VectorizedRecedingHorizon`` per route runs that route's robots (in fleet order); their rows are
+    scattered into fleet order, and one ``solve_fn(P, u0, y0) -> (U, Y, status)`` call covers the whole fleet
+    per step.  Each robot's quantities are therefore exactly those of the single-route mirror for its route.
+    ``dyn_obs``, ``sincos`` and ``sinus_object`` as in ``VectorizedRecedingHorizon``, ``dyn_obs`` in fleet
+    order; ``idx0`` = the reference sample each robot starts at, on its own route (default 0).
+    """
+
+    def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None):
+        self.routes = list(routes)
+        cfg = self.cfg = self.routes[0].cfg
+        self.B = B = len(starts)
+        self.route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
+        assert all(r.cfg is cfg or r.cfg == cfg for r in self.routes)
+        assert ((self.route_of >= 0) & (self.route_of < len(self.routes))).all()
+        starts = np.array(starts, dtype=np.float64).reshape(B, 3)
+        i0 = np.zeros(B, dtype=np.int64) if idx0 is None else np.asarray(idx0, dtype=np.int64).reshape(B)
+        self.parts = []                                           # (robots of the route in fleet order, its mirror)
+        for r, route in enumerate(self.routes):
+            ids = np.nonzero(self.route_of == r)[0]
+            if not len(ids):
+                continue
+            sub = VectorizedRecedingHorizon(route, starts[ids], None if dyn_obs is None else tuple(a[ids] for a in dyn_obs),
+                                            sincos=sincos, sinus_object=sinus_object)
+            sub.idx = i0[ids].copy()
+            self.parts.append((ids, sub))
+        self.t = 0
+        self.U = np.zeros((B, cfg.n_u))
+        self.Y = np.zeros((B, cfg.n1))
+
+    def _gather(self, field, shape, dtype=np.float64):
+        out = np.empty((self.B,) + shape, dtype=dtype)
+        for ids, sub in self.parts:
+            out[ids] = getattr(sub, field)
+        return out
+
+    @property
+    def state(self):
+        return self._gather("state", (3,))
+
+    @property
+    def last_u(self):
+        return self._gather("last_u", (self.cfg.nu,))
+
+    @property
+    def idx(self):
+        return self._gather("idx", (), np.int64)
+
+    @property
+    def done(self):
+        return self._gather("done", (), bool)
+
+    @property
+    def traj(self):
+        rows = []
+        for k in range(len(self.parts[0][1].traj)):
+            row = np.empty((self.B, 3))
+            for ids, sub in self.parts:
+                row[ids] = sub.traj[k]
+            rows.append(row)
+        return rows
+
+    def assemble(self):
+        P = np.empty((self.B, self.cfg.n_p))
+        for ids, sub in self.parts:
+            P[ids] = sub.assemble()
+        return P
+
+    def advance(self, U):
+        for ids, sub in self.parts:
+            sub.advance(U[ids])
+        self.t += self.cfg.num_steps_taken
+
+    def step(self, solve_fn):
+        P = self.assemble()
+        U, Y, st = solve_fn(P, self.U, self.Y)
+        self.U, self.Y = U, Y
+        self.advance(U)
+        return P, st
+
+
+def _fill_route(r, route: harness.Route, keep: list):
+    """Fill the ``nmpc_route`` struct ``r`` from ``route``; the arrays it points to are appended to ``keep``,
+    which must outlive the call that reads the struct."""
+    import ctypes as C
+    from . import _lib
+    cfg = route.cfg
+
+    def arr(v):
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        keep.append(a)
+        return _lib.as_dp(a)
+    vert = np.array(route.vertices, dtype=np.float64).reshape(-1, 2)
+    r.n_ref, r.n_vert, r.n_brake = len(route.x_ref), len(vert), len(route.brake_velocities)
+    r.num_steps_taken = cfg.num_steps_taken
+    r.x_ref, r.y_ref, r.theta_ref = arr(route.x_ref), arr(route.y_ref), arr(route.theta_ref)
+    r.vert_xy = arr(vert) if len(vert) else None
+    r.brake_vel, r.brake_dist = arr(route.brake_velocities), arr(route.brake_distances)
+    r.end = (C.c_double * 3)(*[float(v) for v in route.end])
+    r.base_speed, r.radius = float(route.base_speed), float(route.radius)
+    r.dyn_pad = cfg.vehicle_width / 2 + cfg.vehicle_margin
+    r.weights = (C.c_double * 10)(*cfg.weights())
+
+
 class DeviceRecedingHorizon:
     """``VectorizedRecedingHorizon`` with everything on the GPU: parameter assembly, the batched solve
     and the state advance are kernels of libnmpc_hip.so (``nmpc_loop_*``, include/nmpc_solver.h), and
@@ -384,14 +492,23 @@ class DeviceRecedingHorizon:
     ``solver`` is the ``BatchSolver`` whose handle runs the solves; ``dyn_obs`` as in
     ``VectorizedRecedingHorizon``; ``max_steps`` > 0 records the trajectory on device; ``idx0`` = the
     reference sample each robot starts at (default 0, as the reference).
+
+    ``route`` is one ``harness.Route`` (``nmpc_loop_new``), or a sequence of R routes with ``route_of`` [B]:
+    robot b follows ``route[route_of[b]]`` and ``idx0[b]`` counts on that route (``nmpc_loop_new_routes``;
+    ``route_of`` may be omitted for a single route).  Its host mirror is ``FleetRecedingHorizon``
+    (tests/test_gpu_fleet_loop.py).
     """
 
-    def __init__(self, solver, route: harness.Route, starts, dyn_obs=None, max_steps: int = 0, idx0=None,
-                 sinus_object=False):
+    def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
+                 route_of=None):
         import ctypes as C
         from . import _lib
-        cfg = self.cfg = route.cfg
-        self.solver, self.route, self.lib = solver, route, solver.lib
+        single = isinstance(route, harness.Route)
+        routes = [route] if single else list(route)
+        cfg = self.cfg = routes[0].cfg
+        self.solver, self.lib = solver, solver.lib
+        self.route = route if single else None
+        self.routes = routes
         self.B = B = len(starts)
         self.t = 0
         self.steps = 0
@@ -408,28 +525,23 @@ class DeviceRecedingHorizon:
                 [p1, p2, freq[..., None], rx[..., None], ry[..., None], ang[..., None], sinus[..., None],
                  direction[..., None]], axis=2), dtype=np.float64)
             assert dyn.shape == (B, K, 10)
-        r = _lib.NmpcRoute()
-        keep = []                                              # arrays the struct points to, until nmpc_loop_new returns
-
-        def arr(v):
-            a = np.ascontiguousarray(v, dtype=np.float64)
-            keep.append(a)
-            return _lib.as_dp(a)
-        vert = np.array(route.vertices, dtype=np.float64).reshape(-1, 2)
-        r.n_ref, r.n_vert, r.n_brake = len(route.x_ref), len(vert), len(route.brake_velocities)
-        r.num_steps_taken = cfg.num_steps_taken
-        r.x_ref, r.y_ref, r.theta_ref = arr(route.x_ref), arr(route.y_ref), arr(route.theta_ref)
-        r.vert_xy = arr(vert) if len(vert) else None
-        r.brake_vel, r.brake_dist = arr(route.brake_velocities), arr(route.brake_distances)
-        r.end = (C.c_double * 3)(*[float(v) for v in route.end])
-        r.base_speed, r.radius = float(route.base_speed), float(route.radius)
-        r.dyn_pad = cfg.vehicle_width / 2 + cfg.vehicle_margin
-        r.weights = (C.c_double * 10)(*cfg.weights())
+        keep = []                                              # arrays the structs point to, until nmpc_loop_new* returns
+        rs = (_lib.NmpcRoute * len(routes))()
+        for r, rt in zip(rs, routes):
+            _fill_route(r, rt, keep)
         h = C.c_void_p()
+        i32 = C.POINTER(C.c_int32)
         i0 = None if idx0 is None else np.ascontiguousarray(idx0, dtype=np.int32)
-        solver._check(self.lib.nmpc_loop_new(solver._h, C.byref(r), B, _lib.as_dp(starts),
-                                             None if i0 is None else i0.ctypes.data_as(C.POINTER(C.c_int32)),
-                                             K, _lib.as_dp(dyn), int(max_steps), C.byref(h)))
+        i0p = None if i0 is None else i0.ctypes.data_as(i32)
+        if single:
+            assert route_of is None, "route_of goes with a list of routes"
+            self.route_of = None
+            rc = self.lib.nmpc_loop_new(solver._h, rs, B, _lib.as_dp(starts), i0p, K, _lib.as_dp(dyn), int(max_steps), C.byref(h))
+        else:
+            self.route_of = None if route_of is None else np.ascontiguousarray(route_of, dtype=np.int32).reshape(B)
+            rc = self.lib.nmpc_loop_new_routes(solver._h, rs, len(routes), None if self.route_of is None else self.route_of.ctypes.data_as(i32),
+                                               B, _lib.as_dp(starts), i0p, K, _lib.as_dp(dyn), int(max_steps), C.byref(h))
+        solver._check(rc)
         self._l = h
         self.max_steps = int(max_steps)
 

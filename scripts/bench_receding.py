@@ -2,8 +2,9 @@
 """BASELINE config 4: smooth_velocity weights, per-robot randomised dynamic ellipses, B robots advanced
 for K receding-horizon steps (num_steps_taken = 2), warm starts carried, p rebuilt every step.
 Default: the whole loop on device (nmpc_loop_*: assembly, solve and state advance are kernels, nothing
-crosses PCIe between steps).  --host: parameter assembly on the host (NumPy-vectorised) around
-BatchSolver.solve.  Prints one JSON line."""
+crosses PCIe between steps), every robot on the scene's route; --routes R > 1: the robots follow R routes
+planned between random start / goal points of the scene (frontend.random_fleet).  --host: parameter
+assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -15,13 +16,16 @@ sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config                            # noqa: E402
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
-from mpc_trajectory_generator_amd.trajectory import VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, VectorizedRecedingHorizon    # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8192)
 ap.add_argument("--steps", type=int, default=100)
 ap.add_argument("--scene", type=int, default=11)
 ap.add_argument("--host", action="store_true")
+ap.add_argument("--routes", type=int, default=1,
+                help="routes the fleet follows: 1 = every robot on the scene's own route; R > 1 = frontend.random_fleet(cfg, "
+                     "scene, R, batch, seed=0), robots dealt evenly to R randomly planned routes")
 ap.add_argument("--split", type=int, default=2,
                 help="device loop only: split the fleet into this many sub-fleets, each with its own handle and HIP "
                      "stream, stepped alternately -- one sub-fleet's slow instances overlap the others' bulk")
@@ -34,17 +38,31 @@ sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
 cfg = named_config("cfg4")
-route = harness.scene_route(cfg, args.scene)
-rng = np.random.Generator(np.random.PCG64(0))
-B, n = args.batch, len(route.x_ref)
-i0 = rng.integers(0, max(1, n - 60), B)
-starts = np.stack([np.array(route.x_ref)[i0] + rng.normal(0, 0.05, B), np.array(route.y_ref)[i0] + rng.normal(0, 0.05, B),
-                   np.array(route.theta_ref)[i0] + rng.normal(0, 0.1, B)], axis=1)
 K = cfg.Ndynobs
-jj = np.minimum(n - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
-c = np.stack([np.array(route.x_ref)[jj], np.array(route.y_ref)[jj]], axis=2)
+B = args.batch
+if args.routes == 1:
+    route = harness.scene_route(cfg, args.scene)
+    rng = np.random.Generator(np.random.PCG64(0))
+    n = len(route.x_ref)
+    i0 = rng.integers(0, max(1, n - 60), B)
+    starts = np.stack([np.array(route.x_ref)[i0] + rng.normal(0, 0.05, B), np.array(route.y_ref)[i0] + rng.normal(0, 0.05, B),
+                       np.array(route.theta_ref)[i0] + rng.normal(0, 0.1, B)], axis=1)
+    jj = np.minimum(n - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
+    c = np.stack([np.array(route.x_ref)[jj], np.array(route.y_ref)[jj]], axis=2)
+    routes, route_of = route, None
+else:
+    from mpc_trajectory_generator_amd.frontend import random_fleet
+    routes, route_of, starts, i0 = random_fleet(cfg, args.scene, args.routes, B, seed=0)
+    rng = np.random.Generator(np.random.PCG64(1))
+    # ellipses crossing each robot's own route, 0..29 samples ahead of its start
+    n = np.array([len(r.x_ref) for r in routes])[route_of]
+    first = np.concatenate([[0], np.cumsum([len(r.x_ref) for r in routes])[:-1]])[route_of]
+    xs, ys = np.concatenate([r.x_ref for r in routes]), np.concatenate([r.y_ref for r in routes])
+    jj = first[:, None] + np.minimum(n[:, None] - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
+    c = np.stack([xs[jj], ys[jj]], axis=2)
 dyn = (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
        rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
+fleet = f", {args.routes} routes (frontend.random_fleet, seed 0)" if args.routes > 1 else ""
 solver = BatchSolver(cfg, max_batch=B, **sopts)
 if not args.host:
     from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon
@@ -54,7 +72,8 @@ if not args.host:
     loops, streams = [], []
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
-        loops.append(DeviceRecedingHorizon(sv, route, starts[ids], tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids]))
+        loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
+                                           route_of=None if route_of is None else route_of[ids]))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -76,7 +95,7 @@ if not args.host:
         print(f"windowed cross-track searches {buf[0]}, fell back {buf[1]} ({100.0 * buf[1] / max(buf[0], 1):.1f} %)", file=sys.stderr)
     print(json.dumps({
         "metric": "nmpc_receding_horizon_solves_per_sec", "value": B * (args.steps - 1) / total, "unit": "solves/s",
-        "config": {"workload": f"cfg4 smooth_velocity, scene {args.scene}, B={B}, {args.steps} receding-horizon steps, "
+        "config": {"workload": f"cfg4 smooth_velocity, scene {args.scene}{fleet}, B={B}, {args.steps} receding-horizon steps, "
                                "num_steps_taken=2, warm start (u, y carried; c reset), loop entirely on device"
                                + (f", at most {args.budget} PANOC iterations per solve (NotConvergedOutOfTime beyond)" if args.budget else "")
                                + (f", fleet split into {args.split} sub-fleets on {args.split} streams" if args.split > 1 else ""),
@@ -86,8 +105,11 @@ if not args.host:
         "converged_frac_last_step": float((st["exit_status"] == 0).mean()),
         "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum())}))
     sys.exit(0)
-rh = VectorizedRecedingHorizon(route, starts, dyn)
-rh.idx = i0.astype(np.int64)
+if route_of is None:
+    rh = VectorizedRecedingHorizon(routes, starts, dyn)
+    rh.idx = i0.astype(np.int64)
+else:
+    rh = FleetRecedingHorizon(routes, route_of, starts, dyn, idx0=i0)
 t_solve, t_asm, iters, conv = [], [], [], []
 
 
@@ -111,7 +133,7 @@ for k in range(args.steps):
 total = time.perf_counter() - t0
 print(json.dumps({
     "metric": "nmpc_receding_horizon_solves_per_sec", "value": B * args.steps / total, "unit": "solves/s",
-    "config": {"workload": f"cfg4 smooth_velocity, scene {args.scene}, B={B}, {args.steps} receding-horizon steps, "
+    "config": {"workload": f"cfg4 smooth_velocity, scene {args.scene}{fleet}, B={B}, {args.steps} receding-horizon steps, "
                            "num_steps_taken=2, warm start (u, y carried; c reset), host-side vectorised p assembly"},
     "solver_only_solves_per_sec": B * args.steps / sum(t_solve), "ms_per_step_total": 1e3 * total / args.steps,
     "ms_per_step_solve_incl_pcie": 1e3 * float(np.mean(t_solve)), "ms_per_step_assembly": 1e3 * float(np.mean(t_asm)),
