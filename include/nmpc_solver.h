@@ -68,9 +68,11 @@ typedef struct nmpc_problem {
 } nmpc_problem;
 
 /* OpEn solver configuration (src/mpc/mpc_generator.py:184-186; opengen defaults otherwise).
- * Deviation: the reference stops on wall-clock (max_duration 0.5 s, :9,186); a batch must be
- * deterministic, so the iteration caps apply, plus -- when asked for -- max_total_inner, the
- * deterministic stand-in for max_duration. */
+ * The reference also stops on wall-clock (max_duration 0.5 s, :9,186).  Here that stop is opt-in and
+ * lives outside this struct: nmpc_set_time_limits (per instance, OpEn's max_duration, and per batch).
+ * By default only the iteration caps apply, plus -- when asked for -- max_total_inner, the
+ * deterministic stand-in for max_duration; a solve the clock stops returns exactly what the solve with
+ * max_total_inner = its num_inner_iterations returns. */
 typedef struct nmpc_opts {
     /* ALM knobs: default, then the range nmpc_new accepts (anything else, NaN included, is NMPC_ERR_BAD_OPTS).
      * The ranges are OpEn's builder assertions as recalled in SURVEY.md App. C, not checked against OpEn. */
@@ -103,7 +105,7 @@ typedef struct nmpc_opts {
 typedef enum nmpc_exit {
     NMPC_CONVERGED = 0,
     NMPC_NOT_CONVERGED_ITERATIONS = 1,
-    NMPC_NOT_CONVERGED_OUT_OF_TIME = 2,      /* opts.max_total_inner spent (deterministic max_duration) */
+    NMPC_NOT_CONVERGED_OUT_OF_TIME = 2,      /* opts.max_total_inner spent (deterministic max_duration), or a limit of nmpc_set_time_limits reached */
     NMPC_NOT_CONVERGED_COST = 3,
     NMPC_NOT_CONVERGED_NOT_FINITE = 4        /* Deviation from OpEn, which checks the returned u only: raised as well when
                                                 the cost or the residual norm ||r|| of an inner solve is not finite
@@ -174,6 +176,16 @@ int nmpc_solve_batch_host(nmpc_handle *h, int B, const double *p, double *u, con
                           const double *c0, double *y_out, nmpc_status *status);
 /* Kernel time (HIP events around the launch) of the last nmpc_solve_batch_host call on this handle, in ms. */
 double nmpc_last_batch_ms(const nmpc_handle *h);
+
+/* Wall-clock limits for this handle's later solves, on the device's 100 MHz constant clock; 0 = off (the default).
+ *   max_duration_ms  per instance, from its first start (what status.solve_time_ms measures): OpEn's max_duration
+ *   batch_budget_ms  per launch, from the launch's start on the device: no instance starts a new PANOC iteration after it
+ * Checked where opts.max_total_inner is checked, at the end of each PANOC iteration, with the same consequences.
+ * The instance returns the feasible half step with NMPC_NOT_CONVERGED_OUT_OF_TIME (or what the ALM layer reports after an
+ * out-of-budget inner solve, exactly as with max_total_inner).  Every instance does at least one PANOC iteration.
+ * Applies to nmpc_solve_batch_device/_host and to every step of a loop built on this handle.
+ * NMPC_ERR_BAD_OPTS for a negative, NaN or infinite value, and the limits in force are left unchanged. */
+int nmpc_set_time_limits(nmpc_handle *h, double max_duration_ms, double batch_budget_ms);
 
 /* psi(u; c, y, p), grad_u psi, F1, F2 for B instances (c == NULL: zeros -> plain f; y == NULL: zeros).
  * Outputs may be NULL.  psi [B], grad [B][n_u], F1 [B][n1], F2 [B][n2]. */

@@ -74,8 +74,18 @@ struct nmpc_handle {
     hipEvent_t small_ev[2];
     bool small_ready;
     nmpc_status *d_st;
+    // wall-clock limits (nmpc_set_time_limits): as given, in ms, and in ticks of the 100 MHz constant clock (0 = off); any limit set -> the Timed<> kernels
+    double tl_dur_ms, tl_budget_ms;
+    long long tl_dur, tl_budget;
+    long long *d_t0;           // the launch's start, written by nmpc_stamp_kernel when a budget is set (allocated with the first budget)
     std::string err;
 };
+
+// one clock reading on the device ahead of a launch with a batch budget: the start every instance's batch deadline counts from
+__global__ void nmpc_stamp_kernel(long long *t0)
+{
+    if (threadIdx.x == 0) *t0 = (long long)__builtin_amdgcn_s_memrealtime();
+}
 
 extern "C" {
 
@@ -208,6 +218,7 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
     h->h_pin[0] = h->h_pin[1] = nullptr; h->pin_ev[0] = h->pin_ev[1] = nullptr; h->staging_ready = false;
     h->d_small = h->h_small = nullptr; h->small_ev[0] = h->small_ev[1] = nullptr; h->small_ready = false;
     h->d_st = nullptr;
+    h->tl_dur_ms = h->tl_budget_ms = 0.0; h->tl_dur = h->tl_budget = 0; h->d_t0 = nullptr;
     hipError_t e = hipSetDevice(device_id);
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_queue, sizeof(unsigned int));
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_order, sizeof(int) * (size_t)max_batch);
@@ -233,6 +244,9 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
         e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeDefault>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeNobs50>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeAny>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeDefault>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeNobs50>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeAny>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) { nmpc_free(h); return NMPC_ERR_HIP; }
     } else {
         // two stages per lane: one wave per SIMD (512 registers), the four waves of a CU are one team
@@ -243,6 +257,8 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
         h->team_lds = wg_bytes;
         e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeN40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeAny>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeN40>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeAny>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_eval2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) { nmpc_free(h); return NMPC_ERR_HIP; }
     }
@@ -264,19 +280,53 @@ void nmpc_free(nmpc_handle *h)
     for (int k = 0; k < 2; ++k) if (h->small_ev[k]) (void)hipEventDestroy(h->small_ev[k]);
     (void)hipFree(h->d_p); (void)hipFree(h->d_u); (void)hipFree(h->d_y0); (void)hipFree(h->d_c0); (void)hipFree(h->d_yout);
     (void)hipFree(h->d_psi); (void)hipFree(h->d_grad); (void)hipFree(h->d_F1); (void)hipFree(h->d_F2); (void)hipFree(h->d_st);
+    (void)hipFree(h->d_t0);
     delete h;
 }
 
 int nmpc_ping(const nmpc_handle *h) { return (h && h->alive) ? NMPC_OK : NMPC_ERR_DEAD_HANDLE; }
 const char *nmpc_last_error(const nmpc_handle *h) { return h ? h->err.c_str() : "null handle"; }
 double nmpc_last_batch_ms(const nmpc_handle *h) { return h ? h->last_ms : 0.0; }
+static bool timed(const nmpc_handle *h) { return h->tl_dur > 0 || h->tl_budget > 0; }
 const char *nmpc_kernel_name(const nmpc_handle *h)
 {
     if (!h) return "";
+    if (timed(h)) {
+        if (h->P == 20)
+            return h->shape_default ? "nmpc_solve_hyb_kernel<Timed<ShapeDefault>>"
+                                    : (h->shape_nobs50 ? "nmpc_solve_hyb_kernel<Timed<ShapeNobs50>>" : "nmpc_solve_hyb_kernel<Timed<ShapeAny>>");
+        return h->shape_n40 ? "nmpc_solve_hyb2_kernel<Timed<ShapeN40>>" : "nmpc_solve_hyb2_kernel<Timed<ShapeAny>>";
+    }
     if (h->P == 20)
         return h->shape_default ? "nmpc_solve_hyb_kernel<ShapeDefault>"
                                 : (h->shape_nobs50 ? "nmpc_solve_hyb_kernel<ShapeNobs50>" : "nmpc_solve_hyb_kernel<ShapeAny>");
     return h->shape_n40 ? "nmpc_solve_hyb2_kernel<ShapeN40>" : "nmpc_solve_hyb2_kernel<ShapeAny>";
+}
+
+// a limit in ms -> ticks of the 100 MHz clock: 0 stays 0 (off), anything above it is at least one tick, and at most 2^52 ticks (16 months)
+static long long ms_to_ticks(double ms)
+{
+    if (ms <= 0.0) return 0;
+    const double t = ceil(ms * 1e5);
+    const double cap = 4503599627370496.0;
+    return t < 1.0 ? 1 : (long long)(t < cap ? t : cap);
+}
+
+int nmpc_set_time_limits(nmpc_handle *h, double max_duration_ms, double batch_budget_ms)
+{
+    if (!h) return NMPC_ERR_BAD_ARG;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    // written so that a NaN fails the test: the limits in force stay as they are
+    auto ok = [](double x) { return x >= 0.0 && x <= DBL_MAX; };
+    if (!ok(max_duration_ms) || !ok(batch_budget_ms)) return fail(h, NMPC_ERR_BAD_OPTS, "time limits: negative, NaN or infinite");
+    const long long budget = ms_to_ticks(batch_budget_ms);
+    if (budget > 0 && !h->d_t0) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipMalloc((void **)&h->d_t0, sizeof(long long)));
+    }
+    h->tl_dur_ms = max_duration_ms; h->tl_budget_ms = batch_budget_ms;
+    h->tl_dur = ms_to_ticks(max_duration_ms); h->tl_budget = budget;
+    return NMPC_OK;
 }
 
 static void fill_args(const nmpc_handle *h, KArgs &a, int B)
@@ -287,6 +337,8 @@ static void fill_args(const nmpc_handle *h, KArgs &a, int B)
     a.queue = h->d_queue;
     a.inv_ts = 1.0 / h->pb.ts;
     a.dbg = h->dbg;
+    a.tl_dur = h->tl_dur; a.tl_budget = h->tl_budget;
+    a.tl_t0 = h->tl_budget > 0 ? h->d_t0 : nullptr;
 }
 
 int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_u, const double *d_y0,
@@ -301,6 +353,8 @@ int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_
     KArgs a;
     fill_args(h, a, B);
     a.p = d_p; a.u = d_u; a.y0 = d_y0; a.c0 = d_c0; a.y_out = d_y_out; a.st = d_status;
+    // a batch budget counts from one clock reading on the device, taken before anything of this launch runs (nothing is enqueued without one)
+    if (h->tl_budget > 0) hipLaunchKernelGGL(nmpc_stamp_kernel, dim3(1), dim3(64), 0, s, h->d_t0);
     HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, sizeof(unsigned int), s));
     // one instance per wave, three query points per pass: N_hor <= 20 with one stage per lane (hybrid / tri layouts), 20 < N_hor <= 40 with two
     const int grid = B < h->grid_cap ? B : h->grid_cap;          // waves that take instances
@@ -344,7 +398,16 @@ int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_
         a.team_help = h->team_help;
         a.cull_radius = h->cull_radius;
         const size_t tlds = h->team_lds;
-        if (h->P == 40) {
+        if (timed(h)) {           // the same kernels with the wall-clock test compiled in (nmpc_set_time_limits)
+            if (h->P == 40) {
+                if (h->shape_n40) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeN40>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
+                else hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeAny>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
+            }
+            else if (h->shape_default) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeDefault>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
+            else if (h->shape_nobs50) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeNobs50>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
+            else hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeAny>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
+        }
+        else if (h->P == 40) {
             if (h->shape_n40) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeN40>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
             else hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeAny>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
         }

@@ -85,10 +85,19 @@ struct KArgs {
     int team_owners;           // hybrid kernel: waves per workgroup that take instances from the queue (1..4); the others only help
     int team_help;             // 0: nobody asks for help (experiments, NMPC_TEAM_HELP=0: the single-wave baseline)
     double cull_radius;        // eval_psi's CULL path: circles whose edge is farther than this from the start position are left out of the scan
-    // eval kernel only
-    const double *ev_c;
-    const double *ev_y;
-    double *ev_psi, *ev_grad, *ev_F1, *ev_F2;
+    // (a launch is an evaluation or a solve: their own arguments share the room, so that the argument block keeps its size and layout)
+    union {
+        struct {           // eval kernel only
+            const double *ev_c;
+            const double *ev_y;
+            double *ev_psi, *ev_grad, *ev_F1, *ev_F2;
+        };
+        struct {           // wall-clock limits (nmpc_set_time_limits; read by the Timed<> solve kernels only), in ticks of the 100 MHz constant clock, 0 = off
+            long long tl_dur;          // per instance, from its first start
+            long long tl_budget;       // per launch, from *tl_t0
+            const long long *tl_t0;    // the launch's start, stamped on the device ahead of the solve (nmpc_stamp_kernel); NULL without a budget
+        };
+    };
 };
 
 enum { SC_X0 = 0, SC_Y0, SC_TH0, SC_VINIT, SC_WINIT, SC_XF, SC_YF, SC_THF,
@@ -127,6 +136,11 @@ struct ShapeAny { static constexpr int N = 0, NOBS = -1, NDYN = -1; };
 struct ShapeDefault { static constexpr int N = 20, NOBS = 10, NDYN = 3; };
 struct ShapeNobs50 { static constexpr int N = 20, NOBS = 50, NDYN = 3; };     // BASELINE config 3
 struct ShapeN40 { static constexpr int N = 40, NOBS = 10, NDYN = 3; };        // BASELINE config 2
+// The same shape with the wall-clock limits of nmpc_set_time_limits compiled in: the solve kernels instantiated for Timed<S> test the
+// device's 100 MHz clock where they test opts.max_total_inner; those for S itself hold no clock test and are the untimed kernels.
+template <class S> struct Timed { static constexpr int N = S::N, NOBS = S::NOBS, NDYN = S::NDYN; };
+template <class SH> struct ShapeTimed { static constexpr bool value = false; };
+template <class S> struct ShapeTimed<Timed<S>> { static constexpr bool value = true; };
 template <class SH> __device__ __forceinline__ int shape_N(const KArgs &a) { if constexpr (SH::N > 0) return SH::N; else return a.pb.N; }
 template <class SH> __device__ __forceinline__ int shape_nobs(const KArgs &a) { if constexpr (SH::NOBS >= 0) return SH::NOBS; else return a.pb.nobs; }
 template <class SH> __device__ __forceinline__ int shape_ndyn(const KArgs &a) { if constexpr (SH::NDYN >= 0) return SH::NDYN; else return a.pb.ndyn; }

@@ -51,5 +51,35 @@ __device__ __forceinline__ double fbe_value(double cost, double gamma, double hi
     return cost - (0.5 * gamma) * gg + dist2 * hig;
 }
 
+// ---- wall-clock limits of the Timed<> solve kernels (nmpc_set_time_limits), on the 100 MHz constant clock
+constexpr long long CLK_NEVER = 0x7fffffffffffffffll;
+
+// a 64-bit value every lane holds, as a wave-uniform scalar pair
+__device__ __forceinline__ long long uniform_ll(long long v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// an instance's deadline: the earlier of the launch's (CLK_NEVER without a budget) and its first start + dur (dur 0 = no per-instance limit).
+// The host caps both limits at 2^52 ticks, so no sum here overflows.
+__device__ __forceinline__ long long clk_deadline(long long batch_dl, long long dur, long long t_first)
+{
+    const long long own = dur > 0 ? uniform_ll(t_first) + dur : CLK_NEVER;
+    return own < batch_dl ? own : batch_dl;
+}
+
+// the clock has reached `dl`.  The read is waited for at once, with lgkmcnt(0) alone (s_memrealtime returns out of order with LDS reads): the
+// callers sit at the top of a pass, where no LDS read is in flight, and the fences keep the compiler from moving any across
+__device__ __forceinline__ bool clk_reached(long long dl)
+{
+    __builtin_amdgcn_sched_barrier(0);
+    const long long now = (long long)__builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_sched_barrier(0);
+    return now >= dl;
+}
+
 
 }  // namespace nmpc

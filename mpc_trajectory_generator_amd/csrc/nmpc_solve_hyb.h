@@ -379,6 +379,11 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
     const double tol_ = scalar_own(a.op.tolerance);
     const unsigned max_inner = (unsigned)scalar_own(a.op.max_inner);
     const unsigned budget = (unsigned)scalar_own(a.op.max_total_inner);     // 0 = off
+    // wall-clock limits (nmpc_set_time_limits), Timed<> instantiations only: the launch's deadline on the 100 MHz constant clock; an
+    // instance's own is the earlier of it and its first start + tl_dur (clk_dl, set when the instance is fetched)
+    constexpr bool TIMED = ShapeTimed<SH>::value;
+    long long clk_batch = CLK_NEVER, clk_dl = CLK_NEVER;
+    if constexpr (TIMED) { if (a.tl_budget > 0) clk_batch = uniform_ll(*a.tl_t0) + a.tl_budget; }
     lds_double *Lpar = L + mp.par;
 #define pk_eps_nu Lpar[0]
 #define pk_dy_norm Lpar[1]
@@ -444,7 +449,9 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
 
         const long long dbg_t0 = __builtin_amdgcn_s_memtime();
         // (experiments, NMPC_DEBUG_PRIO: first start and migration count travel with the instance; parked in LDS)
-        Lpar[13] = (double)__builtin_amdgcn_s_memrealtime(); Lpar[14] = 0.0;
+        const auto clk0_ = __builtin_amdgcn_s_memrealtime();
+        long long t_first = (long long)clk0_;              // (Timed<> only: the first start of this instance)
+        Lpar[13] = (double)clk0_; Lpar[14] = 0.0;
         if (k_dbg == 1) { if (hw_slot & 1u) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3); }
         double vref_;
         DynStage dyn;
@@ -521,26 +528,30 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
             pk_last_fpr = pks[6]; pk_last_cost = pks[7];
             nu = (int)pks[8]; inner_total = (unsigned)pks[9]; n_cost = (unsigned)pks[10]; n_grad = (unsigned)pks[11]; n_pass = (unsigned)pks[12];
             Lpar[13] = pks[13]; Lpar[14] = pks[14] + 1.0;
+            if constexpr (TIMED) t_first = (long long)pks[13];
             long_counted = pks[15] != 0.0; q_pass = n_pass;
         }
+        if constexpr (TIMED) clk_dl = clk_deadline(clk_batch, a.tl_dur, t_first);
 
         // phase flags (wave-uniform): set by the state handlers, consumed at the top of the loop
         FlagBit f_start{fl, 1u << 7}, f_back{fl, 1u << 8}, f_trials{fl, 1u << 9}, f_begin{fl, 1u << 11}, f_done{fl, 1u << 12}, f_fb{fl, 1u << 13};
         FlagBit running{fl, 1u << 14}, timed_out{fl, 1u << 15};
         f_start = true; running = true;
         FlagBit posted{fl, 1u << 16};                      // a request of the current iteration is open for the helpers
+        FlagBit clk_late{fl, 1u << 17};                    // (Timed<> only) the clock read at the top of this pass has reached clk_dl
         NMPC_PROBE_STATE                                   // the instrumented builds' probes (nmpc_probe.h)
 
         // an iteration finished (raised by the consumption of a pass; the next pass starts the next step or returns from the inner solver).
         // Written out where it is raised: as a flag it was a test at the top of every pass and a set / clear pair per iteration.
-        // OpEn: while step() && num_iter < max_iter { num_iter++ };  opts.max_total_inner: the deterministic max_duration
+        // OpEn: while step() && num_iter < max_iter { num_iter++ };  opts.max_total_inner: the deterministic max_duration; the Timed<>
+        // kernels' wall-clock limits stop at the same test, so a solve stopped by the clock is the solve with max_total_inner = its count
 #define NMPC_END_ITERATION()                                                                                   \
         do {                                                                                                   \
             iteration++;                                                                                       \
             if (!(num_iter < max_inner)) f_done = true;                                                        \
             else {                                                                                             \
                 num_iter++;                                                                                    \
-                if (budget > 0u && inner_total + num_iter >= budget) { timed_out = true; f_done = true; }      \
+                if ((budget > 0u && inner_total + num_iter >= budget) || (TIMED && clk_late)) { timed_out = true; f_done = true; } \
                 else f_begin = true;                                                                           \
             }                                                                                                  \
         } while (0)
@@ -792,6 +803,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 2) void nmpc_solve_hyb_kernel(KArg
             // ================================================================ one pass: psi at two points
             double psi, pen, egv = 0, egw = 0, eav, eaw;
             n_pass++;
+            if constexpr (TIMED) clk_late = clk_reached(clk_dl);
             // Iteration counts are heavy-tailed: an instance that has already run long is likely the
             // one the whole batch will end up waiting for.  Raise its wave's issue priority while it shares its SIMD with another
             // wave: worth 1-2 % of the headline batch (39.2 against 39.9 ms without; levels at 1k / 2k / 3k or 0.5k / 1k / 1.5k passes

@@ -702,6 +702,10 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
     const double vmin = a.pb.vmin, vmax = a.pb.vmax, wmax = a.pb.wmax;
     const unsigned max_inner = (unsigned)a.op.max_inner;
     const unsigned budget = (unsigned)a.op.max_total_inner;
+    // wall-clock limits, Timed<> instantiations only (nmpc_solve_hyb.h): the launch's deadline, and this instance's (set when it is fetched)
+    constexpr bool TIMED = ShapeTimed<SH>::value;
+    long long clk_batch = CLK_NEVER, clk_dl = CLK_NEVER;
+    if constexpr (TIMED) { if (a.tl_budget > 0) clk_batch = uniform_ll(*a.tl_t0) + a.tl_budget; }
     lds_double *Lpar = L + mp.par;
 
     for (; wid < a.team_owners;) {
@@ -780,6 +784,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
             nu = (int)pks[8]; inner_total = (unsigned)pks[9]; n_cost = (unsigned)pks[10]; n_grad = (unsigned)pks[11]; n_pass = (unsigned)pks[12];
             t_start = (long long)pks[13]; long_counted = pks[15] != 0.0; q_pass = n_pass;
         }
+        if constexpr (TIMED) clk_dl = clk_deadline(clk_batch, a.tl_dur, t_start);
 
         for (;;) {
             bool lb_batch = false;                     // this pass starts with the batch of inner products (f_back, f_begin)
@@ -819,6 +824,8 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
                 need_grad = true; state = D_LS;
             }
             // ---------------------------------------------------------------- an iteration finished
+            // (the Timed<> kernels' wall-clock limits stop at the budget's test: a solve stopped by the clock is the solve with
+            // max_total_inner = its count)
             // (Measured, round 6: handled where it is raised, as in nmpc_solve_hyb.h, this kernel is 3 % SLOWER -- 125.1 against 121.1 ms on
             // cfg 2, with 226 spilled scalars instead of 197 --, although each of the round's three state-machine changes alone is worth 0.3 .. 1.3 %.)
             if (f_end) {
@@ -827,7 +834,7 @@ __global__ __launch_bounds__(64 * TEAM_WAVES, 1) void nmpc_solve_hyb2_kernel(KAr
                 if (!(num_iter < max_inner)) f_done = true;
                 else {
                     num_iter++;
-                    if (budget > 0u && inner_total + num_iter >= budget) { timed_out = true; f_done = true; }
+                    if ((budget > 0u && inner_total + num_iter >= budget) || (TIMED && clk_reached(clk_dl))) { timed_out = true; f_done = true; }
                     else f_begin = true;
                 }
             }

@@ -30,7 +30,8 @@ def problem_from_config(cfg: Config) -> _lib.NmpcProblem:
 class BatchSolver:
     """One handle = one problem shape on one GPU.  Not thread-safe; distinct solvers are."""
 
-    def __init__(self, cfg: Config, max_batch: int = 8192, device: int = 0, experiments: bool = False, **opts):
+    def __init__(self, cfg: Config, max_batch: int = 8192, device: int = 0, experiments: bool = False,
+                 max_duration_ms: float = 0.0, batch_budget_ms: float = 0.0, **opts):
         self.cfg = cfg
         # raises if the HIP library cannot be had.  (experiments: tests / scripts only -- the variant that reads the NMPC_* environment knobs)
         self.lib = _lib.load_library(experiments=experiments)
@@ -53,6 +54,13 @@ class BatchSolver:
             raise SolverError(rc, f"nmpc_new failed: {_lib.ERRORS.get(rc, rc)} "
                                   "(this package needs a HIP device; there is no CPU fallback)")
         self._h = h
+        self.max_duration_ms = self.batch_budget_ms = 0.0
+        if max_duration_ms or batch_budget_ms:
+            try:
+                self.set_time_limits(max_duration_ms, batch_budget_ms)
+            except SolverError:
+                self.close()
+                raise
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -76,6 +84,17 @@ class BatchSolver:
     def oracle_opts(self) -> dict:
         """This handle's options as keyword arguments of the test oracle (field names are shared)."""
         return {name: getattr(self.opts, name) for name, _ in self.opts._fields_ if name != "reserved"}
+
+    def set_time_limits(self, max_duration_ms: float = 0.0, batch_budget_ms: float = 0.0):
+        """Wall-clock limits for the later solves of this handle (nmpc_set_time_limits), in ms on the device's 100 MHz clock; 0 = off.
+
+        ``max_duration_ms`` bounds each instance from its first start (``status["solve_time_ms"]``): OpEn's ``max_duration``.
+        ``batch_budget_ms`` bounds a whole launch: no instance starts a PANOC iteration after it.  Both are tested where
+        ``max_total_inner`` is, so an instance stopped by the clock returns exactly what the solve with ``max_total_inner`` = its
+        ``num_inner_iterations`` returns, with ``NotConvergedOutOfTime``.  A ``DeviceRecedingHorizon`` built on this handle gives every
+        step's solve these limits.  A negative, NaN or infinite value raises (code -2) and leaves the limits in force unchanged."""
+        self._check(self.lib.nmpc_set_time_limits(self._h, float(max_duration_ms), float(batch_budget_ms)))
+        self.max_duration_ms, self.batch_budget_ms = float(max_duration_ms), float(batch_budget_ms)
 
     @property
     def kernel_name(self) -> str:

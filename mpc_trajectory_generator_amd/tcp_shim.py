@@ -14,7 +14,11 @@ in-process C-ABI handle on the GPU -- no socket, no JSON:
   (``keep_multipliers=False`` resets them to zero per call instead; which of the two OpEn does is
   not verifiable here, SURVEY.md App. C.4);
 * a wrong parameter count / guess size / multiplier size yields an error response with OpEn's
-  codes 3003 / 1600 / 1700, a solver failure 2000; non-convergence is NOT an error.
+  codes 3003 / 1600 / 1700, a solver failure 2000; non-convergence is NOT an error;
+* ``max_duration_micros`` is opengen's ``.with_max_duration_micros`` (the reference builds with
+  500 000, src/mpc/mpc_generator.py:9,184-186): each solve stops at the end of the PANOC iteration
+  in which it reaches that time and answers ``NotConvergedOutOfTime`` with its feasible half step.
+  ``None`` (the default) sets no limit.
 
 ``call_batch`` is the batched path: B parameter vectors per call.
 """
@@ -68,11 +72,15 @@ class SolverResponse:
 
 class OptimizerTcpManager:
     def __init__(self, optimizer_path=None, config: Config | None = None, device: int = 0,
-                 max_batch: int = 8192, keep_multipliers: bool = True, **solver_opts):
+                 max_batch: int = 8192, keep_multipliers: bool = True, max_duration_micros: int | None = None,
+                 **solver_opts):
         self.optimizer_path = optimizer_path          # accepted for call-site compatibility, unused
         self.cfg = config if config is not None else load_config()
         self._device, self._max_batch = device, max_batch
         self._opts = solver_opts
+        if max_duration_micros is not None and not float(max_duration_micros) > 0.0:
+            raise ValueError(f"max_duration_micros must be positive (or None for no limit), got {max_duration_micros!r}")
+        self._max_duration_ms = 0.0 if max_duration_micros is None else float(max_duration_micros) / 1000.0
         self._keep_y = keep_multipliers
         self._solver: BatchSolver | None = None
         self._u = self._y = None
@@ -81,7 +89,8 @@ class OptimizerTcpManager:
     def start(self):
         if self._solver is not None:
             raise RuntimeError("optimizer already started")
-        self._solver = BatchSolver(self.cfg, max_batch=self._max_batch, device=self._device, **self._opts)
+        self._solver = BatchSolver(self.cfg, max_batch=self._max_batch, device=self._device,
+                                   max_duration_ms=self._max_duration_ms, **self._opts)
         self._u = np.zeros((1, self._solver.n_u))     # the server's solution buffer starts at zero
         self._y = np.zeros((1, self._solver.n1))
 

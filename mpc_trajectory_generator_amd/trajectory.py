@@ -497,6 +497,11 @@ class DeviceRecedingHorizon:
     robot b follows ``route[route_of[b]]`` and ``idx0[b]`` counts on that route (``nmpc_loop_new_routes``;
     ``route_of`` may be omitted for a single route).  Its host mirror is ``FleetRecedingHorizon``
     (tests/test_gpu_fleet_loop.py).
+
+    Wall-clock limits are the handle's: on a ``solver`` with ``batch_budget_ms`` (``BatchSolver.set_time_limits``) every
+    step's solve gets that budget from the start of its launch on the device, so a fleet can be re-planned within a control
+    period; ``max_duration_ms`` bounds each robot's solve the same way.  Instances the clock stops answer
+    ``NotConvergedOutOfTime`` with the feasible half step, and the next step warm-starts from it as from any other solve.
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
