@@ -126,7 +126,7 @@ typedef struct nmpc_status {
                                         three query points per pass (nmpc_solve_hyb_kernel, N_hor <= 20; a pass whose
                                         trials were evaluated by helper waves of the team counts like one the owner
                                         ran itself, so the figure is deterministic; nmpc_solve_hyb2_kernel likewise for
-                                        20 < N_hor <= 40), one (nmpc_solve_kernel<64>: = num_cost_evals + num_grad_evals) */
+                                        20 < N_hor <= 40) */
     double last_problem_norm_fpr;
     double delta_y_norm_over_c;
     double f2_norm;

@@ -25,59 +25,105 @@
 #include "nmpc_solve_hyb2.h"
 #include "nmpc_loop.h"
 #include "nmpc_order.h"
+#include "nmpc_host.h"
 
 // =================================================================================================
 // C ABI (include/nmpc_solver.h)
 // =================================================================================================
+using nmpc::DevBuf;
+using nmpc::Event;
 using nmpc::KArgs;
 using nmpc::LdsMap;
+using nmpc::PinBuf;
+
+// Every instantiation of the solve kernels: host code names them here and nowhere else.  A row is picked once per handle (nmpc_new), and
+// the name, the LDS attribute and the launch all go through it.  The rows' order is the kernels' order in the gfx950 code object (the
+// first host reference decides it), and the headline kernel is sensitive to where it lies: keep it.
+namespace nmpc {
+struct SolveKernel {
+    const char *name;      // nmpc_kernel_name: recorded profiles are keyed on it
+    void (*fn)(KArgs);
+    int P;                 // family: 20 = nmpc_solve_hyb_kernel, 40 = nmpc_solve_hyb2_kernel
+    bool timed;            // Timed<>: the wall-clock test compiled in (nmpc_set_time_limits)
+    int N, nobs, ndyn;     // the shape it is specialised for; N = 0: any
+};
+#define SOLVE_ROW(K, P, S) {#K "<" #S ">", K<S>, P, ShapeTimed<S>::value, S::N, S::NOBS, S::NDYN}
+static const SolveKernel SOLVE_KERNELS[] = {
+    SOLVE_ROW(nmpc_solve_hyb_kernel, 20, ShapeDefault),
+    SOLVE_ROW(nmpc_solve_hyb_kernel, 20, ShapeNobs50),
+    SOLVE_ROW(nmpc_solve_hyb_kernel, 20, ShapeAny),
+    SOLVE_ROW(nmpc_solve_hyb_kernel, 20, Timed<ShapeDefault>),
+    SOLVE_ROW(nmpc_solve_hyb_kernel, 20, Timed<ShapeNobs50>),
+    SOLVE_ROW(nmpc_solve_hyb_kernel, 20, Timed<ShapeAny>),
+    SOLVE_ROW(nmpc_solve_hyb2_kernel, 40, ShapeN40),
+    SOLVE_ROW(nmpc_solve_hyb2_kernel, 40, ShapeAny),
+    SOLVE_ROW(nmpc_solve_hyb2_kernel, 40, Timed<ShapeN40>),
+    SOLVE_ROW(nmpc_solve_hyb2_kernel, 40, Timed<ShapeAny>),
+};
+#undef SOLVE_ROW
+}  // namespace nmpc
+using nmpc::SolveKernel;
+
+// The three groups of resources a handle makes on first use, each all or none.
+struct Staging {         // host path: buffers sized for max_batch, two pinned bounce buffers (pageable user memory <-> HBM at DMA speed)
+    DevBuf<double> p, u, y0, c0, yout, psi, grad, F1, F2;
+    DevBuf<nmpc_status> st;
+    PinBuf pin[2];
+    Event ev[2];
+    bool ready = false;
+};
+// small batches through the host entry point (the reference's own call is B = 1, src/path_generator.py:385): ONE device arena
+// [p | c0 | y0 | u | y_out | status] per instance block, one pinned mirror, one copy in (p .. u), one copy out (u .. status), two events kept
+struct SmallArena {
+    DevBuf<char> d;
+    PinBuf h;
+    Event ev[2];
+    bool ready = false;
+    void release() { *this = {}; }
+};
+struct Pools {           // instances that leave their wave: parked solver states, the pools' ring buffers and their counters
+    DevBuf<double> park;
+    DevBuf<int> pool;
+    DevBuf<unsigned int> ctr;
+    bool made() const { return park && pool && ctr; }
+    void release() { *this = {}; }
+};
 
 struct nmpc_handle {
-    nmpc_problem pb;
-    nmpc_opts op;
-    int device;
-    int max_batch;
-    bool alive;
-    LdsMap map;
-    int P;                 // 20: three query points per wave, one stage per lane (N_hor <= 20); 40: three points, two stages per lane (20 < N_hor <= 40)
-    bool shape_default;    // (N, Nobs, Ndynobs) == ShapeDefault: the shape-specialised kernel runs
-    bool shape_nobs50;     // ... == ShapeNobs50
-    bool shape_n40;        // ... == ShapeN40
-    int grid_cap;          // resident waves the launch is sized for
-    double last_ms;        // kernel time of the last host-path batch
-    size_t team_lds;       // hybrid kernel: dynamic LDS bytes of one workgroup (four slices + control block)
-    unsigned int *d_queue;
-    int park_min, park_depth;  // hybrid kernel: migrate instances after this many passes (0 = never) / pool depth limit
-    int sched_mode;            // step-aside scheduling (NMPC_SCHED=0 switches it off); long instances time-share beyond sched_theta x resident waves (NMPC_SCHED_THETA)
-    double sched_theta, sched_cold;
-    int team_owners_forced;    // experiments (NMPC_TEAM_OWNERS): waves per workgroup that take instances, 0 = automatic
-    bool team_help;            // experiments (NMPC_TEAM_HELP=0): helpers never asked
-    int waves_per_cu;          // experiments (NMPC_WAVES_PER_CU): resident waves per CU the launch is sized for, 0 = all that fit
-    int dbg;                   // experiments (NMPC_DEBUG_PRIO): KArgs.dbg
-    double cull_radius;        // eval_psi CULL (NMPC_CULL_RADIUS)
-    double *d_park;            // parked solver states, allocated on first use
-    int *d_pool;
-    unsigned int *d_pool_ctr;
-    bool loop_order_prev;      // nmpc_loop_step: launch order from the previous step's pass counts (experiments: NMPC_LOOP_ORDER_PREV=0 switches it off)
-    int *d_order;              // launch order (hard-looking instances first)
-    bool use_order;
-    const nmpc_status *order_hint;   // set by nmpc_loop_step for the duration of its solve: the previous step's statuses (launch order by their pass counts)
-    unsigned char *d_cls;
-    // staging buffers of the host path
-    double *d_p, *d_u, *d_y0, *d_c0, *d_yout, *d_psi, *d_grad, *d_F1, *d_F2;
-    char *h_pin[2];            // pinned bounce buffers of the host entry points (pageable user memory <-> HBM at DMA speed)
-    hipEvent_t pin_ev[2];
-    bool staging_ready;        // every staging resource above exists
-    // small batches through the host entry point (the reference's own call is B = 1, src/path_generator.py:385): ONE device arena
-    // [p | c0 | y0 | u | y_out | status] per instance block, one pinned mirror, one copy in (p .. u), one copy out (u .. status), two events kept
-    char *d_small, *h_small;
-    hipEvent_t small_ev[2];
-    bool small_ready;
-    nmpc_status *d_st;
+    nmpc_problem pb{};
+    nmpc_opts op{};
+    int device = 0;
+    int max_batch = 0;
+    bool alive = true;
+    LdsMap map{};
+    int P = 20;                // 20: three query points per wave, one stage per lane (N_hor <= 20); 40: three points, two stages per lane (20 < N_hor <= 40)
+    const SolveKernel *kernel[2] = {nullptr, nullptr};   // the handle's rows of SOLVE_KERNELS: plain, Timed<>
+    int grid_cap = 0;          // resident waves the launch is sized for
+    double last_ms = 0.0;      // kernel time of the last host-path batch
+    size_t team_lds = 0;       // solve kernels: dynamic LDS bytes of one workgroup (four slices + control block)
+    size_t eval_lds = 0;       // eval kernels: dynamic LDS bytes of one wave (three instances, a slice each)
+    DevBuf<unsigned int> d_queue;
+    int park_min = 500, park_depth = 8;  // hybrid kernel: migrate instances after this many passes (0 = never) / pool depth limit
+    int sched_mode = 1;            // step-aside scheduling (NMPC_SCHED=0 switches it off); long instances time-share beyond sched_theta x resident waves (NMPC_SCHED_THETA)
+    double sched_theta = 0.0, sched_cold = 0.4;
+    bool shape_any = false;        // experiments (NMPC_SHAPE=any): the run-time-shape kernel whatever the shape
+    int team_owners_forced = 0;    // experiments (NMPC_TEAM_OWNERS): waves per workgroup that take instances, 0 = automatic
+    bool team_help = true;         // experiments (NMPC_TEAM_HELP=0): helpers never asked
+    int waves_per_cu = 0;          // experiments (NMPC_WAVES_PER_CU): resident waves per CU the launch is sized for, 0 = all that fit
+    int dbg = 0;                   // experiments (NMPC_DEBUG_PRIO): KArgs.dbg
+    double cull_radius = 0.0;      // eval_psi CULL (NMPC_CULL_RADIUS)
+    Pools pools;                   // made by the first launch that needs them
+    bool loop_order_prev = true;   // nmpc_loop_step: launch order from the previous step's pass counts (experiments: NMPC_LOOP_ORDER_PREV=0 switches it off)
+    DevBuf<int> d_order;           // launch order (hard-looking instances first)
+    bool use_order = true;
+    const nmpc_status *order_hint = nullptr;   // set by nmpc_loop_step for the duration of its solve: the previous step's statuses (launch order by their pass counts)
+    DevBuf<unsigned char> d_cls;
+    Staging stg;
+    SmallArena small;
     // wall-clock limits (nmpc_set_time_limits): as given, in ms, and in ticks of the 100 MHz constant clock (0 = off); any limit set -> the Timed<> kernels
-    double tl_dur_ms, tl_budget_ms;
-    long long tl_dur, tl_budget;
-    long long *d_t0;           // the launch's start, written by nmpc_stamp_kernel when a budget is set (allocated with the first budget)
+    double tl_dur_ms = 0.0, tl_budget_ms = 0.0;
+    long long tl_dur = 0, tl_budget = 0;
+    DevBuf<long long> d_t0;        // the launch's start, written by nmpc_stamp_kernel when a budget is set (allocated with the first budget)
     std::string err;
 };
 
@@ -137,6 +183,7 @@ static int fail(nmpc_handle *h, int code, const char *what, hipError_t e = hipSu
         if (e_ != hipSuccess) return fail((h), NMPC_ERR_HIP, #call, e_);       \
     } while (0)
 
+static constexpr size_t LDS_PER_CU = 160 * 1024;      // bytes of LDS a gfx950 CU has: what one workgroup can ask for
 static LdsMap make_map(const nmpc_problem &pb, int P) { return nmpc::lds_layout(pb.N, pb.nobs, pb.ndyn, P); }
 
 // The knobs of the experiments build (csrc/variants/libnmpc_experiments.so), read once into a new handle: tests use them to check that
@@ -147,7 +194,7 @@ static void read_knobs([[maybe_unused]] nmpc_handle *h)
     auto ival = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
     auto flag = [](const char *name, bool &v) { if (const char *e = getenv(name)) v = atoi(e) != 0; };
     auto pos = [](const char *name, double &v) { if (const char *e = getenv(name)) { const double x = atof(e); if (x > 0.0) v = x; } };
-    if (const char *e = getenv("NMPC_SHAPE"); e && !strcmp(e, "any")) h->shape_default = h->shape_nobs50 = h->shape_n40 = false;   // run-time-shape kernel
+    if (const char *e = getenv("NMPC_SHAPE")) h->shape_any = !strcmp(e, "any");
     ival("NMPC_PARK_MIN", h->park_min);          // 0 switches the slot migration off
     ival("NMPC_PARK_DEPTH", h->park_depth);
     flag("NMPC_LOOP_ORDER_PREV", h->loop_order_prev);
@@ -188,82 +235,40 @@ int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int m
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev)
         return NMPC_ERR_NO_DEVICE;
     nmpc_handle *h = new nmpc_handle();
-    h->pb = *pb; h->op = op; h->device = device_id; h->max_batch = max_batch; h->alive = true; h->last_ms = 0.0;
+    h->pb = *pb; h->op = op; h->device = device_id; h->max_batch = max_batch;
     h->P = pb->N <= 20 ? 20 : 40;      // one stage per lane (nmpc_solve_hyb.h) / two stages per lane (nmpc_solve_hyb2.h); longer horizons are not served
-    h->shape_default = pb->N == nmpc::ShapeDefault::N && pb->nobs == nmpc::ShapeDefault::NOBS &&
-                       pb->ndyn == nmpc::ShapeDefault::NDYN;
-    h->shape_nobs50 = pb->N == nmpc::ShapeNobs50::N && pb->nobs == nmpc::ShapeNobs50::NOBS &&
-                      pb->ndyn == nmpc::ShapeNobs50::NDYN;
-    h->shape_n40 = pb->N == nmpc::ShapeN40::N && pb->nobs == nmpc::ShapeN40::NOBS && pb->ndyn == nmpc::ShapeN40::NDYN;
     h->map = make_map(*pb, h->P == 40 ? 64 : h->P);      // (P = 40: the kernels compute their own map, nmpc_solve_hyb2.h)
-    h->d_queue = nullptr;
-    h->d_park = nullptr; h->d_pool = nullptr; h->d_pool_ctr = nullptr;
-    h->park_min = 500; h->park_depth = 8;
-    h->loop_order_prev = true;
     // long instances time-share beyond this fraction of the resident waves: the favoured half of them for the one-stage kernel (two waves per SIMD),
     // 0.8 for the two-stage kernel (one wave per SIMD); measured flat between 0.4 and 0.7 / 0.5 and 1.0 (profiles/r04/sched_sweep*.txt)
-    h->sched_mode = 1; h->sched_theta = h->P == 20 ? 0.5 : 0.8;
-    h->sched_cold = 0.4;
-    h->team_owners_forced = 0;
-    h->team_help = true; h->waves_per_cu = 0; h->dbg = 0;
+    h->sched_theta = h->P == 20 ? 0.5 : 0.8;
     // culling radius: what the input bounds let the robot travel in a horizon, plus a margin (any value is exact: an evaluation
     // with a stage beyond it scans every circle); NMPC_CULL_RADIUS overrides it (tests use 0.5 m: the fall-back runs all the time)
     h->cull_radius = 1.1 * pb->N * pb->ts * fmax(fabs(pb->vmin), fabs(pb->vmax));
-    h->use_order = true;
-    h->order_hint = nullptr;
     read_knobs(h);
-    h->d_order = nullptr;
-    h->d_cls = nullptr;
-    h->d_p = h->d_u = h->d_y0 = h->d_c0 = h->d_yout = h->d_psi = h->d_grad = h->d_F1 = h->d_F2 = nullptr;
-    h->h_pin[0] = h->h_pin[1] = nullptr; h->pin_ev[0] = h->pin_ev[1] = nullptr; h->staging_ready = false;
-    h->d_small = h->h_small = nullptr; h->small_ev[0] = h->small_ev[1] = nullptr; h->small_ready = false;
-    h->d_st = nullptr;
-    h->tl_dur_ms = h->tl_budget_ms = 0.0; h->tl_dur = h->tl_budget = 0; h->d_t0 = nullptr;
-    hipError_t e = hipSetDevice(device_id);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_queue, sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_order, sizeof(int) * (size_t)max_batch);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_cls, (size_t)max_batch);
-    if (e != hipSuccess) { nmpc_free(h); return NMPC_ERR_HIP; }
+    // the family's row specialised for this shape if there is one (and NMPC_SHAPE=any does not ask otherwise), else its run-time-shape row
+    for (const SolveKernel &k : nmpc::SOLVE_KERNELS)
+        if (k.P == h->P && (k.N == 0 ? !h->kernel[k.timed] : !h->shape_any && k.N == pb->N && k.nobs == pb->nobs && k.ndyn == pb->ndyn))
+            h->kernel[k.timed] = &k;
+    // one LDS slice per instance: the eval kernels hold three per wave, the solve kernels one per wave of a team of four plus the control block
+    const size_t slice = (size_t)(h->P == 40 ? nmpc::lds_layout2(pb->N, pb->nobs, pb->ndyn).total : h->map.total) * sizeof(double);
+    h->eval_lds = 3 * slice;
+    h->team_lds = nmpc::TEAM_WAVES * slice + nmpc::TEAM_CTL_INTS * sizeof(int);
+    if (h->eval_lds > LDS_PER_CU || h->team_lds > LDS_PER_CU) { nmpc_free(h); return NMPC_ERR_BAD_PROBLEM; }
     hipDeviceProp_t prop;
+    hipError_t e = hipSetDevice(device_id);
     (void)hipGetDeviceProperties(&prop, device_id);
-    const size_t lds_bytes = h->P == 40 ? (size_t)nmpc::lds_layout2(pb->N, pb->nobs, pb->ndyn).total * sizeof(double) * 3
-                                        : (size_t)h->map.total * sizeof(double) * (64 / h->P);   // eval kernel: one slice per group
-    if (lds_bytes > 160 * 1024) { nmpc_free(h); return NMPC_ERR_BAD_PROBLEM; }
-    // the solve kernels use one LDS slice per wave; resident waves per CU are bounded by LDS and by
-    // the register budget (2 waves per SIMD).  The hybrid kernel runs workgroups of four waves (teams).
-    int per_cu;
-    if (h->P == 20) {
-        const size_t wg_bytes = nmpc::TEAM_WAVES * (size_t)h->map.total * sizeof(double) + nmpc::TEAM_CTL_INTS * sizeof(int);
-        int wgs = (int)((160 * 1024) / wg_bytes);
-        if (wgs > 2) wgs = 2;
-        if (wgs < 1) { nmpc_free(h); return NMPC_ERR_BAD_PROBLEM; }
-        per_cu = wgs * nmpc::TEAM_WAVES;
-        h->team_lds = wg_bytes;
-        // more than 64 KB of dynamic LDS per workgroup has to be asked for
-        const int bytes = (int)wg_bytes;
-        e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeDefault>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeNobs50>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeAny>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeDefault>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeNobs50>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeAny>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) { nmpc_free(h); return NMPC_ERR_HIP; }
-    } else {
-        // two stages per lane: one wave per SIMD (512 registers), the four waves of a CU are one team
-        const size_t wg_bytes = nmpc::TEAM_WAVES * (size_t)nmpc::lds_layout2(pb->N, pb->nobs, pb->ndyn).total * sizeof(double) +
-                                nmpc::TEAM_CTL_INTS * sizeof(int);
-        if (wg_bytes > 160 * 1024) { nmpc_free(h); return NMPC_ERR_BAD_PROBLEM; }
-        per_cu = nmpc::TEAM_WAVES;
-        h->team_lds = wg_bytes;
-        e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeN40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeAny>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeN40>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeAny>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_eval2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) { nmpc_free(h); return NMPC_ERR_HIP; }
-    }
+    if (e == hipSuccess) e = h->d_queue.alloc(1);
+    if (e == hipSuccess) e = h->d_order.alloc(max_batch);
+    if (e == hipSuccess) e = h->d_cls.alloc(max_batch);
+    // more than 64 KB of dynamic LDS per workgroup has to be asked for
+    for (const SolveKernel &k : nmpc::SOLVE_KERNELS)
+        if (k.P == h->P && e == hipSuccess) e = hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->team_lds);
+    if (h->P == 40 && e == hipSuccess) e = hipFuncSetAttribute((const void *)nmpc::nmpc_eval2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->eval_lds);
+    if (e != hipSuccess) { nmpc_free(h); return NMPC_ERR_HIP; }
+    // resident waves per CU are bounded by LDS and by the register budget.  One stage per lane: two waves per SIMD, so up to two teams of
+    // four waves; two stages per lane: one wave per SIMD (512 registers), the four waves of a CU are one team.
+    int per_cu = nmpc::TEAM_WAVES * (h->P == 20 && 2 * h->team_lds <= LDS_PER_CU ? 2 : 1);
     if (h->waves_per_cu >= 1 && h->waves_per_cu <= per_cu && h->waves_per_cu % nmpc::TEAM_WAVES == 0) per_cu = h->waves_per_cu;
-    if (per_cu < 1) per_cu = 1;
     h->grid_cap = prop.multiProcessorCount * per_cu;
     *out = h;
     return NMPC_OK;
@@ -273,35 +278,14 @@ void nmpc_free(nmpc_handle *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)hipFree(h->d_queue); (void)hipFree(h->d_order); (void)hipFree(h->d_cls);
-    (void)hipFree(h->d_park); (void)hipFree(h->d_pool); (void)hipFree(h->d_pool_ctr);
-    for (int k = 0; k < 2; ++k) { if (h->h_pin[k]) (void)hipHostFree(h->h_pin[k]); if (h->pin_ev[k]) (void)hipEventDestroy(h->pin_ev[k]); }
-    (void)hipFree(h->d_small); if (h->h_small) (void)hipHostFree(h->h_small);
-    for (int k = 0; k < 2; ++k) if (h->small_ev[k]) (void)hipEventDestroy(h->small_ev[k]);
-    (void)hipFree(h->d_p); (void)hipFree(h->d_u); (void)hipFree(h->d_y0); (void)hipFree(h->d_c0); (void)hipFree(h->d_yout);
-    (void)hipFree(h->d_psi); (void)hipFree(h->d_grad); (void)hipFree(h->d_F1); (void)hipFree(h->d_F2); (void)hipFree(h->d_st);
-    (void)hipFree(h->d_t0);
-    delete h;
+    delete h;      // (every buffer and event is released by its member's destructor)
 }
 
 int nmpc_ping(const nmpc_handle *h) { return (h && h->alive) ? NMPC_OK : NMPC_ERR_DEAD_HANDLE; }
 const char *nmpc_last_error(const nmpc_handle *h) { return h ? h->err.c_str() : "null handle"; }
 double nmpc_last_batch_ms(const nmpc_handle *h) { return h ? h->last_ms : 0.0; }
 static bool timed(const nmpc_handle *h) { return h->tl_dur > 0 || h->tl_budget > 0; }
-const char *nmpc_kernel_name(const nmpc_handle *h)
-{
-    if (!h) return "";
-    if (timed(h)) {
-        if (h->P == 20)
-            return h->shape_default ? "nmpc_solve_hyb_kernel<Timed<ShapeDefault>>"
-                                    : (h->shape_nobs50 ? "nmpc_solve_hyb_kernel<Timed<ShapeNobs50>>" : "nmpc_solve_hyb_kernel<Timed<ShapeAny>>");
-        return h->shape_n40 ? "nmpc_solve_hyb2_kernel<Timed<ShapeN40>>" : "nmpc_solve_hyb2_kernel<Timed<ShapeAny>>";
-    }
-    if (h->P == 20)
-        return h->shape_default ? "nmpc_solve_hyb_kernel<ShapeDefault>"
-                                : (h->shape_nobs50 ? "nmpc_solve_hyb_kernel<ShapeNobs50>" : "nmpc_solve_hyb_kernel<ShapeAny>");
-    return h->shape_n40 ? "nmpc_solve_hyb2_kernel<ShapeN40>" : "nmpc_solve_hyb2_kernel<ShapeAny>";
-}
+const char *nmpc_kernel_name(const nmpc_handle *h) { return h ? h->kernel[timed(h)]->name : ""; }
 
 // a limit in ms -> ticks of the 100 MHz clock: 0 stays 0 (off), anything above it is at least one tick, and at most 2^52 ticks (16 months)
 static long long ms_to_ticks(double ms)
@@ -322,10 +306,19 @@ int nmpc_set_time_limits(nmpc_handle *h, double max_duration_ms, double batch_bu
     const long long budget = ms_to_ticks(batch_budget_ms);
     if (budget > 0 && !h->d_t0) {
         HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipMalloc((void **)&h->d_t0, sizeof(long long)));
+        HIP_TRY(h, h->d_t0.alloc(1));
     }
     h->tl_dur_ms = max_duration_ms; h->tl_budget_ms = batch_budget_ms;
     h->tl_dur = ms_to_ticks(max_duration_ms); h->tl_budget = budget;
+    return NMPC_OK;
+}
+
+// what the batch entry points check first (NMPC_OK with B == 0: nothing to do)
+static int check_batch(nmpc_handle *h, int B, const double *p, const double *u)
+{
+    if (!h) return NMPC_ERR_BAD_ARG;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (B < 0 || B > h->max_batch || (B > 0 && (!p || !u))) return fail(h, NMPC_ERR_BAD_ARG, "bad batch arguments");
     return NMPC_OK;
 }
 
@@ -338,47 +331,44 @@ static void fill_args(const nmpc_handle *h, KArgs &a, int B)
     a.inv_ts = 1.0 / h->pb.ts;
     a.dbg = h->dbg;
     a.tl_dur = h->tl_dur; a.tl_budget = h->tl_budget;
-    a.tl_t0 = h->tl_budget > 0 ? h->d_t0 : nullptr;
+    a.tl_t0 = h->tl_budget > 0 ? h->d_t0.p : nullptr;
 }
 
 int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_u, const double *d_y0,
                             const double *d_c0, double *d_y_out, nmpc_status *d_status, void *stream)
 {
-    if (!h) return NMPC_ERR_BAD_ARG;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (B < 0 || B > h->max_batch || (B > 0 && (!d_p || !d_u))) return fail(h, NMPC_ERR_BAD_ARG, "bad batch arguments");
-    if (B == 0) return NMPC_OK;
+    if (const int rc = check_batch(h, B, d_p, d_u); rc || B == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->device));
     KArgs a;
     fill_args(h, a, B);
     a.p = d_p; a.u = d_u; a.y0 = d_y0; a.c0 = d_c0; a.y_out = d_y_out; a.st = d_status;
     // a batch budget counts from one clock reading on the device, taken before anything of this launch runs (nothing is enqueued without one)
-    if (h->tl_budget > 0) hipLaunchKernelGGL(nmpc_stamp_kernel, dim3(1), dim3(64), 0, s, h->d_t0);
+    if (h->tl_budget > 0) hipLaunchKernelGGL(nmpc_stamp_kernel, dim3(1), dim3(64), 0, s, h->d_t0.p);
     HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, sizeof(unsigned int), s));
     // one instance per wave, three query points per pass: N_hor <= 20 with one stage per lane (hybrid / tri layouts), 20 < N_hor <= 40 with two
     const int grid = B < h->grid_cap ? B : h->grid_cap;          // waves that take instances
     if (B > grid) {        // more instances than resident waves: hand the hard-looking ones out first
         if (h->use_order) {
-            if (h->order_hint) hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, h->order_hint, h->d_cls);
-            else hipLaunchKernelGGL(nmpc::nmpc_classify_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a, h->d_cls);
-            hipLaunchKernelGGL(nmpc::nmpc_order_kernel, dim3(1), dim3(1024), 0, s, B, h->d_cls, h->d_order);
+            if (h->order_hint) hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, h->order_hint, h->d_cls.p);
+            else hipLaunchKernelGGL(nmpc::nmpc_classify_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a, h->d_cls.p);
+            hipLaunchKernelGGL(nmpc::nmpc_order_kernel, dim3(1), dim3(1024), 0, s, B, h->d_cls.p, h->d_order.p);
             a.order = h->d_order;
         }
         if ((h->P == 20 && (h->park_min > 0 || h->sched_mode > 0)) || (h->P == 40 && h->sched_mode > 0)) {      // instances may leave their wave at outer-iteration boundaries
             const size_t cap = (size_t)B;                 // ring buffers of this launch: an instance waits in at most one slot at a time
             const size_t cap_max = (size_t)h->max_batch;
-            if (!h->d_park || !h->d_pool || !h->d_pool_ctr) {      // (all three or none: a half-made set is freed and made again)
-                (void)hipFree(h->d_park); (void)hipFree(h->d_pool); (void)hipFree(h->d_pool_ctr);
-                h->d_park = nullptr; h->d_pool = nullptr; h->d_pool_ctr = nullptr;
-                HIP_TRY(h, hipMalloc((void **)&h->d_park, (size_t)h->max_batch * nmpc::park_stride(h->pb.N) * 8));
-                HIP_TRY(h, hipMalloc((void **)&h->d_pool, nmpc::NPOOLS * cap_max * sizeof(int)));
-                HIP_TRY(h, hipMalloc((void **)&h->d_pool_ctr, (4 * nmpc::NPOOLS + 2) * sizeof(unsigned int)));
+            Pools &pl = h->pools;
+            if (!pl.made()) {      // (all three or none: a half-made set is released and made again)
+                pl.release();
+                HIP_TRY(h, pl.park.alloc(cap_max * nmpc::park_stride(h->pb.N)));
+                HIP_TRY(h, pl.pool.alloc(nmpc::NPOOLS * cap_max));
+                HIP_TRY(h, pl.ctr.alloc(4 * nmpc::NPOOLS + 2));
             }
-            HIP_TRY(h, hipMemsetAsync(h->d_pool, 0xFF, nmpc::NPOOLS * cap * sizeof(int), s));
-            HIP_TRY(h, hipMemsetAsync(h->d_pool_ctr, 0, (4 * nmpc::NPOOLS + 2) * sizeof(unsigned int), s));
+            HIP_TRY(h, hipMemsetAsync(pl.pool, 0xFF, nmpc::NPOOLS * cap * sizeof(int), s));
+            HIP_TRY(h, hipMemsetAsync(pl.ctr, 0, (4 * nmpc::NPOOLS + 2) * sizeof(unsigned int), s));
             a.park_min = h->P == 20 ? h->park_min : 0; a.park_depth = h->park_depth;      // (the slot migration is the one-stage kernel's: two waves per SIMD)
-            a.park = h->d_park; a.pool = h->d_pool; a.pool_ctr = h->d_pool_ctr; a.pool_cap = (int)cap;
+            a.park = pl.park; a.pool = pl.pool; a.pool_ctr = pl.ctr; a.pool_cap = (int)cap;
             a.sched_mode = h->sched_mode;
         }
     }
@@ -397,23 +387,8 @@ int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_
         a.sched_cold_cap = (int)(h->sched_cold * (double)(wgs * owners));
         a.team_help = h->team_help;
         a.cull_radius = h->cull_radius;
-        const size_t tlds = h->team_lds;
-        if (timed(h)) {           // the same kernels with the wall-clock test compiled in (nmpc_set_time_limits)
-            if (h->P == 40) {
-                if (h->shape_n40) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeN40>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-                else hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::Timed<nmpc::ShapeAny>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-            }
-            else if (h->shape_default) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeDefault>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-            else if (h->shape_nobs50) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeNobs50>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-            else hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::Timed<nmpc::ShapeAny>>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-        }
-        else if (h->P == 40) {
-            if (h->shape_n40) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeN40>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-            else hipLaunchKernelGGL(nmpc::nmpc_solve_hyb2_kernel<nmpc::ShapeAny>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-        }
-        else if (h->shape_default) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeDefault>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-        else if (h->shape_nobs50) hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeNobs50>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
-        else hipLaunchKernelGGL(nmpc::nmpc_solve_hyb_kernel<nmpc::ShapeAny>, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), tlds, s, a);
+        // (with a limit set: the same kernel with the wall-clock test compiled in, nmpc_set_time_limits)
+        hipLaunchKernelGGL(h->kernel[timed(h)]->fn, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), h->team_lds, s, a);
     }
     HIP_TRY(h, hipGetLastError());
     return NMPC_OK;
@@ -423,26 +398,16 @@ int nmpc_eval_batch_device(nmpc_handle *h, int B, const double *d_p, const doubl
                            const double *d_y, double *d_psi, double *d_grad, double *d_F1, double *d_F2,
                            void *stream)
 {
-    if (!h) return NMPC_ERR_BAD_ARG;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (B < 0 || B > h->max_batch || (B > 0 && (!d_p || !d_u))) return fail(h, NMPC_ERR_BAD_ARG, "bad batch arguments");
-    if (B == 0) return NMPC_OK;
+    if (const int rc = check_batch(h, B, d_p, d_u); rc || B == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->device));
     KArgs a;
     fill_args(h, a, B);
     a.p = d_p; a.u = const_cast<double *>(d_u);
     a.ev_c = d_c; a.ev_y = d_y; a.ev_psi = d_psi; a.ev_grad = d_grad; a.ev_F1 = d_F1; a.ev_F2 = d_F2;
-    if (h->P == 40) {          // two stages per lane: three instances per wave
-        const size_t lds2 = (size_t)nmpc::lds_layout2(h->pb.N, h->pb.nobs, h->pb.ndyn).total * sizeof(double) * 3;
-        hipLaunchKernelGGL(nmpc::nmpc_eval2_kernel, dim3((B + 2) / 3), dim3(64), lds2, s, a);
-        HIP_TRY(h, hipGetLastError());
-        return NMPC_OK;
-    }
-    const int K = 3;                       // instances per wave: the tri layout
-    const int grid = (B + K - 1) / K;
-    const size_t lds = (size_t)h->map.total * sizeof(double) * K;
-    hipLaunchKernelGGL(nmpc::nmpc_eval_kernel<20>, dim3(grid), dim3(64), lds, s, a);
+    const dim3 grid((B + 2) / 3);          // three instances per wave (the tri layout; two stages per lane for P = 40)
+    if (h->P == 40) hipLaunchKernelGGL(nmpc::nmpc_eval2_kernel, grid, dim3(64), h->eval_lds, s, a);
+    else hipLaunchKernelGGL(nmpc::nmpc_eval_kernel<20>, grid, dim3(64), h->eval_lds, s, a);
     HIP_TRY(h, hipGetLastError());
     return NMPC_OK;
 }
@@ -451,26 +416,27 @@ int nmpc_eval_batch_device(nmpc_handle *h, int B, const double *d_p, const doubl
 static constexpr size_t PIN_CHUNK = 4u << 20;
 static int ensure_staging(nmpc_handle *h)
 {
-    if (h->staging_ready) return NMPC_OK;
-    if (h->d_p) return fail(h, NMPC_ERR_HIP, "staging buffers: an earlier allocation failed half way");
+    Staging &g = h->stg;
+    if (g.ready) return NMPC_OK;
+    if (g.p) return fail(h, NMPC_ERR_HIP, "staging buffers: an earlier allocation failed half way");
     const size_t B = (size_t)h->max_batch;
     const size_t np = nmpc_n_p(&h->pb), nu = nmpc_n_u(&h->pb), n1 = nmpc_n1(&h->pb), n2 = nmpc_n2(&h->pb) + 1;
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMalloc((void **)&h->d_p, B * np * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_u, B * nu * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_y0, B * n1 * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_c0, B * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_yout, B * n1 * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_psi, B * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_grad, B * nu * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_F1, B * n1 * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_F2, B * n2 * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_st, B * sizeof(nmpc_status)));
+    HIP_TRY(h, g.p.alloc(B * np));
+    HIP_TRY(h, g.u.alloc(B * nu));
+    HIP_TRY(h, g.y0.alloc(B * n1));
+    HIP_TRY(h, g.c0.alloc(B));
+    HIP_TRY(h, g.yout.alloc(B * n1));
+    HIP_TRY(h, g.psi.alloc(B));
+    HIP_TRY(h, g.grad.alloc(B * nu));
+    HIP_TRY(h, g.F1.alloc(B * n1));
+    HIP_TRY(h, g.F2.alloc(B * n2));
+    HIP_TRY(h, g.st.alloc(B));
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY(h, hipHostMalloc((void **)&h->h_pin[k], PIN_CHUNK, hipHostMallocDefault));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->pin_ev[k], hipEventDisableTiming));
+        HIP_TRY(h, g.pin[k].alloc(PIN_CHUNK));
+        HIP_TRY(h, g.ev[k].create(hipEventDisableTiming));
     }
-    h->staging_ready = true;
+    g.ready = true;
     return NMPC_OK;
 }
 
@@ -482,11 +448,11 @@ static hipError_t h2d_staged(nmpc_handle *h, void *dst, const void *src, size_t 
     int k = 0;
     for (size_t off = 0; off < bytes && e == hipSuccess; off += PIN_CHUNK, k ^= 1) {
         const size_t n = bytes - off < PIN_CHUNK ? bytes - off : PIN_CHUNK;
-        e = hipEventSynchronize(h->pin_ev[k]);                       // (the copy that last used this buffer; a fresh event is complete)
+        e = hipEventSynchronize(h->stg.ev[k]);                       // (the copy that last used this buffer; a fresh event is complete)
         if (e != hipSuccess) break;
-        std::memcpy(h->h_pin[k], (const char *)src + off, n);
-        e = hipMemcpyAsync((char *)dst + off, h->h_pin[k], n, hipMemcpyHostToDevice, nullptr);
-        if (e == hipSuccess) e = hipEventRecord(h->pin_ev[k], nullptr);
+        std::memcpy(h->stg.pin[k], (const char *)src + off, n);
+        e = hipMemcpyAsync((char *)dst + off, h->stg.pin[k], n, hipMemcpyHostToDevice, nullptr);
+        if (e == hipSuccess) e = hipEventRecord(h->stg.ev[k], nullptr);
     }
     return e;
 }
@@ -498,18 +464,18 @@ static hipError_t d2h_staged(nmpc_handle *h, void *dst, const void *src, size_t 
     for (size_t off = 0; off < bytes && e == hipSuccess; off += PIN_CHUNK, k ^= 1) {
         const size_t n = bytes - off < PIN_CHUNK ? bytes - off : PIN_CHUNK;
         if (pend_n[k]) {                                             // drain what this buffer still holds
-            e = hipEventSynchronize(h->pin_ev[k]);
+            e = hipEventSynchronize(h->stg.ev[k]);
             if (e != hipSuccess) break;
-            std::memcpy((char *)dst + pend_off[k], h->h_pin[k], pend_n[k]);
+            std::memcpy((char *)dst + pend_off[k], h->stg.pin[k], pend_n[k]);
         }
-        e = hipMemcpyAsync(h->h_pin[k], (const char *)src + off, n, hipMemcpyDeviceToHost, nullptr);
-        if (e == hipSuccess) e = hipEventRecord(h->pin_ev[k], nullptr);
+        e = hipMemcpyAsync(h->stg.pin[k], (const char *)src + off, n, hipMemcpyDeviceToHost, nullptr);
+        if (e == hipSuccess) e = hipEventRecord(h->stg.ev[k], nullptr);
         pend_off[k] = off; pend_n[k] = n;
     }
     for (int j = 0; j < 2 && e == hipSuccess; ++j, k ^= 1)           // the last one or two chunks, oldest first
         if (pend_n[k]) {
-            e = hipEventSynchronize(h->pin_ev[k]);
-            if (e == hipSuccess) std::memcpy((char *)dst + pend_off[k], h->h_pin[k], pend_n[k]);
+            e = hipEventSynchronize(h->stg.ev[k]);
+            if (e == hipSuccess) std::memcpy((char *)dst + pend_off[k], h->stg.pin[k], pend_n[k]);
             pend_n[k] = 0;
         }
     return e;
@@ -524,32 +490,31 @@ static int solve_small_host(nmpc_handle *h, int B, const double *p, double *u, c
     const size_t o_p = 0, o_c = o_p + cap * np * 8, o_y = o_c + cap * 8, o_u = o_y + cap * n1 * 8, o_yo = o_u + cap * nu * 8,
                  o_st = o_yo + cap * n1 * 8, total = o_st + cap * sizeof(nmpc_status);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->small_ready) {
+    SmallArena &g = h->small;
+    if (!g.ready) {
         // all or none: what an earlier, failed attempt left behind is released first, so a transient failure costs one call, not the handle's small-batch path
-        (void)hipFree(h->d_small); h->d_small = nullptr;
-        if (h->h_small) { (void)hipHostFree(h->h_small); h->h_small = nullptr; }
-        for (int k = 0; k < 2; ++k) if (h->small_ev[k]) { (void)hipEventDestroy(h->small_ev[k]); h->small_ev[k] = nullptr; }
-        HIP_TRY(h, hipMalloc((void **)&h->d_small, total));
-        HIP_TRY(h, hipHostMalloc((void **)&h->h_small, total, hipHostMallocDefault));
-        for (int k = 0; k < 2; ++k) HIP_TRY(h, hipEventCreate(&h->small_ev[k]));
-        h->small_ready = true;
+        g.release();
+        HIP_TRY(h, g.d.alloc(total));
+        HIP_TRY(h, g.h.alloc(total));
+        for (int k = 0; k < 2; ++k) HIP_TRY(h, g.ev[k].create());
+        g.ready = true;
     }
-    char *hs = h->h_small, *ds = h->d_small;
+    char *hs = g.h, *ds = g.d;
     // in: p .. u of the B instances (each array at its arena offset; only what is used travels, as one copy from the first to the last byte used)
     std::memcpy(hs + o_p, p, B * np * 8);
     if (c0) std::memcpy(hs + o_c, c0, B * 8);
     if (y0) std::memcpy(hs + o_y, y0, B * n1 * 8);
     std::memcpy(hs + o_u, u, B * nu * 8);
     HIP_TRY(h, hipMemcpyAsync(ds, hs, o_u + B * nu * 8, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(h, hipEventRecord(h->small_ev[0], nullptr));
+    HIP_TRY(h, hipEventRecord(g.ev[0], nullptr));
     const int rc = nmpc_solve_batch_device(h, B, (const double *)(ds + o_p), (double *)(ds + o_u), y0 ? (const double *)(ds + o_y) : nullptr,
                                            c0 ? (const double *)(ds + o_c) : nullptr, (double *)(ds + o_yo), (nmpc_status *)(ds + o_st), nullptr);
     if (rc) return rc;
-    HIP_TRY(h, hipEventRecord(h->small_ev[1], nullptr));
+    HIP_TRY(h, hipEventRecord(g.ev[1], nullptr));
     HIP_TRY(h, hipMemcpyAsync(hs + o_u, ds + o_u, total - o_u, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(h, hipStreamSynchronize(nullptr));
     float ms = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->small_ev[0], h->small_ev[1]));
+    HIP_TRY(h, hipEventElapsedTime(&ms, g.ev[0], g.ev[1]));
     h->last_ms = (double)ms;
     std::memcpy(u, hs + o_u, B * nu * 8);
     if (y_out) std::memcpy(y_out, hs + o_yo, B * n1 * 8);
@@ -560,80 +525,74 @@ static int solve_small_host(nmpc_handle *h, int B, const double *p, double *u, c
 int nmpc_solve_batch_host(nmpc_handle *h, int B, const double *p, double *u, const double *y0, const double *c0,
                           double *y_out, nmpc_status *status)
 {
-    if (!h) return NMPC_ERR_BAD_ARG;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (B < 0 || B > h->max_batch || (B > 0 && (!p || !u))) return fail(h, NMPC_ERR_BAD_ARG, "bad batch arguments");
-    if (B == 0) return NMPC_OK;
+    if (const int rc = check_batch(h, B, p, u); rc || B == 0) return rc;
     if (B <= SMALL_BATCH) return solve_small_host(h, B, p, u, y0, c0, y_out, status);
     int rc = ensure_staging(h);
     if (rc) return rc;
+    const Staging &g = h->stg;
     const size_t np = nmpc_n_p(&h->pb), nu = nmpc_n_u(&h->pb), n1 = nmpc_n1(&h->pb);
-    HIP_TRY(h, h2d_staged(h, h->d_p, p, B * np * 8));
-    HIP_TRY(h, h2d_staged(h, h->d_u, u, B * nu * 8));
-    if (y0) HIP_TRY(h, h2d_staged(h, h->d_y0, y0, B * n1 * 8));
-    if (c0) HIP_TRY(h, h2d_staged(h, h->d_c0, c0, B * 8));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_TRY(h, h2d_staged(h, g.p, p, B * np * 8));
+    HIP_TRY(h, h2d_staged(h, g.u, u, B * nu * 8));
+    if (y0) HIP_TRY(h, h2d_staged(h, g.y0, y0, B * n1 * 8));
+    if (c0) HIP_TRY(h, h2d_staged(h, g.c0, c0, B * 8));
+    Event e0, e1;
     float ms = 0.f;
-    hipError_t he = hipEventCreate(&e0);
-    if (he == hipSuccess) he = hipEventCreate(&e1);
+    hipError_t he = e0.create();
+    if (he == hipSuccess) he = e1.create();
     if (he == hipSuccess) he = hipEventRecord(e0, nullptr);
     if (he == hipSuccess) {
-        rc = nmpc_solve_batch_device(h, B, h->d_p, h->d_u, y0 ? h->d_y0 : nullptr, c0 ? h->d_c0 : nullptr,
-                                     h->d_yout, h->d_st, nullptr);
+        rc = nmpc_solve_batch_device(h, B, g.p, g.u, y0 ? g.y0.p : nullptr, c0 ? g.c0.p : nullptr,
+                                     g.yout, g.st, nullptr);
         if (rc == NMPC_OK) {
             he = hipEventRecord(e1, nullptr);
             if (he == hipSuccess) he = hipDeviceSynchronize();
             if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
         }
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     if (rc) return rc;
     if (he != hipSuccess) return fail(h, NMPC_ERR_HIP, "solve_batch_host", he);
     h->last_ms = (double)ms;
-    HIP_TRY(h, d2h_staged(h, u, h->d_u, B * nu * 8));
-    if (y_out) HIP_TRY(h, d2h_staged(h, y_out, h->d_yout, B * n1 * 8));
-    if (status) HIP_TRY(h, d2h_staged(h, status, h->d_st, B * sizeof(nmpc_status)));
+    HIP_TRY(h, d2h_staged(h, u, g.u, B * nu * 8));
+    if (y_out) HIP_TRY(h, d2h_staged(h, y_out, g.yout, B * n1 * 8));
+    if (status) HIP_TRY(h, d2h_staged(h, status, g.st, B * sizeof(nmpc_status)));
     return NMPC_OK;
 }
 
 int nmpc_eval_batch_host(nmpc_handle *h, int B, const double *p, const double *u, const double *c, const double *y,
                          double *psi, double *grad, double *F1, double *F2)
 {
-    if (!h) return NMPC_ERR_BAD_ARG;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (B < 0 || B > h->max_batch || (B > 0 && (!p || !u))) return fail(h, NMPC_ERR_BAD_ARG, "bad batch arguments");
-    if (B == 0) return NMPC_OK;
+    if (const int rc = check_batch(h, B, p, u); rc || B == 0) return rc;
     int rc = ensure_staging(h);
     if (rc) return rc;
+    const Staging &g = h->stg;
     const size_t np = nmpc_n_p(&h->pb), nu = nmpc_n_u(&h->pb), n1 = nmpc_n1(&h->pb), n2 = nmpc_n2(&h->pb);
-    HIP_TRY(h, h2d_staged(h, h->d_p, p, B * np * 8));
-    HIP_TRY(h, h2d_staged(h, h->d_u, u, B * nu * 8));
-    if (y) HIP_TRY(h, h2d_staged(h, h->d_y0, y, B * n1 * 8));
-    if (c) HIP_TRY(h, h2d_staged(h, h->d_c0, c, B * 8));
-    rc = nmpc_eval_batch_device(h, B, h->d_p, h->d_u, c ? h->d_c0 : nullptr, y ? h->d_y0 : nullptr, h->d_psi,
-                                h->d_grad, h->d_F1, h->d_F2, nullptr);
+    HIP_TRY(h, h2d_staged(h, g.p, p, B * np * 8));
+    HIP_TRY(h, h2d_staged(h, g.u, u, B * nu * 8));
+    if (y) HIP_TRY(h, h2d_staged(h, g.y0, y, B * n1 * 8));
+    if (c) HIP_TRY(h, h2d_staged(h, g.c0, c, B * 8));
+    rc = nmpc_eval_batch_device(h, B, g.p, g.u, c ? g.c0.p : nullptr, y ? g.y0.p : nullptr, g.psi,
+                                g.grad, g.F1, g.F2, nullptr);
     if (rc) return rc;
     HIP_TRY(h, hipDeviceSynchronize());
-    if (psi) HIP_TRY(h, hipMemcpy(psi, h->d_psi, B * 8, hipMemcpyDeviceToHost));
-    if (grad) HIP_TRY(h, hipMemcpy(grad, h->d_grad, B * nu * 8, hipMemcpyDeviceToHost));
-    if (F1) HIP_TRY(h, hipMemcpy(F1, h->d_F1, B * n1 * 8, hipMemcpyDeviceToHost));
-    if (F2 && n2) HIP_TRY(h, hipMemcpy(F2, h->d_F2, B * n2 * 8, hipMemcpyDeviceToHost));
+    if (psi) HIP_TRY(h, hipMemcpy(psi, g.psi, B * 8, hipMemcpyDeviceToHost));
+    if (grad) HIP_TRY(h, hipMemcpy(grad, g.grad, B * nu * 8, hipMemcpyDeviceToHost));
+    if (F1) HIP_TRY(h, hipMemcpy(F1, g.F1, B * n1 * 8, hipMemcpyDeviceToHost));
+    if (F2 && n2) HIP_TRY(h, hipMemcpy(F2, g.F2, B * n2 * 8, hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 
 // ---- receding-horizon loop on device (nmpc_loop.h) ----
 struct nmpc_loop {
-    nmpc_handle *h;
-    nmpc::LoopArgs a;            // device pointers and constants; t / dyn_in / dyn_out / traj_row change per step
-    int steps, max_steps;
-    double *d_tab;               // every route's tables, one allocation
-    nmpc::LoopRoute *d_routes;   // [R]
-    int *d_route_of;             // [B]
-    double *d_dynpar, *d_state, *d_last_u, *d_dyn[2], *d_P, *d_U, *d_Y, *d_traj;
-    int *d_idx;
-    unsigned char *d_done;
-    nmpc_status *d_st;
+    nmpc_handle *h = nullptr;
+    nmpc::LoopArgs a{};          // device pointers and constants; t / dyn_in / dyn_out / traj_row change per step
+    int steps = 0, max_steps = 0;
+    DevBuf<double> d_tab;        // every route's tables, one allocation
+    DevBuf<nmpc::LoopRoute> d_routes;   // [R]
+    DevBuf<int> d_route_of;      // [B]
+    DevBuf<double> d_dynpar, d_state, d_last_u, d_dyn[2], d_P, d_U, d_Y, d_traj;
+    DevBuf<int> d_idx;
+    DevBuf<unsigned char> d_done;
+    DevBuf<nmpc_status> d_st;
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -664,7 +623,6 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
     if (idx0) for (int b = 0; b < B; ++b) if (idx0[b] < 0 || idx0[b] >= routes[route_of ? route_of[b] : 0].n_ref) return fail(h, NMPC_ERR_BAD_ARG, "idx0 out of range");
     HIP_TRY(h, hipSetDevice(h->device));
     nmpc_loop *l = new nmpc_loop();
-    std::memset(l, 0, sizeof(*l));
     l->h = h;
     l->max_steps = max_steps;
     nmpc::LoopArgs &a = l->a;
@@ -673,22 +631,21 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
     a.s = routes[0].num_steps_taken; a.t = 0;
     a.ts = h->pb.ts;
     const size_t n1 = nmpc_n1(&h->pb), ndynrow = (size_t)a.ndyn * a.N * 5;
-    hipError_t e = hipMalloc((void **)&l->d_tab, (ntab ? ntab : 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_routes, (size_t)R * sizeof(nmpc::LoopRoute));
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_route_of, (size_t)B * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_dynpar, ((size_t)B * (K ? K : 1)) * 10 * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_state, (size_t)B * 3 * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_last_u, (size_t)B * 2 * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_dyn[0], (size_t)B * (ndynrow ? ndynrow : 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_dyn[1], (size_t)B * (ndynrow ? ndynrow : 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_P, (size_t)B * a.n_p * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_U, (size_t)B * a.n_u * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_Y, (size_t)B * n1 * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_idx, (size_t)B * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_done, (size_t)B);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->d_st, (size_t)B * sizeof(nmpc_status));
-    if (e == hipSuccess && max_steps > 0)
-        e = hipMalloc((void **)&l->d_traj, ((size_t)max_steps * a.s + 1) * B * 3 * 8);
+    hipError_t e = l->d_tab.alloc(ntab ? ntab : 1);
+    if (e == hipSuccess) e = l->d_routes.alloc(R);
+    if (e == hipSuccess) e = l->d_route_of.alloc(B);
+    if (e == hipSuccess) e = l->d_dynpar.alloc((size_t)B * (K ? K : 1) * 10);
+    if (e == hipSuccess) e = l->d_state.alloc((size_t)B * 3);
+    if (e == hipSuccess) e = l->d_last_u.alloc((size_t)B * 2);
+    if (e == hipSuccess) e = l->d_dyn[0].alloc((size_t)B * (ndynrow ? ndynrow : 1));
+    if (e == hipSuccess) e = l->d_dyn[1].alloc((size_t)B * (ndynrow ? ndynrow : 1));
+    if (e == hipSuccess) e = l->d_P.alloc((size_t)B * a.n_p);
+    if (e == hipSuccess) e = l->d_U.alloc((size_t)B * a.n_u);
+    if (e == hipSuccess) e = l->d_Y.alloc((size_t)B * n1);
+    if (e == hipSuccess) e = l->d_idx.alloc(B);
+    if (e == hipSuccess) e = l->d_done.alloc(B);
+    if (e == hipSuccess) e = l->d_st.alloc(B);
+    if (e == hipSuccess && max_steps > 0) e = l->d_traj.alloc(((size_t)max_steps * a.s + 1) * B * 3);
     if (e != hipSuccess) { nmpc_loop_free(l); return fail(h, NMPC_ERR_HIP, "nmpc_loop_new: hipMalloc", e); }
     // route tables, route after route: x_ref | y_ref | theta_ref | vertices | brake velocities | brake distances
     std::vector<double> tab(ntab);
@@ -745,11 +702,15 @@ void nmpc_loop_free(nmpc_loop *l)
 {
     if (!l) return;
     (void)hipSetDevice(l->h->device);
-    (void)hipFree(l->d_tab); (void)hipFree(l->d_routes); (void)hipFree(l->d_route_of); (void)hipFree(l->d_dynpar); (void)hipFree(l->d_state); (void)hipFree(l->d_last_u);
-    (void)hipFree(l->d_dyn[0]); (void)hipFree(l->d_dyn[1]); (void)hipFree(l->d_P); (void)hipFree(l->d_U);
-    (void)hipFree(l->d_Y); (void)hipFree(l->d_idx); (void)hipFree(l->d_done); (void)hipFree(l->d_st);
-    (void)hipFree(l->d_traj);
     delete l;
+}
+
+// the loop's readers: on its device, after everything enqueued there has finished
+static int loop_settle(nmpc_handle *h)
+{
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    return NMPC_OK;
 }
 
 int nmpc_loop_step(nmpc_loop *l, void *stream)
@@ -769,7 +730,7 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     // warm start: previous controls and multipliers, penalty back to its initial value (the server's behaviour)
     // launch order: from the second step on, by the pass counts of the step before (read by the classification kernel ahead of the solve, which
     // then overwrites them); the first step has only the inputs to go by
-    h->order_hint = (l->steps > 0 && h->loop_order_prev) ? l->d_st : nullptr;
+    h->order_hint = (l->steps > 0 && h->loop_order_prev) ? l->d_st.p : nullptr;
     const int rc = nmpc_solve_batch_device(h, a.B, l->d_P, l->d_U, l->d_Y, nullptr, l->d_Y, l->d_st, stream);
     h->order_hint = nullptr;
     if (rc) return rc;
@@ -785,8 +746,7 @@ int nmpc_loop_read(nmpc_loop *l, double *state, double *last_u, int32_t *idx, ui
 {
     if (!l) return NMPC_ERR_BAD_ARG;
     nmpc_handle *h = l->h;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipDeviceSynchronize());
+    if (const int rc = loop_settle(h)) return rc;
     const size_t B = (size_t)l->a.B;
     if (state) HIP_TRY(h, hipMemcpy(state, l->d_state, B * 3 * 8, hipMemcpyDeviceToHost));
     if (last_u) HIP_TRY(h, hipMemcpy(last_u, l->d_last_u, B * 2 * 8, hipMemcpyDeviceToHost));
@@ -800,8 +760,7 @@ int nmpc_loop_params(nmpc_loop *l, double *p, double *u, double *y)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
     nmpc_handle *h = l->h;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipDeviceSynchronize());
+    if (const int rc = loop_settle(h)) return rc;
     const size_t B = (size_t)l->a.B;
     if (p) HIP_TRY(h, hipMemcpy(p, l->d_P, B * l->a.n_p * 8, hipMemcpyDeviceToHost));
     if (u) HIP_TRY(h, hipMemcpy(u, l->d_U, B * l->a.n_u * 8, hipMemcpyDeviceToHost));
@@ -816,8 +775,7 @@ int nmpc_loop_trajectory(nmpc_loop *l, double *rows, int max_rows)
     if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "the loop was created without a trajectory buffer");
     const int nrows = l->steps * l->a.s + 1;
     if (max_rows < nrows) return fail(h, NMPC_ERR_BAD_ARG, "trajectory does not fit");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipDeviceSynchronize());
+    if (const int rc = loop_settle(h)) return rc;
     HIP_TRY(h, hipMemcpy(rows, l->d_traj, (size_t)nrows * l->a.B * 3 * 8, hipMemcpyDeviceToHost));
     return nrows;
 }
@@ -839,21 +797,20 @@ static int run_unary_test(nmpc_handle *h, int n, const double *x0, const double 
     if (!h || n < 0 || !x0 || !o0 || !o1) return NMPC_ERR_BAD_ARG;
     if (n == 0) return NMPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    double *d[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevBuf<double> d[4];
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipMalloc((void **)&d[i], (size_t)n * 8);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = d[i].alloc(n);
     if (e == hipSuccess) e = hipMemcpy(d[0], x0, (size_t)n * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && x1) e = hipMemcpy(d[1], x1, (size_t)n * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const int blocks = (n + 255) / 256;
-        if (which == 0) hipLaunchKernelGGL(nmpc_test_sincos_kernel, dim3(blocks), dim3(256), 0, nullptr, n, d[0], d[2], d[3]);
-        else hipLaunchKernelGGL(nmpc_test_divsqrt_kernel, dim3(blocks), dim3(256), 0, nullptr, n, d[0], d[1], d[2], d[3]);
+        if (which == 0) hipLaunchKernelGGL(nmpc_test_sincos_kernel, dim3(blocks), dim3(256), 0, nullptr, n, d[0].p, d[2].p, d[3].p);
+        else hipLaunchKernelGGL(nmpc_test_divsqrt_kernel, dim3(blocks), dim3(256), 0, nullptr, n, d[0].p, d[1].p, d[2].p, d[3].p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(o0, d[2], (size_t)n * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(o1, d[3], (size_t)n * 8, hipMemcpyDeviceToHost);
-    for (int i = 0; i < 4; ++i) (void)hipFree(d[i]);
     return e == hipSuccess ? NMPC_OK : fail(h, NMPC_ERR_HIP, "arithmetic primitive test", e);
 }
 
