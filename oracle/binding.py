@@ -98,6 +98,12 @@ class Oracle:
         self.n1 = self.lib.orc_n1(C.byref(self.pb))
         self.n2 = self.lib.orc_n2(C.byref(self.pb))
 
+    @classmethod
+    def for_config(cls, cfg, **opts):
+        """The oracle for the problem shape of a ``Config``."""
+        return cls(cfg.N_hor, cfg.Nobs, cfg.Ndynobs, cfg.ts, cfg.lin_vel_min, cfg.lin_vel_max,
+                   cfg.ang_vel_max, cfg.lin_acc_min, cfg.lin_acc_max, cfg.ang_acc_max, **opts)
+
     def sincos_array(self, x):
         """(sin, cos) of an array with the canonical sin/cos of the kernels (not libm's)."""
         x = np.ascontiguousarray(x, dtype=np.float64)

@@ -28,10 +28,10 @@ from scipy.optimize import minimize
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from conftest import oracle_for  # noqa: E402
 from mpc_trajectory_generator_amd import named_config  # noqa: E402
+from mpc_trajectory_generator_amd.workloads import baseline_batch  # noqa: E402
+from oracle import Oracle  # noqa: E402
 
 
 def rollout(cfg, u, p):
@@ -89,7 +89,7 @@ def f1(cfg, u, p):
 
 
 def audit(cfg, P, U0, label, rows):
-    o = oracle_for(cfg)
+    o = Oracle.for_config(cfg)
     U, Y, st = o.solve_batch(P, u0=U0, threads=os.cpu_count() or 1)
     N = cfg.N_hor
     lo = np.tile([cfg.lin_vel_min, -cfg.ang_vel_max], N)
@@ -127,10 +127,7 @@ def main():
     U0 = np.vstack([np.zeros((1, cfg.n_u)), d["solutions"][:-1]])
     st1 = audit(cfg, d["params"], U0, "scene-1 closed loop (126 warm-started solves)", rows)
     # (2) BASELINE cfg2 (N_hor = 40), cold start
-    from mpc_trajectory_generator_amd.frontend import random_routes
-    from mpc_trajectory_generator_amd.harness import synthetic_batch
-    cfg2 = named_config("cfg2")
-    P2 = synthetic_batch(cfg2, 11, args.n, seed=0, routes=random_routes(cfg2, 11, 32, seed=1000))
+    cfg2, P2 = baseline_batch("cfg2", args.n)
     st2 = audit(cfg2, P2, None, f"cfg2 cold start (first {args.n} instances)", rows)
     for label, st in (("scene-1 closed loop", st1), ("cfg2", st2)):
         print(f"# {label}: {int((st['exit_status'] != 0).sum())} of {len(st)} not converged")

@@ -250,14 +250,12 @@ def gpu_run(tag, cfgname, B, inst):
     if not os.path.exists(lib_path) or json.load(open(lib_path[:-3] + ".json")).get("source_hash") != _l.source_hash():
         build(json.load(open(lib_path[:-3] + ".json"))["which"] if os.path.exists(lib_path[:-3] + ".json") else tag, tag)      # (built for other sources)
     os.environ["NMPC_LIB_PATH"] = lib_path
-    from mpc_trajectory_generator_amd import named_config, _lib
+    from mpc_trajectory_generator_amd import _lib
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    from mpc_trajectory_generator_amd.harness import synthetic_batch
-    from mpc_trajectory_generator_amd.frontend import random_routes
-    cfg = named_config(cfgname)
+    from mpc_trajectory_generator_amd.workloads import baseline_batch
     full = 8192
+    cfg, P = baseline_batch(cfgname, full)
     sol = BatchSolver(cfg, max_batch=max(full, B))
-    P = synthetic_batch(cfg, 11, full, 0, routes=random_routes(cfg, 11, 32, seed=1000))
     if inst is not None:
         P = P[inst:inst + 1]
     else:

@@ -3,11 +3,11 @@ batches, HIP (through the C ABI) against the oracle.  usage: python scripts/fuzz
 import sys
 import numpy as np
 sys.path.insert(0, ".")
-sys.path.insert(0, "tests")
-from conftest import STATUS_FIELDS, oracle_for
 from mpc_trajectory_generator_amd.config import load_config
 from mpc_trajectory_generator_amd.harness import synthetic_batch
 from mpc_trajectory_generator_amd.solver import BatchSolver
+from mpc_trajectory_generator_amd.workloads import differing
+from oracle import Oracle
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -24,14 +24,12 @@ for case in range(n_cases):
     P = synthetic_batch(cfg, 11, B, int(rng.integers(0, 10 ** 6)), random_dyn=ndyn > 0)
     s = BatchSolver(cfg, max_batch=16, **opts)
     try:
+        orc = Oracle.for_config(cfg, **s.oracle_opts())
         u, y, st = s.solve(P)
-        uo, yo, sto = oracle_for(cfg, **s.oracle_opts()).solve_batch(P, threads=8)
-        ok = np.array_equal(u, uo) and np.array_equal(y, yo) and all(np.array_equal(st[f], sto[f]) for f in STATUS_FIELDS)
+        ok = not differing((u, y, st), orc.solve_batch(P, threads=8))
         # warm restart with user penalties
         c0 = rng.choice([1.0, 5.0, 125.0], size=B)
-        u2, y2, st2 = s.solve(P, u0=u, y0=y, c0=c0)
-        uo2, yo2, sto2 = oracle_for(cfg, **s.oracle_opts()).solve_batch(P, u0=u, y0=y, c0=c0, threads=8)
-        ok = ok and np.array_equal(u2, uo2) and np.array_equal(y2, yo2) and all(np.array_equal(st2[f], sto2[f]) for f in STATUS_FIELDS)
+        ok = ok and not differing(s.solve(P, u0=u, y0=y, c0=c0), orc.solve_batch(P, u0=u, y0=y, c0=c0, threads=8))
     finally:
         s.close()
     bad += not ok

@@ -5,14 +5,9 @@ import json, os, subprocess, sys, time
 import numpy as np
 sys.path.insert(0, ".")
 if len(sys.argv) > 2 and sys.argv[2] == "child":
-    from mpc_trajectory_generator_amd import named_config
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    from mpc_trajectory_generator_amd.harness import synthetic_batch
-    from mpc_trajectory_generator_amd.frontend import random_routes
-    name = sys.argv[1]
-    cfg = named_config(name)
-    P = synthetic_batch(cfg, 11, 512, 0, routes=random_routes(cfg, 11, 32, seed=1000),
-                        synthetic_circles=name == "cfg3", random_dyn=name == "cfg4")
+    from mpc_trajectory_generator_amd.workloads import baseline_batch
+    cfg, P = baseline_batch(sys.argv[1], 512)
     sol = BatchSolver(cfg, max_batch=512, experiments=True)
     st = sol.solve(P)[2]
     out = {"B512_ms": round(min((sol.solve(P), sol.last_batch_ms)[1] for _ in range(3)), 3)}
@@ -34,14 +29,9 @@ for tag, env in (("team", {}), ("no_help", {"NMPC_TEAM_HELP": "0"})):
     res[tag] = json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 else r.stderr[-500:]
 try:   # the CPU port on one thread, the same two instances (oracle = test infrastructure; this is a probe, not the product)
     from oracle import Oracle
-    from mpc_trajectory_generator_amd import named_config
-    from mpc_trajectory_generator_amd.harness import synthetic_batch
-    from mpc_trajectory_generator_amd.frontend import random_routes
-    cfg = named_config(name)
-    P = synthetic_batch(cfg, 11, 512, 0, routes=random_routes(cfg, 11, 32, seed=1000),
-                        synthetic_circles=name == "cfg3", random_dyn=name == "cfg4")
-    o = Oracle(cfg.N_hor, cfg.Nobs, cfg.Ndynobs, cfg.ts, cfg.lin_vel_min, cfg.lin_vel_max, cfg.ang_vel_max,
-               cfg.lin_acc_min, cfg.lin_acc_max, cfg.ang_acc_max)
+    from mpc_trajectory_generator_amd.workloads import baseline_batch
+    cfg, P = baseline_batch(name, 512)
+    o = Oracle.for_config(cfg)
     for tag, b in zip(("hardest", "median"), res["team"]["ids"]):
         t = time.perf_counter(); o.solve_batch(P[b:b + 1], threads=1); res[f"cpu_1thread_{tag}_ms"] = round(1e3 * (time.perf_counter() - t), 2)
 except Exception as e:      # noqa: BLE001

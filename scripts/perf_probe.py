@@ -11,8 +11,7 @@ import numpy as np
 sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config
 from mpc_trajectory_generator_amd.solver import BatchSolver
-from mpc_trajectory_generator_amd.harness import synthetic_batch
-from mpc_trajectory_generator_amd.frontend import random_routes
+from mpc_trajectory_generator_amd.workloads import baseline_batch
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "probe"
 cfg = named_config("cfg1")
@@ -20,7 +19,7 @@ sol = BatchSolver(cfg, max_batch=8192)
 out = {"tag": tag, "kernel": sol.kernel_name}
 P0 = None
 for seed in (0, 1, 2):
-    P = synthetic_batch(cfg, 11, 8192, seed, routes=random_routes(cfg, 11, 32, seed=1000 + seed))
+    P = baseline_batch("cfg1", seed=seed)[1]
     if seed == 0:
         P0 = P
     sol.solve(P)

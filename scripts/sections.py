@@ -10,16 +10,12 @@ import os
 import sys
 import numpy as np
 sys.path.insert(0, ".")
-from mpc_trajectory_generator_amd import named_config
 from mpc_trajectory_generator_amd.solver import BatchSolver
-from mpc_trajectory_generator_amd.harness import synthetic_batch
-from mpc_trajectory_generator_amd.frontend import random_routes
+from mpc_trajectory_generator_amd.workloads import baseline_batch
 
 name = sys.argv[1] if len(sys.argv) > 1 else "cfg1"
 ids = [int(x) for x in sys.argv[2:]] or [170, 330]
-cfg = named_config(name)
-kw = dict(synthetic_circles=(name == "cfg3"), random_dyn=(name == "cfg4"))
-P = synthetic_batch(cfg, 11, 8192, 0, routes=random_routes(cfg, 11, 32, seed=1000), **kw)
+cfg, P = baseline_batch(name)
 sol = BatchSolver(cfg, max_batch=8192)
 for b in ids:
     sol.solve(P[b:b + 1])

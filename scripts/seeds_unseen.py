@@ -3,15 +3,13 @@ import numpy as np
 sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config
 from mpc_trajectory_generator_amd.solver import BatchSolver
-from mpc_trajectory_generator_amd.harness import synthetic_batch
-from mpc_trajectory_generator_amd.frontend import random_routes
+from mpc_trajectory_generator_amd.workloads import baseline_batch
 cfg_name = sys.argv[1] if len(sys.argv) > 1 else "cfg1"
 cfg = named_config(cfg_name)
-kw = dict(synthetic_circles=cfg_name == "cfg3", random_dyn=cfg_name == "cfg4")
 sol = BatchSolver(cfg, max_batch=8192)
 out = {"config": cfg_name}
 for seed in (3, 4, 5, 6, 7):
-    P = synthetic_batch(cfg, 11, 8192, seed, routes=random_routes(cfg, 11, 32, seed=1000 + seed), **kw)
+    P = baseline_batch(cfg_name, seed=seed)[1]
     sol.solve(P)
     ms = []
     for _ in range(3):

@@ -15,10 +15,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mpc_trajectory_generator_amd import harness, named_config  # noqa: E402
-from mpc_trajectory_generator_amd.frontend import random_routes  # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver  # noqa: E402
 from mpc_trajectory_generator_amd.tcp_shim import OptimizerTcpManager  # noqa: E402
+from mpc_trajectory_generator_amd.workloads import baseline_batch  # noqa: E402
 
 TAG = sys.argv[1] if len(sys.argv) > 1 else "time_limits"
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 6
@@ -34,12 +33,6 @@ def emit(rec):
     sink.flush()
 
 
-def bench_batch(name, B=8192, seed=0):
-    cfg = named_config(name)
-    routes = random_routes(cfg, 11, 32, seed=1000 + seed)
-    return cfg, harness.synthetic_batch(cfg, 11, B, seed=seed, routes=routes)
-
-
 def shares(st):
     e = st["exit_status"]
     return {"converged": round(float(np.mean(e == 0)), 4), "out_of_time": round(float(np.mean(e == 2)), 4),
@@ -47,7 +40,7 @@ def shares(st):
 
 
 for name in ("cfg1", "cfg2"):
-    cfg, P = bench_batch(name)
+    cfg, P = baseline_batch(name)
     s = BatchSolver(cfg, max_batch=len(P))
     u_ref, y_ref, st_ref = s.solve(P)                 # (warm-up, and the untimed solve (b) compares with)
     # (a) untimed | timed with an unreachable limit, alternated
@@ -83,7 +76,7 @@ for name in ("cfg1", "cfg2"):
     s.close()
 
 # (c) B = 1 through the shim, cold calls (zero guess and multipliers) of cfg 1's batch
-cfg, P = bench_batch("cfg1", B=48, seed=4)
+cfg, P = baseline_batch("cfg1", B=48, seed=4)
 for lim_us in (None, 500_000, 10_000, 5_000, 2_000, 1_000, 500):
     m = OptimizerTcpManager(config=cfg, max_batch=4, max_duration_micros=lim_us)
     m.start()

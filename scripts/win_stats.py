@@ -5,16 +5,14 @@ import ctypes, json, os, subprocess, sys
 sys.path.insert(0, ".")
 if sys.argv[1] == "child":
     import numpy as np
-    from mpc_trajectory_generator_amd import named_config, _lib
+    from mpc_trajectory_generator_amd import _lib
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    from mpc_trajectory_generator_amd.harness import synthetic_batch
-    from mpc_trajectory_generator_amd.frontend import random_routes
+    from mpc_trajectory_generator_amd.workloads import baseline_batch
     name = sys.argv[2]
-    cfg = named_config(name)
+    cfg, P = baseline_batch(name)
     sol = BatchSolver(cfg, max_batch=8192)
     lib = _lib.load_library()
     out = {}
-    P = synthetic_batch(cfg, 11, 8192, 0, routes=random_routes(cfg, 11, 32, seed=1000), synthetic_circles=name == "cfg3", random_dyn=name == "cfg4")
     sol.solve(P)
     buf = (ctypes.c_ulonglong * 4)()
     if hasattr(lib, "nmpc_debug_win_stats"):

@@ -137,8 +137,7 @@ def run_reference(cfg, graph, start, end, path, vertices, sinus_object, max_call
     """-> recorded exchanges and the trajectory the reference's run() returns."""
     RECORD["p"].clear(), RECORD["u"].clear(), RECORD["exit"].clear()
     MAX_CALLS[0] = max_calls
-    FakeManager.oracle = Oracle(cfg.N_hor, cfg.Nobs, cfg.Ndynobs, cfg.ts, cfg.lin_vel_min, cfg.lin_vel_max,
-                                cfg.ang_vel_max, cfg.lin_acc_min, cfg.lin_acc_max, cfg.ang_acc_max)
+    FakeManager.oracle = Oracle.for_config(cfg)
     pg = PathGenerator(cfg, build=False, verbose=False, sinus_object=sinus_object)
     ppp = pg.ppp
 

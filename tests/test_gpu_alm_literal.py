@@ -97,8 +97,8 @@ def test_team_modes_under_an_epsilon_schedule(monkeypatch, name, B, owners, set_
 def test_full_batch_f2_norm_is_the_plain_norm_of_F2():
     """The bench's own cfg 1 batch: what every instance reports as f2_norm is ||F2(u)|| of the u it returns."""
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    from test_gpu_fullbatch import bench_batch
-    cfg, P = bench_batch("cfg1")
+    from mpc_trajectory_generator_amd.workloads import baseline_batch
+    cfg, P = baseline_batch("cfg1")
     s = BatchSolver(cfg, max_batch=len(P))
     try:
         u, y, st = s.solve(P)

@@ -7,20 +7,12 @@ not depend on its slot, its wave-mates or the launch order) -- plus bit-exact or
 import numpy as np
 import pytest
 
-from conftest import STATUS_FIELDS, oracle_for
+from conftest import oracle_for
 from mpc_trajectory_generator_amd import harness, named_config
+from mpc_trajectory_generator_amd.workloads import baseline_batch, differing
 
 pytestmark = pytest.mark.gpu
 B = 8192
-
-
-def bench_batch(name, seed=0, B=B):
-    from mpc_trajectory_generator_amd.frontend import random_routes
-    cfg = named_config(name)
-    routes = random_routes(cfg, 11, 32, seed=1000 + seed)
-    P = harness.synthetic_batch(cfg, 11, B, seed=seed, routes=routes, synthetic_circles=(name == "cfg3"),
-                                random_dyn=(name == "cfg4"))
-    return cfg, P
 
 
 @pytest.mark.parametrize("name,kernel,sample,B", [("cfg1", "nmpc_solve_hyb_kernel<ShapeDefault>", 64, 8192),
@@ -32,7 +24,7 @@ def bench_batch(name, seed=0, B=B):
                          ids=["cfg1", "cfg2", "cfg3", "cfg4", "cfg3-65536"])
 def test_full_batch_properties_and_sampled_parity(name, kernel, sample, B):
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    cfg, P = bench_batch(name, B=B)
+    cfg, P = baseline_batch(name, B)
     s = BatchSolver(cfg, max_batch=B)
     try:
         assert s.kernel_name == kernel
@@ -52,16 +44,10 @@ def test_full_batch_properties_and_sampled_parity(name, kernel, sample, B):
         assert acc[conv].max() <= cfg.lin_acc_max + 5e-3 and acc[conv].min() >= cfg.lin_acc_min - 5e-3
         # permutation invariance
         perm = np.random.default_rng(0).permutation(B)
-        u2, y2, st2 = s.solve(P[perm])
-        assert np.array_equal(u2, u[perm]) and np.array_equal(y2, y[perm])
-        for f in STATUS_FIELDS:
-            assert np.array_equal(st2[f], st[f][perm]), f
+        assert not differing((u, y, st), s.solve(P[perm]), perm)
         # sampled oracle parity, bit for bit
         idx = np.random.default_rng(1).choice(B, sample, replace=False)
-        uo, yo, sto = oracle_for(cfg).solve_batch(P[idx], threads=8)
-        assert np.array_equal(u[idx], uo) and np.array_equal(y[idx], yo)
-        for f in STATUS_FIELDS:
-            assert np.array_equal(st[f][idx], sto[f]), f
+        assert not differing((u, y, st), oracle_for(cfg).solve_batch(P[idx], threads=8), idx)
     finally:
         s.close()
 
@@ -73,15 +59,12 @@ def test_full_batch_repeatable_on_other_seeds(name, seed):
     scheduler settings have produced such builds of it (csrc/Makefile, NMPC_WIN2 in nmpc_solve_hyb2.h); scripts/determinism_check.py
     is the long form (all configs, more seeds, sampled oracle parity)."""
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    cfg, P = bench_batch(name, seed)
+    cfg, P = baseline_batch(name, B, seed)
     s = BatchSolver(cfg, max_batch=B)
     try:
         u, y, st = s.solve(P)
         perm = np.random.default_rng(seed).permutation(B)
-        u2, y2, st2 = s.solve(P[perm])
-        assert np.array_equal(u2, u[perm]) and np.array_equal(y2, y[perm])
-        for f in STATUS_FIELDS:
-            assert np.array_equal(st2[f], st[f][perm]), f
+        assert not differing((u, y, st), s.solve(P[perm]), perm)
         idx = np.random.default_rng(100 + seed).choice(B, 12, replace=False)
         uo, yo, sto = oracle_for(cfg).solve_batch(P[idx], threads=8)
         assert np.array_equal(u[idx], uo) and np.array_equal(y[idx], yo)

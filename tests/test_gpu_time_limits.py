@@ -17,16 +17,11 @@ import pytest
 from conftest import STATUS_FIELDS, oracle_for
 from mpc_trajectory_generator_amd import harness, named_config
 from mpc_trajectory_generator_amd.config import load_config
+from mpc_trajectory_generator_amd.workloads import baseline_batch, differing
 
 pytestmark = pytest.mark.gpu
 OUT_OF_TIME = 2
 THREADS = 16
-
-
-def _batch(cfg, B, seed=0):
-    from mpc_trajectory_generator_amd.frontend import random_routes
-    routes = random_routes(cfg, 11, 32, seed=1000 + seed)
-    return harness.synthetic_batch(cfg, 11, B, seed=seed, routes=routes)
 
 
 def _same(u, y, st, u2, y2, st2):
@@ -59,8 +54,7 @@ def _untimed_matches_oracle(cfg, P, untimed, n, u0=None, y0=None):
     idx = np.random.default_rng(3).choice(len(P), min(n, len(P)), replace=False)
     uo, yo, so = oracle_for(cfg).solve_batch(P[idx], u0=None if u0 is None else u0[idx], y0=None if y0 is None else y0[idx],
                                              threads=THREADS)
-    u, y, st = untimed
-    assert np.all(_same(u[idx], y[idx], st[idx], uo, yo, so))
+    assert not differing(untimed, (uo, yo, so), idx)
 
 
 def _hip():
@@ -118,11 +112,11 @@ def test_unreachable_limits_change_nothing(name, B, kernel):
         timed_kernel = kernel.replace("<", "<Timed<", 1) + ">"
         assert s.kernel_name == timed_kernel
         u, y, st = s.solve(P)
-        assert np.all(_same(u, y, st, *ref))
+        assert not differing((u, y, st), ref)
         assert not np.any(st["exit_status"] == OUT_OF_TIME)
         s.set_time_limits(0, 0)
         assert s.kernel_name == kernel
-        assert np.all(_same(*s.solve(P), *ref))
+        assert not differing(s.solve(P), ref)
     finally:
         s.close()
 
@@ -131,8 +125,7 @@ def test_unreachable_limits_change_nothing(name, B, kernel):
 @pytest.mark.parametrize("name,B,path", [("cfg1", 4096, "host"), ("cfg2", 4096, "device"), ("cfg1", 4, "device"), ("cfg2", 4, "host")])
 def test_per_instance_limit_replays(name, B, path):
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    cfg = named_config(name)
-    P = _batch(cfg, max(B, 64))
+    cfg, P = baseline_batch(name, max(B, 64))
     s = BatchSolver(cfg, max_batch=max(B, 64))
     try:
         if B < 64:
@@ -158,9 +151,8 @@ def test_per_instance_limit_replays(name, B, path):
 # ---------------------------------------------------------------------------------------------- 3. batch budget
 def test_batch_budget_replays_and_ends_the_batch_early():
     from mpc_trajectory_generator_amd.solver import BatchSolver
-    cfg = named_config("cfg1")
     B = 8192
-    P = _batch(cfg, B)
+    cfg, P = baseline_batch("cfg1", B)
     s = BatchSolver(cfg, max_batch=B)
     try:
         untimed = s.solve(P)
@@ -223,7 +215,7 @@ def test_bad_limits_are_refused_and_keep_the_limits_in_force():
                 s.set_time_limits(*bad)
             assert s.kernel_name == timed and (s.max_duration_ms, s.batch_budget_ms) == (5.0, 0.0)
         # the limits in force still act: a limit far below one solve stops every instance of a cold batch
-        P = _batch(cfg, 8)
+        P = baseline_batch("cfg1", 8)[1]
         s.set_time_limits(0, 0)
         s.set_time_limits(0.001, 0)
         assert s.lib.nmpc_set_time_limits(s._h, -5.0, 0.0) == -2
@@ -237,8 +229,7 @@ def test_bad_limits_are_refused_and_keep_the_limits_in_force():
 
 def test_shim_max_duration():
     from mpc_trajectory_generator_amd.tcp_shim import OptimizerTcpManager
-    cfg = named_config("cfg1")
-    P = _batch(cfg, 3, seed=2)
+    cfg, P = baseline_batch("cfg1", 3, seed=2)
     plain, ref_time, tiny = (OptimizerTcpManager(config=cfg, max_batch=4), OptimizerTcpManager(config=cfg, max_batch=4, max_duration_micros=500_000),
                              OptimizerTcpManager(config=cfg, max_batch=4, max_duration_micros=1))
     for m in (plain, ref_time, tiny):

@@ -1,0 +1,114 @@
+"""CPU: workloads.baseline_batch is bench.py's batch, array for array, and workloads.differing names what is not the same bits.
+
+``bench_py_batch`` below is bench.py's ``make_batch`` written out once more: bench.py cannot import from here and no pull request edits
+it, so this literal is what ties every probe and GPU test that calls ``baseline_batch`` to the batch the benchmark times.  The same goes
+for the two copies tests/conftest.py keeps (STATUS_FIELDS, oracle_for): they are pinned to workloads.PARITY_FIELDS and Oracle.for_config."""
+import numpy as np
+import pytest
+
+import conftest
+from mpc_trajectory_generator_amd import named_config
+from mpc_trajectory_generator_amd.workloads import PARITY_FIELDS, baseline_batch, differing
+from oracle import Oracle
+from oracle.binding import STATUS_DTYPE
+
+
+def bench_py_batch(config, B, seed, scene=11, n_routes=32):
+    from mpc_trajectory_generator_amd.harness import synthetic_batch
+    cfg = named_config(config)
+    kw = dict(synthetic_circles=(config in ("cfg3", "nobs50")), random_dyn=(config in ("cfg4", "smooth_velocity")))
+    routes = None
+    if n_routes > 0:
+        from mpc_trajectory_generator_amd.frontend import random_routes
+        routes = random_routes(cfg, scene, n_routes, seed=1000 + seed)
+    return synthetic_batch(cfg, scene, B, seed=seed, routes=routes, **kw)
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+@pytest.mark.parametrize("name", ["cfg1", "cfg2", "cfg3", "cfg4", "default", "jconf_3_n40", "nobs50", "smooth_velocity"])
+def test_baseline_batch_is_the_benchmarks_batch(name, seed):
+    cfg, P = baseline_batch(name, 64, seed)
+    assert cfg == named_config(name)
+    assert P.shape == (64, cfg.n_p) and np.array_equal(P, bench_py_batch(name, 64, seed))
+
+
+def test_a_smaller_batch_is_the_head_of_a_larger_one():
+    """The generator draws row by row from one stream, so what holds for the first rows holds for a probe's B = 8192 too."""
+    assert np.array_equal(baseline_batch("cfg4", 256)[1][:64], baseline_batch("cfg4", 64)[1])
+
+
+@pytest.mark.parametrize("name", ["cfg1", "cfg3", "cfg4"])
+def test_routes_zero_is_the_scenes_own_route(name):
+    from mpc_trajectory_generator_amd.harness import synthetic_batch
+    cfg, P = baseline_batch(name, 32, 5, routes=0)
+    flags = {"cfg1": {}, "cfg3": dict(synthetic_circles=True), "cfg4": dict(random_dyn=True)}[name]
+    assert np.array_equal(P, synthetic_batch(cfg, 11, 32, 5, **flags))
+    assert np.array_equal(baseline_batch(name, 8, 5, scene=1, routes=0)[1], synthetic_batch(cfg, 1, 8, 5, **flags))
+
+
+def test_the_copies_conftest_keeps_have_not_drifted():
+    assert PARITY_FIELDS == conftest.STATUS_FIELDS
+    cfg, P = baseline_batch("cfg1", 4)
+    a = Oracle.for_config(cfg, max_total_inner=60).solve_batch(P)
+    b = conftest.oracle_for(cfg, max_total_inner=60).solve_batch(P)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    assert all(np.array_equal(a[2][f], b[2][f]) for f in STATUS_DTYPE.names if f != "solve_time_ms")
+    assert a[2]["num_inner_iterations"].max() <= 60 and a[2]["num_inner_iterations"].min() > 0
+
+
+def _triple(rng, B=12):
+    st = np.zeros(B, dtype=STATUS_DTYPE)
+    for f in STATUS_DTYPE.names:
+        st[f] = rng.integers(0, 1000, B)
+    return rng.normal(size=(B, 6)), rng.normal(size=(B, 4)), st
+
+
+def _copy(t):
+    return tuple(x.copy() for x in t)
+
+
+def test_differing_names_what_differs():
+    rng = np.random.default_rng(0)
+    a = _triple(rng)
+    assert differing(a, _copy(a)) == []
+    b = _copy(a)
+    b[0][3, 2] = np.nextafter(b[0][3, 2], 1.0)
+    assert differing(a, b) == ["u"]
+    b[1][0, 0] += 1.0
+    assert differing(a, b) == ["u", "y"]
+    for f in PARITY_FIELDS:
+        c = _copy(a)
+        c[2][f][5] += 1
+        assert differing(a, c) == [f]
+    c = _copy(b)
+    c[2]["cost"][0] += 1.0
+    c[2]["exit_status"][0] += 1
+    assert differing(a, c) == ["exit_status", "cost", "u", "y"]           # fields first, in PARITY_FIELDS order
+    nan = _copy(a)
+    nan[0][0, 0] = a[0][0, 0] = np.nan
+    assert differing(a, nan) == ["u"]                                     # a NaN is never "the same bits" as anything
+
+
+def test_differing_ignores_fields_outside_parity_fields():
+    a = _triple(np.random.default_rng(1))
+    b = _copy(a)
+    b[2]["solve_time_ms"] += 1.0
+    b[2]["reserved"] += 1
+    assert set(STATUS_DTYPE.names) - set(PARITY_FIELDS) == {"solve_time_ms", "reserved"}
+    assert differing(a, b) == []
+
+
+def test_differing_rows_as_permutation_and_as_sample():
+    rng = np.random.default_rng(2)
+    a = _triple(rng)
+    perm = rng.permutation(len(a[0]))
+    b = tuple(x[perm] for x in a)
+    assert differing(a, b, perm) == []
+    assert differing(a, b) != []
+    idx = rng.choice(len(a[0]), 5, replace=False)
+    s = tuple(x[idx].copy() for x in a)
+    assert differing(a, s, idx) == []
+    s[2]["penalty"][4] += 1.0
+    assert differing(a, s, idx) == ["penalty"]
+    s[1][0, 0] += 1.0
+    assert differing(a, s, idx) == ["penalty", "y"]
