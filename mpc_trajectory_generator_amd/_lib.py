@@ -272,3 +272,7 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
 
 def as_dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+
+
+def as_i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None

@@ -138,6 +138,12 @@ def dyn_obstacle(cfg: Config, dyn_obs_list, t, horizon, sinus_object=False):
     return out
 
 
+def dyn_obstacle_flat(cfg: Config, dyn_obs_list, t, horizon, sinus_object=False):
+    """``dyn_obstacle`` with each obstacle's ellipses chained into one flat list of floats, the form the
+    dynamic block of ``p`` holds them in (src/path_generator.py:308-309,315-316)."""
+    return [[float(v) for tup in obs for v in tup] for obs in dyn_obstacle(cfg, dyn_obs_list, t, horizon, sinus_object)]
+
+
 # --------------------------------------------------------------------------------------------
 # parameter vector, one receding-horizon step
 # --------------------------------------------------------------------------------------------
@@ -331,8 +337,4 @@ def _random_dyn_block(cfg, route, idx, rng):
         obs.append([p1, p2, rng.uniform(0.05, 0.1), rng.uniform(0.3, 1.0), rng.uniform(0.3, 1.0),
                     rng.uniform(0, math.pi)])
     t0 = rng.uniform(0, 60.0)
-    block = []
-    for pred in dyn_obstacle(cfg, obs, t0, cfg.N_hor):
-        for tup in pred:
-            block += [float(v) for v in tup]
-    return block
+    return [v for flat in dyn_obstacle_flat(cfg, obs, t0, cfg.N_hor) for v in flat]

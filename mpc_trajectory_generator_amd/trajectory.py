@@ -1,28 +1,44 @@
 """Receding-horizon drivers on top of the solver handle.
 
-``TrajectoryGenerator.run`` follows the reference's ``PathGenerator.run`` loop
-(src/path_generator.py:197-437) call for call -- manager start / ping, per-step parameter
-assembly, ``mpc_step`` (= ``MpcModule.run``, src/mpc/mpc_generator.py:204-237), terminal test, kill
--- so a user of the reference finds the same control flow, with the OpEn TCP manager replaced by
-``tcp_shim.OptimizerTcpManager``.  The visibility-graph A* front-end (extremitypathfinder /
+``RecedingHorizonRobot`` is the per-robot step of the reference's ``PathGenerator.run`` loop
+(src/path_generator.py:290-403), written once and line for line: parameter assembly, control and Euler
+advance (``_euler_advance``, src/mpc/mpc_generator.py:223-235), terminal test.  Two drivers run it, and the
+goldens recorded from the reference's own loop pin it through both (tests/test_harness.py):
+
+``TrajectoryGenerator.run`` follows ``PathGenerator.run`` (:197-437) call for call -- manager start /
+ping, per-step parameters, ``mpc_step`` (= ``MpcModule.run``, src/mpc/mpc_generator.py:204-237), terminal
+test, kill -- so a user of the reference finds the same control flow, with the OpEn TCP manager replaced
+by ``tcp_shim.OptimizerTcpManager``.  The visibility-graph A* front-end (extremitypathfinder /
 pyclipper) is outside this project's scope; a ``harness.Route`` (waypoints + NMPC vertices) is
 what ``run`` starts from.
 
-``BatchedRecedingHorizon`` is the batched counterpart for BASELINE config 4: B independent robots
-advance in lock step, one batched solve per step, controls and multipliers carried as warm starts.
+``BatchedRecedingHorizon`` is the batched counterpart for BASELINE config 4: B such robots advance in
+lock step, one batched solve per step, controls and multipliers carried as warm starts.
+``VectorizedRecedingHorizon`` is its NumPy mirror (bit-identical parameter vectors demanded),
 ``FleetRecedingHorizon`` (host) and ``DeviceRecedingHorizon`` given a list of routes run a fleet whose
 robots follow routes of their own.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import time
 
 import numpy as np
 
-from . import harness
+from . import _lib, harness
 from .config import Config
 from .tcp_shim import OptimizerTcpManager
+
+
+def _euler_advance(cfg: Config, u, take_steps, system_input, states):
+    """Append the controls taken and the poses they lead to: src/mpc/mpc_generator.py:223-235."""
+    system_input += [float(v) for v in u[:cfg.nu * take_steps]]              # :223
+    for i in range(take_steps):                                              # :225-235, Euler diff-drive
+        u_v, u_omega = u[i * cfg.nu], u[1 + i * cfg.nu]
+        x, y, theta = states[-3], states[-2], states[-1]
+        states += [x + cfg.ts * (u_v * math.cos(theta)), y + cfg.ts * (u_v * math.sin(theta)),
+                   theta + cfg.ts * u_omega]
 
 
 def mpc_step(cfg: Config, parameters, mng, take_steps, system_input, states):
@@ -35,13 +51,53 @@ def mpc_step(cfg: Config, parameters, mng, take_steps, system_input, states):
         err = solution.get()
         mng.kill()
         raise RuntimeError(f"MPC Solver error: {err.message}")
-    system_input += u[:cfg.nu * take_steps]                                  # :223
-    for i in range(take_steps):                                              # :225-235, Euler diff-drive
-        u_v, u_omega = u[i * cfg.nu], u[1 + i * cfg.nu]
-        x, y, theta = states[-3], states[-2], states[-1]
-        states += [x + cfg.ts * (u_v * math.cos(theta)), y + cfg.ts * (u_v * math.sin(theta)),
-                   theta + cfg.ts * u_omega]
+    _euler_advance(cfg, u, take_steps, system_input, states)
     return exit_status, solver_time
+
+
+class RecedingHorizonRobot:
+    """What the reference's loop keeps per robot (src/path_generator.py:262-280) and its three uses of it per
+    step.  ``idx0`` = the reference sample the window search starts at (0 in the reference); the clock ``t``
+    is advanced by the driver (:401)."""
+
+    def __init__(self, route: harness.Route, start, dyn_obs_list, sinus_object=False, idx0=0):
+        cfg = self.cfg = route.cfg
+        self.route, self.dyn_obs_list, self.sinus_object = route, dyn_obs_list, sinus_object
+        self.t, self.idx = 0, int(idx0)
+        self.system_input = []                                               # :265
+        self.states = list(map(float, start))                                # :267, flat [x, y, theta, ...]
+        self.constraints = [0.0] * cfg.Nobs * cfg.nobs                       # :273
+        self.dyn_constraints = harness.initial_dyn_constraints(cfg)          # :274-280
+
+    def parameters(self):
+        """The parameter list of this step: src/path_generator.py:293-379."""
+        cfg, route, t = self.cfg, self.route, self.t
+        x_init = self.states[-cfg.nx:]                                       # :293
+        if len(route.vertices):                                              # :295-304
+            self.constraints = harness.static_constraints(route, (x_init[0], x_init[1]))
+        per, k = cfg.N_hor * cfg.ndynobs, cfg.ndynobs * cfg.num_steps_taken
+        if t == 0:                                                           # :306-309
+            for i, obs in enumerate(harness.dyn_obstacle_flat(cfg, self.dyn_obs_list, t * cfg.ts, cfg.N_hor,
+                                                              self.sinus_object)):
+                self.dyn_constraints[i * per:(i + 1) * per] = obs
+        else:                                                                # :310-316 rotate the whole list left, refresh the tails
+            self.dyn_constraints = self.dyn_constraints[k:] + self.dyn_constraints[:k]
+            for i, obs in enumerate(harness.dyn_obstacle_flat(cfg, self.dyn_obs_list,
+                                                              (t + cfg.N_hor - cfg.num_steps_taken) * cfg.ts,
+                                                              cfg.num_steps_taken, self.sinus_object)):
+                self.dyn_constraints[(i + 1) * per - k:(i + 1) * per] = obs
+        lb_idx = max(0, self.idx - 1 * cfg.num_steps_taken)                  # :320-325
+        ub_idx = min(len(route.x_ref), self.idx + 5 * cfg.num_steps_taken)
+        self.idx = harness.closest_index((x_init[0], x_init[1]), route.ref_points[lb_idx:ub_idx]) + lb_idx
+        last_u = self.system_input[-cfg.nu:] if len(self.system_input) else [0.0] * cfg.nu     # :371-374
+        return harness.assemble_params(route, x_init, last_u, self.idx, self.constraints, self.dyn_constraints)
+
+    def apply(self, u):
+        _euler_advance(self.cfg, u, self.cfg.num_steps_taken, self.system_input, self.states)
+
+    def terminal(self):
+        return bool(np.allclose(self.states[-3:-1], self.route.end[0:2], atol=0.05, rtol=0)
+                    and abs(self.system_input[-2]) < 0.005)                  # :397
 
 
 class TrajectoryGenerator:
@@ -56,6 +112,11 @@ class TrajectoryGenerator:
         # build=True triggers OpEn code generation in the reference (:33-34); here the kernels are
         # compiled when the library is first loaded, nothing to do.
 
+    def _result(self, robot):
+        nx = self.config.nx
+        return (robot.states[0::nx], robot.states[1::nx], robot.system_input[0::2], robot.system_input[1::2],
+                self.solver_times, self.overhead_times)
+
     def run(self, route: harness.Route, max_steps: int | None = None, record_parameters: list | None = None):
         """-> (xx, xy, uv, uomega, solver_times, overhead_times), src/path_generator.py:197-437."""
         cfg = self.config
@@ -65,45 +126,20 @@ class TrajectoryGenerator:
         mng.ping()
         self.time_dict["opt_launch"] = int(1000 * (time.time() - t_temp))
         tt = time.time()
-        start, end = list(route.start), list(route.end)
-        x_ref, y_ref = route.x_ref, route.y_ref
-        terminal, t, idx = False, 0, 0
+        terminal = False
         self.solver_times, self.overhead_times = [], []
-        system_input = []
-        states = list(map(float, start))                                      # :267
-        constraints = [0.0] * cfg.Nobs * cfg.nobs                             # :273
-        dyn_constraints = harness.initial_dyn_constraints(cfg)                # :274-280
-        params_per_dyn_obs = cfg.N_hor * cfg.ndynobs
+        robot = RecedingHorizonRobot(route, route.start, route.dyn_obs_list, self.sinus_object)
         limit = 500.0 / cfg.ts if max_steps is None else max_steps
         t_temp = time.time()
         try:
-            while (not terminal) and t < limit:                                   # :290
+            while (not terminal) and robot.t < limit:                             # :290
                 t_overhead = time.time()
-                x_init = states[-cfg.nx:]                                         # :293
-                if len(route.vertices):                                           # :295-304
-                    constraints = harness.static_constraints(route, (x_init[0], x_init[1]))
-                if t == 0:                                                        # :306-309
-                    for i, obs in enumerate(harness.dyn_obstacle(cfg, route.dyn_obs_list, t * cfg.ts, cfg.N_hor,
-                                                                 self.sinus_object)):
-                        dyn_constraints[i * params_per_dyn_obs:(i + 1) * params_per_dyn_obs] = \
-                            [float(v) for tup in obs for v in tup]
-                else:                                                             # :310-316 rotate left, refresh the tail
-                    k = cfg.ndynobs * cfg.num_steps_taken
-                    dyn_constraints = dyn_constraints[k:] + dyn_constraints[:k]
-                    for i, obs in enumerate(harness.dyn_obstacle(cfg, route.dyn_obs_list,
-                                                                 (t + cfg.N_hor - cfg.num_steps_taken) * cfg.ts,
-                                                                 cfg.num_steps_taken, self.sinus_object)):
-                        dyn_constraints[(i + 1) * params_per_dyn_obs - k:(i + 1) * params_per_dyn_obs] = \
-                            [float(v) for tup in obs for v in tup]
-                lb_idx = max(0, idx - 1 * cfg.num_steps_taken)                    # :320-325
-                ub_idx = min(len(x_ref), idx + 5 * cfg.num_steps_taken)
-                idx = harness.closest_index((x_init[0], x_init[1]), route.ref_points[lb_idx:ub_idx]) + lb_idx
-                last_u = system_input[-cfg.nu:] if len(system_input) else [0.0] * cfg.nu     # :371-374
-                parameters = harness.assemble_params(route, x_init, last_u, idx, constraints, dyn_constraints)
+                parameters = robot.parameters()
                 if record_parameters is not None:
                     record_parameters.append(list(parameters))
                 try:                                                              # :384-391
-                    exit_status, solver_time = mpc_step(cfg, parameters, mng, cfg.num_steps_taken, system_input, states)
+                    exit_status, solver_time = mpc_step(cfg, parameters, mng, cfg.num_steps_taken, robot.system_input,
+                                                        robot.states)
                     self.solver_times.append(solver_time)
                 except RuntimeError as err:
                     if self.verbose:
@@ -111,111 +147,80 @@ class TrajectoryGenerator:
                     return None
                 if exit_status in cfg.bad_exit_codes and self.verbose:            # :393-394
                     print(f"[MPC] Bad converge status: {exit_status}")
-                if np.allclose(states[-3:-1], end[0:2], atol=0.05, rtol=0) and abs(system_input[-2]) < 0.005:   # :397
-                    terminal = True
-                t += cfg.num_steps_taken
+                terminal = robot.terminal()
+                robot.t += cfg.num_steps_taken                                    # :401
                 self.overhead_times.append((time.time() - t_overhead) * 1000.0 - solver_time)
         except KeyboardInterrupt:                                             # :405-415: kill the server, return what was driven so far
             if self.verbose:
                 print("[MPC] killing TCP connection to MCP solver...")
             mng.kill()
-            nx = cfg.nx
-            return (states[0::nx], states[1::nx], system_input[0::2], system_input[1::2],
-                    self.solver_times, self.overhead_times)
+            return self._result(robot)
         mng.kill()                                                            # :417
         self.time_dict["mpc_time"] = int(1000 * (time.time() - t_temp))
         self.time_dict["solver_time"] = sum(self.solver_times)
         self.time_dict["mean_solver_time"] = float(np.mean(self.solver_times)) if self.solver_times else 0.0
         self.time_dict["total_time"] = int(1000 * (time.time() - tt))
-        nx = cfg.nx
-        return (states[0::nx], states[1::nx], system_input[0::2], system_input[1::2],
-                self.solver_times, self.overhead_times)
+        return self._result(robot)
 
 
-class BatchedRecedingHorizon:
+class _HostLoop:
+    """What the host drivers share: one step = assemble -> ``solve_fn(P, u0, y0) -> (U, Y, status)`` -> advance."""
+
+    def step(self, solve_fn):
+        P = self.assemble()
+        self.U, self.Y, st = solve_fn(P, self.U, self.Y)
+        self.advance(self.U)
+        return P, st
+
+
+class BatchedRecedingHorizon(_HostLoop):
     """B robots on one route, advanced in lock step with one batched solve per step.
 
-    Per robot and step the parameter vector is filled as ``TrajectoryGenerator.run`` does
-    (closest reference sample in the sliding window, horizon padded with the end pose, braking
-    ``vel_ref``, dynamic block rotated left and refreshed).  ``solve_fn(P, u0, y0) -> (U, Y, status)``
-    is the batched solver (``BatchSolver.solve``); controls and multipliers are carried over as
-    warm starts, the penalty restarts at its initial value, like the sequential path.
+    Each robot is a ``RecedingHorizonRobot`` with its own dynamic obstacles (``dyn_obs_lists``, default the
+    route's) and its own first reference sample (``idx0``, default 0 as the reference), so its parameter vector
+    is filled as ``TrajectoryGenerator.run`` fills it.  ``solve_fn`` is the batched solver
+    (``BatchSolver.solve``); controls and multipliers are carried over as warm starts, the penalty restarts at
+    its initial value, like the sequential path.
     """
 
-    def __init__(self, route: harness.Route, starts, dyn_obs_lists=None, sinus_object=False):
+    def __init__(self, route: harness.Route, starts, dyn_obs_lists=None, sinus_object=False, idx0=None):
         self.route, self.cfg = route, route.cfg
         self.B = len(starts)
-        self.states = [list(map(float, s)) for s in starts]       # per robot: flat [x, y, theta, ...]
-        self.inputs = [[] for _ in range(self.B)]
-        self.idx = [0] * self.B
+        self.robots = [RecedingHorizonRobot(route, s, route.dyn_obs_list if dyn_obs_lists is None else dyn_obs_lists[b],
+                                            sinus_object, 0 if idx0 is None else idx0[b]) for b, s in enumerate(starts)]
         self.t = 0
-        self.dyn_lists = dyn_obs_lists if dyn_obs_lists is not None else [route.dyn_obs_list] * self.B
-        self.sinus_object = sinus_object
-        self.dyn = [harness.initial_dyn_constraints(self.cfg) for _ in range(self.B)]
-        self.constraints = [[0.0] * self.cfg.Nobs * self.cfg.nobs for _ in range(self.B)]
         self.U = np.zeros((self.B, self.cfg.n_u))
         self.Y = np.zeros((self.B, self.cfg.n1))
         self.done = np.zeros(self.B, dtype=bool)
 
+    # per robot: the flat pose list, the flat control list, the reference sample.  Tuples, so that an item
+    # assignment fails instead of changing a temporary (the robots' own lists are the elements).
+    states = property(lambda self: tuple(r.states for r in self.robots))
+    inputs = property(lambda self: tuple(r.system_input for r in self.robots))
+    idx = property(lambda self: tuple(r.idx for r in self.robots))
+
     def assemble(self):
-        cfg, route = self.cfg, self.route
-        per = cfg.N_hor * cfg.ndynobs
-        k = cfg.ndynobs * cfg.num_steps_taken
-        P = np.empty((self.B, cfg.n_p))
-        for b in range(self.B):
-            x_init = self.states[b][-cfg.nx:]
-            if len(route.vertices):
-                self.constraints[b] = harness.static_constraints(route, (x_init[0], x_init[1]))
-            if self.t == 0:
-                preds = harness.dyn_obstacle(cfg, self.dyn_lists[b], 0.0, cfg.N_hor, self.sinus_object)
-                for i, obs in enumerate(preds):
-                    self.dyn[b][i * per:(i + 1) * per] = [float(v) for tup in obs for v in tup]
-            else:
-                self.dyn[b] = self.dyn[b][k:] + self.dyn[b][:k]
-                preds = harness.dyn_obstacle(cfg, self.dyn_lists[b], (self.t + cfg.N_hor - cfg.num_steps_taken) * cfg.ts,
-                                             cfg.num_steps_taken, self.sinus_object)
-                for i, obs in enumerate(preds):
-                    self.dyn[b][(i + 1) * per - k:(i + 1) * per] = [float(v) for tup in obs for v in tup]
-            lb = max(0, self.idx[b] - cfg.num_steps_taken)
-            ub = min(len(route.x_ref), self.idx[b] + 5 * cfg.num_steps_taken)
-            self.idx[b] = harness.closest_index((x_init[0], x_init[1]), route.ref_points[lb:ub]) + lb
-            last_u = self.inputs[b][-cfg.nu:] if self.inputs[b] else [0.0] * cfg.nu
-            P[b] = harness.assemble_params(route, x_init, last_u, self.idx[b], self.constraints[b], self.dyn[b])
-        return P
+        return np.array([r.parameters() for r in self.robots], dtype=np.float64).reshape(self.B, self.cfg.n_p)
 
     def advance(self, U):
-        cfg = self.cfg
-        for b in range(self.B):
-            u = U[b]
-            self.inputs[b] += [float(v) for v in u[:cfg.nu * cfg.num_steps_taken]]
-            st = self.states[b]
-            for i in range(cfg.num_steps_taken):
-                x, y, th = st[-3], st[-2], st[-1]
-                st += [x + cfg.ts * (u[i * cfg.nu] * math.cos(th)), y + cfg.ts * (u[i * cfg.nu] * math.sin(th)),
-                       th + cfg.ts * u[1 + i * cfg.nu]]
-            end = self.route.end
-            self.done[b] = (abs(st[-3] - end[0]) <= 0.05 and abs(st[-2] - end[1]) <= 0.05
-                            and abs(self.inputs[b][-2]) < 0.005)
-        self.t += cfg.num_steps_taken
-
-    def step(self, solve_fn):
-        P = self.assemble()
-        U, Y, st = solve_fn(P, self.U, self.Y)
-        self.U, self.Y = U, Y
-        self.advance(U)
-        return P, st
+        for b, r in enumerate(self.robots):
+            r.apply(U[b])
+            self.done[b] = r.terminal()
+            r.t += self.cfg.num_steps_taken                                   # :401
+        self.t += self.cfg.num_steps_taken
 
 
-class VectorizedRecedingHorizon:
+class VectorizedRecedingHorizon(_HostLoop):
     """``BatchedRecedingHorizon`` with the per-robot Python loops replaced by NumPy array operations
     (BASELINE config 4: 8192 robots x 100 steps).  Same quantities, same order of operations per
     robot -- the test suite demands bit-identical parameter vectors against the loop version.
 
     All robots share the route; dynamic obstacles are per robot: ``dyn_obs`` is ``None`` or a tuple of
-    arrays ``(p1 [B, K, 2], p2 [B, K, 2], freq [B, K], rx [B, K], ry [B, K], angle [B, K])``.
+    arrays ``(p1 [B, K, 2], p2 [B, K, 2], freq [B, K], rx [B, K], ry [B, K], angle [B, K])``; ``idx0`` = the
+    reference sample each robot starts its window search at (default 0, as the reference).
     """
 
-    def __init__(self, route: harness.Route, starts, dyn_obs=None, sincos=None, sinus_object=False):
+    def __init__(self, route: harness.Route, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None):
         cfg = self.cfg = route.cfg
         self.route = route
         self.sinus_object = bool(sinus_object)     # obstacle index 2 follows the sinusoidal law (visibility.py:183-196,210-212)
@@ -227,7 +232,7 @@ class VectorizedRecedingHorizon:
         self.traj = [self.state.copy()]
         self.last_u = np.zeros((B, cfg.nu))
         self.has_input = False
-        self.idx = np.zeros(B, dtype=np.int64)
+        self.idx = np.zeros(B, dtype=np.int64) if idx0 is None else np.array(idx0, dtype=np.int64).reshape(B)
         self.t = 0
         self.dyn_obs = dyn_obs
         K = 0 if dyn_obs is None else dyn_obs[0].shape[1]
@@ -368,15 +373,8 @@ class VectorizedRecedingHorizon:
         self.done = (np.abs(st[:, 0] - end[0]) <= 0.05) & (np.abs(st[:, 1] - end[1]) <= 0.05) & (np.abs(self.last_u[:, 0]) < 0.005)
         self.t += s
 
-    def step(self, solve_fn):
-        P = self.assemble()
-        U, Y, st = solve_fn(P, self.U, self.Y)
-        self.U, self.Y = U, Y
-        self.advance(U)
-        return P, st
 
-
-class FleetRecedingHorizon:
+class FleetRecedingHorizon(_HostLoop):
     """``VectorizedRecedingHorizon`` for a fleet on R routes: robot b follows ``routes[route_of[b]]``.
 
     One ``VectorizedRecedingHorizon`` per route runs that route's robots (in fleet order); their rows are
@@ -394,15 +392,14 @@ class FleetRecedingHorizon:
         assert all(r.cfg is cfg or r.cfg == cfg for r in self.routes)
         assert ((self.route_of >= 0) & (self.route_of < len(self.routes))).all()
         starts = np.array(starts, dtype=np.float64).reshape(B, 3)
-        i0 = np.zeros(B, dtype=np.int64) if idx0 is None else np.asarray(idx0, dtype=np.int64).reshape(B)
         self.parts = []                                           # (robots of the route in fleet order, its mirror)
         for r, route in enumerate(self.routes):
             ids = np.nonzero(self.route_of == r)[0]
             if not len(ids):
                 continue
             sub = VectorizedRecedingHorizon(route, starts[ids], None if dyn_obs is None else tuple(a[ids] for a in dyn_obs),
-                                            sincos=sincos, sinus_object=sinus_object)
-            sub.idx = i0[ids].copy()
+                                            sincos=sincos, sinus_object=sinus_object,
+                                            idx0=None if idx0 is None else np.asarray(idx0).reshape(B)[ids])
             self.parts.append((ids, sub))
         self.t = 0
         self.U = np.zeros((B, cfg.n_u))
@@ -451,19 +448,10 @@ class FleetRecedingHorizon:
             sub.advance(U[ids])
         self.t += self.cfg.num_steps_taken
 
-    def step(self, solve_fn):
-        P = self.assemble()
-        U, Y, st = solve_fn(P, self.U, self.Y)
-        self.U, self.Y = U, Y
-        self.advance(U)
-        return P, st
-
 
 def _fill_route(r, route: harness.Route, keep: list):
     """Fill the ``nmpc_route`` struct ``r`` from ``route``; the arrays it points to are appended to ``keep``,
     which must outlive the call that reads the struct."""
-    import ctypes as C
-    from . import _lib
     cfg = route.cfg
 
     def arr(v):
@@ -506,8 +494,6 @@ class DeviceRecedingHorizon:
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
                  route_of=None):
-        import ctypes as C
-        from . import _lib
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -535,17 +521,15 @@ class DeviceRecedingHorizon:
         for r, rt in zip(rs, routes):
             _fill_route(r, rt, keep)
         h = C.c_void_p()
-        i32 = C.POINTER(C.c_int32)
         i0 = None if idx0 is None else np.ascontiguousarray(idx0, dtype=np.int32)
-        i0p = None if i0 is None else i0.ctypes.data_as(i32)
         if single:
             assert route_of is None, "route_of goes with a list of routes"
             self.route_of = None
-            rc = self.lib.nmpc_loop_new(solver._h, rs, B, _lib.as_dp(starts), i0p, K, _lib.as_dp(dyn), int(max_steps), C.byref(h))
+            rc = self.lib.nmpc_loop_new(solver._h, rs, B, _lib.as_dp(starts), _lib.as_i32p(i0), K, _lib.as_dp(dyn), int(max_steps), C.byref(h))
         else:
             self.route_of = None if route_of is None else np.ascontiguousarray(route_of, dtype=np.int32).reshape(B)
-            rc = self.lib.nmpc_loop_new_routes(solver._h, rs, len(routes), None if self.route_of is None else self.route_of.ctypes.data_as(i32),
-                                               B, _lib.as_dp(starts), i0p, K, _lib.as_dp(dyn), int(max_steps), C.byref(h))
+            rc = self.lib.nmpc_loop_new_routes(solver._h, rs, len(routes), _lib.as_i32p(self.route_of),
+                                               B, _lib.as_dp(starts), _lib.as_i32p(i0), K, _lib.as_dp(dyn), int(max_steps), C.byref(h))
         solver._check(rc)
         self._l = h
         self.max_steps = int(max_steps)
@@ -569,27 +553,23 @@ class DeviceRecedingHorizon:
 
     def read(self):
         """-> (state [B,3], last_u [B,2], idx [B], done [B] bool, status [B]) after synchronising."""
-        import ctypes as C
-        from . import _lib
         B = self.B
         state, last_u = np.empty((B, 3)), np.empty((B, 2))
         idx, done = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.uint8)
         st = np.empty(B, dtype=_lib.STATUS_DTYPE)
         self.solver._check(self.lib.nmpc_loop_read(self._l, _lib.as_dp(state), _lib.as_dp(last_u),
-                                                   idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                   done.ctypes.data_as(C.POINTER(C.c_uint8)), st.ctypes.data))
+                                                   _lib.as_i32p(idx), done.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   st.ctypes.data))
         return state, last_u, idx, done.astype(bool), st
 
     def params(self):
         """-> (P [B,n_p] of the last step, U [B,n_u], Y [B,n1])."""
-        from . import _lib
         P, U, Y = np.empty((self.B, self.cfg.n_p)), np.empty((self.B, self.cfg.n_u)), np.empty((self.B, self.cfg.n1))
         self.solver._check(self.lib.nmpc_loop_params(self._l, _lib.as_dp(P), _lib.as_dp(U), _lib.as_dp(Y)))
         return P, U, Y
 
     def trajectory(self):
         """-> [rows, B, 3]: the start poses and every pose reached so far (needs ``max_steps`` > 0)."""
-        from . import _lib
         rows = self.steps * self.cfg.num_steps_taken + 1
         T = np.empty((rows, self.B, 3))
         n = self.lib.nmpc_loop_trajectory(self._l, _lib.as_dp(T), rows)

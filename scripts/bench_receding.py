@@ -106,8 +106,7 @@ if not args.host:
         "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum())}))
     sys.exit(0)
 if route_of is None:
-    rh = VectorizedRecedingHorizon(routes, starts, dyn)
-    rh.idx = i0.astype(np.int64)
+    rh = VectorizedRecedingHorizon(routes, starts, dyn, idx0=i0)
 else:
     rh = FleetRecedingHorizon(routes, route_of, starts, dyn, idx0=i0)
 t_solve, t_asm, iters, conv = [], [], [], []

@@ -1,6 +1,6 @@
 """The host mirror of a fleet on many routes (``FleetRecedingHorizon``) against the single-route mirror
-(``VectorizedRecedingHorizon``, pinned through tests/test_harness.py to the goldens recorded from the
-reference's PathGenerator.run), with the oracle solving: a fleet's robots must get exactly the bits they
+(``VectorizedRecedingHorizon``, pinned by tests/test_harness.py to ``BatchedRecedingHorizon`` and with it
+to the goldens recorded from the reference's PathGenerator.run), with the oracle solving: a fleet's robots must get exactly the bits they
 get on their own route, and ``frontend.random_fleet`` must deal robots and starts reproducibly."""
 import numpy as np
 
@@ -39,8 +39,7 @@ def test_one_route_equals_vectorized_mirror():
     dyn = _dyn([route], route_of, i0, K, 4)
     o = oracle_for(cfg)
     fleet = FleetRecedingHorizon([route], route_of, starts, dyn, sincos=o.sincos_array, idx0=i0)
-    host = VectorizedRecedingHorizon(route, starts, dyn, sincos=o.sincos_array)
-    host.idx = i0.astype(np.int64)
+    host = VectorizedRecedingHorizon(route, starts, dyn, sincos=o.sincos_array, idx0=i0)
     for k in range(steps):
         Pf, stf = fleet.step(_solve(o))
         Ph, sth = host.step(_solve(o))
@@ -67,8 +66,7 @@ def test_three_routes_equal_three_separate_mirrors():
     alone = []
     for r, route in enumerate(routes):
         ids = np.nonzero(route_of == r)[0]
-        h = VectorizedRecedingHorizon(route, starts[ids], tuple(a[ids] for a in dyn), sincos=o.sincos_array)
-        h.idx = i0[ids].astype(np.int64)
+        h = VectorizedRecedingHorizon(route, starts[ids], tuple(a[ids] for a in dyn), sincos=o.sincos_array, idx0=i0[ids])
         alone.append((ids, h))
     for k in range(steps):
         P, _ = fleet.step(_solve(o))

@@ -97,8 +97,7 @@ def test_cfg4_device_loop_full_fleet(steps, n_mirror):
     s = BatchSolver(cfg, max_batch=B)
     try:
         dev = DeviceRecedingHorizon(s, route, starts, dyn, max_steps=steps, idx0=i0)
-        host = VectorizedRecedingHorizon(route, starts[ids], tuple(a[ids] for a in dyn), sincos=o.sincos_array)
-        host.idx = i0[ids].astype(np.int64)
+        host = VectorizedRecedingHorizon(route, starts[ids], tuple(a[ids] for a in dyn), sincos=o.sincos_array, idx0=i0[ids])
         for k in range(steps):
             dev.step()
             P, st = host.step(lambda P_, U, Y: o.solve_batch(P_, u0=U, y0=Y, threads=8))

@@ -1,6 +1,7 @@
 """GPU: the receding-horizon loop on device (nmpc_loop_*) against its host
-mirror.  The mirror is ``VectorizedRecedingHorizon`` -- itself pinned to the loop version and, through
-tests/test_harness.py, to the goldens recorded from the reference's PathGenerator.run -- driven by the
+mirror.  The mirror is ``VectorizedRecedingHorizon`` -- itself pinned to ``BatchedRecedingHorizon``, whose
+robots run the one literal per-robot step that tests/test_harness.py pins, through that driver and through
+``TrajectoryGenerator.run``, to the goldens recorded from the reference's PathGenerator.run -- driven by the
 oracle and given the kernels' sin / cos, so parameter vectors, states, reference indices and solver
 counters must agree bit for bit, step after step."""
 import numpy as np
@@ -44,8 +45,7 @@ def test_device_loop_equals_host_mirror(name, scene, K, steps, sinus):
     s = BatchSolver(cfg, max_batch=32)
     try:
         dev = DeviceRecedingHorizon(s, route, starts, dyn, max_steps=steps, idx0=i0, sinus_object=sinus)
-        host = VectorizedRecedingHorizon(route, starts, dyn, sincos=o.sincos_array, sinus_object=sinus)   # (third ellipse: sinusoidal law)
-        host.idx = i0.astype(np.int64)
+        host = VectorizedRecedingHorizon(route, starts, dyn, sincos=o.sincos_array, sinus_object=sinus, idx0=i0)   # (third ellipse: sinusoidal law)
         for k in range(steps):
             dev.step()
             P, st = host.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=8))
@@ -81,8 +81,7 @@ def test_device_loop_reaches_goal_and_brakes():
     s = BatchSolver(cfg, max_batch=8)
     try:
         dev = DeviceRecedingHorizon(s, route, starts, None, max_steps=120, idx0=i0)
-        host = VectorizedRecedingHorizon(route, starts, None, sincos=o.sincos_array)
-        host.idx = i0.astype(np.int64)
+        host = VectorizedRecedingHorizon(route, starts, None, sincos=o.sincos_array, idx0=i0)
         for k in range(120):
             dev.step()
             P, st = host.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=6))

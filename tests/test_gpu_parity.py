@@ -395,8 +395,7 @@ def test_batched_receding_horizon_on_gpu_equals_oracle(solvers):
     c = np.stack([np.array(route.x_ref)[i0 + 8], np.array(route.y_ref)[i0 + 8]], axis=1)[:, None, :].repeat(3, axis=1)
     dyn = (c + rng.uniform(-3, 3, (B, 3, 2)), c + rng.uniform(-3, 3, (B, 3, 2)), rng.uniform(0.05, 0.1, (B, 3)),
            rng.uniform(0.3, 1.0, (B, 3)), rng.uniform(0.3, 1.0, (B, 3)), rng.uniform(0, np.pi, (B, 3)))
-    a, b = VectorizedRecedingHorizon(route, starts, dyn), VectorizedRecedingHorizon(route, starts, dyn)
-    a.idx, b.idx = i0.astype(np.int64), i0.astype(np.int64)
+    a, b = VectorizedRecedingHorizon(route, starts, dyn, idx0=i0), VectorizedRecedingHorizon(route, starts, dyn, idx0=i0)
     for k in range(5):
         Pa, sta = a.step(lambda P, U, Y: s.solve(P, u0=U, y0=Y))
         Pb, stb = b.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=8))

@@ -86,18 +86,25 @@ def test_dyn_obstacle_and_vertex_selection_scene12():
                 assert tuple(got[0]) == tuple(d[key + "_first"][j])
 
 
-@pytest.mark.parametrize("name,over,sinus", [("harness_scene1.npz", {}, False),
-                                             ("harness_scene12.npz", dict(num_steps_taken=2, Nobs=4), True)])
+REPLAYS = pytest.mark.parametrize("name,over,sinus", [("harness_scene1.npz", {}, False),
+                                                      ("harness_scene12.npz", dict(num_steps_taken=2, Nobs=4), True)])
+
+
+def recorded_route(d, cfg, sinus):
+    dyn = []
+    if "dyn_obs" in d.files:
+        dyn = [[[o[0], o[1]], [o[2], o[3]], o[4], o[5], o[6], o[7]] for o in d["dyn_obs"]]
+    return harness.Route(cfg, tuple(d["start"]), tuple(d["end"]), [tuple(p) for p in d["path"]],
+                         [tuple(v) for v in d["vertices"]], dyn, sinus)
+
+
+@REPLAYS
 def test_driver_replays_reference_parameter_sequence(name, over, sinus):
     """Feed the recorded solutions to this repo's driver: every parameter vector it sends and the
     trajectory it integrates must equal what the reference's own loop produced, bit for bit."""
     d = load(name)
     cfg = load_config(**over)
-    dyn = []
-    if "dyn_obs" in d.files:
-        dyn = [[[o[0], o[1]], [o[2], o[3]], o[4], o[5], o[6], o[7]] for o in d["dyn_obs"]]
-    route = harness.Route(cfg, tuple(d["start"]), tuple(d["end"]), [tuple(p) for p in d["path"]],
-                          [tuple(v) for v in d["vertices"]], dyn, sinus)
+    route = recorded_route(d, cfg, sinus)
     rec = []
     mng = ReplayManager(d["solutions"], d["exit"])
     gen = TrajectoryGenerator(cfg, sinus_object=sinus, manager_factory=lambda: mng)
@@ -118,6 +125,23 @@ def test_driver_replays_reference_parameter_sequence(name, over, sinus):
         assert np.array_equal(xx, d["xx"]) and np.array_equal(xy, d["xy"])
         assert np.array_equal(uv, d["uv"]) and np.array_equal(uw, d["uw"])
         assert abs(xx[-1] - d["end"][0]) <= 0.05 and abs(xy[-1] - d["end"][1]) <= 0.05
+
+
+@REPLAYS
+def test_batched_driver_replays_reference_parameter_sequence(name, over, sinus):
+    """The same replay through the batched driver with one robot: at every recorded step its parameter
+    vector must equal the one the reference's own loop sent, bit for bit.  Both drivers run the one
+    ``RecedingHorizonRobot``, so this holds by construction -- and stays so."""
+    d = load(name)
+    cfg = load_config(**over)
+    route = recorded_route(d, cfg, sinus)
+    brh = BatchedRecedingHorizon(route, [route.start], sinus_object=sinus)
+    for k in range(len(d["params"])):
+        P, _ = brh.step(lambda P, U, Y: (d["solutions"][k][None, :], Y, None))         # noqa: B023
+        assert P.shape == (1, cfg.n_p) and np.array_equal(P[0], d["params"][k]), k
+    if name == "harness_scene1.npz":                      # scene 1 runs to the goal
+        assert np.array_equal(brh.states[0][0::cfg.nx], d["xx"]) and np.array_equal(brh.states[0][1::cfg.nx], d["xy"])
+        assert brh.done[0]
 
 
 def test_batched_receding_horizon_matches_sequential():
@@ -154,7 +178,7 @@ def test_synthetic_batch_is_deterministic_and_well_formed():
 
 @pytest.mark.parametrize("sinus,K", [(False, 3), (True, 3), (False, 2), (False, 1)])
 def test_vectorized_receding_horizon_equals_loop_version(sinus, K):
-    """NumPy-vectorised batch assembly == the per-robot loops, bit for bit, incl. per-robot dynamic
+    """NumPy-vectorised batch assembly == the per-robot step (``BatchedRecedingHorizon``), bit for bit, incl. per-robot dynamic
     obstacles (linear and sinusoidal law), num_steps_taken = 2 and the braking zone.  K < Ndynobs moving
     obstacles: the reference rotates the whole flat dynamic list (src/path_generator.py:312), so padding slots
     inherit stale ellipses of obstacle 0 -- both versions must reproduce that."""
@@ -166,19 +190,17 @@ def test_vectorized_receding_horizon_equals_loop_version(sinus, K):
     rng = np.random.default_rng(3)
     n = len(route.x_ref)
     starts, lists = [], []
-    for i in [0, 3, n - 25, n - 8, n - 2, 40]:
+    i0 = [0, 3, n - 25, n - 8, n - 2, 40]                          # start the window search where the robot is
+    for i in i0:
         starts.append((route.x_ref[i] + rng.normal(0, 0.05), route.y_ref[i] + rng.normal(0, 0.05), route.theta_ref[i]))
         lists.append([[list(rng.uniform(0, 20, 2)), list(rng.uniform(0, 20, 2)), rng.uniform(0.05, 0.1),
                        rng.uniform(0.3, 1), rng.uniform(0.3, 1), rng.uniform(0, 3)] for _ in range(K)])
     B = len(starts)
-    loop = BatchedRecedingHorizon(route, starts, lists, sinus_object=sinus)
-    for b in range(B):                                              # start the window search where the robot is
-        loop.idx[b] = [0, 3, n - 25, n - 8, n - 2, 40][b]
+    loop = BatchedRecedingHorizon(route, starts, lists, sinus_object=sinus, idx0=i0)
     arr = lambda f: np.array([[f(o_) for o_ in l] for l in lists])  # noqa: E731
     dyn = (arr(lambda o_: o_[0]), arr(lambda o_: o_[1]), arr(lambda o_: o_[2]), arr(lambda o_: o_[3]),
            arr(lambda o_: o_[4]), arr(lambda o_: o_[5]))
-    vec = VectorizedRecedingHorizon(route, starts, dyn, sinus_object=sinus)
-    vec.idx = np.array(loop.idx)
+    vec = VectorizedRecedingHorizon(route, starts, dyn, sinus_object=sinus, idx0=i0)
     solve = lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=4)         # noqa: E731
     stale = False
     for k in range(6):
