@@ -236,6 +236,21 @@ int nmpc_loop_new(nmpc_handle *h, const nmpc_route *route, int B, const double *
 int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const int32_t *route_of,
                          int B, const double *starts, const int32_t *idx0, int K, const double *dyn,
                          int max_steps, nmpc_loop **out);
+/* Peers: the robots of a group see each other as moving ellipses (the rule: DESIGN.md section 5.9).  Every step, between the
+ * assembly of p and the solve, each robot's poses over the horizon are predicted from its state and its previous plan (the
+ * Euler step of the state advance; before the first solve everybody stands still), and for each robot the M robots of its
+ * group whose predicted positions come closest to its own -- min over the stages of the squared distance, below range^2,
+ * sorted by (distance, robot index) -- are written over the ellipse slots K .. K + M - 1 of its p, stage by stage, as
+ * (x, y, rx, ry, theta).  A slot that finds no peer keeps what the assembly put there; the block the loop carries from step
+ * to step never sees peers.
+ *   group_of [B]  the group of each robot, values in [0, B); NULL = one group.  Robots of different groups never see each
+ *                 other, whatever routes they follow.
+ *   M             ellipse slots given to peers, M >= 1 and K + M <= Ndynobs
+ *   rx, ry        the ellipse's radii as the cost reads them (no padding is added), range: all finite and > 0
+ * To be called once, before the loop's first step.  NMPC_ERR_BAD_ARG with a message, and nothing changed, for M < 1,
+ * K + M > Ndynobs, a group_of[b] out of range, an rx, ry or range that is not finite and positive, a call after a step, or
+ * a second call.  A loop without peers enqueues what it enqueued before this function existed. */
+int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range);
 void nmpc_loop_free(nmpc_loop *l);
 /* Enqueues assemble -> solve -> advance on `stream`; does not synchronise. */
 int nmpc_loop_step(nmpc_loop *l, void *stream);

@@ -22,7 +22,7 @@ SYMBOLS = (
     "nmpc_ping", "nmpc_last_error", "nmpc_abi_version", "nmpc_experiments_build", "nmpc_kernel_name", "nmpc_solve_batch_device",
     "nmpc_solve_batch_host", "nmpc_last_batch_ms", "nmpc_set_time_limits", "nmpc_eval_batch_device", "nmpc_eval_batch_host",
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
-    "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
+    "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
     "nmpc_loop_trajectory",
 )
 
@@ -260,6 +260,8 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
                                   C.POINTER(vp)]
     lib.nmpc_loop_new_routes.argtypes = [vp, C.POINTER(NmpcRoute), C.c_int, C.POINTER(C.c_int32), C.c_int, dp, C.POINTER(C.c_int32),
                                          C.c_int, dp, C.c_int, C.POINTER(vp)]
+    lib.nmpc_loop_set_peers.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_double, C.c_double]
+    lib.nmpc_loop_set_peers.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_loop_step.argtypes = [vp, vp]

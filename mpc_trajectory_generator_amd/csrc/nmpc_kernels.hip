@@ -593,6 +593,10 @@ struct nmpc_loop {
     DevBuf<int> d_idx;
     DevBuf<unsigned char> d_done;
     DevBuf<nmpc_status> d_st;
+    bool peers = false;          // nmpc_loop_set_peers: two more kernels per step, between the assembly and the solve
+    nmpc::PeerArgs pa{};
+    DevBuf<double> d_pred;       // [B][N][3]
+    DevBuf<int> d_group_of, d_goff, d_gmem;
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -698,6 +702,51 @@ int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *star
     return nmpc_loop_new_routes(h, r, 1, nullptr, B, starts, idx0, K, dyn, max_steps, out);
 }
 
+int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    const nmpc::LoopArgs &a = l->a;
+    const int B = a.B;
+    if (l->peers) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: the loop has its peers already");
+    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: after the loop's first step");
+    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: M < 1");
+    if (a.K + M > a.ndyn) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: K + M > Ndynobs, no free ellipse slot");
+    for (const double v : {rx, ry, range})
+        if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: rx, ry and range must be finite and positive");
+    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: group_of out of range");
+    // member lists: groups 0 .. B - 1 (most of them empty), each group's robots in ascending index
+    std::vector<int> gof(B, 0), goff(B + 1, 0), gmem(B);
+    if (group_of) for (int b = 0; b < B; ++b) gof[b] = group_of[b];
+    for (int b = 0; b < B; ++b) goff[gof[b] + 1]++;
+    for (int g = 0; g < B; ++g) goff[g + 1] += goff[g];
+    {
+        std::vector<int> at(goff.begin(), goff.end() - 1);
+        for (int b = 0; b < B; ++b) gmem[at[gof[b]]++] = b;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    DevBuf<double> pred;
+    DevBuf<int> d_gof, d_goff, d_gmem;
+    hipError_t e = pred.alloc((size_t)B * a.N * 3);
+    if (e == hipSuccess) e = d_gof.alloc(B);
+    if (e == hipSuccess) e = d_goff.alloc(B + 1);
+    if (e == hipSuccess) e = d_gmem.alloc(B);
+    if (e == hipSuccess) e = hipMemcpy(d_gof, gof.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_goff, goff.data(), (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_gmem, gmem.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_peers: allocation", e);
+    l->d_pred = std::move(pred); l->d_group_of = std::move(d_gof); l->d_goff = std::move(d_goff); l->d_gmem = std::move(d_gmem);
+    nmpc::PeerArgs &p = l->pa;
+    p.B = B; p.N = a.N; p.n_p = a.n_p; p.n_u = a.n_u; p.s = a.s; p.K = a.K; p.M = M;
+    p.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
+    p.ts = a.ts; p.rx = rx; p.ry = ry; p.range2 = range * range;
+    p.state = l->d_state; p.U = l->d_U; p.pred = l->d_pred;
+    p.group_of = l->d_group_of; p.goff = l->d_goff; p.gmem = l->d_gmem; p.P = l->d_P;
+    l->peers = true;
+    return NMPC_OK;
+}
+
 void nmpc_loop_free(nmpc_loop *l)
 {
     if (!l) return;
@@ -727,6 +776,11 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     a.dyn_out = l->d_dyn[cur ^ 1];
     hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(a.B), dim3(64), 0, s, a);
     HIP_TRY(h, hipGetLastError());
+    if (l->peers) {
+        hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, l->pa);
+        hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(a.B), dim3(64), 0, s, l->pa);
+        HIP_TRY(h, hipGetLastError());
+    }
     // warm start: previous controls and multipliers, penalty back to its initial value (the server's behaviour)
     // launch order: from the second step on, by the pass counts of the step before (read by the classification kernel ahead of the solve, which
     // then overwrites them); the first step has only the inputs to go by

@@ -249,4 +249,106 @@ __global__ void nmpc_loop_advance_kernel(LoopArgs a)
     a.done[b] = (fabs(x - end[0]) <= 0.05 && fabs(y - end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
 }
 
+// ---- peers: the robots of a group see each other (nmpc_loop_set_peers; the rule is DESIGN.md section 5.9) ----
+// Two kernels between the assembly and the solve: every robot's predicted poses over the horizon, then per robot the M closest
+// peers of its group written into the ellipse slots [K, K + M) of p.  The carried block (dyn_in / dyn_out) never sees them.
+struct PeerArgs {
+    int B, N, n_p, n_u, s, K, M;
+    int pdyn;                 // where the dynamic block starts in p
+    double ts, rx, ry, range2;
+    const double *state;      // [B][3]
+    const double *U;          // [B][n_u]: the previous plan
+    double *pred;             // [B][N][3]
+    const int *group_of;      // [B]
+    const int *goff;          // [groups + 1]: a group's members are gmem[goff[g] .. goff[g + 1])
+    const int *gmem;          // [B], ascending robot index inside a group
+    double *P;                // [B][n_p]
+};
+
+// one thread per robot: pred[b][k] = the pose after k + 1 Euler steps (the expression of nmpc_loop_advance_kernel) under the
+// previous plan shifted by the s controls already applied, its last control held beyond the plan's end
+__global__ void nmpc_loop_predict_kernel(PeerArgs a)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    const double *u = a.U + (size_t)b * a.n_u;
+    double *out = a.pred + (size_t)b * a.N * 3;
+    double x = a.state[3 * b], y = a.state[3 * b + 1], th = a.state[3 * b + 2];
+    for (int k = 0; k < a.N; ++k) {
+        const int c = a.s + k < a.N ? a.s + k : a.N - 1;
+        const double v = u[2 * c], w = u[2 * c + 1];
+        double sn, cs;
+        sincos_cw(th, sn, cs);
+        x = x + a.ts * (v * cs);
+        y = y + a.ts * (v * sn);
+        th = th + a.ts * w;
+        out[3 * k] = x; out[3 * k + 1] = y; out[3 * k + 2] = th;
+    }
+}
+
+// one wave per robot: D(b, j) = min_k |pred[b][k] - pred[j][k]|^2 over the members j != b of b's group (lanes stride over them),
+// the first M of the candidates D < range^2 in (D, j) order, each written over one ellipse slot of p[b]
+__global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int N = a.N;
+    // the group's member range: the same for the whole wave
+    const int g = a.group_of[b];
+    const int lo = a.goff[g], hi = a.goff[g + 1];
+    for (int k = lane; k < N; k += 64) {
+        own[2 * k] = a.pred[((size_t)b * N + k) * 3];
+        own[2 * k + 1] = a.pred[((size_t)b * N + k) * 3 + 1];
+    }
+    __syncthreads();
+    // the lane's own best NDYN_MAX candidates, sorted by (D, j); no candidate = (inf, INT_MAX), behind every real one
+    constexpr int NONE = 0x7fffffff;
+    double bd[NDYN_MAX];
+    int bj[NDYN_MAX];
+#pragma unroll
+    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = NONE; }
+    for (int i = lo + lane; i < hi; i += 64) {
+        const int j = a.gmem[i];
+        const double *pj = a.pred + (size_t)j * N * 3;
+        double D = __builtin_inf();
+        for (int k = 0; k < N; ++k) {
+            const double dx = own[2 * k] - pj[3 * k], dy = own[2 * k + 1] - pj[3 * k + 1];
+            const double d = dx * dx + dy * dy;
+            if (d < D) D = d;
+        }
+        if (j != b && D < a.range2) {
+            double cd = D;
+            int cj = j;
+#pragma unroll
+            for (int q = 0; q < NDYN_MAX; ++q) {
+                if (cd < bd[q] || (cd == bd[q] && cj < bj[q])) {
+                    const double td = bd[q]; const int tj = bj[q];
+                    bd[q] = cd; bj[q] = cj;
+                    cd = td; cj = tj;
+                }
+            }
+        }
+    }
+    // M rounds: the wave's (D, j) minimum over the lanes' heads; the lane that held it moves on to its next
+    double *pd = a.P + (size_t)b * a.n_p + a.pdyn;
+    const int per = 5 * N;
+    for (int m = 0; m < a.M; ++m) {
+        double d = bd[0];
+        int j = bj[0];
+        wave_argmin(d, j);
+        if (j == NONE) break;                 // (wave-uniform) no candidate left: the remaining slots keep what they hold
+        if (bj[0] == j) {
+#pragma unroll
+            for (int q = 0; q + 1 < NDYN_MAX; ++q) { bd[q] = bd[q + 1]; bj[q] = bj[q + 1]; }
+            bd[NDYN_MAX - 1] = __builtin_inf(); bj[NDYN_MAX - 1] = NONE;
+        }
+        const double *pj = a.pred + (size_t)j * N * 3;
+        double *slot = pd + (size_t)(a.K + m) * per;
+        for (int e = lane; e < per; e += 64) {
+            const int st = e / 5, f = e - st * 5;
+            slot[e] = f == 0 ? pj[3 * st] : (f == 1 ? pj[3 * st + 1] : (f == 2 ? a.rx : (f == 3 ? a.ry : pj[3 * st + 2])));
+        }
+    }
+}
+
 }  // namespace nmpc

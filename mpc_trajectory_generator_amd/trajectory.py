@@ -21,6 +21,7 @@ robots follow routes of their own.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import time
 
@@ -374,6 +375,35 @@ class VectorizedRecedingHorizon(_HostLoop):
         self.t += s
 
 
+@dataclasses.dataclass(frozen=True)
+class Peers:
+    """How the robots of a fleet see each other, for ``FleetRecedingHorizon`` and
+    ``DeviceRecedingHorizon`` alike: every step, the ``slots`` robots of a robot's group whose predicted
+    positions come closest to its own, closer than ``range``, take ellipse slots K .. K + slots - 1 of its
+    parameter vector (K = its scripted obstacles) as ellipses of radii ``rx``, ``ry`` -- the radii the cost
+    reads, nothing is added to them -- at their predicted poses.  ``group_of`` [B] = the group of each robot,
+    values in [0, B) (``None``: one group); robots of different groups never see each other."""
+    slots: int
+    rx: float
+    ry: float
+    range: float
+    group_of: object = None
+
+    def checked(self, B: int, K: int, Ndynobs: int):
+        """-> group_of as an int32 array or None; ValueError for what ``nmpc_loop_set_peers`` refuses."""
+        if self.slots < 1 or K + self.slots > Ndynobs:
+            raise ValueError(f"peers: slots = {self.slots} with {K} scripted obstacles and Ndynobs = {Ndynobs}")
+        for v in (self.rx, self.ry, self.range):
+            if not (math.isfinite(v) and v > 0):
+                raise ValueError("peers: rx, ry and range must be finite and positive")
+        if self.group_of is None:
+            return None
+        g = np.ascontiguousarray(self.group_of, dtype=np.int32).reshape(B)
+        if ((g < 0) | (g >= B)).any():
+            raise ValueError("peers: group_of out of range")
+        return g
+
+
 class FleetRecedingHorizon(_HostLoop):
     """``VectorizedRecedingHorizon`` for a fleet on R routes: robot b follows ``routes[route_of[b]]``.
 
@@ -382,9 +412,13 @@ class FleetRecedingHorizon(_HostLoop):
     per step.  Each robot's quantities are therefore exactly those of the single-route mirror for its route.
     ``dyn_obs``, ``sincos`` and ``sinus_object`` as in ``VectorizedRecedingHorizon``, ``dyn_obs`` in fleet
     order; ``idx0`` = the reference sample each robot starts at, on its own route (default 0).
+
+    ``peers`` (a ``Peers``) lets the robots of a group see each other: ``assemble`` overlays the chosen peers on
+    the gathered parameter vectors.  Peers cross routes, so the rule lives here and not in the per-route mirrors,
+    whose carried dynamic blocks never see it.
     """
 
-    def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None):
+    def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None):
         self.routes = list(routes)
         cfg = self.cfg = self.routes[0].cfg
         self.B = B = len(starts)
@@ -404,6 +438,13 @@ class FleetRecedingHorizon(_HostLoop):
         self.t = 0
         self.U = np.zeros((B, cfg.n_u))
         self.Y = np.zeros((B, cfg.n1))
+        self.sincos = sincos if sincos is not None else (lambda x: (np.sin(x), np.cos(x)))
+        self.K = 0 if dyn_obs is None else dyn_obs[0].shape[1]
+        self.peers = peers
+        if peers is not None:
+            g = peers.checked(B, self.K, cfg.Ndynobs)
+            g = np.zeros(B, dtype=np.int32) if g is None else g
+            self.groups = [np.nonzero(g == v)[0] for v in np.unique(g)]       # members in ascending robot index
 
     def _gather(self, field, shape, dtype=np.float64):
         out = np.empty((self.B,) + shape, dtype=dtype)
@@ -441,7 +482,61 @@ class FleetRecedingHorizon(_HostLoop):
         P = np.empty((self.B, self.cfg.n_p))
         for ids, sub in self.parts:
             P[ids] = sub.assemble()
+        if self.peers is not None:
+            self._overlay_peers(P)
         return P
+
+    def predict(self):
+        """-> pred [B, N, 3]: pred[j, k] = robot j's pose after k + 1 Euler steps (the expression of ``advance``) from
+        its state, under its previous plan shifted by the controls already applied: control k is U[j, s + k], and
+        the plan's last control beyond its end."""
+        cfg = self.cfg
+        N, s, nu = cfg.N_hor, cfg.num_steps_taken, cfg.nu
+        st = self.state
+        x, y, th = st[:, 0], st[:, 1], st[:, 2]
+        pred = np.empty((self.B, N, 3))
+        for k in range(N):
+            c = min(s + k, N - 1)
+            v, w = self.U[:, c * nu], self.U[:, 1 + c * nu]
+            sn, cs = self.sincos(np.ascontiguousarray(th))
+            x, y, th = x + cfg.ts * (v * cs), y + cfg.ts * (v * sn), th + cfg.ts * w
+            pred[:, k, 0], pred[:, k, 1], pred[:, k, 2] = x, y, th
+        return pred
+
+    def _overlay_peers(self, P):
+        """The peers rule on the gathered parameter vectors, in place."""
+        cfg, pe = self.cfg, self.peers
+        N, M = cfg.N_hor, pe.slots
+        per = cfg.ndynobs * N
+        base = cfg.n_p - cfg.nx * N - cfg.Ndynobs * per + self.K * per       # slot K of the dynamic block
+        pred = self.predict()
+        r2 = pe.range * pe.range
+        self.peer_index = np.full((self.B, M), -1)                           # who fills slot K + m of robot b at this step (-1: nobody)
+        for mem in self.groups:
+            G = len(mem)
+            if G < 2:
+                continue
+            px, py = pred[mem, :, 0], pred[mem, :, 1]                        # [G, N]
+            rows = max(1, (1 << 22) // G)                                    # robots of the group per pass: bounds the [rows, G] tables
+            for r0 in range(0, G, rows):
+                me = np.arange(r0, min(G, r0 + rows))
+                D = np.full((len(me), G), np.inf)
+                for k in range(N):                                           # min over the stages, in order
+                    dx, dy = px[me, None, k] - px[None, :, k], py[me, None, k] - py[None, :, k]
+                    d = dx * dx + dy * dy
+                    D = np.where(d < D, d, D)
+                ok = D < r2
+                ok[np.arange(len(me)), me] = False                           # not oneself
+                order = np.argsort(np.where(ok, D, np.inf), axis=1, kind="stable")   # (D, j): members are in ascending j
+                for m in range(min(M, G - 1)):
+                    j = order[:, m]
+                    got = ok[np.arange(len(me)), j]
+                    b, src = mem[me[got]], mem[j[got]]
+                    blk = np.empty((len(b), N, cfg.ndynobs))
+                    blk[..., 0], blk[..., 1], blk[..., 4] = pred[src, :, 0], pred[src, :, 1], pred[src, :, 2]
+                    blk[..., 2], blk[..., 3] = pe.rx, pe.ry
+                    self.peer_index[b, m] = src
+                    P[b, base + m * per:base + (m + 1) * per] = blk.reshape(len(b), per)
 
     def advance(self, U):
         for ids, sub in self.parts:
@@ -490,10 +585,14 @@ class DeviceRecedingHorizon:
     step's solve gets that budget from the start of its launch on the device, so a fleet can be re-planned within a control
     period; ``max_duration_ms`` bounds each robot's solve the same way.  Instances the clock stops answer
     ``NotConvergedOutOfTime`` with the feasible half step, and the next step warm-starts from it as from any other solve.
+
+    ``peers`` (a ``Peers``): the robots of a group see each other (``nmpc_loop_set_peers``); two more
+    kernels per step, between the assembly and the solve.  Its host mirror is ``FleetRecedingHorizon`` with the same ``peers``
+    (tests/test_gpu_peers_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None):
+                 route_of=None, peers=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -533,6 +632,13 @@ class DeviceRecedingHorizon:
         solver._check(rc)
         self._l = h
         self.max_steps = int(max_steps)
+        self.peers = peers
+        if peers is not None:
+            g = None if peers.group_of is None else np.ascontiguousarray(peers.group_of, dtype=np.int32).reshape(B)
+            rc = self.lib.nmpc_loop_set_peers(h, _lib.as_i32p(g), int(peers.slots), float(peers.rx), float(peers.ry), float(peers.range))
+            if rc:
+                self.close()
+                solver._check(rc)
 
     def close(self):
         if getattr(self, "_l", None):

@@ -3,8 +3,9 @@
 for K receding-horizon steps (num_steps_taken = 2), warm starts carried, p rebuilt every step.
 Default: the whole loop on device (nmpc_loop_*: assembly, solve and state advance are kernels, nothing
 crosses PCIe between steps), every robot on the scene's route; --routes R > 1: the robots follow R routes
-planned between random start / goal points of the scene (frontend.random_fleet).  --host: parameter
-assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+planned between random start / goal points of the scene (frontend.random_fleet).  --peers G: the robots see each
+other in groups of G consecutive robots; --peer-slots of the Ndynobs ellipse slots go to peers, the
+rest stay scripted.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -16,7 +17,7 @@ sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config                            # noqa: E402
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
-from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, Peers, VectorizedRecedingHorizon    # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8192)
@@ -32,14 +33,28 @@ ap.add_argument("--split", type=int, default=2,
 ap.add_argument("--budget", type=int, default=0,
                 help="max_total_inner per solve: the deterministic counterpart of the reference's 0.5 s max_duration "
                      "(src/mpc/mpc_generator.py:9,186); 0 = off")
+ap.add_argument("--peers", type=int, default=0,
+                help="G > 0: groups of G consecutive robots (of a sub-fleet, see --split) see each other; 0 = nobody sees anybody")
+ap.add_argument("--peer-slots", type=int, default=2, help="with --peers: ellipse slots given to peers (the other Ndynobs - M stay scripted)")
+ap.add_argument("--peer-range", type=float, default=10.0, help="with --peers: how far a robot sees, in metres")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
 cfg = named_config("cfg4")
-K = cfg.Ndynobs
+K = cfg.Ndynobs - (args.peer_slots if args.peers else 0)
 B = args.batch
+# a peer's ellipse: its half width, this robot's half width and the margin
+peer_radius = cfg.vehicle_width + cfg.vehicle_margin
+
+
+def peers_of(n):
+    """groups of --peers consecutive robots among n"""
+    return Peers(slots=args.peer_slots, rx=peer_radius, ry=peer_radius, range=args.peer_range,
+                 group_of=(np.arange(n) // args.peers).astype(np.int32)) if args.peers else None
+
+
 if args.routes == 1:
     route = harness.scene_route(cfg, args.scene)
     rng = np.random.Generator(np.random.PCG64(0))
@@ -63,6 +78,9 @@ else:
 dyn = (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
        rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
 fleet = f", {args.routes} routes (frontend.random_fleet, seed 0)" if args.routes > 1 else ""
+if args.peers:
+    fleet += (f", {K} scripted ellipses and {args.peer_slots} peer slots per robot, groups of {args.peers} consecutive robots, "
+              f"range {args.peer_range} m, radii {peer_radius} m")
 solver = BatchSolver(cfg, max_batch=B, **sopts)
 if not args.host:
     from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon
@@ -73,7 +91,7 @@ if not args.host:
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
         loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
-                                           route_of=None if route_of is None else route_of[ids]))
+                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids))))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -105,10 +123,12 @@ if not args.host:
         "converged_frac_last_step": float((st["exit_status"] == 0).mean()),
         "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum())}))
     sys.exit(0)
-if route_of is None:
+if route_of is None and not args.peers:
     rh = VectorizedRecedingHorizon(routes, starts, dyn, idx0=i0)
+elif route_of is None:
+    rh = FleetRecedingHorizon([routes], np.zeros(B, dtype=np.int32), starts, dyn, idx0=i0, peers=peers_of(B))
 else:
-    rh = FleetRecedingHorizon(routes, route_of, starts, dyn, idx0=i0)
+    rh = FleetRecedingHorizon(routes, route_of, starts, dyn, idx0=i0, peers=peers_of(B))
 t_solve, t_asm, iters, conv = [], [], [], []
 
 

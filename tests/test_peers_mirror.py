@@ -1,0 +1,225 @@
+"""Peers on the host (``FleetRecedingHorizon(..., peers=Peers(...))``), with the oracle solving.
+
+The mirror's vectorised rule against a literal per-robot loop of the rule written here (prediction, closeness, selection,
+overlay), bit for bit on the parameter vectors over several steps; the carried dynamic block and everything of ``P`` outside
+the peer slots against the loop without peers on the same states and plans; and two robots on routes that are each other's
+reverse, which overlap without peers and keep apart with them."""
+import copy
+import math
+
+import numpy as np
+import pytest
+
+from conftest import oracle_for
+from mpc_trajectory_generator_amd import frontend, named_config
+from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, Peers
+
+
+def _solve(o, threads=8):
+    return lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=threads)
+
+
+def _dyn(routes, route_of, idx0, K, seed):
+    """Per-robot moving ellipses crossing the robot's own route (as tests/test_fleet_mirror.py)."""
+    if not K:
+        return None
+    rng = np.random.default_rng(seed)
+    B = len(route_of)
+    c = np.empty((B, K, 2))
+    for b in range(B):
+        r = routes[route_of[b]]
+        jj = np.minimum(len(r.x_ref) - 1, idx0[b] + rng.integers(0, 30, K))
+        c[b] = np.stack([np.array(r.x_ref)[jj], np.array(r.y_ref)[jj]], axis=1)
+    return (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
+            rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
+
+
+def _slot0(cfg):
+    """Where the dynamic block starts in a parameter vector."""
+    return 20 + cfg.N_hor + 3 * cfg.Nobs
+
+
+def literal_peers(cfg, P, state, U, K, group_of, M, rx, ry, rng_, sincos1):
+    """Section 5.9 robot by robot in Python floats: -> (P overlaid, chosen [B][<= M])."""
+    B, N, s, ts = len(state), cfg.N_hor, cfg.num_steps_taken, cfg.ts
+    pred = []
+    for j in range(B):
+        x, y, th = (float(v) for v in state[j])
+        row = []
+        for k in range(N):
+            c = s + k if s + k < N else N - 1
+            v, w = float(U[j][2 * c]), float(U[j][2 * c + 1])
+            sn, cs = sincos1(th)
+            x = x + ts * (v * cs)
+            y = y + ts * (v * sn)
+            th = th + ts * w
+            row.append((x, y, th))
+        pred.append(row)
+    P = P.copy()
+    chosen = []
+    for b in range(B):
+        cand = []
+        for j in range(B):
+            if j == b or group_of[j] != group_of[b]:
+                continue
+            D = math.inf
+            for k in range(N):
+                dx = pred[b][k][0] - pred[j][k][0]
+                dy = pred[b][k][1] - pred[j][k][1]
+                d = dx * dx + dy * dy
+                if d < D:
+                    D = d
+            if D < rng_ * rng_:
+                cand.append((D, j))
+        cand.sort()
+        chosen.append([j for _, j in cand[:M]])
+        for m, j in enumerate(chosen[-1]):
+            at = _slot0(cfg) + (K + m) * 5 * N
+            for k in range(N):
+                P[b, at + 5 * k:at + 5 * k + 5] = (pred[j][k][0], pred[j][k][1], rx, ry, pred[j][k][2])
+    return P, chosen
+
+
+def _twin_without_peers(fleet):
+    """The same fleet at the same states, plans and carried blocks, without peers; stepping it leaves ``fleet`` alone."""
+    twin = copy.copy(fleet)
+    twin.peers = None
+    twin.parts = []
+    for ids, sub in fleet.parts:
+        sub2 = copy.copy(sub)
+        sub2.dyn = sub.dyn.copy()
+        twin.parts.append((ids, sub2))
+    return twin
+
+
+def _run(cfg, routes, route_of, starts, i0, K, group_of, M, rng_, steps, seed=1, rx=0.37, ry=0.53):
+    """Step a fleet with peers; at every step compare with the literal rule on the loop without peers.  -> per step, the
+    peers the literal rule chose for every robot."""
+    o = oracle_for(cfg)
+    B, N = len(starts), cfg.N_hor
+    dyn = _dyn(routes, route_of, i0, K, seed)
+    g = np.zeros(B, dtype=np.int32) if group_of is None else np.asarray(group_of)
+    fleet = FleetRecedingHorizon(routes, route_of, starts, dyn, sincos=o.sincos_array, idx0=i0,
+                                 peers=Peers(slots=M, rx=rx, ry=ry, range=rng_, group_of=group_of))
+    lo, hi = _slot0(cfg) + K * 5 * N, _slot0(cfg) + (K + M) * 5 * N
+    out = []
+    for k in range(steps):
+        twin = _twin_without_peers(fleet)
+        state, U = fleet.state, fleet.U.copy()
+        P0 = twin.assemble()
+        want, chosen = literal_peers(cfg, P0, state, U, K, g, M, rx, ry, rng_, o.sincos)
+        P, _ = fleet.step(_solve(o))
+        assert np.array_equal(P, want), f"step {k}: columns {np.unique(np.nonzero(P != want)[1])[:10]}"
+        # everything outside the peer slots, and the block carried to the next step, are the loop's without peers
+        assert np.array_equal(P[:, :lo], P0[:, :lo]) and np.array_equal(P[:, hi:], P0[:, hi:]), f"step {k}"
+        for (_, a), (_, b) in zip(fleet.parts, twin.parts):
+            assert np.array_equal(a.dyn, b.dyn), f"step {k}: the carried block saw peers"
+        sel = [[j for j in row if j >= 0] for row in fleet.peer_index.tolist()]
+        assert sel == chosen, f"step {k}"
+        out.append(chosen)
+    return out
+
+
+GROUPS = {"one": lambda B: None, "three": lambda B: (np.arange(B) * 7 % 3 + 2).astype(np.int32),
+          "alone": lambda B: np.arange(B, dtype=np.int32)[::-1].copy()}
+
+
+@pytest.mark.parametrize("groups", list(GROUPS))
+@pytest.mark.parametrize("name,K", [("cfg4", 0), ("cfg4", 1), ("cfg4", 2), ("cfg2", 0)])
+def test_mirror_equals_literal_rule(name, K, groups):
+    """N = 20 (cfg4) and N = 40 (cfg2); K = 0 and K > 0; every M from 1 to Ndynobs - K; a range that excludes everybody, one
+    that splits the fleet and one that excludes nobody; one group, three groups, every robot alone."""
+    cfg = named_config(name)
+    B = 9
+    routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 2, B, seed=17)
+    group_of = GROUPS[groups](B)
+    d0 = np.linalg.norm(starts[:, None, :2] - starts[None, :, :2], axis=2)
+    mid = float(np.median(d0[np.triu_indices(B, 1)]))                       # about half of the pairs start within it
+    steps = 3 if cfg.N_hor == 20 else 2
+    for M in range(1, cfg.Ndynobs - K + 1):
+        for rng_ in (1e-6, mid, 1e4):
+            chosen = _run(cfg, routes, route_of, starts, i0, K, group_of, M, rng_, steps)
+            n = [len(c) for step in chosen for c in step]
+            if rng_ == 1e-6 or groups == "alone":
+                assert max(n) == 0
+            elif rng_ == 1e4 and groups == "one":
+                assert min(n) == M
+            elif rng_ == 1e4:
+                assert min(n) >= 1
+            elif groups == "one":
+                assert min(n) < M and max(n) > 0                          # filled and unfilled slots in one run
+
+
+def test_tie_in_distance_goes_to_the_lower_index():
+    """Robots 1 and 2 with identical states, routes and plans are equally close to robot 0, at every step: robot 0's one slot
+    goes to robot 1.  At the first step, where everybody stands still, robots 3 and 5 stand exactly 1 m to either side of
+    robot 4: its slot shows robot 3's pose."""
+    cfg = named_config("cfg4")
+    pl = frontend.scene_planner(cfg, 5)
+    route = pl.route((1.0, 5.0, 0.0), (15.0, 5.0, 0.0))
+    starts = np.array([[2.0, 5.0, 0.0], [3.0, 5.25, 0.1], [3.0, 5.25, 0.1], [8.0, 7.0, 0.0], [9.0, 7.0, 0.0], [10.0, 7.0, 0.0]])
+    B = len(starts)
+    route_of, i0 = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    group_of = np.array([0, 0, 0, 1, 1, 1], dtype=np.int32)
+    chosen = _run(cfg, [route], route_of, starts, i0, 0, group_of, 1, 50.0, 4)
+    for step in chosen:
+        assert step[0] == [1] and step[1] == [2] and step[2] == [1]
+    assert chosen[0][4] == [3]
+    # the tie is exact, and visible in P: at the first step robot 4's slot holds robot 3's standing pose
+    o = oracle_for(cfg)
+    fleet = FleetRecedingHorizon([route], route_of, starts, None, sincos=o.sincos_array, idx0=i0,
+                                 peers=Peers(slots=1, rx=0.37, ry=0.53, range=50.0, group_of=group_of))
+    P = fleet.assemble()
+    slot = P[4, _slot0(cfg):_slot0(cfg) + 5 * cfg.N_hor].reshape(cfg.N_hor, 5)
+    assert np.array_equal(slot, np.tile([8.0, 7.0, 0.37, 0.53, 0.0], (cfg.N_hor, 1)))
+    pred = fleet.predict()
+    assert ((pred[4, :, 0] - pred[3, :, 0]) ** 2 == (pred[4, :, 0] - pred[5, :, 0]) ** 2).all()
+
+
+def test_peers_arguments_checked():
+    cfg = named_config("cfg4")
+    routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 1, 4, seed=3)
+    dyn = _dyn(routes, route_of, i0, 2, 1)
+    ok = dict(slots=1, rx=0.5, ry=0.5, range=5.0)
+    FleetRecedingHorizon(routes, route_of, starts, dyn, idx0=i0, peers=Peers(**ok))
+    for bad in (dict(slots=0), dict(slots=2), dict(rx=0.0), dict(ry=-1.0), dict(range=math.inf), dict(rx=math.nan),
+                dict(group_of=[0, 1, 4, 0]), dict(group_of=[0, -1, 0, 0])):
+        with pytest.raises(ValueError):
+            FleetRecedingHorizon(routes, route_of, starts, dyn, idx0=i0, peers=Peers(**{**ok, **bad}))
+
+
+# two robots towards each other through the free corridor of scene 5 (a 16 m x 10 m room without obstacles)
+HEAD_ON = dict(a=(1.0, 5.0, 0.0), b=(15.0, 5.0, 0.0), rx=1.0, ry=0.8, range=8.0)
+
+
+def _head_on(peers):
+    cfg = named_config("cfg1")
+    pl = frontend.scene_planner(cfg, 5)
+    a, b = HEAD_ON["a"], HEAD_ON["b"]
+    there = pl.route(a, b)
+    back = pl.route((b[0], b[1], math.pi), (a[0], a[1], math.pi))
+    for r, sign in ((there, 1.0), (back, -1.0)):                          # each other's reverse: the corridor's centre line, both ways
+        assert np.allclose(r.y_ref, a[1]) and (sign * np.diff(r.x_ref) >= 0).all()
+        assert abs(min(r.x_ref) - a[0]) < 0.5 and abs(max(r.x_ref) - b[0]) < 0.5
+    o = oracle_for(cfg)
+    starts = np.array([there.start, back.start])
+    fleet = FleetRecedingHorizon([there, back], [0, 1], starts, None, sincos=o.sincos_array,
+                                 peers=Peers(slots=1, rx=HEAD_ON["rx"], ry=HEAD_ON["ry"], range=HEAD_ON["range"]) if peers else None)
+    for _ in range(400):
+        fleet.step(_solve(o, threads=2))
+        s = fleet.state
+        if s[0, 0] > s[1, 0] + 1.0:                                        # both past the meeting point
+            break
+    else:
+        raise AssertionError("the robots never passed each other")
+    T = np.stack(fleet.traj)
+    return float(np.linalg.norm(T[:, 0, :2] - T[:, 1, :2], axis=1).min())
+
+
+def test_robots_on_reversed_routes_keep_apart():
+    """Smallest separation over the recorded trajectory: below ry without peers (the robots overlap), strictly larger with
+    peers.  The penalty is soft: no absolute clearance is promised (measured values: DESIGN.md section 5.9)."""
+    without, with_ = _head_on(False), _head_on(True)
+    print(f"smallest separation: without peers {without:.4f} m, with peers {with_:.4f} m")
+    assert without < HEAD_ON["ry"]
+    assert with_ > without
