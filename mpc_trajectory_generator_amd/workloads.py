@@ -1,4 +1,5 @@
-"""The BASELINE batch of a configuration and what "the same bits" means, for every probe and test that quotes a number.
+"""The BASELINE batch of a configuration, the fleets of the receding-horizon loop and what "the same bits" means, for every probe
+and test that quotes a number.
 
 bench.py's ``make_batch`` is the contract; tests/test_workloads.py holds ``baseline_batch`` to it array for array."""
 import numpy as np
@@ -32,3 +33,64 @@ def differing(a, b, rows=None):
         ua, ya, sa = ua[rows], ya[rows], sa[rows]
     pairs = [(f, sa[f], sb[f]) for f in PARITY_FIELDS] + [("u", ua, ub), ("y", ya, yb)]
     return [n for n, x, y in pairs if not np.array_equal(x, y)]
+
+
+def moving_ellipses(centres, rng):
+    """centres [B, K, 2] -> the six arrays ``VectorizedRecedingHorizon`` takes as ``dyn_obs``: two end points within 5 m per axis of
+    the centre, a frequency, two radii, an angle; drawn from ``rng`` in that order."""
+    c, s = centres, centres.shape[:2]
+    return (c + rng.uniform(-5, 5, c.shape), c + rng.uniform(-5, 5, c.shape), rng.uniform(0.05, 0.1, s),
+            rng.uniform(0.3, 1.0, s), rng.uniform(0.3, 1.0, s), rng.uniform(0, np.pi, s))
+
+
+def route_fleet(route, B, seed, K=0, back=25):
+    """-> (idx0 [B], starts [B, 3], dyn): B robots started along one route, at samples at least ``back`` before its end, off it by
+    noise (sigma 0.05 m, 0.05 m, 0.1 rad); dyn: K moving ellipses per robot around samples 0..29 ahead of its start, None for K = 0.
+    One stream: (idx0, starts) do not depend on K."""
+    rng = np.random.default_rng(seed)
+    n = len(route.x_ref)
+    xr, yr, tr = np.array(route.x_ref), np.array(route.y_ref), np.array(route.theta_ref)
+    i0 = rng.integers(0, max(1, n - back), B)
+    starts = np.stack([xr[i0] + rng.normal(0, 0.05, B), yr[i0] + rng.normal(0, 0.05, B), tr[i0] + rng.normal(0, 0.1, B)], axis=1)
+    if not K:
+        return i0, starts, None
+    jj = np.minimum(n - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
+    return i0, starts, moving_ellipses(np.stack([xr[jj], yr[jj]], axis=2), rng)
+
+
+def fleet_ellipses(routes, route_of, idx0, K, seed):
+    """-> dyn: K moving ellipses per robot around samples 0..29 ahead of ``idx0`` on the robot's own route (clipped to its end),
+    None for K = 0.  The samples are drawn robot by robot, in fleet order."""
+    if not K:
+        return None
+    rng = np.random.default_rng(seed)
+    c = np.empty((len(route_of), K, 2))
+    for b, r in enumerate(route_of):
+        x, y = np.array(routes[r].x_ref), np.array(routes[r].y_ref)
+        jj = np.minimum(len(x) - 1, idx0[b] + rng.integers(0, 30, K))
+        c[b] = np.stack([x[jj], y[jj]], axis=1)
+    return moving_ellipses(c, rng)
+
+
+def step_differing(dev, host, solve):
+    """Step a ``DeviceRecedingHorizon`` and its host mirror (``solve``: the mirror's solve function) once.
+    -> (names, P, done): the names out of P, U, Y, state, last_u, idx, done, num_inner_iterations, exit_status on which the two are
+    not bit-equal ("P" with its first differing columns), the device's parameter vectors and its ``done``."""
+    dev.step()
+    P, st = host.step(solve)
+    Pd, Ud, Yd = dev.params()
+    state, last_u, idx, done, std = dev.read()
+    pairs = [("P", Pd, P), ("U", Ud, host.U), ("Y", Yd, host.Y), ("state", state, host.state), ("last_u", last_u, host.last_u),
+             ("idx", idx, host.idx), ("done", done, host.done)] + [(f, std[f], st[f]) for f in ("num_inner_iterations", "exit_status")]
+    names = [n for n, x, y in pairs if not np.array_equal(x, y)]
+    if "P" in names:
+        names[0] = f"P at columns {np.unique(np.nonzero(Pd != P)[1])[:10]}"
+    return names, Pd, done
+
+
+def trajectory_differing(dev, host, steps):
+    """After ``steps`` steps of both: [] if the device's trajectory is [steps * num_steps_taken + 1, B, 3] and the mirror's bits."""
+    T = dev.trajectory()
+    if T.shape != (steps * host.cfg.num_steps_taken + 1, dev.B, 3):
+        return [f"trajectory of shape {T.shape}"]
+    return [] if np.array_equal(T, np.stack(host.traj)) else ["trajectory"]

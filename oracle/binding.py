@@ -163,6 +163,10 @@ class Oracle:
             raise RuntimeError(f"orc_solve_batch failed: {rc}")
         return u, y, st
 
+    def warm_solve(self, threads=8):
+        """-> solve(P, U, Y): ``solve_batch`` warm-started from U and Y, as the host loops' ``step`` calls it."""
+        return lambda P, U, Y: self.solve_batch(P, u0=U, y0=Y, threads=threads)
+
     def solve_traced(self, p, u0=None, y0=None, c0=None, cap=4096):
         """One solve with every PANOC step recorded -> u[n_u], y[n1], status (a 0-d structured array), steps[n]
         (STEP_DTYPE; u, y and u_next cut to n_u / n1).  orc_solve_trace gives orc_solve's bits."""

@@ -18,6 +18,7 @@ from mpc_trajectory_generator_amd import named_config                           
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
 from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, Peers, VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.workloads import moving_ellipses, route_fleet   # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8192)
@@ -57,13 +58,7 @@ def peers_of(n):
 
 if args.routes == 1:
     route = harness.scene_route(cfg, args.scene)
-    rng = np.random.Generator(np.random.PCG64(0))
-    n = len(route.x_ref)
-    i0 = rng.integers(0, max(1, n - 60), B)
-    starts = np.stack([np.array(route.x_ref)[i0] + rng.normal(0, 0.05, B), np.array(route.y_ref)[i0] + rng.normal(0, 0.05, B),
-                       np.array(route.theta_ref)[i0] + rng.normal(0, 0.1, B)], axis=1)
-    jj = np.minimum(n - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
-    c = np.stack([np.array(route.x_ref)[jj], np.array(route.y_ref)[jj]], axis=2)
+    i0, starts, dyn = route_fleet(route, B, 0, K, back=60)
     routes, route_of = route, None
 else:
     from mpc_trajectory_generator_amd.frontend import random_fleet
@@ -74,9 +69,7 @@ else:
     first = np.concatenate([[0], np.cumsum([len(r.x_ref) for r in routes])[:-1]])[route_of]
     xs, ys = np.concatenate([r.x_ref for r in routes]), np.concatenate([r.y_ref for r in routes])
     jj = first[:, None] + np.minimum(n[:, None] - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
-    c = np.stack([xs[jj], ys[jj]], axis=2)
-dyn = (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
-       rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
+    dyn = moving_ellipses(np.stack([xs[jj], ys[jj]], axis=2), rng)
 fleet = f", {args.routes} routes (frontend.random_fleet, seed 0)" if args.routes > 1 else ""
 if args.peers:
     fleet += (f", {K} scripted ellipses and {args.peer_slots} peer slots per robot, groups of {args.peers} consecutive robots, "
@@ -90,7 +83,7 @@ if not args.host:
     loops, streams = [], []
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
-        loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
+        loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                            route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids))))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0

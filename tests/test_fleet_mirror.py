@@ -7,42 +7,22 @@ import numpy as np
 from conftest import oracle_for
 from mpc_trajectory_generator_amd import frontend, harness, named_config
 from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, VectorizedRecedingHorizon
-
-
-def _dyn(routes, route_of, idx0, K, seed):
-    """Per-robot moving ellipses crossing the robot's own route (as tests/test_gpu_loop.py::_fleet)."""
-    rng = np.random.default_rng(seed)
-    B = len(route_of)
-    c = np.empty((B, K, 2))
-    for b in range(B):
-        r = routes[route_of[b]]
-        jj = np.minimum(len(r.x_ref) - 1, idx0[b] + rng.integers(0, 30, K))
-        c[b] = np.stack([np.array(r.x_ref)[jj], np.array(r.y_ref)[jj]], axis=1)
-    return (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
-            rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
-
-
-def _solve(o, threads=8):
-    return lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=threads)
+from mpc_trajectory_generator_amd.workloads import fleet_ellipses, route_fleet
 
 
 def test_one_route_equals_vectorized_mirror():
     cfg = named_config("cfg4")
     route = harness.scene_route(cfg, 11)
     B, K, steps = 12, 3, 8
-    rng = np.random.default_rng(3)
-    n = len(route.x_ref)
-    i0 = rng.integers(0, n - 25, B)
-    starts = np.stack([np.array(route.x_ref)[i0] + rng.normal(0, 0.05, B), np.array(route.y_ref)[i0] + rng.normal(0, 0.05, B),
-                       np.array(route.theta_ref)[i0] + rng.normal(0, 0.1, B)], axis=1)
+    i0, starts, _ = route_fleet(route, B, 3)
     route_of = np.zeros(B, dtype=np.int32)
-    dyn = _dyn([route], route_of, i0, K, 4)
+    dyn = fleet_ellipses([route], route_of, i0, K, 4)
     o = oracle_for(cfg)
     fleet = FleetRecedingHorizon([route], route_of, starts, dyn, sincos=o.sincos_array, idx0=i0)
     host = VectorizedRecedingHorizon(route, starts, dyn, sincos=o.sincos_array, idx0=i0)
     for k in range(steps):
-        Pf, stf = fleet.step(_solve(o))
-        Ph, sth = host.step(_solve(o))
+        Pf, stf = fleet.step(o.warm_solve())
+        Ph, sth = host.step(o.warm_solve())
         assert np.array_equal(Pf, Ph), f"step {k}"
         assert np.array_equal(fleet.U, host.U) and np.array_equal(fleet.Y, host.Y)
         assert np.array_equal(fleet.state, host.state) and np.array_equal(fleet.last_u, host.last_u)
@@ -60,7 +40,7 @@ def test_three_routes_equal_three_separate_mirrors():
     i0 = np.array([rng.integers(0, max(1, len(routes[r].x_ref) - 25)) for r in route_of])
     starts = np.stack([[routes[r].x_ref[i], routes[r].y_ref[i], routes[r].theta_ref[i]] for r, i in zip(route_of, i0)])
     starts = starts + rng.normal(0, 0.05, starts.shape)
-    dyn = _dyn(routes, route_of, i0, K, 6)
+    dyn = fleet_ellipses(routes, route_of, i0, K, 6)
     o = oracle_for(cfg)
     fleet = FleetRecedingHorizon(routes, route_of, starts, dyn, sincos=o.sincos_array, idx0=i0)
     alone = []
@@ -69,9 +49,9 @@ def test_three_routes_equal_three_separate_mirrors():
         h = VectorizedRecedingHorizon(route, starts[ids], tuple(a[ids] for a in dyn), sincos=o.sincos_array, idx0=i0[ids])
         alone.append((ids, h))
     for k in range(steps):
-        P, _ = fleet.step(_solve(o))
+        P, _ = fleet.step(o.warm_solve())
         for ids, h in alone:
-            Ph, _ = h.step(_solve(o, threads=4))
+            Ph, _ = h.step(o.warm_solve(threads=4))
             assert np.array_equal(P[ids], Ph), f"step {k}"
             assert np.array_equal(fleet.U[ids], h.U) and np.array_equal(fleet.Y[ids], h.Y)
             assert np.array_equal(fleet.state[ids], h.state) and np.array_equal(fleet.idx[ids], h.idx)

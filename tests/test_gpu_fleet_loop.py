@@ -11,44 +11,11 @@ import pytest
 from conftest import oracle_for
 from mpc_trajectory_generator_amd import _lib, frontend, harness, named_config
 from mpc_trajectory_generator_amd.config import load_config
+from mpc_trajectory_generator_amd.workloads import fleet_ellipses, step_differing, trajectory_differing
 
 pytestmark = pytest.mark.gpu
 
 B = 24
-
-
-def _dyn(routes, route_of, idx0, K, seed):
-    """Per-robot moving ellipses crossing the robot's own route (as tests/test_gpu_loop.py::_fleet)."""
-    if not K:
-        return None
-    rng = np.random.default_rng(seed)
-    n = len(route_of)
-    c = np.empty((n, K, 2))
-    for b in range(n):
-        r = routes[route_of[b]]
-        jj = np.minimum(len(r.x_ref) - 1, idx0[b] + rng.integers(0, 30, K))
-        c[b] = np.stack([np.array(r.x_ref)[jj], np.array(r.y_ref)[jj]], axis=1)
-    return (c + rng.uniform(-5, 5, (n, K, 2)), c + rng.uniform(-5, 5, (n, K, 2)), rng.uniform(0.05, 0.1, (n, K)),
-            rng.uniform(0.3, 1.0, (n, K)), rng.uniform(0.3, 1.0, (n, K)), rng.uniform(0, np.pi, (n, K)))
-
-
-def _compare(dev, host, o, steps, threads=8, on_step=None):
-    for k in range(steps):
-        dev.step()
-        P, st = host.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=threads))
-        Pd, Ud, Yd = dev.params()
-        state, last_u, idx, done, std = dev.read()
-        assert np.array_equal(Pd, P), f"step {k}: parameter vectors differ at columns {np.unique(np.nonzero(Pd != P)[1])[:10]}"
-        assert np.array_equal(Ud, host.U) and np.array_equal(Yd, host.Y), f"step {k}"
-        assert np.array_equal(state, host.state) and np.array_equal(last_u, host.last_u), f"step {k}"
-        assert np.array_equal(idx, host.idx) and np.array_equal(done, host.done), f"step {k}"
-        assert np.array_equal(std["num_inner_iterations"], st["num_inner_iterations"]), f"step {k}"
-        assert np.array_equal(std["exit_status"], st["exit_status"]), f"step {k}"
-        if on_step:
-            on_step(done)
-    T = dev.trajectory()
-    assert T.shape == (steps * host.cfg.num_steps_taken + 1, dev.B, 3)
-    assert np.array_equal(T, np.stack(host.traj))
 
 
 # (config, scene, K, steps, sinusoidal obstacle); "nobs3": fewer circle slots than some routes have vertices -> the
@@ -66,13 +33,16 @@ def test_fleet_loop_equals_host_mirror(name, scene, K, steps, sinus, R):
     routes, route_of, starts, i0 = frontend.random_fleet(cfg, scene, R, B, seed=31 + R)
     if R == B:
         assert sorted(route_of.tolist()) == list(range(B))          # every robot on a route of its own
-    dyn = _dyn(routes, route_of, i0, K, 7 + R)
+    dyn = fleet_ellipses(routes, route_of, i0, K, 7 + R)
     o = oracle_for(cfg)
     s = BatchSolver(cfg, max_batch=32)
     try:
         dev = DeviceRecedingHorizon(s, routes, starts, dyn, max_steps=steps, idx0=i0, sinus_object=sinus, route_of=route_of)
         host = FleetRecedingHorizon(routes, route_of, starts, dyn, sincos=o.sincos_array, sinus_object=sinus, idx0=i0)
-        _compare(dev, host, o, steps)
+        for k in range(steps):
+            bad = step_differing(dev, host, o.warm_solve())[0]
+            assert not bad, f"step {k}: {bad}"
+        assert not trajectory_differing(dev, host, steps)
         dev.close()
     finally:
         s.close()
@@ -98,7 +68,11 @@ def test_fleet_routes_of_different_lengths_brake_and_finish_apart():
     try:
         dev = DeviceRecedingHorizon(s, routes, starts, None, max_steps=steps, idx0=i0, route_of=route_of)
         host = FleetRecedingHorizon(routes, route_of, starts, None, sincos=o.sincos_array, idx0=i0)
-        _compare(dev, host, o, steps, on_step=lambda done: mixed.append(0 < done.sum() < len(done)))
+        for k in range(steps):
+            bad, _, done = step_differing(dev, host, o.warm_solve())
+            assert not bad, f"step {k}: {bad}"
+            mixed.append(0 < done.sum() < len(done))
+        assert not trajectory_differing(dev, host, steps)
         assert any(mixed), "no step with some robots at their goals and others not"
         dev.close()
     finally:
@@ -111,7 +85,7 @@ def test_both_entry_points_same_bits():
     from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon
     cfg = named_config("cfg4")
     routes, _, starts, i0 = frontend.random_fleet(cfg, 11, 1, B, seed=3)
-    dyn = _dyn(routes, np.zeros(B, dtype=np.int32), i0, 3, 4)
+    dyn = fleet_ellipses(routes, np.zeros(B, dtype=np.int32), i0, 3, 4)
     steps = 6
     s1, s2 = BatchSolver(cfg, max_batch=32), BatchSolver(cfg, max_batch=32)
     try:

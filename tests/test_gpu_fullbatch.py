@@ -9,7 +9,7 @@ import pytest
 
 from conftest import oracle_for
 from mpc_trajectory_generator_amd import harness, named_config
-from mpc_trajectory_generator_amd.workloads import baseline_batch, differing
+from mpc_trajectory_generator_amd.workloads import baseline_batch, differing, route_fleet
 
 pytestmark = pytest.mark.gpu
 B = 8192
@@ -83,15 +83,7 @@ def test_cfg4_device_loop_full_fleet(steps, n_mirror):
     from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon, VectorizedRecedingHorizon
     cfg = named_config("cfg4")
     route = harness.scene_route(cfg, 11)
-    rng = np.random.Generator(np.random.PCG64(0))
-    n, K = len(route.x_ref), cfg.Ndynobs
-    xr, yr, tr = np.array(route.x_ref), np.array(route.y_ref), np.array(route.theta_ref)
-    i0 = rng.integers(0, max(1, n - 60), B)
-    starts = np.stack([xr[i0] + rng.normal(0, 0.05, B), yr[i0] + rng.normal(0, 0.05, B), tr[i0] + rng.normal(0, 0.1, B)], axis=1)
-    jj = np.minimum(n - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
-    c = np.stack([xr[jj], yr[jj]], axis=2)
-    dyn = (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
-           rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
+    i0, starts, dyn = route_fleet(route, B, 0, cfg.Ndynobs, back=60)
     ids = np.sort(np.random.default_rng(2).choice(B, n_mirror, replace=False))
     o = oracle_for(cfg)
     s = BatchSolver(cfg, max_batch=B)
@@ -100,7 +92,7 @@ def test_cfg4_device_loop_full_fleet(steps, n_mirror):
         host = VectorizedRecedingHorizon(route, starts[ids], tuple(a[ids] for a in dyn), sincos=o.sincos_array, idx0=i0[ids])
         for k in range(steps):
             dev.step()
-            P, st = host.step(lambda P_, U, Y: o.solve_batch(P_, u0=U, y0=Y, threads=8))
+            P, st = host.step(o.warm_solve())
             if k in (0, 1, steps // 2, steps - 1):
                 Pd, Ud, Yd = dev.params()
                 assert np.array_equal(Pd[ids], P), f"step {k}"

@@ -10,23 +10,9 @@ import pytest
 from conftest import oracle_for
 from mpc_trajectory_generator_amd import harness, named_config
 from mpc_trajectory_generator_amd.config import load_config
+from mpc_trajectory_generator_amd.workloads import route_fleet, step_differing, trajectory_differing
 
 pytestmark = pytest.mark.gpu
-
-
-def _fleet(cfg, route, B, seed, K):
-    rng = np.random.default_rng(seed)
-    n = len(route.x_ref)
-    i0 = rng.integers(0, max(1, n - 25), B)
-    xr, yr, tr = np.array(route.x_ref), np.array(route.y_ref), np.array(route.theta_ref)
-    starts = np.stack([xr[i0] + rng.normal(0, 0.05, B), yr[i0] + rng.normal(0, 0.05, B), tr[i0] + rng.normal(0, 0.1, B)], axis=1)
-    dyn = None
-    if K:
-        jj = np.minimum(n - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
-        c = np.stack([xr[jj], yr[jj]], axis=2)
-        dyn = (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
-               rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
-    return i0, starts, dyn
 
 
 @pytest.mark.parametrize("name,scene,K,steps,sinus", [("cfg4", 11, 3, 12, False), ("cfg4", 1, 2, 40, False), ("cfg1", 11, 0, 8, False),
@@ -40,26 +26,16 @@ def test_device_loop_equals_host_mirror(name, scene, K, steps, sinus):
     cfg = load_config(Nobs=3) if name == "nobs3" else named_config(name)
     route = harness.scene_route(cfg, scene)
     B = 24
-    i0, starts, dyn = _fleet(cfg, route, B, 7 + scene, K)
+    i0, starts, dyn = route_fleet(route, B, 7 + scene, K)
     o = oracle_for(cfg)
     s = BatchSolver(cfg, max_batch=32)
     try:
         dev = DeviceRecedingHorizon(s, route, starts, dyn, max_steps=steps, idx0=i0, sinus_object=sinus)
         host = VectorizedRecedingHorizon(route, starts, dyn, sincos=o.sincos_array, sinus_object=sinus, idx0=i0)   # (third ellipse: sinusoidal law)
         for k in range(steps):
-            dev.step()
-            P, st = host.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=8))
-            Pd, Ud, Yd = dev.params()
-            state, last_u, idx, done, std = dev.read()
-            assert np.array_equal(Pd, P), f"step {k}: parameter vectors differ at columns {np.unique(np.nonzero(Pd != P)[1])[:10]}"
-            assert np.array_equal(Ud, host.U) and np.array_equal(Yd, host.Y)
-            assert np.array_equal(state, host.state) and np.array_equal(last_u, host.last_u)
-            assert np.array_equal(idx, host.idx) and np.array_equal(done, host.done)
-            assert np.array_equal(std["num_inner_iterations"], st["num_inner_iterations"])
-            assert np.array_equal(std["exit_status"], st["exit_status"])
-        T = dev.trajectory()
-        assert T.shape == (steps * cfg.num_steps_taken + 1, B, 3)
-        assert np.array_equal(T, np.stack(host.traj))
+            bad = step_differing(dev, host, o.warm_solve())[0]
+            assert not bad, f"step {k}: {bad}"
+        assert not trajectory_differing(dev, host, steps)
         dev.close()
     finally:
         s.close()
@@ -84,7 +60,7 @@ def test_device_loop_reaches_goal_and_brakes():
         host = VectorizedRecedingHorizon(route, starts, None, sincos=o.sincos_array, idx0=i0)
         for k in range(120):
             dev.step()
-            P, st = host.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=6))
+            P, st = host.step(o.warm_solve(threads=6))
             if k % 10 == 9 or k < 3:
                 Pd, _, _ = dev.params()
                 assert np.array_equal(Pd, P), f"step {k}"

@@ -398,7 +398,7 @@ def test_batched_receding_horizon_on_gpu_equals_oracle(solvers):
     a, b = VectorizedRecedingHorizon(route, starts, dyn, idx0=i0), VectorizedRecedingHorizon(route, starts, dyn, idx0=i0)
     for k in range(5):
         Pa, sta = a.step(lambda P, U, Y: s.solve(P, u0=U, y0=Y))
-        Pb, stb = b.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=8))
+        Pb, stb = b.step(o.warm_solve())
         assert np.array_equal(Pa, Pb) and np.array_equal(a.state, b.state)
         assert np.array_equal(sta["num_inner_iterations"], stb["num_inner_iterations"])
 

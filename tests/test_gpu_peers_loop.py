@@ -8,46 +8,12 @@ import pytest
 
 from conftest import oracle_for
 from mpc_trajectory_generator_amd import _lib, frontend, named_config
+from mpc_trajectory_generator_amd.workloads import fleet_ellipses, step_differing, trajectory_differing
 
 pytestmark = pytest.mark.gpu
 
 B = 24
 RX, RY = 0.37, 0.53          # radii no scripted or padding ellipse has: a slot that shows them holds a peer
-
-
-def _dyn(routes, route_of, idx0, K, seed):
-    """Per-robot moving ellipses crossing the robot's own route (as tests/test_gpu_fleet_loop.py)."""
-    if not K:
-        return None
-    rng = np.random.default_rng(seed)
-    n = len(route_of)
-    c = np.empty((n, K, 2))
-    for b in range(n):
-        r = routes[route_of[b]]
-        jj = np.minimum(len(r.x_ref) - 1, idx0[b] + rng.integers(0, 30, K))
-        c[b] = np.stack([np.array(r.x_ref)[jj], np.array(r.y_ref)[jj]], axis=1)
-    return (c + rng.uniform(-5, 5, (n, K, 2)), c + rng.uniform(-5, 5, (n, K, 2)), rng.uniform(0.05, 0.1, (n, K)),
-            rng.uniform(0.3, 1.0, (n, K)), rng.uniform(0.3, 1.0, (n, K)), rng.uniform(0, np.pi, (n, K)))
-
-
-def _compare(dev, host, o, steps, threads=8, on_step=None):
-    """tests/test_gpu_fleet_loop.py::_compare, with the parameter vectors handed to ``on_step``."""
-    for k in range(steps):
-        dev.step()
-        P, st = host.step(lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=threads))
-        Pd, Ud, Yd = dev.params()
-        state, last_u, idx, done, std = dev.read()
-        assert np.array_equal(Pd, P), f"step {k}: parameter vectors differ at columns {np.unique(np.nonzero(Pd != P)[1])[:10]}"
-        assert np.array_equal(Ud, host.U) and np.array_equal(Yd, host.Y), f"step {k}"
-        assert np.array_equal(state, host.state) and np.array_equal(last_u, host.last_u), f"step {k}"
-        assert np.array_equal(idx, host.idx) and np.array_equal(done, host.done), f"step {k}"
-        assert np.array_equal(std["num_inner_iterations"], st["num_inner_iterations"]), f"step {k}"
-        assert np.array_equal(std["exit_status"], st["exit_status"]), f"step {k}"
-        if on_step:
-            on_step(Pd)
-    T = dev.trajectory()
-    assert T.shape == (steps * host.cfg.num_steps_taken + 1, dev.B, 3)
-    assert np.array_equal(T, np.stack(host.traj))
 
 
 def _filled(cfg, P, K, M):
@@ -82,7 +48,7 @@ def test_peers_loop_equals_host_mirror(name, K, M, steps, groups, rng_):
     from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon, FleetRecedingHorizon, Peers
     cfg = named_config(name)
     routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 3, B, seed=41)
-    dyn = _dyn(routes, route_of, i0, K, 9)
+    dyn = fleet_ellipses(routes, route_of, i0, K, 9)
     group_of = _groups(groups, B)
     peers = Peers(slots=M, rx=RX, ry=RY, range=1e3 if rng_ == "wide" else _narrow(starts, group_of), group_of=group_of)
     o = oracle_for(cfg)
@@ -93,13 +59,14 @@ def test_peers_loop_equals_host_mirror(name, K, M, steps, groups, rng_):
         dev = DeviceRecedingHorizon(s, routes, starts, dyn, max_steps=steps, idx0=i0, route_of=route_of, peers=peers)
         host = FleetRecedingHorizon(routes, route_of, starts, dyn, sincos=o.sincos_array, idx0=i0, peers=peers)
         plain = DeviceRecedingHorizon(s0, routes, starts, dyn, max_steps=steps, idx0=i0, route_of=route_of) if s0 else None
-
-        def on_step(Pd):
+        for k in range(steps):
+            bad, Pd, _ = step_differing(dev, host, o.warm_solve())
+            assert not bad, f"step {k}: {bad}"
             seen.append(_filled(cfg, Pd, K, M))
             if plain:                                  # nobody to see: the loop without peers, bit for bit
                 plain.step()
                 assert np.array_equal(Pd, plain.params()[0])
-        _compare(dev, host, o, steps, on_step=on_step)
+        assert not trajectory_differing(dev, host, steps)
         seen = np.stack(seen)
         if groups == "alone":
             assert not seen.any()
@@ -132,12 +99,13 @@ def test_group_larger_than_a_wave():
     try:
         dev = DeviceRecedingHorizon(s, routes, starts, None, max_steps=steps, idx0=i0, route_of=route_of, peers=peers)
         host = FleetRecedingHorizon(routes, route_of, starts, None, sincos=o.sincos_array, idx0=i0, peers=peers)
-
-        def on_step(Pd):
+        far = np.nonzero(group_of == 7)[0][64:]                           # members a lane reaches only by striding
+        for k in range(steps):
+            bad, Pd, _ = step_differing(dev, host, o.warm_solve())
+            assert not bad, f"step {k}: {bad}"
             seen.append(_filled(cfg, Pd, 0, M))
-            far = np.nonzero(group_of == 7)[0][64:]                       # members a lane reaches only by striding
             assert np.isin(host.peer_index, far).any()
-        _compare(dev, host, o, steps, on_step=on_step)
+        assert not trajectory_differing(dev, host, steps)
         seen = np.stack(seen)
         assert seen[..., M - 1].any() and not seen[..., 0].all()          # full lists and empty ones
         dev.close()
@@ -153,7 +121,7 @@ def test_peers_arguments_validated():
     cfg = named_config("cfg4")
     n, K, steps = 8, 2, 3
     routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 2, n, seed=5)
-    dyn = _dyn(routes, route_of, i0, K, 3)
+    dyn = fleet_ellipses(routes, route_of, i0, K, 3)
     s1, s2 = BatchSolver(cfg, max_batch=16), BatchSolver(cfg, max_batch=16)
     lib = s1.lib
     try:

@@ -152,7 +152,7 @@ def test_batched_receding_horizon_matches_sequential():
     route = harness.scene_route(cfg, 1)
     starts = [route.start, (1.2, 5.3, 0.6), (0.8, 4.6, 0.9)]
     brh = BatchedRecedingHorizon(route, starts)
-    solve = lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=3)          # noqa: E731
+    solve = o.warm_solve(threads=3)
     Ps = [brh.step(solve)[0] for _ in range(4)]
     for b, s in enumerate(starts):
         one = BatchedRecedingHorizon(route, [s])
@@ -201,7 +201,7 @@ def test_vectorized_receding_horizon_equals_loop_version(sinus, K):
     dyn = (arr(lambda o_: o_[0]), arr(lambda o_: o_[1]), arr(lambda o_: o_[2]), arr(lambda o_: o_[3]),
            arr(lambda o_: o_[4]), arr(lambda o_: o_[5]))
     vec = VectorizedRecedingHorizon(route, starts, dyn, sinus_object=sinus, idx0=i0)
-    solve = lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=4)         # noqa: E731
+    solve = o.warm_solve(threads=4)
     stale = False
     for k in range(6):
         Pl, _ = loop.step(solve)

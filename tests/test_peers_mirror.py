@@ -13,25 +13,7 @@ import pytest
 from conftest import oracle_for
 from mpc_trajectory_generator_amd import frontend, named_config
 from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, Peers
-
-
-def _solve(o, threads=8):
-    return lambda P, U, Y: o.solve_batch(P, u0=U, y0=Y, threads=threads)
-
-
-def _dyn(routes, route_of, idx0, K, seed):
-    """Per-robot moving ellipses crossing the robot's own route (as tests/test_fleet_mirror.py)."""
-    if not K:
-        return None
-    rng = np.random.default_rng(seed)
-    B = len(route_of)
-    c = np.empty((B, K, 2))
-    for b in range(B):
-        r = routes[route_of[b]]
-        jj = np.minimum(len(r.x_ref) - 1, idx0[b] + rng.integers(0, 30, K))
-        c[b] = np.stack([np.array(r.x_ref)[jj], np.array(r.y_ref)[jj]], axis=1)
-    return (c + rng.uniform(-5, 5, (B, K, 2)), c + rng.uniform(-5, 5, (B, K, 2)), rng.uniform(0.05, 0.1, (B, K)),
-            rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0.3, 1.0, (B, K)), rng.uniform(0, np.pi, (B, K)))
+from mpc_trajectory_generator_amd.workloads import fleet_ellipses
 
 
 def _slot0(cfg):
@@ -97,7 +79,7 @@ def _run(cfg, routes, route_of, starts, i0, K, group_of, M, rng_, steps, seed=1,
     peers the literal rule chose for every robot."""
     o = oracle_for(cfg)
     B, N = len(starts), cfg.N_hor
-    dyn = _dyn(routes, route_of, i0, K, seed)
+    dyn = fleet_ellipses(routes, route_of, i0, K, seed)
     g = np.zeros(B, dtype=np.int32) if group_of is None else np.asarray(group_of)
     fleet = FleetRecedingHorizon(routes, route_of, starts, dyn, sincos=o.sincos_array, idx0=i0,
                                  peers=Peers(slots=M, rx=rx, ry=ry, range=rng_, group_of=group_of))
@@ -108,7 +90,7 @@ def _run(cfg, routes, route_of, starts, i0, K, group_of, M, rng_, steps, seed=1,
         state, U = fleet.state, fleet.U.copy()
         P0 = twin.assemble()
         want, chosen = literal_peers(cfg, P0, state, U, K, g, M, rx, ry, rng_, o.sincos)
-        P, _ = fleet.step(_solve(o))
+        P, _ = fleet.step(o.warm_solve())
         assert np.array_equal(P, want), f"step {k}: columns {np.unique(np.nonzero(P != want)[1])[:10]}"
         # everything outside the peer slots, and the block carried to the next step, are the loop's without peers
         assert np.array_equal(P[:, :lo], P0[:, :lo]) and np.array_equal(P[:, hi:], P0[:, hi:]), f"step {k}"
@@ -179,7 +161,7 @@ def test_tie_in_distance_goes_to_the_lower_index():
 def test_peers_arguments_checked():
     cfg = named_config("cfg4")
     routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 1, 4, seed=3)
-    dyn = _dyn(routes, route_of, i0, 2, 1)
+    dyn = fleet_ellipses(routes, route_of, i0, 2, 1)
     ok = dict(slots=1, rx=0.5, ry=0.5, range=5.0)
     FleetRecedingHorizon(routes, route_of, starts, dyn, idx0=i0, peers=Peers(**ok))
     for bad in (dict(slots=0), dict(slots=2), dict(rx=0.0), dict(ry=-1.0), dict(range=math.inf), dict(rx=math.nan),
@@ -206,7 +188,7 @@ def _head_on(peers):
     fleet = FleetRecedingHorizon([there, back], [0, 1], starts, None, sincos=o.sincos_array,
                                  peers=Peers(slots=1, rx=HEAD_ON["rx"], ry=HEAD_ON["ry"], range=HEAD_ON["range"]) if peers else None)
     for _ in range(400):
-        fleet.step(_solve(o, threads=2))
+        fleet.step(o.warm_solve(threads=2))
         s = fleet.state
         if s[0, 0] > s[1, 0] + 1.0:                                        # both past the meeting point
             break

@@ -1,4 +1,5 @@
-"""CPU: workloads.baseline_batch is bench.py's batch, array for array, and workloads.differing names what is not the same bits.
+"""CPU: workloads.baseline_batch is bench.py's batch, array for array, workloads.differing names what is not the same bits, and the
+fleets of the receding-horizon loop (route_fleet, fleet_ellipses) are reproducible and stay around each robot's own route.
 
 ``bench_py_batch`` below is bench.py's ``make_batch`` written out once more: bench.py cannot import from here and no pull request edits
 it, so this literal is what ties every probe and GPU test that calls ``baseline_batch`` to the batch the benchmark times.  The same goes
@@ -7,8 +8,8 @@ import numpy as np
 import pytest
 
 import conftest
-from mpc_trajectory_generator_amd import named_config
-from mpc_trajectory_generator_amd.workloads import PARITY_FIELDS, baseline_batch, differing
+from mpc_trajectory_generator_amd import frontend, harness, named_config
+from mpc_trajectory_generator_amd.workloads import PARITY_FIELDS, baseline_batch, differing, fleet_ellipses, route_fleet
 from oracle import Oracle
 from oracle.binding import STATUS_DTYPE
 
@@ -112,3 +113,50 @@ def test_differing_rows_as_permutation_and_as_sample():
     assert differing(a, s, idx) == ["penalty"]
     s[1][0, 0] += 1.0
     assert differing(a, s, idx) == ["penalty", "y"]
+
+
+def _same(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_route_fleet_starts_do_not_depend_on_K_and_follow_the_seed():
+    route = harness.scene_route(named_config("cfg4"), 11)
+    n = len(route.x_ref)
+    i0, starts, dyn = route_fleet(route, 40, 7, K=3)
+    assert i0.shape == (40,) and starts.shape == (40, 3) and i0.min() >= 0 and i0.max() < n - 25
+    assert [a.shape for a in dyn] == [(40, 3, 2), (40, 3, 2), (40, 3), (40, 3), (40, 3), (40, 3)]
+    j0, starts0, none = route_fleet(route, 40, 7)
+    assert none is None and np.array_equal(j0, i0) and np.array_equal(starts0, starts)
+    again = route_fleet(route, 40, 7, K=3)
+    assert _same((i0, starts), again[:2]) and _same(dyn, again[2])
+    other = route_fleet(route, 40, 8, K=3)
+    assert not np.array_equal(other[0], i0) and not np.array_equal(other[1], starts) and not np.array_equal(other[2][0], dyn[0])
+    assert route_fleet(route, 40, 7, back=60)[0].max() < n - 60
+    assert np.array_equal(route_fleet(route, 5, 7, back=2 * n)[0], np.zeros(5))        # a route shorter than ``back``: everybody at its start
+    ref = np.stack([np.array(route.x_ref)[i0], np.array(route.y_ref)[i0], np.array(route.theta_ref)[i0]], axis=1)
+    assert np.abs(starts - ref).max() < 1.0                                           # a sample of the route plus noise
+
+
+def test_fleet_ellipses_stay_around_each_robots_own_route():
+    cfg = named_config("cfg4")
+    B, K = 24, 3
+    routes, route_of, _, idx0 = frontend.random_fleet(cfg, 11, 3, B, seed=41)
+    n = np.array([len(r.x_ref) for r in routes])
+    assert len(set(n.tolist())) > 1, "routes of one length: the clip to the robot's own route is not exercised"
+    idx0 = idx0.copy()
+    idx0[:3] = n[route_of[:3]] - [1, 5, 29]                                            # samples 0..29 ahead reach past these robots' routes
+    assert fleet_ellipses(routes, route_of, idx0, 0, 9) is None
+    dyn = fleet_ellipses(routes, route_of, idx0, K, 9)
+    assert [a.shape for a in dyn] == [(B, K, 2), (B, K, 2), (B, K), (B, K), (B, K), (B, K)]
+    assert _same(dyn, fleet_ellipses(routes, route_of, idx0, K, 9))
+    assert not np.array_equal(dyn[0], fleet_ellipses(routes, route_of, idx0, K, 10)[0])
+    for b in range(B):
+        r = routes[route_of[b]]
+        jj = np.minimum(n[route_of[b]] - 1, idx0[b] + np.arange(30))
+        own = np.stack([np.array(r.x_ref)[jj], np.array(r.y_ref)[jj]], axis=1)        # [30, 2]
+        for ends in dyn[:2]:
+            near = np.abs(ends[b][:, None, :] - own[None, :, :]).max(axis=2) <= 5.0   # [K, 30]: within 5 m per axis of that sample
+            assert near.any(axis=1).all(), b
+    p1, p2, freq, rx, ry, ang = dyn
+    assert freq.min() >= 0.05 and freq.max() < 0.1 and min(rx.min(), ry.min()) >= 0.3 and max(rx.max(), ry.max()) < 1.0
+    assert ang.min() >= 0 and ang.max() < np.pi
