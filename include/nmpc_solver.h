@@ -251,6 +251,27 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
  * K + M > Ndynobs, a group_of[b] out of range, an rx, ry or range that is not finite and positive, a call after a step, or
  * a second call.  A loop without peers enqueues what it enqueued before this function existed. */
 int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range);
+/* Retirement: robots that reach their goal leave the loop, as the reference's `while not terminal` ends for one robot
+ * (src/path_generator.py:290,397).  Off unless on != 0 is given here; a loop without it enqueues what it enqueued before this
+ * function existed.  With it, every robot is active at the first step; after a step's advance an active robot whose terminal
+ * test holds is retired for good, and from the next step on it is not assembled, not solved and not advanced: its state, last_u,
+ * idx, p, u, y and status keep the values of its last step, its done stays 1, and its rows of a recorded trajectory repeat its
+ * final pose.  Each step solves the active robots only, as one batch, in ascending robot index; the wall-clock limits apply to
+ * that batch.  For peers a retired robot is a parked obstacle: its predicted pose is its state at every stage, and it stays a
+ * candidate for the others while receiving no peers itself.  A step with nobody active launches no solve and still counts.
+ * The host sizes a step by the number of active robots, which it learns from the step before: nmpc_loop_step then waits for
+ * the previous step's count (an event on its stream, not the device: loops on other streams keep running).  Only a retiring
+ * loop has this one-step coupling.
+ * To be called once, before the loop's first step: NMPC_ERR_BAD_ARG with a message, and nothing changed, for a call after a
+ * step or a second call. */
+int nmpc_loop_set_retire(nmpc_loop *l, int on);
+/* Synchronises, then gives the number of active robots and retired_at [B] (NULL = skip): the number of steps (solves) a retired
+ * robot took, -1 for an active one.  A loop without retirement reports B and -1 everywhere. */
+int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at);
+/* Steps a retiring loop until nobody is active, max_steps steps are taken or the trajectory buffer is full; returns the number
+ * of steps taken, or < 0.  Between steps it waits as nmpc_loop_step does, and does not synchronise after the last.
+ * NMPC_ERR_BAD_ARG on a loop without retirement. */
+int nmpc_loop_run(nmpc_loop *l, int max_steps, void *stream);
 void nmpc_loop_free(nmpc_loop *l);
 /* Enqueues assemble -> solve -> advance on `stream`; does not synchronise. */
 int nmpc_loop_step(nmpc_loop *l, void *stream);

@@ -23,7 +23,7 @@ SYMBOLS = (
     "nmpc_solve_batch_host", "nmpc_last_batch_ms", "nmpc_set_time_limits", "nmpc_eval_batch_device", "nmpc_eval_batch_host",
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
-    "nmpc_loop_trajectory",
+    "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run",
 )
 
 EXPECTED_ABI = 3      # the nmpc_opts / nmpc_status layouts below are written for this version of include/nmpc_solver.h
@@ -262,6 +262,12 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
                                          C.c_int, dp, C.c_int, C.POINTER(vp)]
     lib.nmpc_loop_set_peers.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_double, C.c_double]
     lib.nmpc_loop_set_peers.restype = C.c_int
+    lib.nmpc_loop_set_retire.argtypes = [vp, C.c_int]
+    lib.nmpc_loop_set_retire.restype = C.c_int
+    lib.nmpc_loop_active.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.nmpc_loop_active.restype = C.c_int
+    lib.nmpc_loop_run.argtypes = [vp, C.c_int, vp]
+    lib.nmpc_loop_run.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_loop_step.argtypes = [vp, vp]

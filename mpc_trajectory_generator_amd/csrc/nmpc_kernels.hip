@@ -597,6 +597,17 @@ struct nmpc_loop {
     nmpc::PeerArgs pa{};
     DevBuf<double> d_pred;       // [B][N][3]
     DevBuf<int> d_group_of, d_goff, d_gmem;
+    // nmpc_loop_set_retire: robots at their goal leave the loop.  A step runs over the active list, the solve over gathered rows, and
+    // the host learns the list's length one step late (nmpc_loop.h)
+    bool retire_called = false, retire = false;
+    nmpc::RetireArgs ra{};
+    nmpc::PackArgs ga{};
+    DevBuf<int> d_act, d_nact, d_retired_at;
+    DevBuf<double> d_sP, d_sU, d_sY;
+    DevBuf<nmpc_status> d_sst;
+    PinBuf h_nact;               // one int: the active robots after the last compaction whose event was waited for
+    Event ev_nact;               // recorded behind the copy of the count
+    bool nact_pending = false;   // a copy is under way: wait for ev_nact before h_nact is read
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -692,6 +703,7 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
     a.tab = l->d_tab; a.routes = l->d_routes; a.route_of = l->d_route_of;
     a.dynpar = l->d_dynpar; a.state = l->d_state; a.last_u = l->d_last_u; a.idx = l->d_idx;
     a.P = l->d_P; a.U = l->d_U; a.done = l->d_done; a.traj = l->d_traj; a.traj_row = 1;
+    a.act = nullptr; a.nact = B;
     *out = l;
     return NMPC_OK;
 }
@@ -743,7 +755,55 @@ int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx,
     p.ts = a.ts; p.rx = rx; p.ry = ry; p.range2 = range * range;
     p.state = l->d_state; p.U = l->d_U; p.pred = l->d_pred;
     p.group_of = l->d_group_of; p.goff = l->d_goff; p.gmem = l->d_gmem; p.P = l->d_P;
+    p.act = nullptr; p.nact = B;
     l->peers = true;
+    return NMPC_OK;
+}
+
+int nmpc_loop_set_retire(nmpc_loop *l, int on)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (l->retire_called) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_retire: called already");
+    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_retire: after the loop's first step");
+    if (!on) { l->retire_called = true; return NMPC_OK; }
+    const nmpc::LoopArgs &a = l->a;
+    const size_t B = (size_t)a.B, n1 = (size_t)nmpc_n1(&h->pb);
+    HIP_TRY(h, hipSetDevice(h->device));
+    DevBuf<int> act, nact, at;
+    DevBuf<double> sP, sU, sY;
+    DevBuf<nmpc_status> sst;
+    PinBuf pin;
+    Event ev;
+    std::vector<int> all(B);
+    for (size_t b = 0; b < B; ++b) all[b] = (int)b;
+    hipError_t e = act.alloc(B);
+    if (e == hipSuccess) e = nact.alloc(1);
+    if (e == hipSuccess) e = at.alloc(B);
+    if (e == hipSuccess) e = sP.alloc(B * a.n_p);
+    if (e == hipSuccess) e = sU.alloc(B * a.n_u);
+    if (e == hipSuccess) e = sY.alloc(B * n1);
+    if (e == hipSuccess) e = sst.alloc(B);
+    if (e == hipSuccess) e = pin.alloc(sizeof(int));
+    if (e == hipSuccess) e = ev.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemcpy(act, all.data(), B * sizeof(int), hipMemcpyHostToDevice);      // everybody is active at step 0
+    if (e == hipSuccess) e = hipMemcpy(nact, &a.B, sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(at, 0xFF, B * sizeof(int));                                    // retired_at = -1
+    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_retire: allocation", e);
+    *(int *)pin.p = a.B;
+    l->d_act = std::move(act); l->d_nact = std::move(nact); l->d_retired_at = std::move(at);
+    l->d_sP = std::move(sP); l->d_sU = std::move(sU); l->d_sY = std::move(sY); l->d_sst = std::move(sst);
+    l->h_nact = std::move(pin); l->ev_nact = std::move(ev);
+    nmpc::RetireArgs &r = l->ra;
+    r.B = a.B; r.N = a.N; r.s = a.s;
+    r.done = l->d_done; r.state = l->d_state; r.retired_at = l->d_retired_at; r.act = l->d_act; r.nact = l->d_nact;
+    r.traj = l->d_traj;
+    nmpc::PackArgs &g = l->ga;
+    g.n_p = a.n_p; g.n_u = a.n_u; g.n1 = (int)n1;
+    g.act = l->d_act; g.P = l->d_P; g.U = l->d_U; g.Y = l->d_Y; g.st = l->d_st;
+    g.sP = l->d_sP; g.sU = l->d_sU; g.sY = l->d_sY; g.sst = l->d_sst;
+    l->retire_called = l->retire = true;
     return NMPC_OK;
 }
 
@@ -762,6 +822,63 @@ static int loop_settle(nmpc_handle *h)
     return NMPC_OK;
 }
 
+// a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
+static int loop_nactive(nmpc_loop *l, int *n)
+{
+    if (l->nact_pending) {
+        HIP_TRY(l->h, hipEventSynchronize(l->ev_nact));
+        l->nact_pending = false;
+    }
+    *n = *(const int *)l->h_nact.p;
+    return NMPC_OK;
+}
+
+// one step of a retiring loop: the kernels of nmpc_loop_step over the active list, the solve on gathered rows, then the compaction
+static int loop_step_retiring(nmpc_loop *l, void *stream)
+{
+    nmpc_handle *h = l->h;
+    hipStream_t s = (hipStream_t)stream;
+    nmpc::LoopArgs &a = l->a;
+    int n = 0;
+    if (const int rc = loop_nactive(l, &n)) return rc;
+    if (n < 0 || n > a.B) return fail(h, NMPC_ERR_HIP, "nmpc_loop_step: active count out of range");
+    a.act = l->d_act; a.nact = n;
+    if (n > 0) {
+        const int cur = l->steps & 1;
+        a.dyn_in = l->d_dyn[cur];
+        a.dyn_out = l->d_dyn[cur ^ 1];
+        hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, a);
+        if (l->peers) {
+            l->pa.act = l->d_act; l->pa.nact = n;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, l->pa);
+            hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, l->pa);
+        }
+        hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, l->ga);
+        HIP_TRY(h, hipGetLastError());
+        // the launch-order hint: the gathered statuses, i.e. the previous solves of these very robots
+        h->order_hint = (l->steps > 0 && h->loop_order_prev) ? l->d_sst.p : nullptr;
+        const int rc = nmpc_solve_batch_device(h, n, l->d_sP, l->d_sU, l->d_sY, nullptr, l->d_sY, l->d_sst, stream);
+        h->order_hint = nullptr;
+        if (rc) return rc;
+        hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, l->ga);
+        hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+    }
+    // (with nobody active the step still counts: the clock advances and the trajectory rows repeat)
+    nmpc::RetireArgs &r = l->ra;
+    r.step = l->steps + 1;
+    r.pred = l->peers ? l->d_pred.p : nullptr;
+    r.traj_row = a.traj_row;
+    hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, r);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(l->h_nact.p, l->d_nact.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipEventRecord(l->ev_nact, s));
+    l->nact_pending = true;
+    a.t += a.s;
+    a.traj_row += a.s;
+    l->steps++;
+    return NMPC_OK;
+}
+
 int nmpc_loop_step(nmpc_loop *l, void *stream)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
@@ -770,6 +887,7 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     if (l->max_steps > 0 && l->steps >= l->max_steps) return fail(h, NMPC_ERR_BAD_ARG, "trajectory buffer is full");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->device));
+    if (l->retire) return loop_step_retiring(l, stream);
     nmpc::LoopArgs &a = l->a;
     const int cur = l->steps & 1;
     a.dyn_in = l->d_dyn[cur];
@@ -793,6 +911,41 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     a.t += a.s;
     a.traj_row += a.s;
     l->steps++;
+    return NMPC_OK;
+}
+
+int nmpc_loop_run(nmpc_loop *l, int max_steps, void *stream)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (!l->retire) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_run: the loop does not retire its robots, it would never end");
+    if (max_steps < 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_run: max_steps < 0");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int taken = 0;
+    while (taken < max_steps && !(l->max_steps > 0 && l->steps >= l->max_steps)) {
+        int n = 0;
+        if (const int rc = loop_nactive(l, &n)) return rc;
+        if (n == 0) break;
+        if (const int rc = nmpc_loop_step(l, stream)) return rc;
+        ++taken;
+    }
+    return taken;
+}
+
+int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (const int rc = loop_settle(h)) return rc;
+    const int B = l->a.B;
+    if (!l->retire) {
+        if (n_active) *n_active = B;
+        if (retired_at) for (int b = 0; b < B; ++b) retired_at[b] = -1;
+        return NMPC_OK;
+    }
+    if (n_active) HIP_TRY(h, hipMemcpy(n_active, l->d_nact, sizeof(int), hipMemcpyDeviceToHost));
+    if (retired_at) HIP_TRY(h, hipMemcpy(retired_at, l->d_retired_at, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 

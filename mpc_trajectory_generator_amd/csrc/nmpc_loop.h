@@ -14,6 +14,15 @@
 // Arithmetic: index selections (window arg-min, vertex window, braking-table filter) use the same
 // unfused IEEE operations as the host mirror (`trajectory.VectorizedRecedingHorizon`), so they are
 // bit-identical to it; sin / cos are the kernels' own sincos_cw (the mirror takes it as a hook).
+//
+// Retirement (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9): a robot whose terminal test holds after an advance leaves the
+// loop for good, as the reference's `while not terminal` ends.  The kernels of a step then run over the list of the robots still
+// active, `act[0 .. nact)` (ascending robot index; NULL = everybody, row i is robot i): the same arithmetic on the same per-robot
+// arrays through one more indirection.  nmpc_loop_compact_kernel rebuilds the list after every advance, and a gather / scatter pair
+// moves the active robots' rows through contiguous buffers, so that the solve sees a batch of nact instances and nothing else.
+// The host sizes a step's launches by nact, which it learns one step late: the count is copied to pinned memory behind an event, and
+// the next nmpc_loop_step waits for THAT event (not for the device: a loop on another stream keeps running).  This coupling of the
+// host to the step before exists only with retirement on; without it a step enqueues what it always did and waits for nothing.
 #pragma once
 
 namespace nmpc {
@@ -44,6 +53,8 @@ struct LoopArgs {
     unsigned char *done;      // [B]
     double *traj;             // [(steps * s + 1)][B][3] or NULL
     int traj_row;             // rows already written
+    const int *act;           // robots this step runs over, ascending; NULL: all B (no retirement)
+    int nact;                 // their number (B without retirement)
 };
 
 // (d, j) lexicographic minimum over the wave, result in every lane: the FIRST minimal index, like np.argmin
@@ -70,7 +81,7 @@ __device__ __forceinline__ double linspace_at(double t0, double ts, int H, int i
 // one wave per robot: fills p[b] and the rotated dynamic block
 __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
 {
-    const int b = blockIdx.x, lane = threadIdx.x;
+    const int b = a.act ? a.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
     // the robot's route: the same for the whole wave (read before any store, so that the loads can be scalar)
     const LoopRoute &rt = a.routes[a.route_of[b]];
     const double *xr = a.tab + rt.xr, *yr = a.tab + rt.yr, *thr = a.tab + rt.thr, *vert = a.tab + rt.vert;
@@ -226,8 +237,9 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
 // one thread per robot: Euler advance over the steps taken (mpc_generator.py:225-235), terminal test (:397)
 __global__ void nmpc_loop_advance_kernel(LoopArgs a)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.B) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nact) return;
+    const int b = a.act ? a.act[i] : i;
     const double *u = a.U + (size_t)b * a.n_u;
     double x = a.state[3 * b], y = a.state[3 * b + 1], th = a.state[3 * b + 2];
     for (int i = 0; i < a.s; ++i) {
@@ -263,14 +275,18 @@ struct PeerArgs {
     const int *goff;          // [groups + 1]: a group's members are gmem[goff[g] .. goff[g + 1])
     const int *gmem;          // [B], ascending robot index inside a group
     double *P;                // [B][n_p]
+    const int *act;           // as in LoopArgs
+    int nact;
 };
 
 // one thread per robot: pred[b][k] = the pose after k + 1 Euler steps (the expression of nmpc_loop_advance_kernel) under the
 // previous plan shifted by the s controls already applied, its last control held beyond the plan's end
+// (a retired robot's row is not computed here: nmpc_loop_compact_kernel parked it)
 __global__ void nmpc_loop_predict_kernel(PeerArgs a)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.B) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nact) return;
+    const int b = a.act ? a.act[i] : i;
     const double *u = a.U + (size_t)b * a.n_u;
     double *out = a.pred + (size_t)b * a.N * 3;
     double x = a.state[3 * b], y = a.state[3 * b + 1], th = a.state[3 * b + 2];
@@ -291,7 +307,7 @@ __global__ void nmpc_loop_predict_kernel(PeerArgs a)
 __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
 {
     __shared__ double own[2 * NMPC_MAX_HORIZON];
-    const int b = blockIdx.x, lane = threadIdx.x;
+    const int b = a.act ? a.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
     const int N = a.N;
     // the group's member range: the same for the whole wave
     const int g = a.group_of[b];
@@ -349,6 +365,97 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
             slot[e] = f == 0 ? pj[3 * st] : (f == 1 ? pj[3 * st + 1] : (f == 2 ? a.rx : (f == 3 ? a.ry : pj[3 * st + 2])));
         }
     }
+}
+
+// ---- retirement: robots that reached their goal leave the loop (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9) ----
+struct RetireArgs {
+    int B, N, s;
+    int step;                 // steps taken, this one included: what retired_at takes
+    const unsigned char *done;   // [B], of this step's advance for the robots it ran over, 1 for every robot retired before
+    const double *state;      // [B][3]
+    int *retired_at;          // [B]: -1 = active
+    int *act;                 // [B]: out, the robots still active in ascending index
+    int *nact;                // [1]: out, their number
+    double *pred;             // [B][N][3] or NULL (no peers)
+    double *traj;             // as in LoopArgs
+    int traj_row;             // the first of this step's s rows
+};
+
+// One workgroup, after the advance: thread t takes the robots [t * chunk, (t + 1) * chunk), so that an exclusive scan of the threads'
+// counts gives each its place in the ascending list.  An active robot that is done is retired at this step: retired_at latches, and
+// with peers its row of pred becomes its final pose at every stage, a copy, for as long as the others look at it.  A robot retired
+// earlier repeats its final pose in this step's trajectory rows.
+__global__ __launch_bounds__(1024) void nmpc_loop_compact_kernel(RetireArgs r)
+{
+    __shared__ int cnt[1024];
+    const int t = threadIdx.x, nt = blockDim.x;
+    const int chunk = (r.B + nt - 1) / nt;
+    const int lo = t * chunk < r.B ? t * chunk : r.B, hi = lo + chunk < r.B ? lo + chunk : r.B;
+    int c = 0;
+    for (int b = lo; b < hi; ++b) {
+        const double x = r.state[3 * b], y = r.state[3 * b + 1], th = r.state[3 * b + 2];
+        if (r.retired_at[b] >= 0) {
+            if (r.traj) {
+                for (int i = 0; i < r.s; ++i) {
+                    double *row = r.traj + ((size_t)(r.traj_row + i) * r.B + b) * 3;
+                    row[0] = x; row[1] = y; row[2] = th;
+                }
+            }
+        } else if (r.done[b]) {
+            r.retired_at[b] = r.step;
+            if (r.pred) {
+                double *out = r.pred + (size_t)b * r.N * 3;
+                for (int k = 0; k < r.N; ++k) { out[3 * k] = x; out[3 * k + 1] = y; out[3 * k + 2] = th; }
+            }
+        } else {
+            ++c;
+        }
+    }
+    cnt[t] = c;
+    __syncthreads();
+    for (int off = 1; off < nt; off <<= 1) {            // inclusive scan
+        const int v = t >= off ? cnt[t - off] : 0;
+        __syncthreads();
+        cnt[t] += v;
+        __syncthreads();
+    }
+    int pos = cnt[t] - c;
+    for (int b = lo; b < hi; ++b)
+        if (r.retired_at[b] < 0) r.act[pos++] = b;      // (the thread's own stores above)
+    if (t == nt - 1) *r.nact = cnt[t];
+}
+
+// the rows the solve reads and writes, of the robots in act, to and from contiguous buffers: row i = robot act[i]
+struct PackArgs {
+    int n_p, n_u, n1;
+    const int *act;
+    double *P, *U, *Y;        // [B][n_p], [B][n_u], [B][n1]: the loop's
+    nmpc_status *st;          // [B]
+    double *sP, *sU, *sY;     // [nact][..]: the solve's
+    nmpc_status *sst;
+};
+
+__device__ __forceinline__ void copy_row(double *dst, const double *src, int n)
+{
+    for (int e = threadIdx.x; e < n; e += blockDim.x) dst[e] = src[e];
+}
+
+// one workgroup per active robot.  The status row goes along: it is the launch-order hint of the solve (the same robot's previous pass count)
+__global__ __launch_bounds__(256) void nmpc_loop_gather_kernel(PackArgs g)
+{
+    const size_t i = blockIdx.x, b = (size_t)g.act[blockIdx.x];
+    copy_row(g.sP + i * g.n_p, g.P + b * g.n_p, g.n_p);
+    copy_row(g.sU + i * g.n_u, g.U + b * g.n_u, g.n_u);
+    copy_row(g.sY + i * g.n1, g.Y + b * g.n1, g.n1);
+    if (threadIdx.x == 0) g.sst[i] = g.st[b];
+}
+
+__global__ __launch_bounds__(256) void nmpc_loop_scatter_kernel(PackArgs g)
+{
+    const size_t i = blockIdx.x, b = (size_t)g.act[blockIdx.x];
+    copy_row(g.U + b * g.n_u, g.sU + i * g.n_u, g.n_u);
+    copy_row(g.Y + b * g.n1, g.sY + i * g.n1, g.n1);
+    if (threadIdx.x == 0) g.st[b] = g.sst[i];
 }
 
 }  // namespace nmpc

@@ -165,13 +165,28 @@ class TrajectoryGenerator:
 
 
 class _HostLoop:
-    """What the host drivers share: one step = assemble -> ``solve_fn(P, u0, y0) -> (U, Y, status)`` -> advance."""
+    """What the host drivers share: one step = assemble -> ``solve_fn(P, u0, y0) -> (U, Y, status)`` -> advance.
+
+    A driver that retires its robots (``FleetRecedingHorizon(retire=True)``) has ``active`` [B] bool: ``solve_fn`` then gets the
+    active rows only, in ascending robot index, every other row of ``U``, ``Y`` and the status keeps what it held, and the step
+    ends with ``retire()``; it returns the parameter vectors and statuses of all B robots, a retired one's from its last step."""
+    active = None
 
     def step(self, solve_fn):
         P = self.assemble()
-        self.U, self.Y, st = solve_fn(P, self.U, self.Y)
+        if self.active is None:
+            self.U, self.Y, st = solve_fn(P, self.U, self.Y)
+            self.advance(self.U)
+            return P, st
+        rows = np.nonzero(self.active)[0]
+        if len(rows):
+            U, Y, st = solve_fn(P[rows], self.U[rows], self.Y[rows])
+            if self.status is None:
+                self.status = np.zeros(len(self.active), dtype=st.dtype)
+            self.U[rows], self.Y[rows], self.status[rows] = U, Y, st
         self.advance(self.U)
-        return P, st
+        self.retire()
+        return P, self.status
 
 
 class BatchedRecedingHorizon(_HostLoop):
@@ -281,7 +296,9 @@ class VectorizedRecedingHorizon(_HostLoop):
         out[..., 4] = ang[:, :, None]
         return out
 
-    def assemble(self):
+    def assemble(self, active=None):
+        """-> P [B, n_p].  ``active`` [B] bool (default: everybody): the other robots keep everything they carry (reference sample,
+        dynamic block), and their rows of P mean nothing."""
         cfg, route, B, N, n = self.cfg, self.route, self.B, self.cfg.N_hor, self.n
         s = cfg.num_steps_taken
         x, y = self.state[:, 0], self.state[:, 1]
@@ -309,9 +326,11 @@ class VectorizedRecedingHorizon(_HostLoop):
                 # the reference rotates the WHOLE flat list left by ndynobs * s entries (:312): inside a block that is a
                 # shift by s stages, and a block's last s stages take the next block's first s (the last block's take
                 # block 0's -- a padding slot can so inherit stale ellipses of obstacle 0 when 0 < K < Ndynobs)
-                flat = self.dyn.reshape(B, -1)
+                flat, held = self.dyn.reshape(B, -1), self.dyn
                 self.dyn = np.roll(flat, -cfg.ndynobs * s, axis=1).reshape(self.dyn.shape)
                 self.dyn[:, :self.K, N - s:] = self._predict((self.t + N - s) * cfg.ts, s)
+                if active is not None:
+                    self.dyn[~active] = held[~active]
         # closest reference sample in the sliding window (:320-325)
         lb = np.maximum(0, self.idx - s)
         ub = np.minimum(n, self.idx + 5 * s)
@@ -321,7 +340,7 @@ class VectorizedRecedingHorizon(_HostLoop):
         jj = np.minimum(j, n - 1)
         d = np.linalg.norm(np.stack([self.x_ref[jj] - x[:, None], self.y_ref[jj] - y[:, None]], axis=2), axis=2)
         d = np.where(ok, d, np.inf)
-        self.idx = lb + np.argmin(d, axis=1)
+        self.idx = lb + np.argmin(d, axis=1) if active is None else np.where(active, lb + np.argmin(d, axis=1), self.idx)
         idx = self.idx
         # horizon references and target (:326-341)
         end = np.array(route.end, dtype=np.float64)
@@ -355,7 +374,9 @@ class VectorizedRecedingHorizon(_HostLoop):
         assert P.shape[1] == cfg.n_p
         return P
 
-    def advance(self, U):
+    def advance(self, U, active=None):
+        """``active`` as in ``assemble``: the other robots stay where they are (their trajectory rows repeat their pose) and keep
+        their ``last_u`` and ``done``."""
         cfg = self.cfg
         s = cfg.num_steps_taken
         st = self.state.copy()
@@ -364,14 +385,17 @@ class VectorizedRecedingHorizon(_HostLoop):
             th = st[:, 2]
             # per robot: x + ts*(v*cos(theta)) with math.cos -> np.cos is the same libm call
             sn, cs = self.sincos(np.ascontiguousarray(th))
-            st = np.stack([st[:, 0] + cfg.ts * (v * cs), st[:, 1] + cfg.ts * (v * sn),
-                           th + cfg.ts * w], axis=1)
+            new = np.stack([st[:, 0] + cfg.ts * (v * cs), st[:, 1] + cfg.ts * (v * sn),
+                            th + cfg.ts * w], axis=1)
+            st = new if active is None else np.where(active[:, None], new, st)
             self.traj.append(st.copy())
         self.state = st
-        self.last_u = U[:, (s - 1) * cfg.nu:s * cfg.nu].copy()
+        last_u = U[:, (s - 1) * cfg.nu:s * cfg.nu].copy()
+        self.last_u = last_u if active is None else np.where(active[:, None], last_u, self.last_u)
         self.has_input = True
         end = self.route.end
-        self.done = (np.abs(st[:, 0] - end[0]) <= 0.05) & (np.abs(st[:, 1] - end[1]) <= 0.05) & (np.abs(self.last_u[:, 0]) < 0.005)
+        done = (np.abs(st[:, 0] - end[0]) <= 0.05) & (np.abs(st[:, 1] - end[1]) <= 0.05) & (np.abs(self.last_u[:, 0]) < 0.005)
+        self.done = done if active is None else np.where(active, done, self.done)
         self.t += s
 
 
@@ -416,9 +440,15 @@ class FleetRecedingHorizon(_HostLoop):
     ``peers`` (a ``Peers``) lets the robots of a group see each other: ``assemble`` overlays the chosen peers on
     the gathered parameter vectors.  Peers cross routes, so the rule lives here and not in the per-route mirrors,
     whose carried dynamic blocks never see it.
+
+    ``retire=True``: a robot whose terminal test holds after an advance leaves the loop for good, as the reference's
+    ``while not terminal`` ends for one robot.  Everybody is ``active`` at the first step; a retired robot
+    is not assembled, solved or advanced again, keeps every value of its last step (``done`` stays True, its trajectory rows repeat
+    its final pose), and ``retired_at[b]`` = the steps (solves) it took, -1 while it is active.  For peers it is a parked obstacle:
+    predicted at its state at every stage, a candidate for the others, given no peers itself.  ``step`` solves the active rows only.
     """
 
-    def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None):
+    def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False):
         self.routes = list(routes)
         cfg = self.cfg = self.routes[0].cfg
         self.B = B = len(starts)
@@ -445,6 +475,22 @@ class FleetRecedingHorizon(_HostLoop):
             g = peers.checked(B, self.K, cfg.Ndynobs)
             g = np.zeros(B, dtype=np.int32) if g is None else g
             self.groups = [np.nonzero(g == v)[0] for v in np.unique(g)]       # members in ascending robot index
+        self.steps = 0
+        if retire:
+            self.active = np.ones(B, dtype=bool)
+            self.retired_at = np.full(B, -1, dtype=np.int32)
+            self.P = np.zeros((B, cfg.n_p))                                   # a retired robot's row: of its last step
+            self.status = None                                                # [B], made by the first solve (its dtype is the solver's)
+
+    @property
+    def n_active(self):
+        return self.B if self.active is None else int(self.active.sum())
+
+    def retire(self):
+        """After an advance: the active robots that are done leave."""
+        now = self.active & self.done
+        self.retired_at[now] = self.steps
+        self.active &= ~now
 
     def _gather(self, field, shape, dtype=np.float64):
         out = np.empty((self.B,) + shape, dtype=dtype)
@@ -479,9 +525,13 @@ class FleetRecedingHorizon(_HostLoop):
         return rows
 
     def assemble(self):
-        P = np.empty((self.B, self.cfg.n_p))
+        act = self.active
+        P = np.empty((self.B, self.cfg.n_p)) if act is None else self.P
         for ids, sub in self.parts:
-            P[ids] = sub.assemble()
+            if act is None:
+                P[ids] = sub.assemble()
+            else:
+                P[ids[act[ids]]] = sub.assemble(act[ids])[act[ids]]
         if self.peers is not None:
             self._overlay_peers(P)
         return P
@@ -489,7 +539,7 @@ class FleetRecedingHorizon(_HostLoop):
     def predict(self):
         """-> pred [B, N, 3]: pred[j, k] = robot j's pose after k + 1 Euler steps (the expression of ``advance``) from
         its state, under its previous plan shifted by the controls already applied: control k is U[j, s + k], and
-        the plan's last control beyond its end."""
+        the plan's last control beyond its end.  A retired robot is parked: pred[j, k] = its state, a copy."""
         cfg = self.cfg
         N, s, nu = cfg.N_hor, cfg.num_steps_taken, cfg.nu
         st = self.state
@@ -501,6 +551,8 @@ class FleetRecedingHorizon(_HostLoop):
             sn, cs = self.sincos(np.ascontiguousarray(th))
             x, y, th = x + cfg.ts * (v * cs), y + cfg.ts * (v * sn), th + cfg.ts * w
             pred[:, k, 0], pred[:, k, 1], pred[:, k, 2] = x, y, th
+        if self.active is not None:
+            pred[~self.active] = st[~self.active, None, :]
         return pred
 
     def _overlay_peers(self, P):
@@ -531,6 +583,8 @@ class FleetRecedingHorizon(_HostLoop):
                 for m in range(min(M, G - 1)):
                     j = order[:, m]
                     got = ok[np.arange(len(me)), j]
+                    if self.active is not None:
+                        got &= self.active[mem[me]]                          # a retired robot's p is not touched
                     b, src = mem[me[got]], mem[j[got]]
                     blk = np.empty((len(b), N, cfg.ndynobs))
                     blk[..., 0], blk[..., 1], blk[..., 4] = pred[src, :, 0], pred[src, :, 1], pred[src, :, 2]
@@ -540,8 +594,9 @@ class FleetRecedingHorizon(_HostLoop):
 
     def advance(self, U):
         for ids, sub in self.parts:
-            sub.advance(U[ids])
+            sub.advance(U[ids], None if self.active is None else self.active[ids])
         self.t += self.cfg.num_steps_taken
+        self.steps += 1
 
 
 def _fill_route(r, route: harness.Route, keep: list):
@@ -589,10 +644,15 @@ class DeviceRecedingHorizon:
     ``peers`` (a ``Peers``): the robots of a group see each other (``nmpc_loop_set_peers``); two more
     kernels per step, between the assembly and the solve.  Its host mirror is ``FleetRecedingHorizon`` with the same ``peers``
     (tests/test_gpu_peers_loop.py).
+
+    ``retire=True``: robots that reach their goal leave the loop (``nmpc_loop_set_retire``); every step solves
+    the active robots only, ``active()`` tells who is left and ``run(max_steps)`` steps until nobody is.  ``step`` then waits for the
+    step before to have counted its active robots (an event, not the device).  Its host mirror is ``FleetRecedingHorizon`` with
+    ``retire=True`` (tests/test_gpu_retire_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None):
+                 route_of=None, peers=None, retire=False):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -639,6 +699,12 @@ class DeviceRecedingHorizon:
             if rc:
                 self.close()
                 solver._check(rc)
+        self.retire = bool(retire)
+        if retire:
+            rc = self.lib.nmpc_loop_set_retire(h, 1)
+            if rc:
+                self.close()
+                solver._check(rc)
 
     def close(self):
         if getattr(self, "_l", None):
@@ -656,6 +722,22 @@ class DeviceRecedingHorizon:
         self.solver._check(self.lib.nmpc_loop_step(self._l, stream))
         self.t += self.cfg.num_steps_taken
         self.steps += 1
+
+    def run(self, max_steps, stream=None):
+        """A retiring loop: step until nobody is active, ``max_steps`` steps are taken or the trajectory buffer is full.
+        -> the number of steps taken; does not synchronise after the last."""
+        n = self.lib.nmpc_loop_run(self._l, int(max_steps), stream)
+        if n < 0:
+            self.solver._check(n)
+        self.t += n * self.cfg.num_steps_taken
+        self.steps += n
+        return n
+
+    def active(self):
+        """-> (n_active, retired_at [B] int32) after synchronising: the steps each retired robot took, -1 for an active one."""
+        n, at = C.c_int32(), np.empty(self.B, dtype=np.int32)
+        self.solver._check(self.lib.nmpc_loop_active(self._l, C.byref(n), _lib.as_i32p(at)))
+        return n.value, at
 
     def read(self):
         """-> (state [B,3], last_u [B,2], idx [B], done [B] bool, status [B]) after synchronising."""

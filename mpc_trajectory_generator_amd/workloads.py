@@ -6,7 +6,7 @@ import numpy as np
 
 from .config import named_config
 from .frontend import random_routes
-from .harness import synthetic_batch
+from .harness import scene_route, synthetic_batch
 
 # what the generator adds per configuration: config 3 a synthetic circle field, config 4 random moving ellipses
 _GENERATOR_FLAGS = {"cfg3": dict(synthetic_circles=True), "nobs50": dict(synthetic_circles=True),
@@ -72,16 +72,44 @@ def fleet_ellipses(routes, route_of, idx0, K, seed):
     return moving_ellipses(c, rng)
 
 
-def step_differing(dev, host, solve):
-    """Step a ``DeviceRecedingHorizon`` and its host mirror (``solve``: the mirror's solve function) once.
+def staggered_fleet(cfg, scene=1, planned=3, seed=5, back=(2, 5, 12, 40)):
+    """-> (routes, route_of, starts, idx0): the scene's own route and ``planned`` random ones (``random_routes`` with ``seed``), and on
+    each route one robot per entry of ``back``, standing on the route that many samples before its end.  The robots reach their goals
+    many steps apart: the fleet of the retirement tests."""
+    routes = [scene_route(cfg, scene)] + random_routes(cfg, scene, planned, seed=seed)
+    n = np.array([len(r.x_ref) for r in routes])
+    route_of = np.repeat(np.arange(len(routes)), len(back)).astype(np.int32)
+    i0 = np.maximum(0, n[route_of] - np.tile(np.array(back), len(routes))).astype(np.int32)
+    starts = np.stack([[routes[r].x_ref[i], routes[r].y_ref[i], routes[r].theta_ref[i]] for r, i in zip(route_of, i0)])
+    return routes, route_of, starts, i0
+
+
+def move_near_goal(routes, route_of, starts, idx0, back):
+    """-> (starts, idx0) with robot b, for b < len(back), standing on its route ``back[b]`` samples before the end: robots that
+    arrive within a few steps, among the others of a ``random_fleet``."""
+    starts, idx0 = np.array(starts, dtype=np.float64), np.array(idx0, dtype=np.int32)
+    for b, k in enumerate(back):
+        r = routes[route_of[b]]
+        idx0[b] = max(0, len(r.x_ref) - k)
+        starts[b] = [r.x_ref[idx0[b]], r.y_ref[idx0[b]], r.theta_ref[idx0[b]]]
+    return starts, idx0
+
+
+def step_differing(dev, host, solve, dev_step=None):
+    """Step a ``DeviceRecedingHorizon`` (``dev_step(dev)`` if given, else ``dev.step()``) and its host mirror (``solve``: the mirror's
+    solve function) once.
     -> (names, P, done): the names out of P, U, Y, state, last_u, idx, done, num_inner_iterations, exit_status on which the two are
-    not bit-equal ("P" with its first differing columns), the device's parameter vectors and its ``done``."""
-    dev.step()
+    not bit-equal ("P" with its first differing columns), the device's parameter vectors and its ``done``.  A retiring pair
+    (``retire=True``: the mirror's ``solve`` sees the active rows only) is also compared on retired_at and n_active."""
+    dev.step() if dev_step is None else dev_step(dev)
     P, st = host.step(solve)
     Pd, Ud, Yd = dev.params()
     state, last_u, idx, done, std = dev.read()
     pairs = [("P", Pd, P), ("U", Ud, host.U), ("Y", Yd, host.Y), ("state", state, host.state), ("last_u", last_u, host.last_u),
              ("idx", idx, host.idx), ("done", done, host.done)] + [(f, std[f], st[f]) for f in ("num_inner_iterations", "exit_status")]
+    if host.active is not None:
+        n_active, retired_at = dev.active()
+        pairs += [("retired_at", retired_at, host.retired_at), ("n_active", n_active, host.n_active)]
     names = [n for n, x, y in pairs if not np.array_equal(x, y)]
     if "P" in names:
         names[0] = f"P at columns {np.unique(np.nonzero(Pd != P)[1])[:10]}"

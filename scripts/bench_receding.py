@@ -5,7 +5,9 @@ Default: the whole loop on device (nmpc_loop_*: assembly, solve and state advanc
 crosses PCIe between steps), every robot on the scene's route; --routes R > 1: the robots follow R routes
 planned between random start / goal points of the scene (frontend.random_fleet).  --peers G: the robots see each
 other in groups of G consecutive robots; --peer-slots of the Ndynobs ellipse slots go to peers, the
-rest stay scripted.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+rest stay scripted.  --retire: robots that reach their goal leave the loop (nmpc_loop_set_retire); the run ends when nobody is
+active or after --steps steps, and reports the steps and solves it took.  --back: how close to the route's end robots may start
+(--routes 1); a small value gives a fleet whose robots arrive all through the run.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -38,6 +40,9 @@ ap.add_argument("--peers", type=int, default=0,
                 help="G > 0: groups of G consecutive robots (of a sub-fleet, see --split) see each other; 0 = nobody sees anybody")
 ap.add_argument("--peer-slots", type=int, default=2, help="with --peers: ellipse slots given to peers (the other Ndynobs - M stay scripted)")
 ap.add_argument("--peer-range", type=float, default=10.0, help="with --peers: how far a robot sees, in metres")
+ap.add_argument("--retire", action="store_true",
+                help="device loop only: retire the robots that reach their goal; run until nobody is active, --steps at the most")
+ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
@@ -58,7 +63,7 @@ def peers_of(n):
 
 if args.routes == 1:
     route = harness.scene_route(cfg, args.scene)
-    i0, starts, dyn = route_fleet(route, B, 0, K, back=60)
+    i0, starts, dyn = route_fleet(route, B, 0, K, back=args.back)
     routes, route_of = route, None
 else:
     from mpc_trajectory_generator_amd.frontend import random_fleet
@@ -84,7 +89,7 @@ if not args.host:
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
         loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
-                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids))))
+                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids)), retire=args.retire))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -92,11 +97,22 @@ if not args.host:
         rh.step(strm)                           # step 0 = cold start; timed separately
     st0 = np.concatenate([rh.read()[4] for rh in loops])        # (synchronises)
     t0 = time.perf_counter()
-    for k in range(1, args.steps):
-        for rh, strm in zip(loops, streams):
-            rh.step(strm)
+    steps = args.steps
+    if args.retire:
+        # a sub-fleet's step waits for the count of its own step before, while the other sub-fleets' steps run on their streams
+        while any([rh.steps < args.steps and rh.run(1, strm) for rh, strm in zip(loops, streams)]):
+            pass
+    else:
+        for k in range(1, args.steps):
+            for rh, strm in zip(loops, streams):
+                rh.step(strm)
     outs = [rh.read() for rh in loops]          # synchronises
     total = time.perf_counter() - t0
+    solves = B * (args.steps - 1)
+    if args.retire:
+        steps = max(rh.steps for rh in loops)
+        # after the first step: a retired robot took retired_at solves, an active one as many as its sub-fleet took steps
+        solves = int(sum(np.where(at < 0, rh.steps, at).sum() for rh in loops for at in [rh.active()[1]])) - B
     done = np.concatenate([o[3] for o in outs])
     st = np.concatenate([o[4] for o in outs])
     from mpc_trajectory_generator_amd import _lib
@@ -105,13 +121,16 @@ if not args.host:
         _lib.load_library().nmpc_debug_win_stats(buf, 0)
         print(f"windowed cross-track searches {buf[0]}, fell back {buf[1]} ({100.0 * buf[1] / max(buf[0], 1):.1f} %)", file=sys.stderr)
     print(json.dumps({
-        "metric": "nmpc_receding_horizon_solves_per_sec", "value": B * (args.steps - 1) / total, "unit": "solves/s",
+        "metric": "nmpc_receding_horizon_solves_per_sec", "value": solves / total, "unit": "solves/s",
         "config": {"workload": f"cfg4 smooth_velocity, scene {args.scene}{fleet}, B={B}, {args.steps} receding-horizon steps, "
                                "num_steps_taken=2, warm start (u, y carried; c reset), loop entirely on device"
+                               + (f", robots start up to {args.back} samples before the route's end" if args.back != 60 else "")
+                               + (", robots retire at their goals" if args.retire else "")
                                + (f", at most {args.budget} PANOC iterations per solve (NotConvergedOutOfTime beyond)" if args.budget else "")
                                + (f", fleet split into {args.split} sub-fleets on {args.split} streams" if args.split > 1 else ""),
                    "kernel": solver.kernel_name},
-        "ms_per_step": 1e3 * total / (args.steps - 1), "mean_inner_iters_first_step": float(st0["num_inner_iterations"].mean()),
+        "steps": steps, "solves": solves + B, "seconds_after_first_step": total,
+        "ms_per_step": 1e3 * total / max(steps - 1, 1), "mean_inner_iters_first_step": float(st0["num_inner_iterations"].mean()),
         "mean_inner_iters_last_step": float(st["num_inner_iterations"].mean()),
         "converged_frac_last_step": float((st["exit_status"] == 0).mean()),
         "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum())}))
