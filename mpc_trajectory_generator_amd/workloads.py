@@ -2,11 +2,13 @@
 and test that quotes a number.
 
 bench.py's ``make_batch`` is the contract; tests/test_workloads.py holds ``baseline_batch`` to it array for array."""
+import math
+
 import numpy as np
 
 from .config import named_config
 from .frontend import random_routes
-from .harness import scene_route, synthetic_batch
+from .harness import Route, scene_route, synthetic_batch
 
 # what the generator adds per configuration (BASELINE.md section 4): config 3 a synthetic circle field, config 4 random moving ellipses
 _GENERATOR_FLAGS = {"cfg3": dict(synthetic_circles=True), "nobs50": dict(synthetic_circles=True),
@@ -84,6 +86,31 @@ def staggered_fleet(cfg, scene=1, planned=3, seed=5, back=(2, 5, 12, 40)):
     return routes, route_of, starts, i0
 
 
+def handmade_route(cfg, waypoints, vertices=()):
+    """-> a ``harness.Route`` through the literal ``waypoints`` [(x, y), ...] (two at least, the first two apart) with the circle centres
+    ``vertices``: the start heading points along the first segment, the end heading is 0.  Routes no planner gives: of a few samples,
+    of one, with many vertices, with none."""
+    w = [(float(x), float(y)) for x, y in waypoints]
+    th0 = math.atan2(w[1][1] - w[0][1], w[1][0] - w[0][0])
+    return Route(cfg, (w[0][0], w[0][1], th0), (w[-1][0], w[-1][1], 0.0), w, [(float(x), float(y)) for x, y in vertices])
+
+
+def tiled_fleet(routes, route_of, starts, idx0, copies):
+    """-> (routes, route_of, starts, idx0) of the fleet repeated: round(m * copies) robots, m = the robots given (``copies`` may be
+    fractional), robot b a copy of base robot b % m.  Without peers the robots of a loop do not depend on each other, so row b of a
+    loop over the tiled fleet is row b % m of a loop over the base fleet."""
+    m = len(starts)
+    rows = np.arange(int(round(m * copies))) % m
+    return list(routes), np.asarray(route_of)[rows].astype(np.int32), np.array(starts, dtype=np.float64)[rows], \
+        np.asarray(idx0)[rows].astype(np.int32)
+
+
+def stale_idx0(idx0, behind):
+    """-> the start indices moved back by ``behind`` samples, clipped at 0: robots whose window search starts that far behind where
+    they stand, so that the closest sample lies deep inside the first window."""
+    return np.maximum(0, np.asarray(idx0) - behind).astype(np.int32)
+
+
 def move_near_goal(routes, route_of, starts, idx0, back):
     """-> (starts, idx0) with robot b, for b < len(back), standing on its route ``back[b]`` samples before the end: robots that
     arrive within a few steps, among the others of a ``random_fleet``."""
@@ -95,9 +122,9 @@ def move_near_goal(routes, route_of, starts, idx0, back):
     return starts, idx0
 
 
-def step_differing(dev, host, solve, dev_step=None):
+def step_differing(dev, host, solve, dev_step=None, rows=None):
     """Step a ``DeviceRecedingHorizon`` (``dev_step(dev)`` if given, else ``dev.step()``) and its host mirror (``solve``: the mirror's
-    solve function) once.
+    solve function) once.  ``rows`` [dev.B]: the device runs a ``tiled_fleet`` of the mirror's, its robot b is the mirror's rows[b].
     -> (names, P, done): the names out of P, U, Y, state, last_u, idx, done, num_inner_iterations, exit_status on which the two are
     not bit-equal ("P" with its first differing columns), the device's parameter vectors and its ``done``.  A retiring pair
     (``retire=True``: the mirror's ``solve`` sees the active rows only) is also compared on retired_at and n_active."""
@@ -109,16 +136,22 @@ def step_differing(dev, host, solve, dev_step=None):
              ("idx", idx, host.idx), ("done", done, host.done)] + [(f, std[f], st[f]) for f in ("num_inner_iterations", "exit_status")]
     if host.active is not None:
         n_active, retired_at = dev.active()
-        pairs += [("retired_at", retired_at, host.retired_at), ("n_active", n_active, host.n_active)]
+        pairs.append(("retired_at", retired_at, host.retired_at))
+    if rows is not None:
+        pairs = [(n, x, y[rows]) for n, x, y in pairs]
+    if host.active is not None:
+        pairs.append(("n_active", n_active, host.n_active if rows is None else int(host.active[rows].sum())))
     names = [n for n, x, y in pairs if not np.array_equal(x, y)]
     if "P" in names:
-        names[0] = f"P at columns {np.unique(np.nonzero(Pd != P)[1])[:10]}"
+        names[0] = f"P at columns {np.unique(np.nonzero(Pd != pairs[0][2])[1])[:10]}"
     return names, Pd, done
 
 
-def trajectory_differing(dev, host, steps):
-    """After ``steps`` steps of both: [] if the device's trajectory is [steps * num_steps_taken + 1, B, 3] and the mirror's bits."""
+def trajectory_differing(dev, host, steps, rows=None):
+    """After ``steps`` steps of both: [] if the device's trajectory is [steps * num_steps_taken + 1, B, 3] and the mirror's bits
+    (``rows`` as in ``step_differing``)."""
     T = dev.trajectory()
     if T.shape != (steps * host.cfg.num_steps_taken + 1, dev.B, 3):
         return [f"trajectory of shape {T.shape}"]
-    return [] if np.array_equal(T, np.stack(host.traj)) else ["trajectory"]
+    Th = np.stack(host.traj)
+    return [] if np.array_equal(T, Th if rows is None else Th[:, rows]) else ["trajectory"]

@@ -1,5 +1,6 @@
 """CPU: workloads.baseline_batch is bench.py's batch, array for array, workloads.differing names what is not the same bits, and the
-fleets of the receding-horizon loop (route_fleet, fleet_ellipses) are reproducible and stay around each robot's own route.
+fleets of the receding-horizon loop (route_fleet, fleet_ellipses) are reproducible and stay around each robot's own route; the
+builders of the loop's edge shapes (handmade_route, tiled_fleet, stale_idx0) keep their contracts.
 
 ``bench_py_batch`` below is bench.py's ``make_batch`` written out once more: bench.py cannot import from here and no pull request edits
 it, so this literal is what ties every probe and GPU test that calls ``baseline_batch`` to the batch the benchmark times.  The same goes
@@ -9,7 +10,8 @@ import pytest
 
 import conftest
 from mpc_trajectory_generator_amd import frontend, harness, named_config
-from mpc_trajectory_generator_amd.workloads import PARITY_FIELDS, baseline_batch, differing, fleet_ellipses, route_fleet
+from mpc_trajectory_generator_amd.workloads import (PARITY_FIELDS, baseline_batch, differing, fleet_ellipses, handmade_route, route_fleet,
+                                                    staggered_fleet, stale_idx0, tiled_fleet)
 from oracle import Oracle
 from oracle.binding import STATUS_DTYPE
 
@@ -160,3 +162,41 @@ def test_fleet_ellipses_stay_around_each_robots_own_route():
     p1, p2, freq, rx, ry, ang = dyn
     assert freq.min() >= 0.05 and freq.max() < 0.1 and min(rx.min(), ry.min()) >= 0.3 and max(rx.max(), ry.max()) < 1.0
     assert ang.min() >= 0 and ang.max() < np.pi
+
+
+def test_handmade_route_is_the_route_of_its_literal_waypoints():
+    cfg = named_config("cfg1")
+    s = harness.SCENES[1]
+    r = handmade_route(cfg, s["waypoints"], s["vertices"])
+    ref = harness.scene_route(cfg, 1)
+    assert (r.x_ref, r.y_ref, r.theta_ref) == (ref.x_ref, ref.y_ref, ref.theta_ref)      # the samples depend on the waypoints alone
+    assert r.vertices == [tuple(map(float, v)) for v in s["vertices"]] and r.waypoints == [tuple(map(float, w)) for w in s["waypoints"]]
+    assert r.start == (1.0, 5.0, np.arctan2(10.5, 3.5)) and r.end == (19.0, 10.0, 0.0)     # heading along the first segment; 0 at the end
+    assert (r.brake_velocities, r.brake_distances, r.base_speed, r.radius) == (ref.brake_velocities, ref.brake_distances, ref.base_speed, ref.radius)
+    bare = handmade_route(cfg, [(2, 2), (2, 3.5)])
+    assert bare.vertices == [] and len(bare.x_ref) == 5 and bare.start[2] == np.pi / 2 and bare.end == (2.0, 3.5, 0.0)
+    assert (bare.x_ref[-1], bare.y_ref[-1]) == (2.0, 3.5)
+    assert len(handmade_route(cfg, [(2, 2), (2.2, 2)]).x_ref) == 1                         # the goal within one sample's travel
+    many = handmade_route(cfg, [(0, 0), (5, 0)], np.zeros((150, 2)))
+    assert len(many.vertices) == 150 and all(isinstance(v, tuple) for v in many.vertices)
+
+
+@pytest.mark.parametrize("copies,B", [(1, 16), (2, 32), (1025 / 16, 1025), (2050 / 16, 2050), (0.5, 8)])
+def test_tiled_fleet_robot_b_is_base_robot_b_mod_m(copies, B):
+    base = staggered_fleet(named_config("cfg1"))
+    routes, route_of, starts, idx0 = tiled_fleet(*base, copies)
+    assert len(routes) == len(base[0]) and all(a is b for a, b in zip(routes, base[0]))
+    assert route_of.shape == (B,) and starts.shape == (B, 3) and idx0.shape == (B,)
+    assert route_of.dtype == np.int32 and idx0.dtype == np.int32 and starts.dtype == np.float64
+    rows = np.arange(B) % 16
+    assert np.array_equal(route_of, base[1][rows]) and np.array_equal(starts, base[2][rows]) and np.array_equal(idx0, base[3][rows])
+    starts[0, 0] += 1.0
+    assert base[2][0, 0] != starts[0, 0]                                                  # a copy, not a view of the base fleet
+
+
+def test_stale_idx0_moves_back_and_clips_at_zero():
+    i0 = np.array([100, 54, 53, 0, 7], dtype=np.int32)
+    out = stale_idx0(i0, 54)
+    assert out.tolist() == [46, 0, 0, 0, 0] and out.dtype == np.int32
+    assert stale_idx0(i0, 0).tolist() == i0.tolist() and i0.tolist() == [100, 54, 53, 0, 7]
+    assert stale_idx0([10, 3], 5).tolist() == [5, 0]
