@@ -272,6 +272,30 @@ int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at);
  * of steps taken, or < 0.  Between steps it waits as nmpc_loop_step does, and does not synchronise after the last.
  * NMPC_ERR_BAD_ARG on a loop without retirement. */
 int nmpc_loop_run(nmpc_loop *l, int max_steps, void *stream);
+/* Clearance monitor: per robot, the closest approach to the static circles, to the scripted ellipses and to the other robots of
+ * its monitor group over everything driven so far, and the trajectory row of each (the rule: DESIGN.md section 5.9).  It observes
+ * only: no p, u, y, state or status differs by a bit from the loop without it.  One more kernel per step, after the advance, over
+ * the robots the step drove (those it retires at its end included); for the s = num_steps_taken rows r the step appends, with the
+ * pose (x, y) of row r and p the robot's parameter vector of this step as the solve read it, in unfused f64:
+ *   circle   sqrt(dx*dx + dy*dy) - rc over the circle slots of p with rc > 0, in metres (negative: inside)
+ *   ellipse  (a*a)/(rx*rx) + (c*c)/(ry*ry), a = dx*cos A + dy*sin A, c = dx*sin A - dy*cos A, over the K scripted slots, at the
+ *            slot's entry for that pose (below 1: inside the padded ellipse, the cost's own quantity); peer and unused slots are not read
+ *   peer2    dx*dx + dy*dy to every other robot j of the group in the same row; a robot retired before the step stands at its state
+ * Each record is the lexicographic minimum of (value, row) -- (value, row, j) for peers -- so among equal values the earlier row,
+ * then the smaller robot index; a comparison that is false (a NaN value) keeps the record.  Initially +inf, row -1, peer -1, which
+ * is what a robot keeps that never meets an obstacle of that kind; a retired robot keeps its record.
+ *   group_of [B]  the monitor's own groups, values in [0, B); NULL = one group of all B.  Independent of nmpc_loop_set_peers.
+ * To be called once, before the loop's first step, on a loop that records its trajectory (max_steps > 0: the step's rows are read
+ * from that table).  NMPC_ERR_BAD_ARG with a message, and nothing changed, for a call after a step, a second call, a group_of[b]
+ * out of range or a loop with max_steps == 0 (a NULL loop: NMPC_ERR_BAD_ARG).  A loop without a monitor enqueues what it enqueued
+ * before this function existed. */
+typedef struct nmpc_clearance {      /* 40 bytes */
+    double circle, ellipse, peer2;
+    int32_t circle_row, ellipse_row, peer_row, peer;
+} nmpc_clearance;
+int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of);
+/* Synchronises, then copies the records out [B]; on a loop without a monitor the initial record everywhere. */
+int nmpc_loop_clearance(nmpc_loop *l, nmpc_clearance *out);
 void nmpc_loop_free(nmpc_loop *l);
 /* Enqueues assemble -> solve -> advance on `stream`; does not synchronise. */
 int nmpc_loop_step(nmpc_loop *l, void *stream);

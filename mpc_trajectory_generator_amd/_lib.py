@@ -23,7 +23,7 @@ SYMBOLS = (
     "nmpc_solve_batch_host", "nmpc_last_batch_ms", "nmpc_set_time_limits", "nmpc_eval_batch_device", "nmpc_eval_batch_host",
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
-    "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run",
+    "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run", "nmpc_loop_set_monitor", "nmpc_loop_clearance",
 )
 
 EXPECTED_ABI = 3      # the nmpc_opts / nmpc_status layouts below are written for this version of include/nmpc_solver.h
@@ -74,6 +74,11 @@ STATUS_DTYPE = np.dtype([("exit_status", "<i4"), ("num_outer_iterations", "<u4")
                          ("f2_norm", "<f8"), ("penalty", "<f8"), ("cost", "<f8"),
                          ("solve_time_ms", "<f8")])
 assert STATUS_DTYPE.itemsize == 72
+
+# nmpc_clearance: a robot's closest approaches and the trajectory rows they happened at (nmpc_loop_set_monitor)
+CLEARANCE_DTYPE = np.dtype([("circle", "<f8"), ("ellipse", "<f8"), ("peer2", "<f8"),
+                            ("circle_row", "<i4"), ("ellipse_row", "<i4"), ("peer_row", "<i4"), ("peer", "<i4")])
+assert CLEARANCE_DTYPE.itemsize == 40
 
 
 def _sources():
@@ -268,6 +273,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_active.restype = C.c_int
     lib.nmpc_loop_run.argtypes = [vp, C.c_int, vp]
     lib.nmpc_loop_run.restype = C.c_int
+    lib.nmpc_loop_set_monitor.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.nmpc_loop_set_monitor.restype = C.c_int
+    lib.nmpc_loop_clearance.argtypes = [vp, vp]
+    lib.nmpc_loop_clearance.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_loop_step.argtypes = [vp, vp]

@@ -608,6 +608,10 @@ struct nmpc_loop {
     PinBuf h_nact;               // one int: the active robots after the last compaction whose event was waited for
     Event ev_nact;               // recorded behind the copy of the count
     bool nact_pending = false;   // a copy is under way: wait for ev_nact before h_nact is read
+    bool monitor = false;        // nmpc_loop_set_monitor: one more kernel per step, after the advance
+    nmpc::MonitorArgs ma{};
+    DevBuf<int> d_mon_group_of, d_mon_goff, d_mon_gmem;
+    DevBuf<nmpc_clearance> d_clear;      // [B]
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -714,6 +718,27 @@ int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *star
     return nmpc_loop_new_routes(h, r, 1, nullptr, B, starts, idx0, K, dyn, max_steps, out);
 }
 
+// member lists of the groups 0 .. B - 1 (most of them empty; group_of NULL: everybody in group 0), each group's robots in ascending
+// index, on the device: group_of [B], goff [B + 1], gmem [B] (PeerArgs)
+static hipError_t upload_groups(const int32_t *group_of, int B, DevBuf<int> &d_gof, DevBuf<int> &d_goff, DevBuf<int> &d_gmem)
+{
+    std::vector<int> gof(B, 0), goff(B + 1, 0), gmem(B);
+    if (group_of) for (int b = 0; b < B; ++b) gof[b] = group_of[b];
+    for (int b = 0; b < B; ++b) goff[gof[b] + 1]++;
+    for (int g = 0; g < B; ++g) goff[g + 1] += goff[g];
+    {
+        std::vector<int> at(goff.begin(), goff.end() - 1);
+        for (int b = 0; b < B; ++b) gmem[at[gof[b]]++] = b;
+    }
+    hipError_t e = d_gof.alloc(B);
+    if (e == hipSuccess) e = d_goff.alloc(B + 1);
+    if (e == hipSuccess) e = d_gmem.alloc(B);
+    if (e == hipSuccess) e = hipMemcpy(d_gof, gof.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_goff, goff.data(), (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_gmem, gmem.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
+    return e;
+}
+
 int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
@@ -728,25 +753,11 @@ int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx,
     for (const double v : {rx, ry, range})
         if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: rx, ry and range must be finite and positive");
     if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: group_of out of range");
-    // member lists: groups 0 .. B - 1 (most of them empty), each group's robots in ascending index
-    std::vector<int> gof(B, 0), goff(B + 1, 0), gmem(B);
-    if (group_of) for (int b = 0; b < B; ++b) gof[b] = group_of[b];
-    for (int b = 0; b < B; ++b) goff[gof[b] + 1]++;
-    for (int g = 0; g < B; ++g) goff[g + 1] += goff[g];
-    {
-        std::vector<int> at(goff.begin(), goff.end() - 1);
-        for (int b = 0; b < B; ++b) gmem[at[gof[b]]++] = b;
-    }
     HIP_TRY(h, hipSetDevice(h->device));
     DevBuf<double> pred;
     DevBuf<int> d_gof, d_goff, d_gmem;
     hipError_t e = pred.alloc((size_t)B * a.N * 3);
-    if (e == hipSuccess) e = d_gof.alloc(B);
-    if (e == hipSuccess) e = d_goff.alloc(B + 1);
-    if (e == hipSuccess) e = d_gmem.alloc(B);
-    if (e == hipSuccess) e = hipMemcpy(d_gof, gof.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_goff, goff.data(), (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_gmem, gmem.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload_groups(group_of, B, d_gof, d_goff, d_gmem);
     if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_peers: allocation", e);
     l->d_pred = std::move(pred); l->d_group_of = std::move(d_gof); l->d_goff = std::move(d_goff); l->d_gmem = std::move(d_gmem);
     nmpc::PeerArgs &p = l->pa;
@@ -807,6 +818,40 @@ int nmpc_loop_set_retire(nmpc_loop *l, int on)
     return NMPC_OK;
 }
 
+static const nmpc_clearance CLEARANCE_NONE = {__builtin_inf(), __builtin_inf(), __builtin_inf(), -1, -1, -1, -1};
+
+int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    const nmpc::LoopArgs &a = l->a;
+    const int B = a.B;
+    if (l->monitor) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: the loop has its monitor already");
+    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: after the loop's first step");
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: the loop records no trajectory (max_steps == 0)");
+    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: group_of out of range");
+    HIP_TRY(h, hipSetDevice(h->device));
+    DevBuf<int> d_gof, d_goff, d_gmem;
+    DevBuf<nmpc_clearance> rec;
+    const std::vector<nmpc_clearance> none(B, CLEARANCE_NONE);
+    hipError_t e = rec.alloc(B);
+    if (e == hipSuccess) e = upload_groups(group_of, B, d_gof, d_goff, d_gmem);
+    if (e == hipSuccess) e = hipMemcpy(rec, none.data(), (size_t)B * sizeof(nmpc_clearance), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_monitor: allocation", e);
+    l->d_clear = std::move(rec); l->d_mon_group_of = std::move(d_gof); l->d_mon_goff = std::move(d_goff); l->d_mon_gmem = std::move(d_gmem);
+    nmpc::MonitorArgs &m = l->ma;
+    m.B = B; m.N = a.N; m.nobs = a.nobs; m.K = a.K; m.n_p = a.n_p; m.s = a.s;
+    m.pcirc = nmpc::NZ + a.N; m.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
+    m.P = l->d_P; m.state = l->d_state; m.traj = l->d_traj;
+    m.retired_at = nullptr;          // the step fills it in: nmpc_loop_set_retire may come after this call
+    m.group_of = l->d_mon_group_of; m.goff = l->d_mon_goff; m.gmem = l->d_mon_gmem;
+    m.rec = l->d_clear;
+    m.act = nullptr;
+    l->monitor = true;
+    return NMPC_OK;
+}
+
 void nmpc_loop_free(nmpc_loop *l)
 {
     if (!l) return;
@@ -831,6 +876,16 @@ static int loop_nactive(nmpc_loop *l, int *n)
     }
     *n = *(const int *)l->h_nact.p;
     return NMPC_OK;
+}
+
+// the monitor's kernel over the n robots the step's advance ran over (LoopArgs::act as the advance saw it; the compaction comes after)
+static void launch_monitor(nmpc_loop *l, int n, hipStream_t s)
+{
+    nmpc::MonitorArgs &m = l->ma;
+    m.traj_row = l->a.traj_row;
+    m.act = l->a.act;
+    m.retired_at = l->retire ? l->d_retired_at.p : nullptr;
+    hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, m);
 }
 
 // one step of a retiring loop: the kernels of nmpc_loop_step over the active list, the solve on gathered rows, then the compaction
@@ -862,6 +917,7 @@ static int loop_step_retiring(nmpc_loop *l, void *stream)
         if (rc) return rc;
         hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, l->ga);
         hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+        if (l->monitor) launch_monitor(l, n, s);
     }
     // (with nobody active the step still counts: the clock advances and the trajectory rows repeat)
     nmpc::RetireArgs &r = l->ra;
@@ -907,6 +963,7 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     h->order_hint = nullptr;
     if (rc) return rc;
     hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, a);
+    if (l->monitor) launch_monitor(l, a.B, s);
     HIP_TRY(h, hipGetLastError());
     a.t += a.s;
     a.traj_row += a.s;
@@ -946,6 +1003,20 @@ int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at)
     }
     if (n_active) HIP_TRY(h, hipMemcpy(n_active, l->d_nact, sizeof(int), hipMemcpyDeviceToHost));
     if (retired_at) HIP_TRY(h, hipMemcpy(retired_at, l->d_retired_at, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+    return NMPC_OK;
+}
+
+int nmpc_loop_clearance(nmpc_loop *l, nmpc_clearance *out)
+{
+    if (!l || !out) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (const int rc = loop_settle(h)) return rc;
+    const int B = l->a.B;
+    if (!l->monitor) {
+        for (int b = 0; b < B; ++b) out[b] = CLEARANCE_NONE;
+        return NMPC_OK;
+    }
+    HIP_TRY(h, hipMemcpy(out, l->d_clear, (size_t)B * sizeof(nmpc_clearance), hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 

@@ -458,4 +458,116 @@ __global__ __launch_bounds__(256) void nmpc_loop_scatter_kernel(PackArgs g)
     if (threadIdx.x == 0) g.st[b] = g.sst[i];
 }
 
+// ---- clearance monitor: each robot's closest approach to circles, scripted ellipses and groupmates (nmpc_loop_set_monitor; the
+// rule is DESIGN.md section 5.9).  It observes: the record is the only thing it writes.
+struct MonitorArgs {
+    int B, N, nobs, K, n_p, s;
+    int pcirc, pdyn;          // where the circle slots and the dynamic block start in p
+    const double *P;          // [B][n_p]: this step's parameter vectors as the solve read them
+    const double *state;      // [B][3]: where a robot retired before this step stands
+    const double *traj;       // the loop's trajectory table
+    int traj_row;             // the first of this step's s rows
+    const int *retired_at;    // [B] as the step found it (the compaction has not run yet), or NULL: nobody retires
+    const int *group_of;      // [B]: the monitor's own groups, lists as in PeerArgs
+    const int *goff;
+    const int *gmem;
+    nmpc_clearance *rec;      // [B]
+    const int *act;           // as in LoopArgs
+};
+
+// (v, r, j) lexicographic minimum over the wave, result in every lane
+__device__ __forceinline__ void wave_argmin3(double &d, int &r, int &j)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double od = __shfl_xor(d, off);
+        const int orow = __shfl_xor(r, off);
+        const int oj = __shfl_xor(j, off);
+        if (od < d || (od == d && (orow < r || (orow == r && oj < j)))) { d = od; r = orow; j = oj; }
+    }
+}
+
+// One wave per robot the step drove, after the advance: the robot's s new poses go to LDS; lanes stride over the (pose, circle slot)
+// and (pose, scripted ellipse) pairs of its p, then over the members of its group, each lane walking the s rows of its member (a
+// robot retired earlier stands at its state: the compaction writes its rows later); every lane keeps its lexicographic minimum, three
+// wave reductions follow, and lane 0 folds them into the record.  A lane that saw nothing holds (inf, INT_MAX): behind every value.
+__global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(MonitorArgs m)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    const int b = m.act ? m.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
+    const int s = m.s, N = m.N, row0 = m.traj_row;
+    const int g = m.group_of[b];
+    const int lo = m.goff[g], hi = m.goff[g + 1];
+    for (int i = lane; i < s; i += 64) {
+        const double *row = m.traj + ((size_t)(row0 + i) * m.B + b) * 3;
+        own[2 * i] = row[0];
+        own[2 * i + 1] = row[1];
+    }
+    __syncthreads();
+    constexpr int NONE = 0x7fffffff;
+    const double *p = m.P + (size_t)b * m.n_p;
+    // ---- static circles: sqrt(dx^2 + dy^2) - r over the slots with r > 0
+    double cv = __builtin_inf();
+    int cr = NONE;
+    {
+        const double *pc = p + m.pcirc;
+        const int tot = s * m.nobs;
+        for (int e = lane; e < tot; e += 64) {
+            const int i = e / m.nobs, c = e - i * m.nobs;
+            const double rc = pc[3 * c + 2];
+            if (rc > 0.0) {
+                const double dx = own[2 * i] - pc[3 * c], dy = own[2 * i + 1] - pc[3 * c + 1];
+                const double v = sqrt(dx * dx + dy * dy) - rc;
+                const int r = row0 + i;
+                if (v < cv || (v == cv && r < cr)) { cv = v; cr = r; }
+            }
+        }
+        wave_argmin(cv, cr);
+    }
+    // ---- scripted ellipses: the cost's level (a/rx)^2 + (c/ry)^2 at entry i of slot k, for the pose after control i
+    double ev = __builtin_inf();
+    int er = NONE;
+    {
+        const double *pd = p + m.pdyn;
+        const int tot = s * m.K;
+        for (int e = lane; e < tot; e += 64) {
+            const int i = e / m.K, k = e - i * m.K;
+            const double *q = pd + ((size_t)k * N + i) * 5;
+            const double dx = own[2 * i] - q[0], dy = own[2 * i + 1] - q[1];
+            double sn, cs;
+            sincos_cw(q[4], sn, cs);
+            const double al = dx * cs + dy * sn, ac = dx * sn - dy * cs;
+            const double v = (al * al) / (q[2] * q[2]) + (ac * ac) / (q[3] * q[3]);
+            const int r = row0 + i;
+            if (v < ev || (v == ev && r < er)) { ev = v; er = r; }
+        }
+        wave_argmin(ev, er);
+    }
+    // ---- groupmates: squared distance between centres, in the same row
+    double pv = __builtin_inf();
+    int pr = NONE, pj = NONE;
+    for (int at = lo + lane; at < hi; at += 64) {
+        const int j = m.gmem[at];
+        if (j == b) continue;
+        const bool parked = m.retired_at && m.retired_at[j] >= 0;
+        for (int i = 0; i < s; ++i) {
+            const double *q = parked ? m.state + 3 * (size_t)j : m.traj + ((size_t)(row0 + i) * m.B + j) * 3;
+            const double dx = own[2 * i] - q[0], dy = own[2 * i + 1] - q[1];
+            const double v = dx * dx + dy * dy;
+            const int r = row0 + i;
+            if (v < pv || (v == pv && (r < pr || (r == pr && j < pj)))) { pv = v; pr = r; pj = j; }
+        }
+    }
+    wave_argmin3(pv, pr, pj);
+    if (lane == 0) {
+        nmpc_clearance c = m.rec[b];
+        if (cv < c.circle || (cv == c.circle && cr < c.circle_row)) { c.circle = cv; c.circle_row = cr; }
+        if (ev < c.ellipse || (ev == c.ellipse && er < c.ellipse_row)) { c.ellipse = ev; c.ellipse_row = er; }
+        if (pv < c.peer2 || (pv == c.peer2 && (pr < c.peer_row || (pr == c.peer_row && pj < c.peer)))) {
+            c.peer2 = pv; c.peer_row = pr; c.peer = pj;
+        }
+        m.rec[b] = c;
+    }
+}
+
 }  // namespace nmpc

@@ -428,6 +428,32 @@ class Peers:
         return g
 
 
+@dataclasses.dataclass(frozen=True)
+class Monitor:
+    """The clearance monitor, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon`` alike: per robot,
+    the closest approach to the static circles, to the scripted ellipses and to the other robots of its monitor group over the
+    poses driven so far, and the trajectory row of each (``clearance``, a ``_lib.CLEARANCE_DTYPE`` array [B]).  It observes only.
+    ``group_of`` [B] = the monitor group of each robot, values in [0, B) (``None``: one group of all B), whatever ``Peers`` says."""
+    group_of: object = None
+
+    def checked(self, B: int):
+        """-> group_of as an int32 array or None; ValueError for what ``nmpc_loop_set_monitor`` refuses."""
+        if self.group_of is None:
+            return None
+        g = np.ascontiguousarray(self.group_of, dtype=np.int32).reshape(B)
+        if ((g < 0) | (g >= B)).any():
+            raise ValueError("monitor: group_of out of range")
+        return g
+
+
+def no_clearance(B: int):
+    """-> the initial records [B]: +inf, row -1, peer -1."""
+    rec = np.empty(B, dtype=_lib.CLEARANCE_DTYPE)
+    rec["circle"] = rec["ellipse"] = rec["peer2"] = np.inf
+    rec["circle_row"] = rec["ellipse_row"] = rec["peer_row"] = rec["peer"] = -1
+    return rec
+
+
 class FleetRecedingHorizon(_HostLoop):
     """``VectorizedRecedingHorizon`` for a fleet on R routes: robot b follows ``routes[route_of[b]]``.
 
@@ -446,9 +472,14 @@ class FleetRecedingHorizon(_HostLoop):
     is not assembled, solved or advanced again, keeps every value of its last step (``done`` stays True, its trajectory rows repeat
     its final pose), and ``retired_at[b]`` = the steps (solves) it took, -1 while it is active.  For peers it is a parked obstacle:
     predicted at its state at every stage, a candidate for the others, given no peers itself.  ``step`` solves the active rows only.
+
+    ``monitor`` (a ``Monitor``): ``clearance`` [B] holds every robot's closest approaches, updated by
+    ``advance`` from the rows it appends to ``traj`` and the parameter vectors ``assemble`` returned for this step, for the robots
+    the step drove.  Nothing else reads it.
     """
 
-    def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False):
+    def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
+                 monitor=None):
         self.routes = list(routes)
         cfg = self.cfg = self.routes[0].cfg
         self.B = B = len(starts)
@@ -481,6 +512,12 @@ class FleetRecedingHorizon(_HostLoop):
             self.retired_at = np.full(B, -1, dtype=np.int32)
             self.P = np.zeros((B, cfg.n_p))                                   # a retired robot's row: of its last step
             self.status = None                                                # [B], made by the first solve (its dtype is the solver's)
+        self.monitor = monitor
+        if monitor is not None:
+            g = monitor.checked(B)
+            g = np.zeros(B, dtype=np.int32) if g is None else g
+            self.monitor_groups = [np.nonzero(g == v)[0] for v in np.unique(g)]   # members in ascending robot index
+            self.clearance = no_clearance(B)
 
     @property
     def n_active(self):
@@ -534,6 +571,7 @@ class FleetRecedingHorizon(_HostLoop):
                 P[ids[act[ids]]] = sub.assemble(act[ids])[act[ids]]
         if self.peers is not None:
             self._overlay_peers(P)
+        self._P_step = P                                                     # what this step's solve reads: the monitor's p
         return P
 
     def predict(self):
@@ -595,8 +633,67 @@ class FleetRecedingHorizon(_HostLoop):
     def advance(self, U):
         for ids, sub in self.parts:
             sub.advance(U[ids], None if self.active is None else self.active[ids])
+        if self.monitor is not None:
+            self._monitor_update()
         self.t += self.cfg.num_steps_taken
         self.steps += 1
+
+    def _monitor_update(self):
+        """The monitor's rule on the s rows this step appended, for the robots it drove (``active`` as the
+        step found it: ``retire`` comes after).  The rows ascend, so inside a step a strictly smaller value is the only way to win;
+        within a row the first minimum over the group's members, who are in ascending index, is the smallest robot index."""
+        cfg, rec, P = self.cfg, self.clearance, self._P_step
+        B, N, s, K = self.B, cfg.N_hor, cfg.num_steps_taken, self.K
+        drove = np.ones(B, dtype=bool) if self.active is None else self.active
+        if not drove.any():
+            return
+        pcirc = 20 + N
+        pdyn = pcirc + cfg.nobs * cfg.Nobs
+        circ = P[:, pcirc:pdyn].reshape(B, cfg.Nobs, cfg.nobs)
+        dyn = P[:, pdyn:pdyn + cfg.Ndynobs * N * cfg.ndynobs].reshape(B, cfg.Ndynobs, N, cfg.ndynobs)
+
+        def lowest(v, seen):
+            """-> per robot the smallest value among the seen ones that are not NaN, +inf without any"""
+            return np.where(seen & ~np.isnan(v), v, np.inf).min(axis=1, initial=np.inf)
+
+        def take(better, value, row, fields):
+            better = better & drove
+            rec[fields[0]][better] = value[better]
+            rec[fields[1]][better] = row
+
+        for i in range(s):
+            r = self.steps * s + 1 + i
+            pose = np.empty((B, 3))
+            for ids, sub in self.parts:
+                pose[ids] = sub.traj[len(sub.traj) - s + i]
+            x, y = pose[:, 0], pose[:, 1]
+            dx, dy = x[:, None] - circ[..., 0], y[:, None] - circ[..., 1]
+            v = lowest(np.sqrt(dx * dx + dy * dy) - circ[..., 2], circ[..., 2] > 0)
+            take(v < rec["circle"], v, r, ("circle", "circle_row"))
+            if K:
+                e = dyn[:, :K, i, :]
+                dx, dy = x[:, None] - e[..., 0], y[:, None] - e[..., 1]
+                sn, cs = self.sincos(np.ascontiguousarray(e[..., 4]))
+                a, c = dx * cs + dy * sn, dx * sn - dy * cs
+                v = lowest((a * a) / (e[..., 2] * e[..., 2]) + (c * c) / (e[..., 3] * e[..., 3]), np.ones((B, K), dtype=bool))
+                take(v < rec["ellipse"], v, r, ("ellipse", "ellipse_row"))
+            for mem in self.monitor_groups:
+                G = len(mem)
+                if G < 2:
+                    continue
+                gx, gy = x[mem], y[mem]
+                rows = max(1, (1 << 22) // G)                                # robots of the group per pass: bounds the [rows, G] tables
+                for r0 in range(0, G, rows):
+                    me = np.arange(r0, min(G, r0 + rows))
+                    dx, dy = gx[me, None] - gx[None, :], gy[me, None] - gy[None, :]
+                    d = dx * dx + dy * dy
+                    d = np.where(np.isnan(d), np.inf, d)
+                    d[np.arange(len(me)), me] = np.inf                       # not oneself
+                    j = np.argmin(d, axis=1)
+                    v = d[np.arange(len(me)), j]
+                    better = (v < rec["peer2"][mem[me]]) & drove[mem[me]]
+                    b = mem[me[better]]
+                    rec["peer2"][b], rec["peer_row"][b], rec["peer"][b] = v[better], r, mem[j[better]]
 
 
 def _fill_route(r, route: harness.Route, keep: list):
@@ -645,6 +742,11 @@ class DeviceRecedingHorizon:
     kernels per step, between the assembly and the solve.  Its host mirror is ``FleetRecedingHorizon`` with the same ``peers``
     (tests/test_gpu_peers_loop.py).
 
+    ``monitor`` (a ``Monitor``, needs ``max_steps`` > 0): every robot's closest approach to circles, scripted ellipses and the robots
+    of its monitor group is kept on the device (``nmpc_loop_set_monitor``), one more kernel per step after the
+    advance; ``clearance()`` reads the records.  Its host mirror is ``FleetRecedingHorizon`` with the same ``monitor``
+    (tests/test_gpu_monitor_loop.py).
+
     ``retire=True``: robots that reach their goal leave the loop (``nmpc_loop_set_retire``); every step solves
     the active robots only, ``active()`` tells who is left and ``run(max_steps)`` steps until nobody is.  ``step`` then waits for the
     step before to have counted its active robots (an event, not the device).  Its host mirror is ``FleetRecedingHorizon`` with
@@ -652,7 +754,7 @@ class DeviceRecedingHorizon:
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None, retire=False):
+                 route_of=None, peers=None, retire=False, monitor=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -705,6 +807,13 @@ class DeviceRecedingHorizon:
             if rc:
                 self.close()
                 solver._check(rc)
+        self.monitor = monitor
+        if monitor is not None:
+            g = None if monitor.group_of is None else np.ascontiguousarray(monitor.group_of, dtype=np.int32).reshape(B)
+            rc = self.lib.nmpc_loop_set_monitor(h, _lib.as_i32p(g))
+            if rc:
+                self.close()
+                solver._check(rc)
 
     def close(self):
         if getattr(self, "_l", None):
@@ -738,6 +847,13 @@ class DeviceRecedingHorizon:
         n, at = C.c_int32(), np.empty(self.B, dtype=np.int32)
         self.solver._check(self.lib.nmpc_loop_active(self._l, C.byref(n), _lib.as_i32p(at)))
         return n.value, at
+
+    def clearance(self):
+        """-> the monitor's records [B] (``_lib.CLEARANCE_DTYPE``: circle, ellipse, peer2, circle_row, ellipse_row, peer_row, peer)
+        after synchronising; without a ``monitor`` the initial record everywhere."""
+        rec = np.empty(self.B, dtype=_lib.CLEARANCE_DTYPE)
+        self.solver._check(self.lib.nmpc_loop_clearance(self._l, rec.ctypes.data))
+        return rec
 
     def read(self):
         """-> (state [B,3], last_u [B,2], idx [B], done [B] bool, status [B]) after synchronising."""

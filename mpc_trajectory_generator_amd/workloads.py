@@ -147,6 +147,15 @@ def step_differing(dev, host, solve, dev_step=None, rows=None):
     return names, Pd, done
 
 
+def clearance_differing(dev, host):
+    """The fields of the clearance records (``dev``: a ``DeviceRecedingHorizon`` with a monitor or its ``clearance()``, ``host``: its
+    mirror or the mirror's ``clearance``) that are not bit-equal; a value compares by its bytes, so -0.0 is not 0.0 and a NaN equals
+    itself."""
+    a = dev.clearance() if callable(getattr(dev, "clearance", None)) else dev
+    b = getattr(host, "clearance", host)
+    return [f for f in a.dtype.names if a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes() or a[f].shape != b[f].shape]
+
+
 def trajectory_differing(dev, host, steps, rows=None):
     """After ``steps`` steps of both: [] if the device's trajectory is [steps * num_steps_taken + 1, B, 3] and the mirror's bits
     (``rows`` as in ``step_differing``)."""

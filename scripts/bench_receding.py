@@ -7,7 +7,9 @@ planned between random start / goal points of the scene (frontend.random_fleet).
 other in groups of G consecutive robots; --peer-slots of the Ndynobs ellipse slots go to peers, the
 rest stay scripted.  --retire: robots that reach their goal leave the loop (nmpc_loop_set_retire); the run ends when nobody is
 active or after --steps steps, and reports the steps and solves it took.  --back: how close to the route's end robots may start
-(--routes 1); a small value gives a fleet whose robots arrive all through the run.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+(--routes 1); a small value gives a fleet whose robots arrive all through the run.  --monitor [G]: the clearance monitor (nmpc_loop_set_monitor,
+DESIGN.md section 5.9) in groups of G consecutive robots, default the --peers groups or 32; the result line then has, from its records, the shares
+of robots that were inside a circle, inside a padded ellipse and closer to a groupmate than two peer radii, and the fleet's smallest value of each.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -19,7 +21,7 @@ sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config                            # noqa: E402
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
-from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, Peers, VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
 from mpc_trajectory_generator_amd.workloads import moving_ellipses, route_fleet   # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -42,9 +44,18 @@ ap.add_argument("--peer-slots", type=int, default=2, help="with --peers: ellipse
 ap.add_argument("--peer-range", type=float, default=10.0, help="with --peers: how far a robot sees, in metres")
 ap.add_argument("--retire", action="store_true",
                 help="device loop only: retire the robots that reach their goal; run until nobody is active, --steps at the most")
+ap.add_argument("--monitor", type=int, nargs="?", const=0, default=None, metavar="G",
+                help="device loop only: keep every robot's closest approach to circles, scripted ellipses and the robots of its group of G "
+                     "consecutive robots (of a sub-fleet) on the device, and report them; G defaults to the --peers groups, or 32")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
+if args.monitor is not None:
+    if args.host or args.steps < 1:
+        ap.error("--monitor reads the trajectory the device loop records: it needs the device loop (no --host) and --steps >= 1")
+    if args.monitor < 0:
+        ap.error("--monitor G: G >= 1")
+    args.monitor = args.monitor or args.peers or 32
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
@@ -59,6 +70,11 @@ def peers_of(n):
     """groups of --peers consecutive robots among n"""
     return Peers(slots=args.peer_slots, rx=peer_radius, ry=peer_radius, range=args.peer_range,
                  group_of=(np.arange(n) // args.peers).astype(np.int32)) if args.peers else None
+
+
+def monitor_of(n):
+    """groups of --monitor consecutive robots among n"""
+    return Monitor(group_of=(np.arange(n) // args.monitor).astype(np.int32)) if args.monitor else None
 
 
 if args.routes == 1:
@@ -89,7 +105,7 @@ if not args.host:
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
         loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
-                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids)), retire=args.retire))
+                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids))))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -115,6 +131,15 @@ if not args.host:
         solves = int(sum(np.where(at < 0, rh.steps, at).sum() for rh in loops for at in [rh.active()[1]])) - B
     done = np.concatenate([o[3] for o in outs])
     st = np.concatenate([o[4] for o in outs])
+    quality = {}
+    if args.monitor:
+        rec = np.concatenate([rh.clearance() for rh in loops])
+        quality = {"clearance": {
+            "groups_of": args.monitor, "inside_circle_frac": float((rec["circle"] < 0).mean()),
+            "inside_ellipse_frac": float((rec["ellipse"] < 1).mean()),
+            "closer_than_two_peer_radii_frac": float((rec["peer2"] < (2 * peer_radius) ** 2).mean()), "two_peer_radii_m": 2 * peer_radius,
+            "min_circle_m": float(rec["circle"].min()), "min_ellipse_level": float(rec["ellipse"].min()),
+            "min_peer_m": float(np.sqrt(rec["peer2"].min()))}}
     from mpc_trajectory_generator_amd import _lib
     if hasattr(_lib.load_library(), "nmpc_debug_win_stats"):        # instrumented build (-DNMPC_WIN_STATS, scripts/win_stats.py)
         buf = (ctypes.c_ulonglong * 2)()
@@ -126,6 +151,7 @@ if not args.host:
                                "num_steps_taken=2, warm start (u, y carried; c reset), loop entirely on device"
                                + (f", robots start up to {args.back} samples before the route's end" if args.back != 60 else "")
                                + (", robots retire at their goals" if args.retire else "")
+                               + (f", clearance monitor in groups of {args.monitor}" if args.monitor else "")
                                + (f", at most {args.budget} PANOC iterations per solve (NotConvergedOutOfTime beyond)" if args.budget else "")
                                + (f", fleet split into {args.split} sub-fleets on {args.split} streams" if args.split > 1 else ""),
                    "kernel": solver.kernel_name},
@@ -133,7 +159,7 @@ if not args.host:
         "ms_per_step": 1e3 * total / max(steps - 1, 1), "mean_inner_iters_first_step": float(st0["num_inner_iterations"].mean()),
         "mean_inner_iters_last_step": float(st["num_inner_iterations"].mean()),
         "converged_frac_last_step": float((st["exit_status"] == 0).mean()),
-        "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum())}))
+        "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum()), **quality}))
     sys.exit(0)
 if route_of is None and not args.peers:
     rh = VectorizedRecedingHorizon(routes, starts, dyn, idx0=i0)

@@ -1,0 +1,215 @@
+"""GPU: the clearance monitor of the on-device loop (nmpc_loop_set_monitor, nmpc_loop_clearance, ``nmpc_loop_monitor_kernel``;
+DESIGN.md section 5.9) against its host mirror ``FleetRecedingHorizon(..., monitor=...)`` -- itself pinned to the literal rule by
+tests/test_monitor_mirror.py -- driven by the oracle and given the kernels' sin / cos.  After EVERY step the loop's arrays
+(``step_differing``) and the seven fields of every robot's record (``clearance_differing``) must be the mirror's bits: the record is
+cumulative, so a late check could hide an early wrong row.  The trajectories are compared at the end.
+
+What each case makes the kernel do:
+
+* ``cfg1-three-routes``: circles only (K = 0), one group of 12, nobody retires.
+* ``cfg4-ellipses-retire``: K = 3 scripted ellipses with the sinusoidal law, a robot that retires in the step that still updates it
+  and is parked from then on.
+* ``staggered-peers``: peer overlay slots in p (not read), groups = routes, retirement; parked robots are read from ``state`` while the
+  compaction has not yet written their rows, and records are made against them (asserted on the mirror).
+* ``group130``: lanes of the member loop take a third member (130 > 2 * 64) and the (value, row, robot) reduction picks across
+  strides; beside it a group of one, whose loop is empty.
+* ``cfg2`` / ``cfg2-s3``: N_hor = 40 with one step taken per solve, which is cfg 2's own setting, and the same fleet with three
+  (``load_config`` overrides), so that s = 1 and s > 1 both run at the long horizon (cfg 1 takes one step, cfg 4 two).
+* ``moving-circle-window``: 150 vertices against 10 circle slots, the window moves with the robot; ``no-vertices``: every radius 0.
+* ``one-robot``: B = 1, alone in its group."""
+import numpy as np
+import pytest
+
+from conftest import oracle_for
+from mpc_trajectory_generator_amd import frontend, harness, named_config
+from mpc_trajectory_generator_amd.config import JCONF_3, load_config
+from mpc_trajectory_generator_amd.workloads import (clearance_differing, staggered_fleet, step_differing, trajectory_differing)
+from test_loop_shapes_mirror import CASES, large_group_fleet
+from test_monitor_mirror import near_goal_cfg4_fleet
+from test_retire_mirror import PEERS
+
+pytestmark = pytest.mark.gpu
+
+
+def _fleet(which):
+    """-> dict(cfg, routes, route_of, starts, idx0, dyn, sinus, peers, retire, groups, steps)"""
+    from mpc_trajectory_generator_amd.trajectory import Peers
+    base = dict(dyn=None, sinus=False, peers=None, retire=False, groups=None)
+    if which == "cfg1-three-routes":
+        cfg = named_config("cfg1")
+        routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 3, 12, seed=5)
+        return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, steps=8)}
+    if which == "cfg4-ellipses-retire":
+        cfg, routes, route_of, starts, i0, dyn = near_goal_cfg4_fleet()
+        return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, dyn=dyn, sinus=True, retire=True, steps=10)}
+    if which == "staggered-peers":
+        cfg = named_config("cfg1")
+        routes, route_of, starts, i0 = staggered_fleet(cfg)
+        return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, peers=Peers(group_of=route_of, **PEERS),
+                               retire=True, groups=route_of, steps=14)}
+    if which == "group130":
+        cfg, routes, route_of, starts, i0, _ = large_group_fleet()
+        groups = np.full(131, 77, dtype=np.int32)
+        groups[40] = 3                                             # one robot alone, in the middle of the others' member list
+        route_of, starts, i0 = route_of[:131].copy(), starts[:131].copy(), i0[:131].copy()
+        # the group's last member (position 129: lane 1's third member) starts 1 cm beside robot 5, on its route
+        route_of[130], starts[130], i0[130] = route_of[5], starts[5] + [0.01, 0.0, 0.0], i0[5]
+        return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, groups=groups, steps=4)}
+    if which in ("cfg2", "cfg2-s3"):
+        cfg = named_config("cfg2") if which == "cfg2" else load_config(**{**JCONF_3, "N_hor": 40, "num_steps_taken": 3})
+        assert cfg.N_hor == 40 and cfg.num_steps_taken == (1 if which == "cfg2" else 3)
+        routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 2, 8, seed=13)
+        return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, steps=6)}
+    if which in ("moving-circle-window", "no-vertices"):
+        c = CASES["verts150-nobs10" if which == "moving-circle-window" else "no-vertices"]()
+        assert (len(c.route.vertices) > c.cfg.Nobs) if which == "moving-circle-window" else len(c.route.vertices) == 0
+        return {**base, **dict(cfg=c.cfg, routes=[c.route], route_of=np.zeros(len(c.starts), dtype=np.int32), starts=c.starts, idx0=c.idx0,
+                               dyn=c.dyn, sinus=c.sinus, steps=4)}
+    if which == "one-robot":
+        cfg = named_config("cfg4")
+        routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 1, 1, seed=9)
+        from mpc_trajectory_generator_amd.workloads import fleet_ellipses
+        return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, dyn=fleet_ellipses(routes, route_of, i0, 2, 4),
+                               steps=5)}
+    raise KeyError(which)
+
+
+FLEETS = ["cfg1-three-routes", "cfg4-ellipses-retire", "staggered-peers", "group130", "cfg2", "cfg2-s3", "moving-circle-window",
+          "no-vertices", "one-robot"]
+
+
+@pytest.mark.parametrize("which", FLEETS)
+def test_monitored_loop_equals_host_mirror(which):
+    from mpc_trajectory_generator_amd.solver import BatchSolver
+    from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon, FleetRecedingHorizon, Monitor, no_clearance
+    f = _fleet(which)
+    cfg, B = f["cfg"], len(f["starts"])
+    o = oracle_for(cfg)
+    monitor = Monitor(group_of=f["groups"])
+    common = dict(idx0=f["idx0"], sinus_object=f["sinus"], peers=f["peers"], retire=f["retire"], monitor=monitor)
+    s = BatchSolver(cfg, max_batch=B)
+    try:
+        dev = DeviceRecedingHorizon(s, f["routes"], f["starts"], f["dyn"], max_steps=f["steps"], route_of=f["route_of"], **common)
+        host = FleetRecedingHorizon(f["routes"], f["route_of"], f["starts"], f["dyn"], sincos=o.sincos_array, **common)
+        assert not clearance_differing(dev, no_clearance(B))           # before the first step: the initial record
+        moved, parked_seen = 0, False
+        for k in range(f["steps"]):
+            before = host.clearance.copy()
+            retired = None if host.active is None else ~host.active
+            bad = step_differing(dev, host, o.warm_solve(threads=16))[0] + clearance_differing(dev, host)
+            assert not bad, f"step {k}: {bad}"
+            moved += int((host.clearance != before).sum())
+            if retired is not None and retired.any():
+                assert (host.clearance[retired] == before[retired]).all(), f"step {k}: a retired robot's record moved"
+                new = host.clearance["peer_row"] > k * cfg.num_steps_taken
+                parked_seen |= bool(np.isin(host.clearance["peer"][new], np.nonzero(retired)[0]).any())
+        assert not trajectory_differing(dev, host, f["steps"])
+        rec = host.clearance
+        dev.close()
+    finally:
+        s.close()
+    print(which, "records changed", moved, "times; smallest circle", rec["circle"].min(), "ellipse", rec["ellipse"].min(),
+          "peer", np.sqrt(rec["peer2"].min()))
+    assert moved > 0
+    # the kinds the fleet has were seen, the others kept the initial record
+    K = 0 if f["dyn"] is None else f["dyn"][0].shape[1]
+    g = np.zeros(B, dtype=np.int64) if f["groups"] is None else np.asarray(f["groups"])
+    alone = np.bincount(g, minlength=B)[g] == 1
+    assert (np.isfinite(rec["ellipse"]) == (K > 0)).all() and ((rec["ellipse_row"] >= 1) == (K > 0)).all()
+    assert (np.isfinite(rec["peer2"]) == ~alone).all() and ((rec["peer"] >= 0) == ~alone).all()
+    # a planned route may have no bend; with more vertices than slots the reference's window [closest, Nobs) is empty far along the route
+    nv = np.array([len(f["routes"][r].vertices) for r in f["route_of"]])
+    never, always = (nv == 0) | (cfg.Nobs == 0), (nv > 0) & (nv <= cfg.Nobs)
+    seen = np.isfinite(rec["circle"])
+    assert (seen == (rec["circle_row"] >= 1)).all() and not seen[never].any() and seen[always].all()
+    assert seen.any() == (which != "no-vertices")
+    if which in ("cfg4-ellipses-retire", "staggered-peers"):
+        assert (host.retired_at >= 0).any() and host.n_active > 0, "no step with some robots retired and others active"
+    if which == "staggered-peers":
+        assert parked_seen, "no record was made against a parked robot"
+    if which == "group130":
+        mem = np.nonzero(g == 77)[0]
+        assert len(mem) == 130 and mem[129] == 130 and rec["peer"][5] == 130, "robot 5's record does not name the member a lane reaches in its third stride"
+
+
+def test_monitored_loop_is_the_unmonitored_loop():
+    """A monitored and an unmonitored device loop over one fleet (scripted ellipses, peers and retirement on): p, u, y, state,
+    last_u, idx, done, the status counters and the trajectory are equal at every step."""
+    from mpc_trajectory_generator_amd.solver import BatchSolver
+    from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon, Monitor, Peers
+    cfg, routes, route_of, starts, i0, dyn = near_goal_cfg4_fleet(K=2)
+    steps = 8
+    peers = Peers(slots=1, rx=0.37, ry=0.53, range=5.0)
+    s1, s2 = BatchSolver(cfg, max_batch=16), BatchSolver(cfg, max_batch=16)
+    try:
+        a, b = (DeviceRecedingHorizon(s, routes, starts, dyn, max_steps=steps, idx0=i0, route_of=route_of, peers=peers, retire=True, monitor=m)
+                for s, m in ((s1, Monitor(group_of=route_of)), (s2, None)))
+        for k in range(steps):
+            a.step()
+            b.step()
+            for x, y in zip(a.params() + a.read()[:4], b.params() + b.read()[:4]):
+                assert np.array_equal(x, y), f"step {k}"
+            sa, sb = a.read()[4], b.read()[4]
+            for f in ("exit_status", "num_inner_iterations", "num_outer_iterations", "num_cost_evals", "num_grad_evals", "cost", "penalty"):
+                assert np.array_equal(sa[f], sb[f]), (k, f)
+            assert np.array_equal(a.active()[1], b.active()[1])
+            assert np.array_equal(a.trajectory(), b.trajectory()), f"step {k}"
+        assert np.isfinite(a.clearance()["peer2"]).all()
+        from mpc_trajectory_generator_amd.trajectory import no_clearance
+        assert not clearance_differing(b, no_clearance(len(starts)))       # without a monitor: the initial record everywhere
+        a.close()
+        b.close()
+    finally:
+        s1.close()
+        s2.close()
+
+
+def test_monitor_arguments_validated():
+    """A NULL loop, a call after a step, a second call, a group_of out of range and a loop that records no trajectory:
+    NMPC_ERR_BAD_ARG (with a message wherever there is a handle to carry one) and nothing changed -- the loop still steps, a refused
+    loop reports the initial record, and the handle then solves a batch exactly like the oracle."""
+    from mpc_trajectory_generator_amd import _lib
+    from mpc_trajectory_generator_amd.solver import BatchSolver
+    from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon, Monitor, no_clearance
+    cfg = named_config("cfg1")
+    routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 3, 8, seed=2)
+    s = BatchSolver(cfg, max_batch=16)
+    lib = s.lib
+
+    def refused(loop, g=None):
+        rc = lib.nmpc_loop_set_monitor(loop._l, _lib.as_i32p(None if g is None else np.ascontiguousarray(g, dtype=np.int32)))
+        msg = lib.nmpc_last_error(s._h).decode()
+        assert rc == -3 and msg and "nmpc_loop_set_monitor" in msg, (rc, msg)
+        return msg
+
+    try:
+        assert lib.nmpc_loop_set_monitor(None, None) == -3
+        a = DeviceRecedingHorizon(s, routes, starts, None, max_steps=4, idx0=i0, route_of=route_of)
+        for g in ([0, 1, 2, 3, 4, 5, 6, 8], [0, 0, 0, -1, 0, 0, 0, 0]):
+            assert "group_of" in refused(a, g)
+        a.step()
+        assert "step" in refused(a)
+        a.step()
+        assert not clearance_differing(a, no_clearance(8))
+        a.close()
+        b = DeviceRecedingHorizon(s, routes, starts, None, idx0=i0, route_of=route_of)             # max_steps = 0
+        assert "trajectory" in refused(b)
+        b.step()
+        assert not clearance_differing(b, no_clearance(8))
+        b.close()
+        with pytest.raises(Exception):
+            DeviceRecedingHorizon(s, routes, starts, None, idx0=i0, route_of=route_of, monitor=Monitor())
+        c = DeviceRecedingHorizon(s, routes, starts, None, max_steps=4, idx0=i0, route_of=route_of, monitor=Monitor(group_of=[7] * 8))
+        assert "already" in refused(c)
+        c.step()
+        c.step()
+        rec = c.clearance()
+        assert np.isfinite(rec["peer2"]).all() and np.isfinite(rec["circle"]).all() and (rec["peer_row"] >= 1).all()
+        c.close()
+        P = harness.synthetic_batch(cfg, 11, 8, 77)
+        u, y, st = s.solve(P)
+        uo, yo, sto = oracle_for(cfg).solve_batch(P, threads=8)
+        assert np.array_equal(u, uo) and np.array_equal(y, yo)
+        assert np.array_equal(st["num_inner_iterations"], sto["num_inner_iterations"])
+    finally:
+        s.close()
