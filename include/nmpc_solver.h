@@ -272,6 +272,29 @@ int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at);
  * of steps taken, or < 0.  Between steps it waits as nmpc_loop_step does, and does not synchronise after the last.
  * NMPC_ERR_BAD_ARG on a loop without retirement. */
 int nmpc_loop_run(nmpc_loop *l, int max_steps, void *stream);
+/* Missions: a robot drives a sequence of routes, leg after leg, as the reference's user calls `PathGenerator.run(graph, start, end)`
+ * again from where the robot stands (src/main.py:23, src/path_generator.py:197-290).  Off unless asked for here; a loop without
+ * missions enqueues what it enqueued before this function existed.  Robot b's legs are the routes leg_route[leg_off[b] ..
+ * leg_off[b + 1]), indices into the R routes of the loop, the first one the route_of[b] it was created with.  With missions, one
+ * more kernel per step, after the advance (and the monitor) and before the active list is rebuilt: an active robot whose terminal
+ * test holds against the goal of its current route ends that leg at this step (leg_at = the loop's step count, this step included).
+ * If it has another leg it is re-dispatched in the same step and stays active: leg + 1, route_of = that leg's route, idx = 0,
+ * last_u = (0, 0), every entry of its u and y +0.0, done = 0; its state, carried dynamic block, p, status and clearance record are
+ * not touched.  The next step therefore treats it as `run()` called anew from its pose: window search from sample 0 of the new
+ * route, that route's circles, goal, weights, base speed, radius and braking tables, no previous control in p, a cold solve.  After
+ * its last leg it is retired as nmpc_loop_set_retire describes, retired_at equal to that leg's leg_at.  Every leg is solved at
+ * least once.  One deviation from the reference: the loop's clock and the carried dynamic block run on across legs (the scripted
+ * ellipses belong to the world, not to a leg); with K == 0 a mission equals, bit for bit, its legs driven one after another.
+ *   leg_off   [B + 1]         ascending from 0, every robot has at least one leg
+ *   leg_route [leg_off[B]]    values in [0, R), leg_route[leg_off[b]] == route_of[b]
+ * To be called once, after nmpc_loop_set_retire(l, 1) and before the loop's first step.  NMPC_ERR_BAD_ARG with a message, and
+ * nothing changed, for a NULL argument, a loop that does not retire, a call after a step, a second call, leg_off[0] != 0, a robot
+ * with no leg, a leg_route entry outside [0, R), or a first leg that is not the robot's route_of. */
+int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *leg_route);
+/* Synchronises, then copies what is asked for (NULL = skip): leg [B] the leg each robot is on, route_of [B] its current route,
+ * leg_at [leg_off[B]] the steps at which each leg ended (-1: not yet).  A loop without missions reports leg = 0 and the route_of of
+ * its creation, and writes no leg_at. */
+int nmpc_loop_legs(nmpc_loop *l, int32_t *leg, int32_t *route_of, int32_t *leg_at);
 /* Clearance monitor: per robot, the closest approach to the static circles, to the scripted ellipses and to the other robots of
  * its monitor group over everything driven so far, and the trajectory row of each (the rule: DESIGN.md section 5.9).  It observes
  * only: no p, u, y, state or status differs by a bit from the loop without it.  One more kernel per step, after the advance, over

@@ -24,6 +24,7 @@ SYMBOLS = (
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
     "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run", "nmpc_loop_set_monitor", "nmpc_loop_clearance",
+    "nmpc_loop_set_missions", "nmpc_loop_legs",
 )
 
 EXPECTED_ABI = 3      # the nmpc_opts / nmpc_status layouts below are written for this version of include/nmpc_solver.h
@@ -277,6 +278,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_monitor.restype = C.c_int
     lib.nmpc_loop_clearance.argtypes = [vp, vp]
     lib.nmpc_loop_clearance.restype = C.c_int
+    lib.nmpc_loop_set_missions.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.nmpc_loop_set_missions.restype = C.c_int
+    lib.nmpc_loop_legs.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.nmpc_loop_legs.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_loop_step.argtypes = [vp, vp]

@@ -612,6 +612,13 @@ struct nmpc_loop {
     nmpc::MonitorArgs ma{};
     DevBuf<int> d_mon_group_of, d_mon_goff, d_mon_gmem;
     DevBuf<nmpc_clearance> d_clear;      // [B]
+    // nmpc_loop_set_missions: a robot at its goal takes up the next route of its mission; one more kernel per step, before the compaction
+    bool missions = false;
+    int R = 1;
+    std::vector<int> h_route_of;         // [B] as given at creation
+    nmpc::DispatchArgs da{};
+    DevBuf<int> d_leg_off, d_leg_route, d_leg, d_leg_at;
+    int n_legs = 0;                      // leg_off[B]
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -644,6 +651,7 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
     nmpc_loop *l = new nmpc_loop();
     l->h = h;
     l->max_steps = max_steps;
+    l->R = R;
     nmpc::LoopArgs &a = l->a;
     a.B = B; a.N = h->pb.N; a.nobs = h->pb.nobs; a.ndyn = h->pb.ndyn; a.K = K;
     a.n_p = nmpc_n_p(&h->pb); a.n_u = nmpc_n_u(&h->pb);
@@ -685,6 +693,7 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
     }
     std::vector<int> rof(B, 0);
     if (route_of) for (int b = 0; b < B; ++b) rof[b] = route_of[b];
+    l->h_route_of = rof;
     e = ntab ? hipMemcpy(l->d_tab, tab.data(), ntab * 8, hipMemcpyHostToDevice) : hipSuccess;
     if (e == hipSuccess) e = hipMemcpy(l->d_routes, desc.data(), (size_t)R * sizeof(nmpc::LoopRoute), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(l->d_route_of, rof.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
@@ -852,6 +861,48 @@ int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of)
     return NMPC_OK;
 }
 
+int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *leg_route)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    const nmpc::LoopArgs &a = l->a;
+    const int B = a.B;
+    if (!leg_off || !leg_route) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off or leg_route is NULL");
+    if (!l->retire) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: the loop does not retire its robots (nmpc_loop_set_retire first)");
+    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: after the loop's first step");
+    if (l->missions) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: the loop has its missions already");
+    if (leg_off[0] != 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off[0] != 0");
+    for (int b = 0; b < B; ++b)
+        if (leg_off[b + 1] <= leg_off[b]) return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_missions: robot " + std::to_string(b) + " has no leg").c_str());
+    const int T = leg_off[B];
+    for (int i = 0; i < T; ++i)
+        if (leg_route[i] < 0 || leg_route[i] >= l->R) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_route out of range");
+    for (int b = 0; b < B; ++b)
+        if (leg_route[leg_off[b]] != l->h_route_of[b])
+            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_missions: the first leg of robot " + std::to_string(b) + " is not its route_of").c_str());
+    HIP_TRY(h, hipSetDevice(h->device));
+    DevBuf<int> off, route, leg, at;
+    hipError_t e = off.alloc((size_t)B + 1);
+    if (e == hipSuccess) e = route.alloc(T);
+    if (e == hipSuccess) e = leg.alloc(B);
+    if (e == hipSuccess) e = at.alloc(T);
+    if (e == hipSuccess) e = hipMemcpy(off, leg_off, ((size_t)B + 1) * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(route, leg_route, (size_t)T * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(leg, 0, (size_t)B * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(at, 0xFF, (size_t)T * sizeof(int));                            // leg_at = -1
+    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_missions: allocation", e);
+    l->d_leg_off = std::move(off); l->d_leg_route = std::move(route); l->d_leg = std::move(leg); l->d_leg_at = std::move(at);
+    l->n_legs = T;
+    nmpc::DispatchArgs &d = l->da;
+    d.n_u = a.n_u; d.n1 = nmpc_n1(&h->pb);
+    d.act = l->d_act; d.done = l->d_done;
+    d.leg_off = l->d_leg_off; d.leg_route = l->d_leg_route; d.leg = l->d_leg; d.leg_at = l->d_leg_at;
+    d.route_of = l->d_route_of; d.idx = l->d_idx; d.last_u = l->d_last_u; d.U = l->d_U; d.Y = l->d_Y;
+    l->missions = true;
+    return NMPC_OK;
+}
+
 void nmpc_loop_free(nmpc_loop *l)
 {
     if (!l) return;
@@ -918,6 +969,10 @@ static int loop_step_retiring(nmpc_loop *l, void *stream)
         hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, l->ga);
         hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
         if (l->monitor) launch_monitor(l, n, s);
+        if (l->missions) {
+            l->da.step = l->steps + 1;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_dispatch_kernel, dim3(n), dim3(64), 0, s, l->da);
+        }
     }
     // (with nobody active the step still counts: the clock advances and the trajectory rows repeat)
     nmpc::RetireArgs &r = l->ra;
@@ -1003,6 +1058,22 @@ int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at)
     }
     if (n_active) HIP_TRY(h, hipMemcpy(n_active, l->d_nact, sizeof(int), hipMemcpyDeviceToHost));
     if (retired_at) HIP_TRY(h, hipMemcpy(retired_at, l->d_retired_at, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+    return NMPC_OK;
+}
+
+int nmpc_loop_legs(nmpc_loop *l, int32_t *leg, int32_t *route_of, int32_t *leg_at)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (const int rc = loop_settle(h)) return rc;
+    const size_t B = (size_t)l->a.B;
+    if (route_of) HIP_TRY(h, hipMemcpy(route_of, l->d_route_of, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (!l->missions) {
+        if (leg) for (size_t b = 0; b < B; ++b) leg[b] = 0;
+        return NMPC_OK;
+    }
+    if (leg) HIP_TRY(h, hipMemcpy(leg, l->d_leg, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (leg_at) HIP_TRY(h, hipMemcpy(leg_at, l->d_leg_at, (size_t)l->n_legs * sizeof(int), hipMemcpyDeviceToHost));
     return NMPC_OK;
 }
 

@@ -570,4 +570,45 @@ __global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(MonitorArgs m)
     }
 }
 
+// ---- missions: a robot at its goal takes up its next route (nmpc_loop_set_missions; the rule is DESIGN.md section 5.9) ----
+struct DispatchArgs {
+    int n_u, n1;
+    int step;                 // steps taken, this one included: what leg_at takes
+    const int *act;           // the robots this step's advance ran over (the compaction comes after)
+    unsigned char *done;      // [B], of this step's advance; cleared for a robot that goes on, so that the compaction keeps it
+    const int *leg_off;       // [B + 1]: robot b drives the routes leg_route[leg_off[b] .. leg_off[b + 1]) in turn
+    const int *leg_route;     // [leg_off[B]]
+    int *leg;                 // [B]: the leg a robot is on, counted inside its mission
+    int *leg_at;              // [leg_off[B]]: the steps at which each leg ended, -1 = not yet
+    int *route_of;            // [B]: LoopArgs::route_of, written here and nowhere else
+    int *idx;                 // [B]
+    double *last_u;           // [B][2]
+    double *U, *Y;            // [B][n_u], [B][n1]: the loop's (the scatter has run)
+};
+
+// One wave per robot the step drove, after the advance (and the monitor) and before the compaction.  A robot whose terminal test holds
+// ends its leg at this step; if its mission has another leg it starts that route as a loop started anew from where it stands: window
+// search from sample 0, no previous control, a cold solve.  Its state, carried dynamic block, p, status and clearance record stay.
+__global__ __launch_bounds__(64) void nmpc_loop_dispatch_kernel(DispatchArgs d)
+{
+    const int b = d.act[blockIdx.x], lane = threadIdx.x;
+    // the same for the whole wave (read before any store, so that the loads can be scalar)
+    const int fin = d.done[b], leg = d.leg[b], lo = d.leg_off[b], hi = d.leg_off[b + 1];
+    if (!fin) return;
+    const bool more = lo + leg + 1 < hi;
+    const int next = more ? d.leg_route[lo + leg + 1] : 0;
+    if (lane == 0) d.leg_at[lo + leg] = d.step;
+    if (!more) return;                        // the last leg: the compaction retires the robot
+    double *u = d.U + (size_t)b * d.n_u, *y = d.Y + (size_t)b * d.n1;
+    for (int e = lane; e < d.n_u; e += 64) u[e] = 0.0;
+    for (int e = lane; e < d.n1; e += 64) y[e] = 0.0;
+    if (lane == 0) {
+        d.leg[b] = leg + 1;
+        d.route_of[b] = next;
+        d.idx[b] = 0;
+        d.last_u[2 * b] = 0.0; d.last_u[2 * b + 1] = 0.0;
+        d.done[b] = 0;
+    }
+}
+
 }  // namespace nmpc

@@ -446,6 +446,32 @@ class Monitor:
         return g
 
 
+@dataclasses.dataclass(frozen=True)
+class Missions:
+    """A sequence of routes per robot, driven leg after leg, for ``FleetRecedingHorizon`` and
+    ``DeviceRecedingHorizon`` alike, both with ``retire=True``: ``legs[b]`` = the indices of robot b's routes in the order it drives
+    them, the first one its ``route_of``.  A robot whose terminal test holds takes up its next leg in the same step, as the
+    reference's user calls ``PathGenerator.run`` again from where the robot stands, and retires after its last."""
+    legs: object
+
+    def checked(self, B: int, R: int, route_of):
+        """-> (leg_off [B + 1], leg_route [leg_off[B]]) as int32 arrays; ValueError for what ``nmpc_loop_set_missions`` refuses."""
+        legs = [np.asarray(m, dtype=np.int64).reshape(-1) for m in self.legs]
+        if len(legs) != B:
+            raise ValueError(f"missions: {len(legs)} missions for {B} robots")
+        if any(len(m) < 1 for m in legs):
+            raise ValueError("missions: a robot with no leg")
+        off = np.zeros(B + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(m) for m in legs])
+        route = np.concatenate(legs)
+        if ((route < 0) | (route >= R)).any():
+            raise ValueError("missions: a leg's route out of range")
+        first = np.zeros(B, dtype=np.int64) if route_of is None else np.asarray(route_of, dtype=np.int64).reshape(B)
+        if not np.array_equal(route[off[:-1]], first):
+            raise ValueError("missions: a robot's first leg is not its route_of")
+        return off, np.ascontiguousarray(route, dtype=np.int32)
+
+
 def no_clearance(B: int):
     """-> the initial records [B]: +inf, row -1, peer -1."""
     rec = np.empty(B, dtype=_lib.CLEARANCE_DTYPE)
@@ -476,10 +502,15 @@ class FleetRecedingHorizon(_HostLoop):
     ``monitor`` (a ``Monitor``): ``clearance`` [B] holds every robot's closest approaches, updated by
     ``advance`` from the rows it appends to ``traj`` and the parameter vectors ``assemble`` returned for this step, for the robots
     the step drove.  Nothing else reads it.
+
+    ``missions`` (a ``Missions``, needs ``retire=True``): ``retire`` re-dispatches an active robot that is done and has another leg
+    instead of retiring it: ``leg`` [B] and ``route_of`` [B] move on, ``leg_at`` [B, Lmax] takes the step count
+    at which each leg ended (-1: not yet, or no such leg), the robot's reference sample, ``last_u``, ``U`` and ``Y`` rows are zeroed
+    and ``done`` cleared, and the robot moves to the mirror of its new route with its state, carried dynamic block and trajectory.
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None):
+                 monitor=None, missions=None):
         self.routes = list(routes)
         cfg = self.cfg = self.routes[0].cfg
         self.B = B = len(starts)
@@ -487,15 +518,19 @@ class FleetRecedingHorizon(_HostLoop):
         assert all(r.cfg is cfg or r.cfg == cfg for r in self.routes)
         assert ((self.route_of >= 0) & (self.route_of < len(self.routes))).all()
         starts = np.array(starts, dtype=np.float64).reshape(B, 3)
-        self.parts = []                                           # (robots of the route in fleet order, its mirror)
-        for r, route in enumerate(self.routes):
-            ids = np.nonzero(self.route_of == r)[0]
-            if not len(ids):
-                continue
-            sub = VectorizedRecedingHorizon(route, starts[ids], None if dyn_obs is None else tuple(a[ids] for a in dyn_obs),
-                                            sincos=sincos, sinus_object=sinus_object,
-                                            idx0=None if idx0 is None else np.asarray(idx0).reshape(B)[ids])
-            self.parts.append((ids, sub))
+        self._dyn_obs, self._sincos, self._sinus_object = dyn_obs, sincos, sinus_object
+        self._traj_head = []                                      # the rows before the parts' own first (``_regroup``)
+        self._group(starts, idx0)
+        self.missions = missions
+        if missions is not None:
+            if not retire:
+                raise ValueError("missions need retire=True")
+            off, route = missions.checked(B, len(self.routes), self.route_of)
+            self.legs = [route[off[b]:off[b + 1]].astype(np.int64) for b in range(B)]
+            self.n_legs = np.diff(off).astype(np.int64)
+            self.leg = np.zeros(B, dtype=np.int32)
+            self.leg_at = np.full((B, int(self.n_legs.max())), -1, dtype=np.int32)
+            self.route_of = self.route_of.copy()
         self.t = 0
         self.U = np.zeros((B, cfg.n_u))
         self.Y = np.zeros((B, cfg.n1))
@@ -519,13 +554,50 @@ class FleetRecedingHorizon(_HostLoop):
             self.monitor_groups = [np.nonzero(g == v)[0] for v in np.unique(g)]   # members in ascending robot index
             self.clearance = no_clearance(B)
 
+    def _group(self, starts, idx0):
+        """``parts`` = (robots of the route in fleet order, its mirror), for every route somebody is on."""
+        B, dyn_obs = self.B, self._dyn_obs
+        self.parts = []
+        for r, route in enumerate(self.routes):
+            ids = np.nonzero(self.route_of == r)[0]
+            if not len(ids):
+                continue
+            sub = VectorizedRecedingHorizon(route, starts[ids], None if dyn_obs is None else tuple(a[ids] for a in dyn_obs),
+                                            sincos=self._sincos, sinus_object=self._sinus_object,
+                                            idx0=None if idx0 is None else np.asarray(idx0).reshape(B)[ids])
+            self.parts.append((ids, sub))
+
+    def _regroup(self, last_u, idx, done):
+        """The robots into the mirrors of ``route_of`` as it is now, each with what it carries: state, dynamic block, clock and the
+        ``last_u``, ``idx`` and ``done`` given; the trajectory so far is kept here.  The clock ``t`` and ``has_input`` are the fleet's:
+        every part advances them at every step, whoever is active, so any part's will do.  The whole trajectory is copied at every
+        step that re-dispatches somebody: fine for the fleets of the tests, quadratic for a long run of a big one."""
+        assert len({(sub.t, sub.has_input, len(sub.traj)) for _, sub in self.parts}) == 1
+        state, dyn = self.state, self._gather("dyn", self.parts[0][1].dyn.shape[1:])
+        t, has_input = self.parts[0][1].t, self.parts[0][1].has_input
+        self._traj_head = self.traj[:-1]
+        self._group(state, idx)
+        for ids, sub in self.parts:
+            sub.last_u, sub.done, sub.dyn, sub.t, sub.has_input = last_u[ids], done[ids], dyn[ids], t, has_input
+
     @property
     def n_active(self):
         return self.B if self.active is None else int(self.active.sum())
 
     def retire(self):
-        """After an advance: the active robots that are done leave."""
+        """After an advance: the active robots that are done leave; with missions, those with another leg start it instead."""
         now = self.active & self.done
+        if self.missions is not None:
+            self.leg_at[now, self.leg[now]] = self.steps
+            go = now & (self.leg + 1 < self.n_legs)
+            if go.any():
+                self.leg[go] += 1
+                self.route_of[go] = [self.legs[b][self.leg[b]] for b in np.nonzero(go)[0]]
+                self.U[go], self.Y[go] = 0.0, 0.0
+                last_u, idx, done = self.last_u, self.idx, self.done
+                last_u[go], idx[go], done[go] = 0.0, 0, False
+                self._regroup(last_u, idx, done)
+            now = now & ~go
         self.retired_at[now] = self.steps
         self.active &= ~now
 
@@ -553,7 +625,7 @@ class FleetRecedingHorizon(_HostLoop):
 
     @property
     def traj(self):
-        rows = []
+        rows = list(self._traj_head)
         for k in range(len(self.parts[0][1].traj)):
             row = np.empty((self.B, 3))
             for ids, sub in self.parts:
@@ -751,10 +823,15 @@ class DeviceRecedingHorizon:
     the active robots only, ``active()`` tells who is left and ``run(max_steps)`` steps until nobody is.  ``step`` then waits for the
     step before to have counted its active robots (an event, not the device).  Its host mirror is ``FleetRecedingHorizon`` with
     ``retire=True`` (tests/test_gpu_retire_loop.py).
+
+    ``missions`` (a ``Missions``, needs ``retire=True``): every robot drives the routes of its mission leg after leg and retires after
+    the last (``nmpc_loop_set_missions``); one more kernel per step, before the active list is rebuilt.
+    ``legs()`` tells where everybody is.  Its host mirror is ``FleetRecedingHorizon`` with the same ``missions``
+    (tests/test_gpu_missions_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None, retire=False, monitor=None):
+                 route_of=None, peers=None, retire=False, monitor=None, missions=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -814,6 +891,20 @@ class DeviceRecedingHorizon:
             if rc:
                 self.close()
                 solver._check(rc)
+        self.missions = missions
+        self._leg_off = None
+        if missions is not None:
+            try:
+                if not retire:
+                    raise ValueError("missions need retire=True")
+                self._leg_off, leg_route = missions.checked(B, len(routes), self.route_of)
+            except ValueError:
+                self.close()
+                raise
+            rc = self.lib.nmpc_loop_set_missions(h, _lib.as_i32p(self._leg_off), _lib.as_i32p(leg_route))
+            if rc:
+                self.close()
+                solver._check(rc)
 
     def close(self):
         if getattr(self, "_l", None):
@@ -847,6 +938,21 @@ class DeviceRecedingHorizon:
         n, at = C.c_int32(), np.empty(self.B, dtype=np.int32)
         self.solver._check(self.lib.nmpc_loop_active(self._l, C.byref(n), _lib.as_i32p(at)))
         return n.value, at
+
+    def legs(self):
+        """-> (leg [B], route_of [B], leg_at [B, Lmax]) int32 after synchronising: the leg each robot is on, its current route, and the
+        step count at which each of its legs ended (-1: not yet, or no such leg); without ``missions`` leg 0, the routes of the
+        creation and one column of -1."""
+        B, off = self.B, self._leg_off
+        leg, route_of = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        flat = None if off is None else np.empty(int(off[-1]), dtype=np.int32)
+        self.solver._check(self.lib.nmpc_loop_legs(self._l, _lib.as_i32p(leg), _lib.as_i32p(route_of), _lib.as_i32p(flat)))
+        if off is None:
+            return leg, route_of, np.full((B, 1), -1, dtype=np.int32)
+        n = np.diff(off)
+        leg_at = np.full((B, int(n.max())), -1, dtype=np.int32)
+        leg_at[np.arange(leg_at.shape[1])[None, :] < n[:, None]] = flat
+        return leg, route_of, leg_at
 
     def clearance(self):
         """-> the monitor's records [B] (``_lib.CLEARANCE_DTYPE``: circle, ellipse, peer2, circle_row, ellipse_row, peer_row, peer)

@@ -95,6 +95,23 @@ def handmade_route(cfg, waypoints, vertices=()):
     return Route(cfg, (w[0][0], w[0][1], th0), (w[-1][0], w[-1][1], 0.0), w, [(float(x), float(y)) for x, y in vertices])
 
 
+def mission_fleet(cfg, corners, n_legs, first=None, offsets=None, vertices=()):
+    """-> (routes, route_of, starts, idx0, legs): ``routes[i]`` = ``handmade_route`` from ``corners[i]`` to ``corners[i + 1]`` (a leg's first
+    waypoint is the goal of the leg before; ``vertices`` on every one), and one robot per entry of ``n_legs`` whose mission is that many
+    consecutive routes from ``first[b]`` on (default 0).  Robot b starts at the first corner of its mission, heading along the leg,
+    moved by ``offsets[b]`` = (dx, dy, dtheta) if given; idx0 is 0 as the reference's.  ``legs`` is what ``trajectory.Missions`` takes."""
+    c = [(float(x), float(y)) for x, y in corners]
+    routes = [handmade_route(cfg, [c[i], c[i + 1]], vertices) for i in range(len(c) - 1)]
+    B = len(n_legs)
+    first = [0] * B if first is None else list(first)
+    legs = [list(range(f, f + n)) for f, n in zip(first, n_legs)]
+    assert all(n >= 1 and m[-1] < len(routes) for n, m in zip(n_legs, legs))
+    starts = np.array([routes[f].start for f in first], dtype=np.float64).reshape(B, 3)
+    if offsets is not None:
+        starts = starts + np.asarray(offsets, dtype=np.float64).reshape(B, 3)
+    return routes, np.array(first, dtype=np.int32), starts, np.zeros(B, dtype=np.int32), legs
+
+
 def tiled_fleet(routes, route_of, starts, idx0, copies):
     """-> (routes, route_of, starts, idx0) of the fleet repeated: round(m * copies) robots, m = the robots given (``copies`` may be
     fractional), robot b a copy of base robot b % m.  Without peers the robots of a loop do not depend on each other, so row b of a
@@ -127,7 +144,8 @@ def step_differing(dev, host, solve, dev_step=None, rows=None):
     solve function) once.  ``rows`` [dev.B]: the device runs a ``tiled_fleet`` of the mirror's, its robot b is the mirror's rows[b].
     -> (names, P, done): the names out of P, U, Y, state, last_u, idx, done, num_inner_iterations, exit_status on which the two are
     not bit-equal ("P" with its first differing columns), the device's parameter vectors and its ``done``.  A retiring pair
-    (``retire=True``: the mirror's ``solve`` sees the active rows only) is also compared on retired_at and n_active."""
+    (``retire=True``: the mirror's ``solve`` sees the active rows only) is also compared on retired_at and n_active, a pair with
+    missions on leg, route_of and leg_at."""
     dev.step() if dev_step is None else dev_step(dev)
     P, st = host.step(solve)
     Pd, Ud, Yd = dev.params()
@@ -137,6 +155,8 @@ def step_differing(dev, host, solve, dev_step=None, rows=None):
     if host.active is not None:
         n_active, retired_at = dev.active()
         pairs.append(("retired_at", retired_at, host.retired_at))
+    if getattr(host, "missions", None) is not None:
+        pairs += list(zip(("leg", "route_of", "leg_at"), dev.legs(), (host.leg, host.route_of, host.leg_at)))
     if rows is not None:
         pairs = [(n, x, y[rows]) for n, x, y in pairs]
     if host.active is not None:

@@ -44,6 +44,9 @@ ap.add_argument("--peer-slots", type=int, default=2, help="with --peers: ellipse
 ap.add_argument("--peer-range", type=float, default=10.0, help="with --peers: how far a robot sees, in metres")
 ap.add_argument("--retire", action="store_true",
                 help="device loop only: retire the robots that reach their goal; run until nobody is active, --steps at the most")
+ap.add_argument("--legs", type=int, default=1, metavar="L",
+                help="with --retire: every robot drives a mission of L legs (nmpc_loop_set_missions), its route and the same route "
+                     "driven backwards in turn, and retires after the last; the result line gains legs_done")
 ap.add_argument("--monitor", type=int, nargs="?", const=0, default=None, metavar="G",
                 help="device loop only: keep every robot's closest approach to circles, scripted ellipses and the robots of its group of G "
                      "consecutive robots (of a sub-fleet) on the device, and report them; G defaults to the --peers groups, or 32")
@@ -56,6 +59,8 @@ if args.monitor is not None:
     if args.monitor < 0:
         ap.error("--monitor G: G >= 1")
     args.monitor = args.monitor or args.peers or 32
+if args.legs < 1 or (args.legs > 1 and (not args.retire or args.host)):
+    ap.error("--legs L: L >= 1, and L > 1 needs --retire on the device loop")
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
@@ -96,6 +101,18 @@ if args.peers:
     fleet += (f", {K} scripted ellipses and {args.peer_slots} peer slots per robot, groups of {args.peers} consecutive robots, "
               f"range {args.peer_range} m, radii {peer_radius} m")
 solver = BatchSolver(cfg, max_batch=B, **sopts)
+missions_of = lambda ids: None
+if args.legs > 1:
+    # route r driven backwards is route R + r: the same waypoints and circles from the goal to the start
+    from mpc_trajectory_generator_amd.trajectory import Missions
+    fwd = [routes] if route_of is None else list(routes)
+    # (like workloads.handmade_route: the start heading along the first segment, the end heading 0; a mission never reads a leg's start)
+    import math
+    routes = fwd + [harness.Route(cfg, (w[0][0], w[0][1], math.atan2(w[1][1] - w[0][1], w[1][0] - w[0][0])), (w[-1][0], w[-1][1], 0.0), w,
+                                  list(r.vertices)) for r in fwd for w in [list(r.waypoints)[::-1]]]
+    route_of = np.zeros(B, dtype=np.int32) if route_of is None else route_of
+    missions_of = lambda ids: Missions([[int(route_of[b]) + len(fwd) * (k % 2) for k in range(args.legs)] for b in ids])
+    fleet += f", missions of {args.legs} legs (the route and its reverse in turn)"
 if not args.host:
     from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon
     import ctypes
@@ -105,7 +122,8 @@ if not args.host:
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
         loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
-                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids))))
+                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
+                                           missions=missions_of(ids)))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -132,14 +150,16 @@ if not args.host:
     done = np.concatenate([o[3] for o in outs])
     st = np.concatenate([o[4] for o in outs])
     quality = {}
+    if args.legs > 1:
+        quality["legs_done"] = int(sum((rh.legs()[2] >= 0).sum() for rh in loops))
     if args.monitor:
         rec = np.concatenate([rh.clearance() for rh in loops])
-        quality = {"clearance": {
+        quality["clearance"] = {
             "groups_of": args.monitor, "inside_circle_frac": float((rec["circle"] < 0).mean()),
             "inside_ellipse_frac": float((rec["ellipse"] < 1).mean()),
             "closer_than_two_peer_radii_frac": float((rec["peer2"] < (2 * peer_radius) ** 2).mean()), "two_peer_radii_m": 2 * peer_radius,
             "min_circle_m": float(rec["circle"].min()), "min_ellipse_level": float(rec["ellipse"].min()),
-            "min_peer_m": float(np.sqrt(rec["peer2"].min()))}}
+            "min_peer_m": float(np.sqrt(rec["peer2"].min()))}
     from mpc_trajectory_generator_amd import _lib
     if hasattr(_lib.load_library(), "nmpc_debug_win_stats"):        # instrumented build (-DNMPC_WIN_STATS, scripts/win_stats.py)
         buf = (ctypes.c_ulonglong * 2)()
