@@ -331,6 +331,55 @@ int nmpc_loop_params(nmpc_loop *l, double *p, double *u, double *y);
 /* Recorded trajectory: rows [steps * num_steps_taken + 1][B][3]; returns the row count (or < 0). */
 int nmpc_loop_trajectory(nmpc_loop *l, double *rows, int max_rows);
 
+/* ---- a route per robot, planned on device ---------------------------------------------------------
+ * Batched shortest paths over the visibility graph of one scene: what the reference's front-end answers for one start / goal pair
+ * (src/visibility/visibility.py:49-88: inflate the obstacles and deflate the boundary, build the visibility graph, shortest path;
+ * :126-139 maps the path's corners back to original vertices, which stays with the caller), for B pairs at once, so that every robot
+ * of a fleet can have its own start and goal as the reference's user gives them (src/path_generator.py:197-251).  A planner is a
+ * handle of its own, independent of nmpc_handle and of any problem shape; like a handle it is not thread-safe, distinct planners are.
+ * The rule -- the segment test, the search and its tie rule -- is DESIGN.md section 5.11; its host statement is
+ * frontend.plan_batch_mirror, whose bits the kernels give.
+ *
+ * The scene (visibility.py:49-67 has produced the polygons): the graph's nodes (the corners a path can bend around) and every edge
+ * of the inflated obstacles and the deflated boundary.  Limits: n_node <= 254, 3 <= n_edge <= 1024. */
+typedef struct nmpc_scene {
+    int32_t n_node, n_edge, n_poly, reserved;
+    const double *node_xy;     /* [n_node][2]                                     visibility.py:69-80   */
+    const double *edge;        /* [n_edge][4] x1 y1 x2 y2, polygon by polygon: the obstacles first, the boundary last */
+    const int32_t *poly_off;   /* [n_poly + 1]: polygon k owns the edges poly_off[k] .. poly_off[k + 1]; ascending from 0 to n_edge,
+                                  three edges per polygon at least */
+} nmpc_scene;
+
+typedef struct nmpc_planner nmpc_planner;
+
+/* Copies the scene to HIP device `device_id`, judges the node-node visibility there (one kernel over the n_node^2 pairs; synchronises) and
+ * makes room for `max_batch` queries (1 .. 2^20).  NMPC_ERR_BAD_ARG, with nothing allocated, for a NULL argument, a scene outside the
+ * limits, a malformed poly_off or a max_batch out of range; NMPC_ERR_NO_DEVICE / NMPC_ERR_HIP as nmpc_new. */
+int nmpc_planner_new(const nmpc_scene *scene, int device_id, int max_batch, nmpc_planner **out);
+void nmpc_planner_free(nmpc_planner *pl);
+/* The node-node visibility vis [n_node][n_node] to host memory: entry (i, j) = 1 if the segment from node i to node j is free. */
+int nmpc_planner_visibility(nmpc_planner *pl, uint8_t *vis);
+/* B queries; the points of a query are [start, goal] + nodes, n = n_node + 2.  Two kernels: the visibility of the query's own
+ * 2 n_node + 1 segments -- (start, node k), (goal, node k), (start, goal) -- then per query Dijkstra over the n points: at most n
+ * rounds, each settling the unsettled point with the smallest (distance, index).  The search stops when that distance is not
+ * finite or the point is the goal, and relaxes every unsettled visible point j on the strict dist[i] + |p_i - p_j| < dist[j].
+ * A NaN or infinite coordinate blocks every segment it is part of: such a query ends as "no path".
+ * Device path: every pointer is device memory on the planner's device; enqueued on `stream`, no synchronisation.
+ *   d_start, d_goal [B][2]
+ *   d_n_wp   [B]            waypoints of the path, start and goal included; 0 = no path
+ *   d_wp     [B][n]         their point indices from 0 (the start) to 1 (the goal), -1 behind them
+ *   d_length [B]            the path's length, +inf without a path
+ *   d_vis    [B][2 n_node + 1]  the visibility of the query's own segments, or NULL (kept in the planner's scratch)
+ * B == 0 is NMPC_OK and launches nothing; B < 0, B > max_batch or a NULL required pointer is NMPC_ERR_BAD_ARG.  A planner's
+ * asynchronous calls must be ordered on one stream at a time. */
+int nmpc_plan_batch_device(nmpc_planner *pl, int B, const double *d_start, const double *d_goal, int32_t *d_n_wp, int32_t *d_wp,
+                           double *d_length, uint8_t *d_vis, void *stream);
+/* Host path: same operands in host memory; copies in, plans, copies out, synchronises. */
+int nmpc_plan_batch_host(nmpc_planner *pl, int B, const double *start, const double *goal, int32_t *n_wp, int32_t *wp,
+                         double *length, uint8_t *vis);
+/* Kernel time (HIP events around the two launches) of the last nmpc_plan_batch_host call on this planner, in ms. */
+double nmpc_planner_last_ms(const nmpc_planner *pl);
+
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);
 /* a/b and sqrt(a) as the device computes them: out_div/out_sqrt [n]. */

@@ -25,6 +25,7 @@ SYMBOLS = (
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
     "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run", "nmpc_loop_set_monitor", "nmpc_loop_clearance",
     "nmpc_loop_set_missions", "nmpc_loop_legs",
+    "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
 EXPECTED_ABI = 3      # the nmpc_opts / nmpc_status layouts below are written for this version of include/nmpc_solver.h
@@ -66,6 +67,11 @@ class NmpcRoute(C.Structure):
                 ("brake_vel", _dp), ("brake_dist", _dp),
                 ("end", C.c_double * 3), ("base_speed", C.c_double), ("radius", C.c_double),
                 ("dyn_pad", C.c_double), ("weights", C.c_double * 10)]
+
+
+class NmpcScene(C.Structure):
+    _fields_ = [("n_node", C.c_int32), ("n_edge", C.c_int32), ("n_poly", C.c_int32), ("reserved", C.c_int32),
+                ("node_xy", C.POINTER(C.c_double)), ("edge", C.POINTER(C.c_double)), ("poly_off", C.POINTER(C.c_int32))]
 
 
 STATUS_DTYPE = np.dtype([("exit_status", "<i4"), ("num_outer_iterations", "<u4"),
@@ -284,6 +290,14 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_legs.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
+    lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]
+    lib.nmpc_planner_free.argtypes = [vp]
+    lib.nmpc_planner_free.restype = None
+    lib.nmpc_planner_visibility.argtypes = [vp, C.POINTER(C.c_uint8)]
+    lib.nmpc_plan_batch_device.argtypes = [vp, C.c_int] + [vp] * 7
+    lib.nmpc_plan_batch_host.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, C.POINTER(C.c_uint8)]
+    lib.nmpc_planner_last_ms.argtypes = [vp]
+    lib.nmpc_planner_last_ms.restype = C.c_double
     lib.nmpc_loop_step.argtypes = [vp, vp]
     lib.nmpc_loop_read.argtypes = [vp, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), vp]
     lib.nmpc_loop_params.argtypes = [vp, dp, dp, dp]

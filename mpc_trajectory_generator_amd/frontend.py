@@ -6,18 +6,22 @@ vehicle width with mitred joins and deflates the boundary (src/visibility/visibi
 (:69-88), and the path corners are mapped back to the nearest original vertices, which become the
 NMPC's circle centres (:126-139).  Neither package is available here, so this module is an own
 implementation of the same geometry -- **unpinned** against the reference's dependencies
-(validated geometrically: tests/test_frontend.py).  It runs once per trajectory on the CPU; it is
-not on the GPU hot path.
+(validated geometrically: tests/test_frontend.py).  ``VisibilityPlanner`` runs once per trajectory on the CPU.  A fleet whose
+robots each have their own start and goal plans on the device instead: ``DevicePlanner`` answers a batch of queries with two
+kernels (csrc/nmpc_plan.h), bit for bit what ``plan_batch_mirror`` computes here with NumPy.
 """
 from __future__ import annotations
 
+import ctypes as C
+import dataclasses
 import heapq
 import math
 
 import numpy as np
 
-from . import harness
+from . import _lib, harness
 from .config import Config
+from .solver import SolverError
 
 _EPS = 1e-9
 
@@ -274,3 +278,256 @@ def random_fleet(cfg: Config, scene: int, R: int, B: int, seed: int):
     base = np.stack([ref[r][i] for r, i in zip(route_of, idx0)]) if B else np.zeros((0, 3))
     starts = base + np.stack([rng.normal(0, 0.05, B), rng.normal(0, 0.05, B), rng.normal(0, 0.1, B)], axis=1)
     return routes, route_of, starts, idx0
+
+
+# ---- batched planning: the rule of ``VisibilityPlanner._free`` / ``shortest_path`` in arithmetic the device reproduces bit for bit
+# (unfused f64 + - * / and sqrt).  ``plan_batch_mirror`` is the NumPy statement, ``DevicePlanner`` the kernels.
+PLAN_MAX_NODES = 254        # V: a query has V + 2 points, four per lane of a wave at the most
+PLAN_MAX_EDGES = 1024       # E: the edges are staged in LDS
+_SAMPLES = (0.5, 0.25, 0.75, 0.0625, 0.9375)
+
+
+@dataclasses.dataclass
+class PlanScene:
+    """What the planner kernels read of a ``VisibilityPlanner``: ``nodes`` [V, 2], every polygon edge ``edges`` [E, 4] = (x1, y1, x2, y2)
+    with the obstacles first and the deflated boundary last, ``poly_off`` [n_poly + 1] and ``node_vertex`` [V, 2], the closest
+    original vertex of each node (``original_vertices`` per node: static, so computed here)."""
+    nodes: np.ndarray
+    edges: np.ndarray
+    poly_off: np.ndarray
+    node_vertex: np.ndarray
+    _nn: object = None
+
+    @property
+    def visibility(self):
+        """Node-node visibility [V, V] uint8 by the mirror's segment test: entry (i, j) judges the segment from node i to node j."""
+        if self._nn is None:
+            V = len(self.nodes)
+            i, j = np.divmod(np.arange(V * V), max(V, 1))
+            self._nn = _free_batch(self, self.nodes[i], self.nodes[j]).reshape(V, V).astype(np.uint8)
+        return self._nn
+
+
+def plan_scene(planner: VisibilityPlanner) -> PlanScene:
+    """The ``PlanScene`` of a planner (kept on the planner: it is static); ValueError beyond V <= 254 nodes or E <= 1024 edges."""
+    sc = getattr(planner, "_plan_scene", None)
+    if sc is not None:
+        return sc
+    polys = list(planner.obstacles) + [planner.boundary]
+    V, E = len(planner.nodes), sum(len(p) for p in polys)
+    if V > PLAN_MAX_NODES or E > PLAN_MAX_EDGES:
+        raise ValueError(f"scene with {V} nodes and {E} edges: the batched planner takes {PLAN_MAX_NODES} and {PLAN_MAX_EDGES} at the most")
+    edges = np.array([[*poly[i], *poly[(i + 1) % len(poly)]] for poly in polys for i in range(len(poly))], dtype=np.float64).reshape(E, 4)
+    off = np.zeros(len(polys) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(p) for p in polys])
+    nodes = np.array(planner.nodes, dtype=np.float64).reshape(V, 2)
+    allv = [v for o in planner.original_obstacles for v in o] + list(planner.original_boundary)
+    nv = np.array([allv[harness.closest_index(c, allv)] for c in planner.nodes], dtype=np.float64).reshape(V, 2)
+    sc = planner._plan_scene = PlanScene(nodes, edges, off, nv)
+    return sc
+
+
+def _free_batch(sc: PlanScene, a, b, chunk=8192):
+    """``VisibilityPlanner._free`` for S segments a[s] -> b[s] at once -> bool [S].  Every comparison keeps the sense it has in the
+    literal code, so one that is false because of a NaN has the same consequence."""
+    a, b = np.asarray(a, dtype=np.float64).reshape(-1, 2), np.asarray(b, dtype=np.float64).reshape(-1, 2)
+    if len(a) > chunk:
+        return np.concatenate([_free_batch(sc, a[i:i + chunk], b[i:i + chunk], chunk) for i in range(0, len(a), chunk)])
+    x1, y1, x2, y2 = (sc.edges[:, k][None, :] for k in range(4))
+    ex, ey = x2 - x1, y2 - y1
+    with np.errstate(all="ignore"):
+        ax, ay, bx, by = a[:, 0:1], a[:, 1:2], b[:, 0:1], b[:, 1:2]
+        dx, dy = ax - bx, ay - by
+        short = (np.sqrt(dx * dx + dy * dy) < 1e-12)[:, 0]
+        # proper crossing with any edge (_seg_intersect_strict)
+        ux, uy = bx - ax, by - ay
+        o1 = ux * (y1 - ay) - uy * (x1 - ax)
+        o2 = ux * (y2 - ay) - uy * (x2 - ax)
+        o3 = ex * (ay - y1) - ey * (ax - x1)
+        o4 = ex * (by - y1) - ey * (bx - x1)
+        blocked = ((o1 * o2 < -_EPS) & (o3 * o4 < -_EPS)).any(axis=1)
+        # the interior samples against containment (_point_in_polygon: on an edge first, then the even-odd crossing)
+        h = np.sqrt(ex * ex + ey * ey)
+        tol = 1e-9 * np.where(h > 1.0, h, 1.0)
+        xlo, xhi = np.where(x2 < x1, x2, x1) - 1e-9, np.where(x2 > x1, x2, x1) + 1e-9
+        ylo, yhi = np.where(y2 < y1, y2, y1) - 1e-9, np.where(y2 > y1, y2, y1) + 1e-9
+        n_poly = len(sc.poly_off) - 1
+        for s in _SAMPLES:
+            x, y = ax + s * (bx - ax), ay + s * (by - ay)
+            cross = ex * (y - y1) - ey * (x - x1)
+            on = (np.abs(cross) <= tol) & (xlo <= x) & (x <= xhi) & (ylo <= y) & (y <= yhi)
+            straddle = (y1 > y) != (y2 > y)
+            xi = x1 + ((y - y1) * ex) / np.where(straddle, ey, 1.0)
+            hit = straddle & (xi > x)
+            for k in range(n_poly):
+                lo, hi = sc.poly_off[k], sc.poly_off[k + 1]
+                on_k = on[:, lo:hi].any(axis=1)
+                inside = (hit[:, lo:hi].sum(axis=1) & 1).astype(bool)
+                if k < n_poly - 1:
+                    blocked |= ~on_k & inside              # strictly inside an obstacle
+                else:
+                    blocked |= ~(on_k | inside)            # not inside the boundary, its edges counting as inside
+    return short | ~blocked
+
+
+@dataclasses.dataclass
+class PlanResult:
+    """B queries' answers.  The points of a query are [start, goal] + nodes, n = V + 2:
+    ``n_wp`` [B] int32 waypoints of the path, 0 = no path; ``wp`` [B, n] int32 their point indices from 0 to 1, -1 behind them;
+    ``length`` [B] the path's length (+inf: no path); ``vis`` [B, 2V + 1] uint8 the visibility of the query's own segments
+    (start, node k), (goal, node k), (start, goal)."""
+    n_wp: np.ndarray
+    wp: np.ndarray
+    length: np.ndarray
+    vis: np.ndarray
+
+
+def _query_points(starts, goals):
+    starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(-1, 2))
+    goals = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).reshape(-1, 2))
+    if len(starts) != len(goals):
+        raise ValueError(f"{len(starts)} starts for {len(goals)} goals")
+    return starts, goals
+
+
+def plan_batch_mirror(planner: VisibilityPlanner, starts, goals) -> PlanResult:
+    """Shortest visibility-graph paths for B queries at once (starts, goals [B, 2]), the host mirror of ``DevicePlanner.plan``.
+    Segments are judged by ``_free``'s rule (``_free_batch``); the search is Dijkstra with a fixed tie rule in place of
+    ``shortest_path``'s A*: at most n rounds, each settling the unsettled point with the smallest (dist, index), stopping when that
+    distance is not finite (no path) or the point is the goal, and relaxing every unsettled visible j on the strict
+    ``dist[i] + sqrt(dx*dx + dy*dy) < dist[j]``."""
+    sc = plan_scene(planner)
+    starts, goals = _query_points(starts, goals)
+    B, V = len(starts), len(sc.nodes)
+    n = V + 2
+    # the query's own segments: (start, node k), (goal, node k), (start, goal)
+    a = np.concatenate([np.repeat(starts[:, None], V, 1), np.repeat(goals[:, None], V, 1), starts[:, None]], axis=1)
+    b = np.concatenate([np.broadcast_to(sc.nodes[None], (B, V, 2))] * 2 + [goals[:, None]], axis=1)
+    vis = _free_batch(sc, a.reshape(-1, 2), b.reshape(-1, 2)).reshape(B, 2 * V + 1).astype(np.uint8)
+    nn = sc.visibility.astype(bool)
+    nn = np.where(np.arange(V)[:, None] <= np.arange(V)[None, :], nn, nn.T)      # a pair is judged from its lower index, as `visible` does
+    pts = np.concatenate([starts[:, None], goals[:, None], np.broadcast_to(sc.nodes[None], (B, V, 2))], axis=1)
+    dist = np.full((B, n), np.inf)
+    dist[:, 0] = 0.0
+    prev = np.full((B, n), -1, dtype=np.int32)
+    settled = np.zeros((B, n), dtype=bool)
+    live = np.ones(B, dtype=bool)
+    rows = np.arange(B)
+    # who the start, the goal and (below) a node see among the n points; a point's own entry is never read
+    sg, no = vis[:, 2 * V:] != 0, np.zeros((B, 1), dtype=bool)
+    row_s = np.concatenate([no, sg, vis[:, :V] != 0], axis=1)
+    row_g = np.concatenate([sg, no, vis[:, V:2 * V] != 0], axis=1)
+    with np.errstate(all="ignore"):
+        for _ in range(n):
+            if not live.any():
+                break
+            masked = np.where(settled, np.inf, dist)
+            i = np.argmin(masked, axis=1)                                         # the first minimum: (dist, index) order
+            d = masked[rows, i]
+            live &= d < np.inf                                                    # nothing reachable is left: no path
+            settled[rows[live], i[live]] = True
+            live &= i != 1
+            row = np.where((i == 0)[:, None], row_s, row_g)
+            if V:
+                k = np.maximum(i - 2, 0)
+                row_n = np.concatenate([vis[rows, k][:, None] != 0, vis[rows, V + k][:, None] != 0, nn[k]], axis=1)
+                row = np.where((i >= 2)[:, None], row_n, row)
+            dx, dy = pts[rows, i, 0:1] - pts[:, :, 0], pts[rows, i, 1:2] - pts[:, :, 1]
+            cand = d[:, None] + np.sqrt(dx * dx + dy * dy)
+            take = live[:, None] & ~settled & row & (cand < dist)
+            dist[take] = cand[take]
+            prev[take] = np.broadcast_to(i[:, None].astype(np.int32), (B, n))[take]
+    n_wp = np.zeros(B, dtype=np.int32)
+    wp = np.full((B, n), -1, dtype=np.int32)
+    for q in np.nonzero(settled[:, 1])[0]:
+        path, j = [1], 1
+        for _ in range(n):                                                        # the walk back is bounded like the device's
+            if j == 0:
+                break
+            j = int(prev[q, j])
+            path.append(j)
+        n_wp[q] = len(path)
+        wp[q, :len(path)] = path[::-1]
+    return PlanResult(n_wp, wp, dist[:, 1].copy(), vis)
+
+
+def plan_routes(planner: VisibilityPlanner, res: PlanResult, starts, ends, sinus_object=False):
+    """The ``harness.Route`` of every query of a ``PlanResult`` (starts, ends [B, 3] poses whose (x, y) were the queries), what
+    ``VisibilityPlanner.route`` builds from ``shortest_path``: waypoints = the coordinates of ``wp``, vertices = ``node_vertex`` of the
+    interior waypoints, the planner's ``dyn_obs_list``.  ValueError naming the first robot without a path."""
+    sc = plan_scene(planner)
+    starts, ends = np.asarray(starts, dtype=np.float64).reshape(-1, 3), np.asarray(ends, dtype=np.float64).reshape(-1, 3)
+    bad = np.nonzero(res.n_wp == 0)[0]
+    if len(bad):
+        raise ValueError(f"robot {int(bad[0])}: no collision-free path between start and goal")
+    nv = [tuple(map(float, v)) for v in sc.node_vertex]
+    out = []
+    for b in range(len(starts)):
+        s, e = tuple(map(float, starts[b])), tuple(map(float, ends[b]))
+        pts = [s[:2], e[:2]] + planner.nodes
+        idx = [int(j) for j in res.wp[b, :res.n_wp[b]]]
+        out.append(harness.Route(planner.cfg, s, e, [pts[j] for j in idx], [nv[j - 2] for j in idx[1:-1]], planner.dyn_obs_list, sinus_object))
+    return out
+
+
+class DevicePlanner:
+    """``plan_batch_mirror`` on the GPU: the planner kernels of libnmpc_hip.so (``nmpc_planner_*`` / ``nmpc_plan_batch_*``,
+    include/nmpc_solver.h; csrc/nmpc_plan.h), bit for bit the mirror's answers (tests/test_gpu_plan.py).  The scene goes to the device
+    once, where its node-node visibility is judged; ``plan`` then answers up to ``max_batch`` queries per call.  There is no CPU
+    fall-back: without a HIP device the constructor raises."""
+
+    def __init__(self, planner: VisibilityPlanner, device: int = 0, max_batch: int = 8192):
+        self.planner, self.scene = planner, plan_scene(planner)
+        self.max_batch = int(max_batch)
+        self.lib = _lib.load_library()
+        sc = self.scene
+        self.V = len(sc.nodes)
+        nodes, edges, off = (np.ascontiguousarray(sc.nodes, dtype=np.float64), np.ascontiguousarray(sc.edges, dtype=np.float64),
+                             np.ascontiguousarray(sc.poly_off, dtype=np.int32))
+        s = _lib.NmpcScene(self.V, len(edges), len(off) - 1, 0, _lib.as_dp(nodes), _lib.as_dp(edges), _lib.as_i32p(off))
+        h = C.c_void_p()
+        rc = self.lib.nmpc_planner_new(C.byref(s), int(device), self.max_batch, C.byref(h))
+        if rc != 0:
+            raise SolverError(rc, f"nmpc_planner_new failed: {_lib.ERRORS.get(rc, rc)} (this package needs a HIP device; there is no CPU fallback)")
+        self._pl = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise SolverError(rc, f"{what}: {_lib.ERRORS.get(rc, rc)}")
+
+    def close(self):
+        if getattr(self, "_pl", None):
+            self.lib.nmpc_planner_free(self._pl)
+            self._pl = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def last_ms(self):
+        """Kernel time of the last ``plan`` call, in ms (HIP events around its two launches)."""
+        return float(self.lib.nmpc_planner_last_ms(self._pl))
+
+    def visibility(self):
+        """The node-node visibility [V, V] uint8 as the device judged it."""
+        vis = np.zeros((self.V, self.V), dtype=np.uint8)
+        self._check(self.lib.nmpc_planner_visibility(self._pl, vis.ctypes.data_as(C.POINTER(C.c_uint8))), "nmpc_planner_visibility")
+        return vis
+
+    def plan(self, starts, goals) -> PlanResult:
+        """starts, goals [B, 2] -> ``PlanResult``, B <= max_batch."""
+        starts, goals = _query_points(starts, goals)
+        B, n = len(starts), self.V + 2
+        res = PlanResult(np.zeros(B, dtype=np.int32), np.full((B, n), -1, dtype=np.int32), np.full(B, np.inf), np.zeros((B, 2 * self.V + 1), dtype=np.uint8))
+        self._check(self.lib.nmpc_plan_batch_host(self._pl, B, _lib.as_dp(starts), _lib.as_dp(goals), _lib.as_i32p(res.n_wp), _lib.as_i32p(res.wp),
+                                                  _lib.as_dp(res.length), res.vis.ctypes.data_as(C.POINTER(C.c_uint8))), "nmpc_plan_batch_host")
+        return res
+
+    def routes(self, starts, ends, sinus_object=False):
+        """starts, ends [B, 3] poses -> a ``harness.Route`` per robot from its start to its end (``plan_routes`` of ``plan``), as
+        ``VisibilityPlanner.route`` builds one; ValueError naming the first robot without a path."""
+        starts, ends = np.asarray(starts, dtype=np.float64).reshape(-1, 3), np.asarray(ends, dtype=np.float64).reshape(-1, 3)
+        return plan_routes(self.planner, self.plan(starts[:, :2], ends[:, :2]), starts, ends, sinus_object)

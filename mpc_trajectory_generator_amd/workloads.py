@@ -7,7 +7,7 @@ import math
 import numpy as np
 
 from .config import named_config
-from .frontend import random_routes
+from .frontend import (PlanResult, VisibilityPlanner, _point_in_polygon, offset_polygon, plan_batch_mirror, plan_routes, random_routes, scene_planner)
 from .harness import Route, scene_route, synthetic_batch
 
 # what the generator adds per configuration: config 3 a synthetic circle field, config 4 random moving ellipses
@@ -110,6 +110,72 @@ def mission_fleet(cfg, corners, n_legs, first=None, offsets=None, vertices=()):
     if offsets is not None:
         starts = starts + np.asarray(offsets, dtype=np.float64).reshape(B, 3)
     return routes, np.array(first, dtype=np.int32), starts, np.zeros(B, dtype=np.int32), legs
+
+
+def square_grid_planner(cfg, cols=5, rows=4, boundary=None):
+    """A planner on cols x rows unit squares on a 3 m grid inside a rectangle (or inside ``boundary``): a synthetic scene with 4 cols rows
+    nodes and as many edges plus the boundary's; 5 x 4 gives 80 nodes and 84 edges, more points than a wave has lanes."""
+    obstacles = [[(3.0 * i + 2, 3.0 * j + 2), (3.0 * i + 3, 3.0 * j + 2), (3.0 * i + 3, 3.0 * j + 3), (3.0 * i + 2, 3.0 * j + 3)]
+                 for i in range(cols) for j in range(rows)]
+    boundary = boundary or [(0.0, 0.0), (3.0 * cols + 2, 0.0), (3.0 * cols + 2, 3.0 * rows + 2), (0.0, 3.0 * rows + 2)]
+    return VisibilityPlanner(cfg, boundary, obstacles)
+
+
+def free_point_sampler(pl, rng):
+    """-> a function drawing one collision-free point of the planner's scene from ``rng``, as ``random_routes`` draws them: uniform in
+    the bounding box of the deflated boundary, strictly inside it and not within 0.25 m of an inflated obstacle."""
+    xs, ys = [p[0] for p in pl.boundary], [p[1] for p in pl.boundary]
+    grown = [offset_polygon(o, 0.25) for o in pl.obstacles]
+
+    def sample():
+        while True:
+            p = (rng.uniform(min(xs), max(xs)), rng.uniform(min(ys), max(ys)))
+            if _point_in_polygon(p, pl.boundary, strict=True) and not any(_point_in_polygon(p, o, strict=False) for o in grown):
+                return p
+    return sample
+
+
+def own_route_fleet(cfg, scene, B, seed, legs=1, plan=None, min_length=12.0):
+    """-> (routes, route_of, starts, idx0, legs): every robot its own start and goal, and ``legs`` legs each: B * legs routes, robot b's
+    the routes b * legs .. b * legs + legs - 1, a leg starting at the goal of the leg before.  ``route_of`` [B] is each robot's first
+    route, ``starts`` [B, 3] its start pose heading along the first segment, ``idx0`` 0 as the reference's, and the last entry is what
+    ``trajectory.Missions`` takes.  The points are collision free, drawn as ``random_routes`` draws them; ``plan`` =
+    ``(starts [n, 2], goals [n, 2]) -> frontend.PlanResult`` answers a leg's queries at once: ``frontend.plan_batch_mirror`` on the scene's
+    planner by default, or the ``plan`` of a ``DevicePlanner`` built on ``scene_planner(cfg, scene)``.  A query without a path or
+    shorter than ``min_length`` is drawn again (both ends on the first leg, the goal on a later one), in robot order."""
+    pl = scene_planner(cfg, scene)
+    if plan is None:
+        plan = lambda s, g: plan_batch_mirror(pl, s, g)      # noqa: E731
+    sample = free_point_sampler(pl, np.random.Generator(np.random.PCG64(seed)))
+    points = np.empty((B, legs + 1, 2))
+    wp, n_wp = [None] * legs, [None] * legs
+    for k in range(legs):
+        todo = np.arange(B)
+        wp[k], n_wp[k] = np.empty((B, len(pl.nodes) + 2), dtype=np.int32), np.empty(B, dtype=np.int32)
+        for attempt in range(200):
+            for b in todo:
+                if k == 0:
+                    points[b, 0] = sample()
+                points[b, k + 1] = sample()
+            res = plan(points[todo, k], points[todo, k + 1])
+            wp[k][todo], n_wp[k][todo] = res.wp, res.n_wp
+            todo = todo[(res.n_wp == 0) | ~(res.length >= min_length)]
+            if not len(todo):
+                break
+        else:
+            raise RuntimeError(f"own_route_fleet: no route of {min_length} m from where robot {int(todo[0])} stands after 200 draws")
+    nodes = np.array(pl.nodes, dtype=np.float64).reshape(-1, 2)
+    routes = []
+    for b in range(B):
+        for k in range(legs):
+            pts = np.concatenate([points[b, k:k + 2], nodes])[wp[k][b, :n_wp[k][b]]]
+            th0 = math.atan2(pts[1][1] - pts[0][1], pts[1][0] - pts[0][0])
+            th1 = math.atan2(pts[-1][1] - pts[-2][1], pts[-1][0] - pts[-2][0])
+            one = PlanResult(n_wp[k][b:b + 1], wp[k][b:b + 1], None, None)
+            routes += plan_routes(pl, one, [(*points[b, k], th0)], [(*points[b, k + 1], th1)])
+    route_of = (np.arange(B) * legs).astype(np.int32)
+    starts = np.array([routes[r].start for r in route_of], dtype=np.float64).reshape(B, 3)
+    return routes, route_of, starts, np.zeros(B, dtype=np.int32), [list(range(r, r + legs)) for r in route_of]
 
 
 def tiled_fleet(routes, route_of, starts, idx0, copies):

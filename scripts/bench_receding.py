@@ -9,7 +9,10 @@ rest stay scripted.  --retire: robots that reach their goal leave the loop (nmpc
 active or after --steps steps, and reports the steps and solves it took.  --back: how close to the route's end robots may start
 (--routes 1); a small value gives a fleet whose robots arrive all through the run.  --monitor [G]: the clearance monitor (nmpc_loop_set_monitor,
 DESIGN.md section 5.9) in groups of G consecutive robots, default the --peers groups or 32; the result line then has, from its records, the shares
-of robots that were inside a circle, inside a padded ellipse and closer to a groupmate than two peer radii, and the fleet's smallest value of each.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+of robots that were inside a circle, inside a padded ellipse and closer to a groupmate than two peer radii, and the fleet's smallest value of each.
+--own-routes: every robot its own start and goal (workloads.own_route_fleet, seed 0), with --retire --legs L its own mission of L legs, each leg
+from the goal of the one before; the routes are planned on the device (frontend.DevicePlanner), and the result line
+gains plan_ms (the planner kernels' time over all batches, redraws included) and routes_planned.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -47,6 +50,9 @@ ap.add_argument("--retire", action="store_true",
 ap.add_argument("--legs", type=int, default=1, metavar="L",
                 help="with --retire: every robot drives a mission of L legs (nmpc_loop_set_missions), its route and the same route "
                      "driven backwards in turn, and retires after the last; the result line gains legs_done")
+ap.add_argument("--own-routes", action="store_true",
+                help="device loop only: every robot its own start and goal (and, with --legs L, its own L legs), planned on the device; "
+                     "takes the place of --routes")
 ap.add_argument("--monitor", type=int, nargs="?", const=0, default=None, metavar="G",
                 help="device loop only: keep every robot's closest approach to circles, scripted ellipses and the robots of its group of G "
                      "consecutive robots (of a sub-fleet) on the device, and report them; G defaults to the --peers groups, or 32")
@@ -61,6 +67,8 @@ if args.monitor is not None:
     args.monitor = args.monitor or args.peers or 32
 if args.legs < 1 or (args.legs > 1 and (not args.retire or args.host)):
     ap.error("--legs L: L >= 1, and L > 1 needs --retire on the device loop")
+if args.own_routes and (args.host or args.routes != 1):
+    ap.error("--own-routes: on the device loop, and in place of --routes")
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
@@ -82,7 +90,23 @@ def monitor_of(n):
     return Monitor(group_of=(np.arange(n) // args.monitor).astype(np.int32)) if args.monitor else None
 
 
-if args.routes == 1:
+planning = {}
+legs_of = None
+if args.own_routes:
+    from mpc_trajectory_generator_amd.frontend import DevicePlanner, scene_planner
+    from mpc_trajectory_generator_amd.workloads import fleet_ellipses, own_route_fleet
+    dp = DevicePlanner(scene_planner(cfg, args.scene), max_batch=B)
+    planning = {"plan_ms": 0.0, "routes_planned": 0}
+
+    def plan(s, g):
+        res = dp.plan(s, g)
+        planning["plan_ms"] += dp.last_ms
+        return res
+    routes, route_of, starts, i0, legs_of = own_route_fleet(cfg, args.scene, B, 0, legs=args.legs, plan=plan)
+    dp.close()
+    planning["routes_planned"] = len(routes)
+    dyn = fleet_ellipses(routes, route_of, i0, K, seed=1)      # ellipses crossing each robot's first route
+elif args.routes == 1:
     route = harness.scene_route(cfg, args.scene)
     i0, starts, dyn = route_fleet(route, B, 0, K, back=args.back)
     routes, route_of = route, None
@@ -97,12 +121,23 @@ else:
     jj = first[:, None] + np.minimum(n[:, None] - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
     dyn = moving_ellipses(np.stack([xs[jj], ys[jj]], axis=2), rng)
 fleet = f", {args.routes} routes (frontend.random_fleet, seed 0)" if args.routes > 1 else ""
+if args.own_routes:
+    fleet = f", every robot its own start and goal (workloads.own_route_fleet, seed 0; {len(routes)} routes planned on the device)"
 if args.peers:
     fleet += (f", {K} scripted ellipses and {args.peer_slots} peer slots per robot, groups of {args.peers} consecutive robots, "
               f"range {args.peer_range} m, radii {peer_radius} m")
 solver = BatchSolver(cfg, max_batch=B, **sopts)
 missions_of = lambda ids: None
-if args.legs > 1:
+routes_of = lambda ids: (routes, None if route_of is None else route_of[ids])
+if args.own_routes:
+    # a sub-fleet takes its own robots' routes only: robot b's are b * L .. b * L + L - 1, and the sub-fleets are runs of consecutive robots
+    from mpc_trajectory_generator_amd.trajectory import Missions
+    L = args.legs
+    routes_of = lambda ids: (routes[ids[0] * L:(ids[-1] + 1) * L], route_of[ids] - ids[0] * L)
+    if L > 1:
+        missions_of = lambda ids: Missions([[r - ids[0] * L for r in legs_of[b]] for b in ids])
+        fleet += f", missions of {L} legs"
+elif args.legs > 1:
     # route r driven backwards is route R + r: the same waypoints and circles from the goal to the start
     from mpc_trajectory_generator_amd.trajectory import Missions
     fwd = [routes] if route_of is None else list(routes)
@@ -121,8 +156,9 @@ if not args.host:
     loops, streams = [], []
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
-        loops.append(DeviceRecedingHorizon(sv, routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
-                                           route_of=None if route_of is None else route_of[ids], peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
+        sub_routes, sub_route_of = routes_of(ids)
+        loops.append(DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
+                                           route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
                                            missions=missions_of(ids)))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
@@ -179,7 +215,7 @@ if not args.host:
         "ms_per_step": 1e3 * total / max(steps - 1, 1), "mean_inner_iters_first_step": float(st0["num_inner_iterations"].mean()),
         "mean_inner_iters_last_step": float(st["num_inner_iterations"].mean()),
         "converged_frac_last_step": float((st["exit_status"] == 0).mean()),
-        "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum()), **quality}))
+        "out_of_time_frac_last_step": float((st["exit_status"] == 2).mean()), "robots_at_goal": int(done.sum()), **quality, **planning}))
     sys.exit(0)
 if route_of is None and not args.peers:
     rh = VectorizedRecedingHorizon(routes, starts, dyn, idx0=i0)
