@@ -1,4 +1,4 @@
-// nmpc_host.h -- what the host side of the C ABI (nmpc_kernels.hip) owns on a device: memory, pinned host memory and events, each released
+// nmpc_host.h -- what the host side of the C ABI (nmpc_kernels.hip, nmpc_loop_host.h, nmpc_plan_host.h) owns on a device: memory, pinned host memory and events, each released
 // with the struct that holds it, so that no list of frees follows the structs by hand.  Not copyable; move assignment only, which is what
 // a group of them uses to let go of everything it holds (`*this = {}`).
 #pragma once
@@ -14,6 +14,18 @@ struct DevBuf {          // n elements of T on the current device
     DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
     ~DevBuf() { (void)hipFree(p); }
     hipError_t alloc(size_t n) { return hipMalloc((void **)&p, n * sizeof(T)); }      // (of an empty one)
+    hipError_t alloc_fill(size_t n, int byte)          // alloc + every byte set
+    {
+        const hipError_t e = alloc(n);
+        return e == hipSuccess ? hipMemset(p, byte, n * sizeof(T)) : e;
+    }
+    hipError_t upload(const T *src, size_t n)          // alloc + n elements from host memory
+    {
+        const hipError_t e = alloc(n);
+        return e == hipSuccess ? hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) : e;
+    }
+    // n elements to host memory; dst NULL: the caller did not ask for them
+    hipError_t read(T *dst, size_t n) const { return dst ? hipMemcpy(dst, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess; }
     operator T *() const { return p; }
 };
 

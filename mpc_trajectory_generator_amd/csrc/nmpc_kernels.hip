@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -575,682 +576,16 @@ int nmpc_eval_batch_host(nmpc_handle *h, int B, const double *p, const double *u
                                 g.grad, g.F1, g.F2, nullptr);
     if (rc) return rc;
     HIP_TRY(h, hipDeviceSynchronize());
-    if (psi) HIP_TRY(h, hipMemcpy(psi, g.psi, B * 8, hipMemcpyDeviceToHost));
-    if (grad) HIP_TRY(h, hipMemcpy(grad, g.grad, B * nu * 8, hipMemcpyDeviceToHost));
-    if (F1) HIP_TRY(h, hipMemcpy(F1, g.F1, B * n1 * 8, hipMemcpyDeviceToHost));
-    if (F2 && n2) HIP_TRY(h, hipMemcpy(F2, g.F2, B * n2 * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(h, g.psi.read(psi, B));
+    HIP_TRY(h, g.grad.read(grad, B * nu));
+    HIP_TRY(h, g.F1.read(F1, B * n1));
+    if (n2) HIP_TRY(h, g.F2.read(F2, B * n2));
     return NMPC_OK;
 }
 
-// ---- receding-horizon loop on device (nmpc_loop.h) ----
-struct nmpc_loop {
-    nmpc_handle *h = nullptr;
-    nmpc::LoopArgs a{};          // device pointers and constants; t / dyn_in / dyn_out / traj_row change per step
-    int steps = 0, max_steps = 0;
-    DevBuf<double> d_tab;        // every route's tables, one allocation
-    DevBuf<nmpc::LoopRoute> d_routes;   // [R]
-    DevBuf<int> d_route_of;      // [B]
-    DevBuf<double> d_dynpar, d_state, d_last_u, d_dyn[2], d_P, d_U, d_Y, d_traj;
-    DevBuf<int> d_idx;
-    DevBuf<unsigned char> d_done;
-    DevBuf<nmpc_status> d_st;
-    bool peers = false;          // nmpc_loop_set_peers: two more kernels per step, between the assembly and the solve
-    nmpc::PeerArgs pa{};
-    DevBuf<double> d_pred;       // [B][N][3]
-    DevBuf<int> d_group_of, d_goff, d_gmem;
-    // nmpc_loop_set_retire: robots at their goal leave the loop.  A step runs over the active list, the solve over gathered rows, and
-    // the host learns the list's length one step late (nmpc_loop.h)
-    bool retire_called = false, retire = false;
-    nmpc::RetireArgs ra{};
-    nmpc::PackArgs ga{};
-    DevBuf<int> d_act, d_nact, d_retired_at;
-    DevBuf<double> d_sP, d_sU, d_sY;
-    DevBuf<nmpc_status> d_sst;
-    PinBuf h_nact;               // one int: the active robots after the last compaction whose event was waited for
-    Event ev_nact;               // recorded behind the copy of the count
-    bool nact_pending = false;   // a copy is under way: wait for ev_nact before h_nact is read
-    bool monitor = false;        // nmpc_loop_set_monitor: one more kernel per step, after the advance
-    nmpc::MonitorArgs ma{};
-    DevBuf<int> d_mon_group_of, d_mon_goff, d_mon_gmem;
-    DevBuf<nmpc_clearance> d_clear;      // [B]
-    // nmpc_loop_set_missions: a robot at its goal takes up the next route of its mission; one more kernel per step, before the compaction
-    bool missions = false;
-    int R = 1;
-    std::vector<int> h_route_of;         // [B] as given at creation
-    nmpc::DispatchArgs da{};
-    DevBuf<int> d_leg_off, d_leg_route, d_leg, d_leg_at;
-    int n_legs = 0;                      // leg_off[B]
-};
-
-static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
-{
-    return r->n_ref >= 1 && r->n_vert >= 0 && r->n_brake >= 1 && r->num_steps_taken >= 1 && r->num_steps_taken <= h->pb.N &&
-           r->x_ref && r->y_ref && r->theta_ref && r->brake_vel && r->brake_dist && (r->n_vert == 0 || r->vert_xy);
-}
-
-int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const int32_t *route_of, int B, const double *starts,
-                         const int32_t *idx0, int K, const double *dyn, int max_steps, nmpc_loop **out)
-{
-    if (!h || !routes || !out || !starts) return NMPC_ERR_BAD_ARG;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (B < 1 || B > h->max_batch || K < 0 || K > h->pb.ndyn || (K > 0 && !dyn) || max_steps < 0)
-        return fail(h, NMPC_ERR_BAD_ARG, "bad loop arguments");
-    if (R < 1) return fail(h, NMPC_ERR_BAD_ARG, "R < 1: no route");
-    if (!route_of && R > 1) return fail(h, NMPC_ERR_BAD_ARG, "route_of == NULL with R > 1");
-    if (route_of) for (int b = 0; b < B; ++b) if (route_of[b] < 0 || route_of[b] >= R) return fail(h, NMPC_ERR_BAD_ARG, "route_of out of range");
-    size_t ntab = 0;
-    for (int i = 0; i < R; ++i) {
-        const nmpc_route *r = routes + i;
-        if (!route_ok(h, r)) return fail(h, NMPC_ERR_BAD_ARG, R == 1 ? "bad route" : ("bad route " + std::to_string(i)).c_str());
-        if (r->num_steps_taken != routes[0].num_steps_taken)
-            return fail(h, NMPC_ERR_BAD_ARG, "routes differ in num_steps_taken (the fleet moves in lock step)");
-        ntab += 3 * (size_t)r->n_ref + 2 * (size_t)r->n_vert + 2 * (size_t)r->n_brake;
-    }
-    if (ntab > 0x7fffffff) return fail(h, NMPC_ERR_BAD_ARG, "route tables too large");
-    if (idx0) for (int b = 0; b < B; ++b) if (idx0[b] < 0 || idx0[b] >= routes[route_of ? route_of[b] : 0].n_ref) return fail(h, NMPC_ERR_BAD_ARG, "idx0 out of range");
-    HIP_TRY(h, hipSetDevice(h->device));
-    nmpc_loop *l = new nmpc_loop();
-    l->h = h;
-    l->max_steps = max_steps;
-    l->R = R;
-    nmpc::LoopArgs &a = l->a;
-    a.B = B; a.N = h->pb.N; a.nobs = h->pb.nobs; a.ndyn = h->pb.ndyn; a.K = K;
-    a.n_p = nmpc_n_p(&h->pb); a.n_u = nmpc_n_u(&h->pb);
-    a.s = routes[0].num_steps_taken; a.t = 0;
-    a.ts = h->pb.ts;
-    const size_t n1 = nmpc_n1(&h->pb), ndynrow = (size_t)a.ndyn * a.N * 5;
-    hipError_t e = l->d_tab.alloc(ntab ? ntab : 1);
-    if (e == hipSuccess) e = l->d_routes.alloc(R);
-    if (e == hipSuccess) e = l->d_route_of.alloc(B);
-    if (e == hipSuccess) e = l->d_dynpar.alloc((size_t)B * (K ? K : 1) * 10);
-    if (e == hipSuccess) e = l->d_state.alloc((size_t)B * 3);
-    if (e == hipSuccess) e = l->d_last_u.alloc((size_t)B * 2);
-    if (e == hipSuccess) e = l->d_dyn[0].alloc((size_t)B * (ndynrow ? ndynrow : 1));
-    if (e == hipSuccess) e = l->d_dyn[1].alloc((size_t)B * (ndynrow ? ndynrow : 1));
-    if (e == hipSuccess) e = l->d_P.alloc((size_t)B * a.n_p);
-    if (e == hipSuccess) e = l->d_U.alloc((size_t)B * a.n_u);
-    if (e == hipSuccess) e = l->d_Y.alloc((size_t)B * n1);
-    if (e == hipSuccess) e = l->d_idx.alloc(B);
-    if (e == hipSuccess) e = l->d_done.alloc(B);
-    if (e == hipSuccess) e = l->d_st.alloc(B);
-    if (e == hipSuccess && max_steps > 0) e = l->d_traj.alloc(((size_t)max_steps * a.s + 1) * B * 3);
-    if (e != hipSuccess) { nmpc_loop_free(l); return fail(h, NMPC_ERR_HIP, "nmpc_loop_new: hipMalloc", e); }
-    // route tables, route after route: x_ref | y_ref | theta_ref | vertices | brake velocities | brake distances
-    std::vector<double> tab(ntab);
-    std::vector<nmpc::LoopRoute> desc(R);
-    size_t off = 0;
-    for (int i = 0; i < R; ++i) {
-        const nmpc_route *r = routes + i;
-        nmpc::LoopRoute &d = desc[i];
-        std::memset(&d, 0, sizeof(d));
-        auto put = [&](const double *src, size_t n) { const int at = (int)off; if (n) std::memcpy(tab.data() + off, src, 8 * n); off += n; return at; };
-        d.xr = put(r->x_ref, r->n_ref); d.yr = put(r->y_ref, r->n_ref); d.thr = put(r->theta_ref, r->n_ref);
-        d.vert = put(r->vert_xy, 2 * (size_t)r->n_vert);
-        d.bv = put(r->brake_vel, r->n_brake); d.bd = put(r->brake_dist, r->n_brake);
-        d.n_ref = r->n_ref; d.n_vert = r->n_vert; d.n_brake = r->n_brake;
-        for (int k = 0; k < 3; ++k) d.end[k] = r->end[k];
-        d.base = r->base_speed; d.radius = r->radius; d.pad = r->dyn_pad;
-        for (int k = 0; k < 10; ++k) d.w[k] = r->weights[k];
-    }
-    std::vector<int> rof(B, 0);
-    if (route_of) for (int b = 0; b < B; ++b) rof[b] = route_of[b];
-    l->h_route_of = rof;
-    e = ntab ? hipMemcpy(l->d_tab, tab.data(), ntab * 8, hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpy(l->d_routes, desc.data(), (size_t)R * sizeof(nmpc::LoopRoute), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(l->d_route_of, rof.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess && K) e = hipMemcpy(l->d_dynpar, dyn, (size_t)B * K * 10 * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(l->d_state, starts, (size_t)B * 3 * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && l->d_traj) e = hipMemcpy(l->d_traj, starts, (size_t)B * 3 * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(l->d_last_u, 0, (size_t)B * 2 * 8);
-    if (e == hipSuccess) e = hipMemset(l->d_U, 0, (size_t)B * a.n_u * 8);
-    if (e == hipSuccess) e = hipMemset(l->d_Y, 0, (size_t)B * n1 * 8);
-    if (e == hipSuccess) e = idx0 ? hipMemcpy(l->d_idx, idx0, (size_t)B * sizeof(int), hipMemcpyHostToDevice)
-                                  : hipMemset(l->d_idx, 0, (size_t)B * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(l->d_done, 0, (size_t)B);
-    if (e == hipSuccess) e = hipMemset(l->d_st, 0, (size_t)B * sizeof(nmpc_status));
-    if (e == hipSuccess && ndynrow) {          // padding block: zeros with unit radii (path_generator.py:274-280)
-        std::vector<double> pad((size_t)B * ndynrow, 0.0);
-        for (size_t i = 0; i < pad.size(); i += 5) { pad[i + 2] = 1.0; pad[i + 3] = 1.0; }
-        e = hipMemcpy(l->d_dyn[0], pad.data(), pad.size() * 8, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) { nmpc_loop_free(l); return fail(h, NMPC_ERR_HIP, "nmpc_loop_new: initialisation", e); }
-    a.tab = l->d_tab; a.routes = l->d_routes; a.route_of = l->d_route_of;
-    a.dynpar = l->d_dynpar; a.state = l->d_state; a.last_u = l->d_last_u; a.idx = l->d_idx;
-    a.P = l->d_P; a.U = l->d_U; a.done = l->d_done; a.traj = l->d_traj; a.traj_row = 1;
-    a.act = nullptr; a.nact = B;
-    *out = l;
-    return NMPC_OK;
-}
-
-int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *starts, const int32_t *idx0, int K,
-                  const double *dyn, int max_steps, nmpc_loop **out)
-{
-    return nmpc_loop_new_routes(h, r, 1, nullptr, B, starts, idx0, K, dyn, max_steps, out);
-}
-
-// member lists of the groups 0 .. B - 1 (most of them empty; group_of NULL: everybody in group 0), each group's robots in ascending
-// index, on the device: group_of [B], goff [B + 1], gmem [B] (PeerArgs)
-static hipError_t upload_groups(const int32_t *group_of, int B, DevBuf<int> &d_gof, DevBuf<int> &d_goff, DevBuf<int> &d_gmem)
-{
-    std::vector<int> gof(B, 0), goff(B + 1, 0), gmem(B);
-    if (group_of) for (int b = 0; b < B; ++b) gof[b] = group_of[b];
-    for (int b = 0; b < B; ++b) goff[gof[b] + 1]++;
-    for (int g = 0; g < B; ++g) goff[g + 1] += goff[g];
-    {
-        std::vector<int> at(goff.begin(), goff.end() - 1);
-        for (int b = 0; b < B; ++b) gmem[at[gof[b]]++] = b;
-    }
-    hipError_t e = d_gof.alloc(B);
-    if (e == hipSuccess) e = d_goff.alloc(B + 1);
-    if (e == hipSuccess) e = d_gmem.alloc(B);
-    if (e == hipSuccess) e = hipMemcpy(d_gof, gof.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_goff, goff.data(), (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_gmem, gmem.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
-    return e;
-}
-
-int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    const nmpc::LoopArgs &a = l->a;
-    const int B = a.B;
-    if (l->peers) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: the loop has its peers already");
-    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: after the loop's first step");
-    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: M < 1");
-    if (a.K + M > a.ndyn) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: K + M > Ndynobs, no free ellipse slot");
-    for (const double v : {rx, ry, range})
-        if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: rx, ry and range must be finite and positive");
-    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: group_of out of range");
-    HIP_TRY(h, hipSetDevice(h->device));
-    DevBuf<double> pred;
-    DevBuf<int> d_gof, d_goff, d_gmem;
-    hipError_t e = pred.alloc((size_t)B * a.N * 3);
-    if (e == hipSuccess) e = upload_groups(group_of, B, d_gof, d_goff, d_gmem);
-    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_peers: allocation", e);
-    l->d_pred = std::move(pred); l->d_group_of = std::move(d_gof); l->d_goff = std::move(d_goff); l->d_gmem = std::move(d_gmem);
-    nmpc::PeerArgs &p = l->pa;
-    p.B = B; p.N = a.N; p.n_p = a.n_p; p.n_u = a.n_u; p.s = a.s; p.K = a.K; p.M = M;
-    p.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
-    p.ts = a.ts; p.rx = rx; p.ry = ry; p.range2 = range * range;
-    p.state = l->d_state; p.U = l->d_U; p.pred = l->d_pred;
-    p.group_of = l->d_group_of; p.goff = l->d_goff; p.gmem = l->d_gmem; p.P = l->d_P;
-    p.act = nullptr; p.nact = B;
-    l->peers = true;
-    return NMPC_OK;
-}
-
-int nmpc_loop_set_retire(nmpc_loop *l, int on)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (l->retire_called) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_retire: called already");
-    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_retire: after the loop's first step");
-    if (!on) { l->retire_called = true; return NMPC_OK; }
-    const nmpc::LoopArgs &a = l->a;
-    const size_t B = (size_t)a.B, n1 = (size_t)nmpc_n1(&h->pb);
-    HIP_TRY(h, hipSetDevice(h->device));
-    DevBuf<int> act, nact, at;
-    DevBuf<double> sP, sU, sY;
-    DevBuf<nmpc_status> sst;
-    PinBuf pin;
-    Event ev;
-    std::vector<int> all(B);
-    for (size_t b = 0; b < B; ++b) all[b] = (int)b;
-    hipError_t e = act.alloc(B);
-    if (e == hipSuccess) e = nact.alloc(1);
-    if (e == hipSuccess) e = at.alloc(B);
-    if (e == hipSuccess) e = sP.alloc(B * a.n_p);
-    if (e == hipSuccess) e = sU.alloc(B * a.n_u);
-    if (e == hipSuccess) e = sY.alloc(B * n1);
-    if (e == hipSuccess) e = sst.alloc(B);
-    if (e == hipSuccess) e = pin.alloc(sizeof(int));
-    if (e == hipSuccess) e = ev.create(hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemcpy(act, all.data(), B * sizeof(int), hipMemcpyHostToDevice);      // everybody is active at step 0
-    if (e == hipSuccess) e = hipMemcpy(nact, &a.B, sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(at, 0xFF, B * sizeof(int));                                    // retired_at = -1
-    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_retire: allocation", e);
-    *(int *)pin.p = a.B;
-    l->d_act = std::move(act); l->d_nact = std::move(nact); l->d_retired_at = std::move(at);
-    l->d_sP = std::move(sP); l->d_sU = std::move(sU); l->d_sY = std::move(sY); l->d_sst = std::move(sst);
-    l->h_nact = std::move(pin); l->ev_nact = std::move(ev);
-    nmpc::RetireArgs &r = l->ra;
-    r.B = a.B; r.N = a.N; r.s = a.s;
-    r.done = l->d_done; r.state = l->d_state; r.retired_at = l->d_retired_at; r.act = l->d_act; r.nact = l->d_nact;
-    r.traj = l->d_traj;
-    nmpc::PackArgs &g = l->ga;
-    g.n_p = a.n_p; g.n_u = a.n_u; g.n1 = (int)n1;
-    g.act = l->d_act; g.P = l->d_P; g.U = l->d_U; g.Y = l->d_Y; g.st = l->d_st;
-    g.sP = l->d_sP; g.sU = l->d_sU; g.sY = l->d_sY; g.sst = l->d_sst;
-    l->retire_called = l->retire = true;
-    return NMPC_OK;
-}
-
-static const nmpc_clearance CLEARANCE_NONE = {__builtin_inf(), __builtin_inf(), __builtin_inf(), -1, -1, -1, -1};
-
-int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    const nmpc::LoopArgs &a = l->a;
-    const int B = a.B;
-    if (l->monitor) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: the loop has its monitor already");
-    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: after the loop's first step");
-    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: the loop records no trajectory (max_steps == 0)");
-    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: group_of out of range");
-    HIP_TRY(h, hipSetDevice(h->device));
-    DevBuf<int> d_gof, d_goff, d_gmem;
-    DevBuf<nmpc_clearance> rec;
-    const std::vector<nmpc_clearance> none(B, CLEARANCE_NONE);
-    hipError_t e = rec.alloc(B);
-    if (e == hipSuccess) e = upload_groups(group_of, B, d_gof, d_goff, d_gmem);
-    if (e == hipSuccess) e = hipMemcpy(rec, none.data(), (size_t)B * sizeof(nmpc_clearance), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_monitor: allocation", e);
-    l->d_clear = std::move(rec); l->d_mon_group_of = std::move(d_gof); l->d_mon_goff = std::move(d_goff); l->d_mon_gmem = std::move(d_gmem);
-    nmpc::MonitorArgs &m = l->ma;
-    m.B = B; m.N = a.N; m.nobs = a.nobs; m.K = a.K; m.n_p = a.n_p; m.s = a.s;
-    m.pcirc = nmpc::NZ + a.N; m.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
-    m.P = l->d_P; m.state = l->d_state; m.traj = l->d_traj;
-    m.retired_at = nullptr;          // the step fills it in: nmpc_loop_set_retire may come after this call
-    m.group_of = l->d_mon_group_of; m.goff = l->d_mon_goff; m.gmem = l->d_mon_gmem;
-    m.rec = l->d_clear;
-    m.act = nullptr;
-    l->monitor = true;
-    return NMPC_OK;
-}
-
-int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *leg_route)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    const nmpc::LoopArgs &a = l->a;
-    const int B = a.B;
-    if (!leg_off || !leg_route) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off or leg_route is NULL");
-    if (!l->retire) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: the loop does not retire its robots (nmpc_loop_set_retire first)");
-    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: after the loop's first step");
-    if (l->missions) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: the loop has its missions already");
-    if (leg_off[0] != 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off[0] != 0");
-    for (int b = 0; b < B; ++b)
-        if (leg_off[b + 1] <= leg_off[b]) return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_missions: robot " + std::to_string(b) + " has no leg").c_str());
-    const int T = leg_off[B];
-    for (int i = 0; i < T; ++i)
-        if (leg_route[i] < 0 || leg_route[i] >= l->R) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_route out of range");
-    for (int b = 0; b < B; ++b)
-        if (leg_route[leg_off[b]] != l->h_route_of[b])
-            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_missions: the first leg of robot " + std::to_string(b) + " is not its route_of").c_str());
-    HIP_TRY(h, hipSetDevice(h->device));
-    DevBuf<int> off, route, leg, at;
-    hipError_t e = off.alloc((size_t)B + 1);
-    if (e == hipSuccess) e = route.alloc(T);
-    if (e == hipSuccess) e = leg.alloc(B);
-    if (e == hipSuccess) e = at.alloc(T);
-    if (e == hipSuccess) e = hipMemcpy(off, leg_off, ((size_t)B + 1) * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(route, leg_route, (size_t)T * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(leg, 0, (size_t)B * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(at, 0xFF, (size_t)T * sizeof(int));                            // leg_at = -1
-    if (e != hipSuccess) return fail(h, NMPC_ERR_HIP, "nmpc_loop_set_missions: allocation", e);
-    l->d_leg_off = std::move(off); l->d_leg_route = std::move(route); l->d_leg = std::move(leg); l->d_leg_at = std::move(at);
-    l->n_legs = T;
-    nmpc::DispatchArgs &d = l->da;
-    d.n_u = a.n_u; d.n1 = nmpc_n1(&h->pb);
-    d.act = l->d_act; d.done = l->d_done;
-    d.leg_off = l->d_leg_off; d.leg_route = l->d_leg_route; d.leg = l->d_leg; d.leg_at = l->d_leg_at;
-    d.route_of = l->d_route_of; d.idx = l->d_idx; d.last_u = l->d_last_u; d.U = l->d_U; d.Y = l->d_Y;
-    l->missions = true;
-    return NMPC_OK;
-}
-
-void nmpc_loop_free(nmpc_loop *l)
-{
-    if (!l) return;
-    (void)hipSetDevice(l->h->device);
-    delete l;
-}
-
-// the loop's readers: on its device, after everything enqueued there has finished
-static int loop_settle(nmpc_handle *h)
-{
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipDeviceSynchronize());
-    return NMPC_OK;
-}
-
-// a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
-static int loop_nactive(nmpc_loop *l, int *n)
-{
-    if (l->nact_pending) {
-        HIP_TRY(l->h, hipEventSynchronize(l->ev_nact));
-        l->nact_pending = false;
-    }
-    *n = *(const int *)l->h_nact.p;
-    return NMPC_OK;
-}
-
-// the monitor's kernel over the n robots the step's advance ran over (LoopArgs::act as the advance saw it; the compaction comes after)
-static void launch_monitor(nmpc_loop *l, int n, hipStream_t s)
-{
-    nmpc::MonitorArgs &m = l->ma;
-    m.traj_row = l->a.traj_row;
-    m.act = l->a.act;
-    m.retired_at = l->retire ? l->d_retired_at.p : nullptr;
-    hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, m);
-}
-
-// one step of a retiring loop: the kernels of nmpc_loop_step over the active list, the solve on gathered rows, then the compaction
-static int loop_step_retiring(nmpc_loop *l, void *stream)
-{
-    nmpc_handle *h = l->h;
-    hipStream_t s = (hipStream_t)stream;
-    nmpc::LoopArgs &a = l->a;
-    int n = 0;
-    if (const int rc = loop_nactive(l, &n)) return rc;
-    if (n < 0 || n > a.B) return fail(h, NMPC_ERR_HIP, "nmpc_loop_step: active count out of range");
-    a.act = l->d_act; a.nact = n;
-    if (n > 0) {
-        const int cur = l->steps & 1;
-        a.dyn_in = l->d_dyn[cur];
-        a.dyn_out = l->d_dyn[cur ^ 1];
-        hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, a);
-        if (l->peers) {
-            l->pa.act = l->d_act; l->pa.nact = n;
-            hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, l->pa);
-            hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, l->pa);
-        }
-        hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, l->ga);
-        HIP_TRY(h, hipGetLastError());
-        // the launch-order hint: the gathered statuses, i.e. the previous solves of these very robots
-        h->order_hint = (l->steps > 0 && h->loop_order_prev) ? l->d_sst.p : nullptr;
-        const int rc = nmpc_solve_batch_device(h, n, l->d_sP, l->d_sU, l->d_sY, nullptr, l->d_sY, l->d_sst, stream);
-        h->order_hint = nullptr;
-        if (rc) return rc;
-        hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, l->ga);
-        hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
-        if (l->monitor) launch_monitor(l, n, s);
-        if (l->missions) {
-            l->da.step = l->steps + 1;
-            hipLaunchKernelGGL(nmpc::nmpc_loop_dispatch_kernel, dim3(n), dim3(64), 0, s, l->da);
-        }
-    }
-    // (with nobody active the step still counts: the clock advances and the trajectory rows repeat)
-    nmpc::RetireArgs &r = l->ra;
-    r.step = l->steps + 1;
-    r.pred = l->peers ? l->d_pred.p : nullptr;
-    r.traj_row = a.traj_row;
-    hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, r);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(l->h_nact.p, l->d_nact.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipEventRecord(l->ev_nact, s));
-    l->nact_pending = true;
-    a.t += a.s;
-    a.traj_row += a.s;
-    l->steps++;
-    return NMPC_OK;
-}
-
-int nmpc_loop_step(nmpc_loop *l, void *stream)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (l->max_steps > 0 && l->steps >= l->max_steps) return fail(h, NMPC_ERR_BAD_ARG, "trajectory buffer is full");
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (l->retire) return loop_step_retiring(l, stream);
-    nmpc::LoopArgs &a = l->a;
-    const int cur = l->steps & 1;
-    a.dyn_in = l->d_dyn[cur];
-    a.dyn_out = l->d_dyn[cur ^ 1];
-    hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(a.B), dim3(64), 0, s, a);
-    HIP_TRY(h, hipGetLastError());
-    if (l->peers) {
-        hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, l->pa);
-        hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(a.B), dim3(64), 0, s, l->pa);
-        HIP_TRY(h, hipGetLastError());
-    }
-    // warm start: previous controls and multipliers, penalty back to its initial value (the server's behaviour)
-    // launch order: from the second step on, by the pass counts of the step before (read by the classification kernel ahead of the solve, which
-    // then overwrites them); the first step has only the inputs to go by
-    h->order_hint = (l->steps > 0 && h->loop_order_prev) ? l->d_st.p : nullptr;
-    const int rc = nmpc_solve_batch_device(h, a.B, l->d_P, l->d_U, l->d_Y, nullptr, l->d_Y, l->d_st, stream);
-    h->order_hint = nullptr;
-    if (rc) return rc;
-    hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, a);
-    if (l->monitor) launch_monitor(l, a.B, s);
-    HIP_TRY(h, hipGetLastError());
-    a.t += a.s;
-    a.traj_row += a.s;
-    l->steps++;
-    return NMPC_OK;
-}
-
-int nmpc_loop_run(nmpc_loop *l, int max_steps, void *stream)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
-    if (!l->retire) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_run: the loop does not retire its robots, it would never end");
-    if (max_steps < 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_run: max_steps < 0");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int taken = 0;
-    while (taken < max_steps && !(l->max_steps > 0 && l->steps >= l->max_steps)) {
-        int n = 0;
-        if (const int rc = loop_nactive(l, &n)) return rc;
-        if (n == 0) break;
-        if (const int rc = nmpc_loop_step(l, stream)) return rc;
-        ++taken;
-    }
-    return taken;
-}
-
-int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (const int rc = loop_settle(h)) return rc;
-    const int B = l->a.B;
-    if (!l->retire) {
-        if (n_active) *n_active = B;
-        if (retired_at) for (int b = 0; b < B; ++b) retired_at[b] = -1;
-        return NMPC_OK;
-    }
-    if (n_active) HIP_TRY(h, hipMemcpy(n_active, l->d_nact, sizeof(int), hipMemcpyDeviceToHost));
-    if (retired_at) HIP_TRY(h, hipMemcpy(retired_at, l->d_retired_at, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
-    return NMPC_OK;
-}
-
-int nmpc_loop_legs(nmpc_loop *l, int32_t *leg, int32_t *route_of, int32_t *leg_at)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (const int rc = loop_settle(h)) return rc;
-    const size_t B = (size_t)l->a.B;
-    if (route_of) HIP_TRY(h, hipMemcpy(route_of, l->d_route_of, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (!l->missions) {
-        if (leg) for (size_t b = 0; b < B; ++b) leg[b] = 0;
-        return NMPC_OK;
-    }
-    if (leg) HIP_TRY(h, hipMemcpy(leg, l->d_leg, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (leg_at) HIP_TRY(h, hipMemcpy(leg_at, l->d_leg_at, (size_t)l->n_legs * sizeof(int), hipMemcpyDeviceToHost));
-    return NMPC_OK;
-}
-
-int nmpc_loop_clearance(nmpc_loop *l, nmpc_clearance *out)
-{
-    if (!l || !out) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (const int rc = loop_settle(h)) return rc;
-    const int B = l->a.B;
-    if (!l->monitor) {
-        for (int b = 0; b < B; ++b) out[b] = CLEARANCE_NONE;
-        return NMPC_OK;
-    }
-    HIP_TRY(h, hipMemcpy(out, l->d_clear, (size_t)B * sizeof(nmpc_clearance), hipMemcpyDeviceToHost));
-    return NMPC_OK;
-}
-
-int nmpc_loop_read(nmpc_loop *l, double *state, double *last_u, int32_t *idx, uint8_t *done, nmpc_status *status)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (const int rc = loop_settle(h)) return rc;
-    const size_t B = (size_t)l->a.B;
-    if (state) HIP_TRY(h, hipMemcpy(state, l->d_state, B * 3 * 8, hipMemcpyDeviceToHost));
-    if (last_u) HIP_TRY(h, hipMemcpy(last_u, l->d_last_u, B * 2 * 8, hipMemcpyDeviceToHost));
-    if (idx) HIP_TRY(h, hipMemcpy(idx, l->d_idx, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (done) HIP_TRY(h, hipMemcpy(done, l->d_done, B, hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(h, hipMemcpy(status, l->d_st, B * sizeof(nmpc_status), hipMemcpyDeviceToHost));
-    return NMPC_OK;
-}
-
-int nmpc_loop_params(nmpc_loop *l, double *p, double *u, double *y)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (const int rc = loop_settle(h)) return rc;
-    const size_t B = (size_t)l->a.B;
-    if (p) HIP_TRY(h, hipMemcpy(p, l->d_P, B * l->a.n_p * 8, hipMemcpyDeviceToHost));
-    if (u) HIP_TRY(h, hipMemcpy(u, l->d_U, B * l->a.n_u * 8, hipMemcpyDeviceToHost));
-    if (y) HIP_TRY(h, hipMemcpy(y, l->d_Y, B * (size_t)nmpc_n1(&h->pb) * 8, hipMemcpyDeviceToHost));
-    return NMPC_OK;
-}
-
-int nmpc_loop_trajectory(nmpc_loop *l, double *rows, int max_rows)
-{
-    if (!l || !rows) return NMPC_ERR_BAD_ARG;
-    nmpc_handle *h = l->h;
-    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "the loop was created without a trajectory buffer");
-    const int nrows = l->steps * l->a.s + 1;
-    if (max_rows < nrows) return fail(h, NMPC_ERR_BAD_ARG, "trajectory does not fit");
-    if (const int rc = loop_settle(h)) return rc;
-    HIP_TRY(h, hipMemcpy(rows, l->d_traj, (size_t)nrows * l->a.B * 3 * 8, hipMemcpyDeviceToHost));
-    return nrows;
-}
-
-// ---- a route per robot, planned on device (nmpc_plan.h) ----
-struct nmpc_planner {
-    int device = 0, max_batch = 0;
-    int V = 0, E = 0, n_poly = 0;
-    double last_ms = 0.0;
-    DevBuf<double> d_node, d_edge;
-    DevBuf<int> d_poff;
-    DevBuf<unsigned char> d_nn;          // [V][V]
-    DevBuf<unsigned char> d_qvis;        // [max_batch][2V + 1]: a batch's own segments when the caller keeps no copy
-    DevBuf<double> d_start, d_goal, d_len;      // the host path's operands
-    DevBuf<int> d_nwp, d_wp;
-    Event ev[2];
-};
-
-static constexpr int PLAN_MAX_BATCH = 1 << 20;      // max_batch * (2V + 1) segments are counted in an int
-
-static void launch_visible(const nmpc_planner *pl, int n_seg, bool queries, const double *d_start, const double *d_goal,
-                           unsigned char *out, hipStream_t s)
-{
-    nmpc::PlanVisArgs a{pl->V, pl->E, pl->n_poly, n_seg, queries ? 1 : 0, pl->d_node, pl->d_edge, pl->d_poff, d_start, d_goal, out};
-    const int blocks = (n_seg + nmpc::PLAN_VIS_BLOCK - 1) / nmpc::PLAN_VIS_BLOCK;
-    hipLaunchKernelGGL(nmpc::nmpc_plan_visible_kernel, dim3(blocks), dim3(nmpc::PLAN_VIS_BLOCK), 0, s, a);
-}
-
-int nmpc_planner_new(const nmpc_scene *sc, int device_id, int max_batch, nmpc_planner **out)
-{
-    if (!sc || !out || max_batch < 1 || max_batch > PLAN_MAX_BATCH) return NMPC_ERR_BAD_ARG;
-    const int V = sc->n_node, E = sc->n_edge, np = sc->n_poly;
-    if (V < 0 || V > nmpc::PLAN_MAX_NODES || E < 3 || E > nmpc::PLAN_MAX_EDGES || np < 1 || np > nmpc::PLAN_MAX_POLYS ||
-        !sc->edge || !sc->poly_off || (V > 0 && !sc->node_xy))
-        return NMPC_ERR_BAD_ARG;
-    if (sc->poly_off[0] != 0 || sc->poly_off[np] != E) return NMPC_ERR_BAD_ARG;
-    for (int k = 0; k < np; ++k)
-        if (sc->poly_off[k + 1] - sc->poly_off[k] < 3 || sc->poly_off[k + 1] > E) return NMPC_ERR_BAD_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) return NMPC_ERR_NO_DEVICE;
-    nmpc_planner *pl = new nmpc_planner();
-    pl->device = device_id; pl->max_batch = max_batch; pl->V = V; pl->E = E; pl->n_poly = np;
-    const size_t B = (size_t)max_batch, per = 2 * (size_t)V + 1;
-    hipError_t e = hipSetDevice(device_id);
-    if (e == hipSuccess) e = pl->d_node.alloc(2 * (size_t)(V > 0 ? V : 1));
-    if (e == hipSuccess) e = pl->d_edge.alloc(4 * (size_t)E);
-    if (e == hipSuccess) e = pl->d_poff.alloc(np + 1);
-    if (e == hipSuccess) e = pl->d_nn.alloc((size_t)(V > 0 ? V * V : 1));
-    if (e == hipSuccess) e = pl->d_qvis.alloc(B * per);
-    if (e == hipSuccess) e = pl->d_start.alloc(2 * B);
-    if (e == hipSuccess) e = pl->d_goal.alloc(2 * B);
-    if (e == hipSuccess) e = pl->d_len.alloc(B);
-    if (e == hipSuccess) e = pl->d_nwp.alloc(B);
-    if (e == hipSuccess) e = pl->d_wp.alloc(B * (size_t)(V + 2));
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = pl->ev[i].create();
-    if (e == hipSuccess && V > 0) e = hipMemcpy(pl->d_node, sc->node_xy, 2 * (size_t)V * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pl->d_edge, sc->edge, 4 * (size_t)E * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pl->d_poff, sc->poly_off, (size_t)(np + 1) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && V > 0) {
-        launch_visible(pl, V * V, false, nullptr, nullptr, pl->d_nn, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { nmpc_planner_free(pl); return NMPC_ERR_HIP; }
-    *out = pl;
-    return NMPC_OK;
-}
-
-void nmpc_planner_free(nmpc_planner *pl)
-{
-    if (!pl) return;
-    (void)hipSetDevice(pl->device);
-    delete pl;
-}
-
-double nmpc_planner_last_ms(const nmpc_planner *pl) { return pl ? pl->last_ms : 0.0; }
-
-int nmpc_planner_visibility(nmpc_planner *pl, uint8_t *vis)
-{
-    if (!pl || !vis) return NMPC_ERR_BAD_ARG;
-    HIP_TRY(nullptr, hipSetDevice(pl->device));
-    if (pl->V > 0) HIP_TRY(nullptr, hipMemcpy(vis, pl->d_nn, (size_t)pl->V * pl->V, hipMemcpyDeviceToHost));
-    return NMPC_OK;
-}
-
-int nmpc_plan_batch_device(nmpc_planner *pl, int B, const double *d_start, const double *d_goal, int32_t *d_n_wp, int32_t *d_wp,
-                           double *d_length, uint8_t *d_vis, void *stream)
-{
-    if (!pl || B < 0 || B > pl->max_batch) return NMPC_ERR_BAD_ARG;
-    if (B == 0) return NMPC_OK;
-    if (!d_start || !d_goal || !d_n_wp || !d_wp || !d_length) return NMPC_ERR_BAD_ARG;
-    HIP_TRY(nullptr, hipSetDevice(pl->device));
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char *vis = d_vis ? d_vis : pl->d_qvis.p;
-    launch_visible(pl, B * (2 * pl->V + 1), true, d_start, d_goal, vis, s);
-    HIP_TRY(nullptr, hipGetLastError());
-    nmpc::PlanPathArgs a{pl->V, pl->d_node, pl->d_nn, d_start, d_goal, vis, d_n_wp, d_wp, d_length};
-    hipLaunchKernelGGL(nmpc::nmpc_plan_path_kernel, dim3(B), dim3(64), 0, s, a);
-    HIP_TRY(nullptr, hipGetLastError());
-    return NMPC_OK;
-}
-
-int nmpc_plan_batch_host(nmpc_planner *pl, int B, const double *start, const double *goal, int32_t *n_wp, int32_t *wp, double *length,
-                         uint8_t *vis)
-{
-    if (!pl || B < 0 || B > pl->max_batch) return NMPC_ERR_BAD_ARG;
-    if (B == 0) return NMPC_OK;
-    if (!start || !goal || !n_wp || !wp || !length) return NMPC_ERR_BAD_ARG;
-    HIP_TRY(nullptr, hipSetDevice(pl->device));
-    const size_t n = (size_t)pl->V + 2, per = 2 * (size_t)pl->V + 1;
-    HIP_TRY(nullptr, hipMemcpy(pl->d_start, start, 2 * (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(nullptr, hipMemcpy(pl->d_goal, goal, 2 * (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(nullptr, hipEventRecord(pl->ev[0], nullptr));
-    if (const int rc = nmpc_plan_batch_device(pl, B, pl->d_start, pl->d_goal, pl->d_nwp, pl->d_wp, pl->d_len, nullptr, nullptr)) return rc;
-    HIP_TRY(nullptr, hipEventRecord(pl->ev[1], nullptr));
-    HIP_TRY(nullptr, hipEventSynchronize(pl->ev[1]));
-    float ms = 0.f;
-    HIP_TRY(nullptr, hipEventElapsedTime(&ms, pl->ev[0], pl->ev[1]));
-    pl->last_ms = ms;
-    HIP_TRY(nullptr, hipMemcpy(n_wp, pl->d_nwp, (size_t)B * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(nullptr, hipMemcpy(wp, pl->d_wp, (size_t)B * n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(nullptr, hipMemcpy(length, pl->d_len, (size_t)B * 8, hipMemcpyDeviceToHost));
-    if (vis) HIP_TRY(nullptr, hipMemcpy(vis, pl->d_qvis, (size_t)B * per, hipMemcpyDeviceToHost));
-    return NMPC_OK;
-}
+// ---- receding-horizon loop on device (kernels: nmpc_loop.h) and a route per robot, planned on device (kernels: nmpc_plan.h) ----
+#include "nmpc_loop_host.h"
+#include "nmpc_plan_host.h"
 
 // ---- arithmetic primitives, for bit-level checks against the oracle ----
 __global__ void nmpc_test_sincos_kernel(int n, const double *x, double *s, double *c)

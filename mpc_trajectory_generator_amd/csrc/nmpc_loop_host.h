@@ -1,0 +1,516 @@
+// nmpc_loop_host.h -- host side of the receding-horizon loop on device (its kernels: nmpc_loop.h): struct nmpc_loop and the nmpc_loop_*
+// entry points of include/nmpc_solver.h.  Part of the one translation unit: nmpc_kernels.hip includes it inside its extern "C" block,
+// after the handle, fail, HIP_TRY and nmpc_solve_batch_device.
+//
+// A loop is its base (assemble -> solve -> advance) plus up to four stages, each a sub-struct with its device buffers and its kernels'
+// argument block.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop
+// as it was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the
+// configuration final: loop_wire then sets every pointer one stage reads of another's, and nmpc_loop_step is ONE sequence of kernels
+// in which a stage adds its own.
+#pragma once
+
+// member lists of the groups 0 .. B - 1 (most of them empty), each group's robots in ascending index (PeerArgs, MonitorArgs)
+struct LoopGroups {
+    DevBuf<int> group_of, goff, gmem;      // [B], [B + 1], [B]
+    // group_of NULL: everybody in group 0
+    hipError_t upload(const int32_t *of, int B)
+    {
+        std::vector<int> gof(B, 0), off(B + 1, 0), mem(B);
+        if (of) for (int b = 0; b < B; ++b) gof[b] = of[b];
+        for (int b = 0; b < B; ++b) off[gof[b] + 1]++;
+        for (int g = 0; g < B; ++g) off[g + 1] += off[g];
+        {
+            std::vector<int> at(off.begin(), off.end() - 1);
+            for (int b = 0; b < B; ++b) mem[at[gof[b]]++] = b;
+        }
+        hipError_t e = group_of.upload(gof.data(), B);
+        if (e == hipSuccess) e = goff.upload(off.data(), (size_t)B + 1);
+        if (e == hipSuccess) e = gmem.upload(mem.data(), B);
+        return e;
+    }
+};
+struct LoopPeers {           // nmpc_loop_set_peers: two more kernels per step, between the assembly and the solve
+    nmpc::PeerArgs a{};
+    DevBuf<double> pred;     // [B][N][3]
+    LoopGroups groups;
+    bool made() const { return pred != nullptr; }
+};
+// nmpc_loop_set_retire: robots at their goal leave the loop.  A step runs over the active list, the solve over gathered rows, and
+// the host learns the list's length one step late (nmpc_loop.h)
+struct LoopRetire {
+    bool called = false;         // the setter has been taken, with on = 0 too
+    nmpc::RetireArgs a{};
+    nmpc::PackArgs pack{};
+    DevBuf<int> act, nact, retired_at;
+    DevBuf<double> sP, sU, sY;
+    DevBuf<nmpc_status> sst;
+    PinBuf h_nact;               // one int: the active robots after the last compaction whose event was waited for
+    Event ev_nact;               // recorded behind the copy of the count
+    bool nact_pending = false;   // a copy is under way: wait for ev_nact before h_nact is read
+    bool made() const { return act != nullptr; }
+};
+struct LoopMonitor {         // nmpc_loop_set_monitor: one more kernel per step, after the advance
+    nmpc::MonitorArgs a{};
+    LoopGroups groups;
+    DevBuf<nmpc_clearance> rec;      // [B]
+    bool made() const { return rec != nullptr; }
+};
+// nmpc_loop_set_missions: a robot at its goal takes up the next route of its mission; one more kernel per step, before the compaction
+struct LoopMissions {
+    nmpc::DispatchArgs a{};
+    DevBuf<int> leg_off, leg_route, leg, leg_at;
+    int n_legs = 0;                  // leg_off[B]
+    bool made() const { return leg_off != nullptr; }
+};
+
+struct nmpc_loop {
+    nmpc_handle *h = nullptr;
+    nmpc::LoopArgs a{};          // device pointers and constants; t / dyn_in / dyn_out / traj_row / nact change per step
+    int steps = 0, max_steps = 0;
+    int R = 1;
+    std::vector<int> h_route_of;         // [B] as given at creation
+    DevBuf<double> d_tab;        // every route's tables, one allocation
+    DevBuf<nmpc::LoopRoute> d_routes;   // [R]
+    DevBuf<int> d_route_of;      // [B]
+    DevBuf<double> d_dynpar, d_state, d_last_u, d_dyn[2], d_P, d_U, d_Y, d_traj;
+    DevBuf<int> d_idx;
+    DevBuf<unsigned char> d_done;
+    DevBuf<nmpc_status> d_st;
+    LoopPeers peers;
+    LoopRetire retire;
+    LoopMonitor monitor;
+    LoopMissions missions;
+};
+
+static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
+{
+    return r->n_ref >= 1 && r->n_vert >= 0 && r->n_brake >= 1 && r->num_steps_taken >= 1 && r->num_steps_taken <= h->pb.N &&
+           r->x_ref && r->y_ref && r->theta_ref && r->brake_vel && r->brake_dist && (r->n_vert == 0 || r->vert_xy);
+}
+
+void nmpc_loop_free(nmpc_loop *l)
+{
+    if (!l) return;
+    (void)hipSetDevice(l->h->device);
+    delete l;
+}
+
+int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const int32_t *route_of, int B, const double *starts,
+                         const int32_t *idx0, int K, const double *dyn, int max_steps, nmpc_loop **out)
+{
+    if (!h || !routes || !out || !starts) return NMPC_ERR_BAD_ARG;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (B < 1 || B > h->max_batch || K < 0 || K > h->pb.ndyn || (K > 0 && !dyn) || max_steps < 0)
+        return fail(h, NMPC_ERR_BAD_ARG, "bad loop arguments");
+    if (R < 1) return fail(h, NMPC_ERR_BAD_ARG, "R < 1: no route");
+    if (!route_of && R > 1) return fail(h, NMPC_ERR_BAD_ARG, "route_of == NULL with R > 1");
+    if (route_of) for (int b = 0; b < B; ++b) if (route_of[b] < 0 || route_of[b] >= R) return fail(h, NMPC_ERR_BAD_ARG, "route_of out of range");
+    size_t ntab = 0;
+    for (int i = 0; i < R; ++i) {
+        const nmpc_route *r = routes + i;
+        if (!route_ok(h, r)) return fail(h, NMPC_ERR_BAD_ARG, R == 1 ? "bad route" : ("bad route " + std::to_string(i)).c_str());
+        if (r->num_steps_taken != routes[0].num_steps_taken)
+            return fail(h, NMPC_ERR_BAD_ARG, "routes differ in num_steps_taken (the fleet moves in lock step)");
+        ntab += 3 * (size_t)r->n_ref + 2 * (size_t)r->n_vert + 2 * (size_t)r->n_brake;
+    }
+    if (ntab > 0x7fffffff) return fail(h, NMPC_ERR_BAD_ARG, "route tables too large");
+    if (idx0) for (int b = 0; b < B; ++b) if (idx0[b] < 0 || idx0[b] >= routes[route_of ? route_of[b] : 0].n_ref) return fail(h, NMPC_ERR_BAD_ARG, "idx0 out of range");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // (a return below releases what the loop holds so far, on its device)
+    std::unique_ptr<nmpc_loop, decltype(&nmpc_loop_free)> l(new nmpc_loop(), nmpc_loop_free);
+    l->h = h;
+    l->max_steps = max_steps;
+    l->R = R;
+    nmpc::LoopArgs &a = l->a;
+    a.B = B; a.N = h->pb.N; a.nobs = h->pb.nobs; a.ndyn = h->pb.ndyn; a.K = K;
+    a.n_p = nmpc_n_p(&h->pb); a.n_u = nmpc_n_u(&h->pb);
+    a.s = routes[0].num_steps_taken; a.t = 0;
+    a.ts = h->pb.ts;
+    const size_t n1 = nmpc_n1(&h->pb), ndynrow = (size_t)a.ndyn * a.N * 5;
+    // route tables, route after route: x_ref | y_ref | theta_ref | vertices | brake velocities | brake distances
+    std::vector<double> tab(ntab);
+    std::vector<nmpc::LoopRoute> desc(R);
+    size_t off = 0;
+    for (int i = 0; i < R; ++i) {
+        const nmpc_route *r = routes + i;
+        nmpc::LoopRoute &d = desc[i];
+        std::memset(&d, 0, sizeof(d));
+        auto put = [&](const double *src, size_t n) { const int at = (int)off; if (n) std::memcpy(tab.data() + off, src, 8 * n); off += n; return at; };
+        d.xr = put(r->x_ref, r->n_ref); d.yr = put(r->y_ref, r->n_ref); d.thr = put(r->theta_ref, r->n_ref);
+        d.vert = put(r->vert_xy, 2 * (size_t)r->n_vert);
+        d.bv = put(r->brake_vel, r->n_brake); d.bd = put(r->brake_dist, r->n_brake);
+        d.n_ref = r->n_ref; d.n_vert = r->n_vert; d.n_brake = r->n_brake;
+        for (int k = 0; k < 3; ++k) d.end[k] = r->end[k];
+        d.base = r->base_speed; d.radius = r->radius; d.pad = r->dyn_pad;
+        for (int k = 0; k < 10; ++k) d.w[k] = r->weights[k];
+    }
+    l->h_route_of.assign(B, 0);
+    if (route_of) l->h_route_of.assign(route_of, route_of + B);
+    HIP_TRY(h, l->d_tab.upload(tab.data(), ntab));
+    HIP_TRY(h, l->d_routes.upload(desc.data(), R));
+    HIP_TRY(h, l->d_route_of.upload(l->h_route_of.data(), B));
+    if (K) HIP_TRY(h, l->d_dynpar.upload(dyn, (size_t)B * K * 10));
+    else HIP_TRY(h, l->d_dynpar.alloc(10 * (size_t)B));
+    HIP_TRY(h, l->d_state.upload(starts, (size_t)B * 3));
+    if (max_steps > 0) {
+        HIP_TRY(h, l->d_traj.alloc(((size_t)max_steps * a.s + 1) * B * 3));
+        HIP_TRY(h, hipMemcpy(l->d_traj, starts, (size_t)B * 3 * 8, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(h, l->d_last_u.alloc_fill((size_t)B * 2, 0));
+    HIP_TRY(h, l->d_P.alloc((size_t)B * a.n_p));
+    HIP_TRY(h, l->d_U.alloc_fill((size_t)B * a.n_u, 0));
+    HIP_TRY(h, l->d_Y.alloc_fill((size_t)B * n1, 0));
+    if (idx0) HIP_TRY(h, l->d_idx.upload(idx0, B));
+    else HIP_TRY(h, l->d_idx.alloc_fill(B, 0));
+    HIP_TRY(h, l->d_done.alloc_fill(B, 0));
+    HIP_TRY(h, l->d_st.alloc_fill(B, 0));
+    {          // padding block: zeros with unit radii (path_generator.py:274-280)
+        std::vector<double> pad(B * (ndynrow ? ndynrow : 1), 0.0);
+        for (size_t i = 0; ndynrow && i < pad.size(); i += 5) { pad[i + 2] = 1.0; pad[i + 3] = 1.0; }
+        HIP_TRY(h, l->d_dyn[0].upload(pad.data(), pad.size()));
+        HIP_TRY(h, l->d_dyn[1].alloc(pad.size()));
+    }
+    a.tab = l->d_tab; a.routes = l->d_routes; a.route_of = l->d_route_of;
+    a.dynpar = l->d_dynpar; a.state = l->d_state; a.last_u = l->d_last_u; a.idx = l->d_idx;
+    a.P = l->d_P; a.U = l->d_U; a.done = l->d_done; a.traj = l->d_traj; a.traj_row = 1;
+    a.act = nullptr; a.nact = B;
+    *out = l.release();
+    return NMPC_OK;
+}
+
+int nmpc_loop_new(nmpc_handle *h, const nmpc_route *r, int B, const double *starts, const int32_t *idx0, int K,
+                  const double *dyn, int max_steps, nmpc_loop **out)
+{
+    return nmpc_loop_new_routes(h, r, 1, nullptr, B, starts, idx0, K, dyn, max_steps, out);
+}
+
+// what every setter checks first, l != NULL given: a live handle, a loop that has not taken its first step and does not have
+// the setter's stage yet.  Leaves the loop's device current.
+static int loop_setter(nmpc_loop *l, const char *fn, bool has, const char *already)
+{
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (has) return fail(h, NMPC_ERR_BAD_ARG, (std::string(fn) + ": " + already).c_str());
+    if (l->steps > 0) return fail(h, NMPC_ERR_BAD_ARG, (std::string(fn) + ": after the loop's first step").c_str());
+    HIP_TRY(h, hipSetDevice(h->device));
+    return NMPC_OK;
+}
+
+int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_peers", l->peers.made(), "the loop has its peers already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopArgs &a = l->a;
+    const int B = a.B;
+    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: M < 1");
+    if (a.K + M > a.ndyn) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: K + M > Ndynobs, no free ellipse slot");
+    for (const double v : {rx, ry, range})
+        if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: rx, ry and range must be finite and positive");
+    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: group_of out of range");
+    LoopPeers st;
+    HIP_TRY(h, st.pred.alloc((size_t)B * a.N * 3));
+    HIP_TRY(h, st.groups.upload(group_of, B));
+    nmpc::PeerArgs &p = st.a;
+    p.B = B; p.N = a.N; p.n_p = a.n_p; p.n_u = a.n_u; p.s = a.s; p.K = a.K; p.M = M;
+    p.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
+    p.ts = a.ts; p.rx = rx; p.ry = ry; p.range2 = range * range;
+    p.state = l->d_state; p.U = l->d_U; p.pred = st.pred;
+    p.group_of = st.groups.group_of; p.goff = st.groups.goff; p.gmem = st.groups.gmem; p.P = l->d_P;
+    l->peers = std::move(st);
+    return NMPC_OK;
+}
+
+int nmpc_loop_set_retire(nmpc_loop *l, int on)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_retire", l->retire.called, "called already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopArgs &a = l->a;
+    const size_t B = (size_t)a.B, n1 = (size_t)nmpc_n1(&h->pb);
+    LoopRetire st;
+    st.called = true;
+    if (on) {
+        std::vector<int> all(B);
+        for (size_t b = 0; b < B; ++b) all[b] = (int)b;
+        HIP_TRY(h, st.act.upload(all.data(), B));                  // everybody is active at step 0
+        HIP_TRY(h, st.nact.upload(&a.B, 1));
+        HIP_TRY(h, st.retired_at.alloc_fill(B, 0xFF));             // retired_at = -1
+        HIP_TRY(h, st.sP.alloc(B * a.n_p));
+        HIP_TRY(h, st.sU.alloc(B * a.n_u));
+        HIP_TRY(h, st.sY.alloc(B * n1));
+        HIP_TRY(h, st.sst.alloc(B));
+        HIP_TRY(h, st.h_nact.alloc(sizeof(int)));
+        HIP_TRY(h, st.ev_nact.create(hipEventDisableTiming));
+        *(int *)st.h_nact.p = a.B;
+        nmpc::RetireArgs &r = st.a;
+        r.B = a.B; r.N = a.N; r.s = a.s;
+        r.done = l->d_done; r.state = l->d_state; r.retired_at = st.retired_at; r.act = st.act; r.nact = st.nact;
+        r.traj = l->d_traj;
+        nmpc::PackArgs &g = st.pack;
+        g.n_p = a.n_p; g.n_u = a.n_u; g.n1 = (int)n1;
+        g.act = st.act; g.P = l->d_P; g.U = l->d_U; g.Y = l->d_Y; g.st = l->d_st;
+        g.sP = st.sP; g.sU = st.sU; g.sY = st.sY; g.sst = st.sst;
+    }
+    l->retire = std::move(st);
+    return NMPC_OK;
+}
+
+static const nmpc_clearance CLEARANCE_NONE = {__builtin_inf(), __builtin_inf(), __builtin_inf(), -1, -1, -1, -1};
+
+int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_monitor", l->monitor.made(), "the loop has its monitor already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopArgs &a = l->a;
+    const int B = a.B;
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: the loop records no trajectory (max_steps == 0)");
+    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: group_of out of range");
+    LoopMonitor st;
+    const std::vector<nmpc_clearance> none(B, CLEARANCE_NONE);
+    HIP_TRY(h, st.rec.upload(none.data(), B));
+    HIP_TRY(h, st.groups.upload(group_of, B));
+    nmpc::MonitorArgs &m = st.a;
+    m.B = B; m.N = a.N; m.nobs = a.nobs; m.K = a.K; m.n_p = a.n_p; m.s = a.s;
+    m.pcirc = nmpc::NZ + a.N; m.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
+    m.P = l->d_P; m.state = l->d_state; m.traj = l->d_traj;
+    m.group_of = st.groups.group_of; m.goff = st.groups.goff; m.gmem = st.groups.gmem;
+    m.rec = st.rec;
+    l->monitor = std::move(st);
+    return NMPC_OK;
+}
+
+int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *leg_route)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_missions", l->missions.made(), "the loop has its missions already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopArgs &a = l->a;
+    const int B = a.B;
+    if (!leg_off || !leg_route) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off or leg_route is NULL");
+    if (!l->retire.made()) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: the loop does not retire its robots (nmpc_loop_set_retire first)");
+    if (leg_off[0] != 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off[0] != 0");
+    for (int b = 0; b < B; ++b)
+        if (leg_off[b + 1] <= leg_off[b]) return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_missions: robot " + std::to_string(b) + " has no leg").c_str());
+    const int T = leg_off[B];
+    for (int i = 0; i < T; ++i)
+        if (leg_route[i] < 0 || leg_route[i] >= l->R) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_route out of range");
+    for (int b = 0; b < B; ++b)
+        if (leg_route[leg_off[b]] != l->h_route_of[b])
+            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_missions: the first leg of robot " + std::to_string(b) + " is not its route_of").c_str());
+    LoopMissions st;
+    HIP_TRY(h, st.leg_off.upload(leg_off, (size_t)B + 1));
+    HIP_TRY(h, st.leg_route.upload(leg_route, T));
+    HIP_TRY(h, st.leg.alloc_fill(B, 0));
+    HIP_TRY(h, st.leg_at.alloc_fill(T, 0xFF));                     // leg_at = -1
+    st.n_legs = T;
+    nmpc::DispatchArgs &d = st.a;
+    d.n_u = a.n_u; d.n1 = nmpc_n1(&h->pb);
+    d.done = l->d_done;
+    d.leg_off = st.leg_off; d.leg_route = st.leg_route; d.leg = st.leg; d.leg_at = st.leg_at;
+    d.route_of = l->d_route_of; d.idx = l->d_idx; d.last_u = l->d_last_u; d.U = l->d_U; d.Y = l->d_Y;
+    l->missions = std::move(st);
+    return NMPC_OK;
+}
+
+// a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
+static int loop_nactive(nmpc_loop *l, int *n)
+{
+    LoopRetire &r = l->retire;
+    if (r.nact_pending) {
+        HIP_TRY(l->h, hipEventSynchronize(r.ev_nact));
+        r.nact_pending = false;
+    }
+    *n = *(const int *)r.h_nact.p;
+    return NMPC_OK;
+}
+
+// Run by step 0, when no setter can follow: the pointers that cross stages.  The robots a step runs over are the retirement's active
+// list (NULL without: everybody, row i is robot i), for the base and for every stage; the monitor reads retired_at as the step
+// found it, and the compaction parks a retired robot's predictions for the peers.  A stage that is not made has nothing to give (NULL).
+static void loop_wire(nmpc_loop *l)
+{
+    const int *act = l->retire.act;
+    l->a.act = l->peers.a.act = l->monitor.a.act = l->missions.a.act = act;
+    l->monitor.a.retired_at = l->retire.retired_at;
+    l->retire.a.pred = l->peers.pred;
+}
+
+// One step: assemble -> solve -> advance over the n robots still active, every stage's kernels where they belong.  Without retirement
+// n = B and the host waits for nothing; with it the step waits for the count of the step before (an event), solves on gathered rows
+// and rebuilds the active list behind the advance.
+int nmpc_loop_step(nmpc_loop *l, void *stream)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (l->max_steps > 0 && l->steps >= l->max_steps) return fail(h, NMPC_ERR_BAD_ARG, "trajectory buffer is full");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (l->steps == 0) loop_wire(l);
+    nmpc::LoopArgs &a = l->a;
+    LoopRetire &r = l->retire;
+    const bool retiring = r.made();
+    int n = a.B;
+    if (retiring) {
+        if (const int rc = loop_nactive(l, &n)) return rc;
+        if (n < 0 || n > a.B) return fail(h, NMPC_ERR_HIP, "nmpc_loop_step: active count out of range");
+    }
+    a.nact = n;
+    if (n > 0) {
+        const int cur = l->steps & 1;
+        a.dyn_in = l->d_dyn[cur];
+        a.dyn_out = l->d_dyn[cur ^ 1];
+        hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, a);
+        if (l->peers.made()) {
+            l->peers.a.nact = n;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, l->peers.a);
+            hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, l->peers.a);
+        }
+        if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, r.pack);
+        HIP_TRY(h, hipGetLastError());
+        // warm start: previous controls and multipliers, penalty back to its initial value (the server's behaviour).  The solve runs on
+        // the loop's own rows, or on the gathered ones: rows 0 .. n - 1 are then the active robots
+        double *P = l->d_P, *U = l->d_U, *Y = l->d_Y;
+        nmpc_status *st = l->d_st;
+        if (retiring) { P = r.sP; U = r.sU; Y = r.sY; st = r.sst; }
+        // launch order: from the second step on, by the pass counts of these very robots' solves of the step before (read by the
+        // classification kernel ahead of the solve, which then overwrites them); the first step has only the inputs to go by
+        h->order_hint = (l->steps > 0 && h->loop_order_prev) ? st : nullptr;
+        const int rc = nmpc_solve_batch_device(h, n, P, U, Y, nullptr, Y, st, stream);
+        h->order_hint = nullptr;
+        if (rc) return rc;
+        if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, r.pack);
+        hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+        if (l->monitor.made()) {       // over the robots the advance ran over: the compaction comes after
+            l->monitor.a.traj_row = a.traj_row;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, l->monitor.a);
+        }
+        if (l->missions.made()) {
+            l->missions.a.step = l->steps + 1;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_dispatch_kernel, dim3(n), dim3(64), 0, s, l->missions.a);
+        }
+    }
+    if (retiring) {
+        // (with nobody active the step still counts: the clock advances and the trajectory rows repeat)
+        r.a.step = l->steps + 1;
+        r.a.traj_row = a.traj_row;
+        hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, r.a);
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (retiring) {
+        HIP_TRY(h, hipMemcpyAsync(r.h_nact.p, r.nact.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipEventRecord(r.ev_nact, s));
+        r.nact_pending = true;
+    }
+    a.t += a.s;
+    a.traj_row += a.s;
+    l->steps++;
+    return NMPC_OK;
+}
+
+int nmpc_loop_run(nmpc_loop *l, int max_steps, void *stream)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (!l->retire.made()) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_run: the loop does not retire its robots, it would never end");
+    if (max_steps < 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_run: max_steps < 0");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int taken = 0;
+    while (taken < max_steps && !(l->max_steps > 0 && l->steps >= l->max_steps)) {
+        int n = 0;
+        if (const int rc = loop_nactive(l, &n)) return rc;
+        if (n == 0) break;
+        if (const int rc = nmpc_loop_step(l, stream)) return rc;
+        ++taken;
+    }
+    return taken;
+}
+
+// what every reader does first: on the loop's device, after everything enqueued there has finished
+static int loop_settle(nmpc_loop *l)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    HIP_TRY(l->h, hipSetDevice(l->h->device));
+    HIP_TRY(l->h, hipDeviceSynchronize());
+    return NMPC_OK;
+}
+
+int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    const int B = l->a.B;
+    if (!l->retire.made()) {
+        if (n_active) *n_active = B;
+        if (retired_at) for (int b = 0; b < B; ++b) retired_at[b] = -1;
+        return NMPC_OK;
+    }
+    HIP_TRY(l->h, l->retire.nact.read(n_active, 1));
+    HIP_TRY(l->h, l->retire.retired_at.read(retired_at, B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_legs(nmpc_loop *l, int32_t *leg, int32_t *route_of, int32_t *leg_at)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    const size_t B = (size_t)l->a.B;
+    HIP_TRY(l->h, l->d_route_of.read(route_of, B));
+    if (!l->missions.made()) {
+        if (leg) for (size_t b = 0; b < B; ++b) leg[b] = 0;
+        return NMPC_OK;
+    }
+    HIP_TRY(l->h, l->missions.leg.read(leg, B));
+    HIP_TRY(l->h, l->missions.leg_at.read(leg_at, l->missions.n_legs));
+    return NMPC_OK;
+}
+
+int nmpc_loop_clearance(nmpc_loop *l, nmpc_clearance *out)
+{
+    if (!out) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_settle(l)) return rc;
+    const int B = l->a.B;
+    if (!l->monitor.made()) {
+        for (int b = 0; b < B; ++b) out[b] = CLEARANCE_NONE;
+        return NMPC_OK;
+    }
+    HIP_TRY(l->h, l->monitor.rec.read(out, B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_read(nmpc_loop *l, double *state, double *last_u, int32_t *idx, uint8_t *done, nmpc_status *status)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    nmpc_handle *h = l->h;
+    const size_t B = (size_t)l->a.B;
+    HIP_TRY(h, l->d_state.read(state, B * 3));
+    HIP_TRY(h, l->d_last_u.read(last_u, B * 2));
+    HIP_TRY(h, l->d_idx.read(idx, B));
+    HIP_TRY(h, l->d_done.read(done, B));
+    HIP_TRY(h, l->d_st.read(status, B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_params(nmpc_loop *l, double *p, double *u, double *y)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    nmpc_handle *h = l->h;
+    const size_t B = (size_t)l->a.B;
+    HIP_TRY(h, l->d_P.read(p, B * l->a.n_p));
+    HIP_TRY(h, l->d_U.read(u, B * l->a.n_u));
+    HIP_TRY(h, l->d_Y.read(y, B * (size_t)nmpc_n1(&h->pb)));
+    return NMPC_OK;
+}
+
+int nmpc_loop_trajectory(nmpc_loop *l, double *rows, int max_rows)
+{
+    if (!l || !rows) return NMPC_ERR_BAD_ARG;
+    nmpc_handle *h = l->h;
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "the loop was created without a trajectory buffer");
+    const int nrows = l->steps * l->a.s + 1;
+    if (max_rows < nrows) return fail(h, NMPC_ERR_BAD_ARG, "trajectory does not fit");
+    if (const int rc = loop_settle(l)) return rc;
+    HIP_TRY(h, l->d_traj.read(rows, (size_t)nrows * l->a.B * 3));
+    return nrows;
+}

@@ -399,6 +399,16 @@ class VectorizedRecedingHorizon(_HostLoop):
         self.t += s
 
 
+def _checked_groups(who, group_of, B):
+    """-> ``group_of`` [B] as an int32 array with values in [0, B), or None (one group); ValueError otherwise."""
+    if group_of is None:
+        return None
+    g = np.ascontiguousarray(group_of, dtype=np.int32).reshape(B)
+    if ((g < 0) | (g >= B)).any():
+        raise ValueError(f"{who}: group_of out of range")
+    return g
+
+
 @dataclasses.dataclass(frozen=True)
 class Peers:
     """How the robots of a fleet see each other, for ``FleetRecedingHorizon`` and
@@ -420,12 +430,7 @@ class Peers:
         for v in (self.rx, self.ry, self.range):
             if not (math.isfinite(v) and v > 0):
                 raise ValueError("peers: rx, ry and range must be finite and positive")
-        if self.group_of is None:
-            return None
-        g = np.ascontiguousarray(self.group_of, dtype=np.int32).reshape(B)
-        if ((g < 0) | (g >= B)).any():
-            raise ValueError("peers: group_of out of range")
-        return g
+        return _checked_groups("peers", self.group_of, B)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -438,12 +443,7 @@ class Monitor:
 
     def checked(self, B: int):
         """-> group_of as an int32 array or None; ValueError for what ``nmpc_loop_set_monitor`` refuses."""
-        if self.group_of is None:
-            return None
-        g = np.ascontiguousarray(self.group_of, dtype=np.int32).reshape(B)
-        if ((g < 0) | (g >= B)).any():
-            raise ValueError("monitor: group_of out of range")
-        return g
+        return _checked_groups("monitor", self.group_of, B)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -874,23 +874,14 @@ class DeviceRecedingHorizon:
         self.peers = peers
         if peers is not None:
             g = None if peers.group_of is None else np.ascontiguousarray(peers.group_of, dtype=np.int32).reshape(B)
-            rc = self.lib.nmpc_loop_set_peers(h, _lib.as_i32p(g), int(peers.slots), float(peers.rx), float(peers.ry), float(peers.range))
-            if rc:
-                self.close()
-                solver._check(rc)
+            self._set(self.lib.nmpc_loop_set_peers(h, _lib.as_i32p(g), int(peers.slots), float(peers.rx), float(peers.ry), float(peers.range)))
         self.retire = bool(retire)
         if retire:
-            rc = self.lib.nmpc_loop_set_retire(h, 1)
-            if rc:
-                self.close()
-                solver._check(rc)
+            self._set(self.lib.nmpc_loop_set_retire(h, 1))
         self.monitor = monitor
         if monitor is not None:
             g = None if monitor.group_of is None else np.ascontiguousarray(monitor.group_of, dtype=np.int32).reshape(B)
-            rc = self.lib.nmpc_loop_set_monitor(h, _lib.as_i32p(g))
-            if rc:
-                self.close()
-                solver._check(rc)
+            self._set(self.lib.nmpc_loop_set_monitor(h, _lib.as_i32p(g)))
         self.missions = missions
         self._leg_off = None
         if missions is not None:
@@ -901,10 +892,13 @@ class DeviceRecedingHorizon:
             except ValueError:
                 self.close()
                 raise
-            rc = self.lib.nmpc_loop_set_missions(h, _lib.as_i32p(self._leg_off), _lib.as_i32p(leg_route))
-            if rc:
-                self.close()
-                solver._check(rc)
+            self._set(self.lib.nmpc_loop_set_missions(h, _lib.as_i32p(self._leg_off), _lib.as_i32p(leg_route)))
+
+    def _set(self, rc):
+        """A setter's answer during construction: a refusal frees the loop before it is raised."""
+        if rc:
+            self.close()
+            self.solver._check(rc)
 
     def close(self):
         if getattr(self, "_l", None):

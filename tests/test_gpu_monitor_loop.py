@@ -11,6 +11,9 @@ What each case makes the kernel do:
   and is parked from then on.
 * ``staggered-peers``: peer overlay slots in p (not read), groups = routes, retirement; parked robots are read from ``state`` while the
   compaction has not yet written their rows, and records are made against them (asserted on the mirror).
+* ``staggered-peers-setters-reversed``: the same fleet and mirror, the device loop created bare and given its stages by the raw setters
+  in the order monitor -> retire -> peers, the reverse of ``DeviceRecedingHorizon``'s: every pointer one stage reads of another's
+  (the active list, ``retired_at``, the parked predictions) belongs to a stage that did not exist when its reader was set.
 * ``group130``: lanes of the member loop take a third member (130 > 2 * 64) and the (value, row, robot) reduction picks across
   strides; beside it a group of one, whose loop is empty.
 * ``cfg2`` / ``cfg2-s3``: N_hor = 40 with one step taken per solve, which is cfg 2's own setting, and the same fleet with three
@@ -32,9 +35,9 @@ pytestmark = pytest.mark.gpu
 
 
 def _fleet(which):
-    """-> dict(cfg, routes, route_of, starts, idx0, dyn, sinus, peers, retire, groups, steps)"""
+    """-> dict(cfg, routes, route_of, starts, idx0, dyn, sinus, peers, retire, groups, steps, raw_setters)"""
     from mpc_trajectory_generator_amd.trajectory import Peers
-    base = dict(dyn=None, sinus=False, peers=None, retire=False, groups=None)
+    base = dict(dyn=None, sinus=False, peers=None, retire=False, groups=None, raw_setters=False)
     if which == "cfg1-three-routes":
         cfg = named_config("cfg1")
         routes, route_of, starts, i0 = frontend.random_fleet(cfg, 11, 3, 12, seed=5)
@@ -42,11 +45,11 @@ def _fleet(which):
     if which == "cfg4-ellipses-retire":
         cfg, routes, route_of, starts, i0, dyn = near_goal_cfg4_fleet()
         return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, dyn=dyn, sinus=True, retire=True, steps=10)}
-    if which == "staggered-peers":
+    if which in ("staggered-peers", "staggered-peers-setters-reversed"):
         cfg = named_config("cfg1")
         routes, route_of, starts, i0 = staggered_fleet(cfg)
         return {**base, **dict(cfg=cfg, routes=routes, route_of=route_of, starts=starts, idx0=i0, peers=Peers(group_of=route_of, **PEERS),
-                               retire=True, groups=route_of, steps=14)}
+                               retire=True, groups=route_of, steps=14, raw_setters=which != "staggered-peers")}
     if which == "group130":
         cfg, routes, route_of, starts, i0, _ = large_group_fleet()
         groups = np.full(131, 77, dtype=np.int32)
@@ -74,8 +77,22 @@ def _fleet(which):
     raise KeyError(which)
 
 
-FLEETS = ["cfg1-three-routes", "cfg4-ellipses-retire", "staggered-peers", "group130", "cfg2", "cfg2-s3", "moving-circle-window",
-          "no-vertices", "one-robot"]
+FLEETS = ["cfg1-three-routes", "cfg4-ellipses-retire", "staggered-peers", "staggered-peers-setters-reversed", "group130", "cfg2", "cfg2-s3",
+          "moving-circle-window", "no-vertices", "one-robot"]
+
+
+def _bare_loop_then_setters(s, f, monitor):
+    """-> the fleet's device loop, created with no stage and given monitor, retirement and peers in that order through the C ABI"""
+    from mpc_trajectory_generator_amd import _lib
+    from mpc_trajectory_generator_amd.trajectory import DeviceRecedingHorizon
+    dev = DeviceRecedingHorizon(s, f["routes"], f["starts"], f["dyn"], max_steps=f["steps"], route_of=f["route_of"], idx0=f["idx0"],
+                                sinus_object=f["sinus"])
+    lib, peers = s.lib, f["peers"]
+    mon_groups, peer_groups = (np.ascontiguousarray(g, dtype=np.int32) for g in (monitor.group_of, peers.group_of))
+    assert lib.nmpc_loop_set_monitor(dev._l, _lib.as_i32p(mon_groups)) == 0
+    assert lib.nmpc_loop_set_retire(dev._l, 1) == 0
+    assert lib.nmpc_loop_set_peers(dev._l, _lib.as_i32p(peer_groups), peers.slots, peers.rx, peers.ry, peers.range) == 0
+    return dev
 
 
 @pytest.mark.parametrize("which", FLEETS)
@@ -89,7 +106,10 @@ def test_monitored_loop_equals_host_mirror(which):
     common = dict(idx0=f["idx0"], sinus_object=f["sinus"], peers=f["peers"], retire=f["retire"], monitor=monitor)
     s = BatchSolver(cfg, max_batch=B)
     try:
-        dev = DeviceRecedingHorizon(s, f["routes"], f["starts"], f["dyn"], max_steps=f["steps"], route_of=f["route_of"], **common)
+        if f["raw_setters"]:
+            dev = _bare_loop_then_setters(s, f, monitor)
+        else:
+            dev = DeviceRecedingHorizon(s, f["routes"], f["starts"], f["dyn"], max_steps=f["steps"], route_of=f["route_of"], **common)
         host = FleetRecedingHorizon(f["routes"], f["route_of"], f["starts"], f["dyn"], sincos=o.sincos_array, **common)
         assert not clearance_differing(dev, no_clearance(B))           # before the first step: the initial record
         moved, parked_seen = 0, False
