@@ -14,9 +14,9 @@ what ``run`` starts from.
 
 ``BatchedRecedingHorizon`` is the batched counterpart for BASELINE config 4: B such robots advance in
 lock step, one batched solve per step, controls and multipliers carried as warm starts.
-``VectorizedRecedingHorizon`` is its NumPy mirror (bit-identical parameter vectors demanded),
-``FleetRecedingHorizon`` (host) and ``DeviceRecedingHorizon`` given a list of routes run a fleet whose
-robots follow routes of their own.
+``VectorizedRecedingHorizon`` is its NumPy mirror (bit-identical parameter vectors demanded): one step over flat per-robot arrays,
+each robot's route looked up in a table, as the device loop has it.  ``FleetRecedingHorizon`` (host, that same step) and
+``DeviceRecedingHorizon`` given a list of routes run a fleet whose robots follow routes of their own.
 """
 from __future__ import annotations
 
@@ -226,19 +226,60 @@ class BatchedRecedingHorizon(_HostLoop):
         self.t += self.cfg.num_steps_taken
 
 
+def _atan2(y, x):
+    """``math.atan2`` element by element: the reference's, and the per-robot loop's (visibility.py:184).  ``np.arctan2`` is not
+    libm's on every machine, and where it is not it differs from it in the last bits of some results."""
+    return np.array([math.atan2(a, b) for a, b in zip(y.ravel(), x.ravel())], dtype=np.float64).reshape(y.shape)
+
+
+class _RouteTable:
+    """What a step reads of R routes, side by side (the device's ``LoopRoute`` table, csrc/nmpc_loop_host.h): row r = route r, padded to
+    the longest route's, with each route's own lengths ``n``, ``nv``, ``nb`` [R]; ``end`` [R, 3], ``base`` (speed) and ``radius`` [R].
+    ``ref`` [R * width, 3] = the reference samples (x, y, theta), ``width`` rows per route; row ``n`` of a route, one past its last
+    sample, is its goal pose: what a horizon reads beyond the route.  ``bv`` goes on with N_hor zeros past the longest braking table:
+    what a horizon reads beyond a table.  ``head`` [R, Nobs, nobs] = the circles a route of no more than Nobs vertices always shows."""
+
+    def __init__(self, routes, cfg):
+        def pad(rows, fill=0.0, more=0, tail=()):
+            """-> (the rows side by side, ``more`` entries longer than the longest, ``fill`` past a row's own; the lengths [R])"""
+            rows = [np.array(v, dtype=np.float64).reshape((-1,) + tail) for v in rows]
+            out = np.empty((len(rows), max(len(v) for v in rows) + more) + tail)
+            out[:] = fill
+            for r, v in enumerate(rows):
+                out[r, :len(v)] = v
+            return out, np.array([len(v) for v in rows], dtype=np.int64)
+        self.end = np.array([r.end for r in routes], dtype=np.float64).reshape(-1, 3)
+        ref, self.n = pad([np.stack([r.x_ref, r.y_ref, r.theta_ref], axis=1) for r in routes], self.end[:, None, :], 1, (3,))
+        self.ref, self.width = ref.reshape(-1, 3), ref.shape[1]
+        self.vert, self.nv = pad([r.vertices for r in routes], tail=(2,))
+        self.bv, self.nb = pad([r.brake_velocities for r in routes], more=cfg.N_hor)
+        self.bd = pad([r.brake_distances for r in routes])[0]
+        self.base = np.array([r.base_speed for r in routes], dtype=np.float64)
+        self.radius = np.array([r.radius for r in routes], dtype=np.float64)
+        self.head = np.zeros((len(routes), cfg.Nobs, cfg.nobs))
+        for r, m in enumerate(np.minimum(self.nv, cfg.Nobs)):
+            self.head[r, :m, 0:2], self.head[r, :m, 2] = self.vert[r, :m], self.radius[r]
+
+
 class VectorizedRecedingHorizon(_HostLoop):
     """``BatchedRecedingHorizon`` with the per-robot Python loops replaced by NumPy array operations
     (BASELINE config 4: 8192 robots x 100 steps).  Same quantities, same order of operations per
     robot -- the test suite demands bit-identical parameter vectors against the loop version.
 
-    All robots share the route; dynamic obstacles are per robot: ``dyn_obs`` is ``None`` or a tuple of
+    Everything is kept per robot in flat [B] arrays, as the device loop keeps it, and a robot's route is looked up through
+    ``route_of[b]`` in a ``_RouteTable``: here all robots share the one route (``route_of`` = 0), ``FleetRecedingHorizon`` is the
+    same step on many.  Dynamic obstacles are per robot: ``dyn_obs`` is ``None`` or a tuple of
     arrays ``(p1 [B, K, 2], p2 [B, K, 2], freq [B, K], rx [B, K], ry [B, K], angle [B, K])``; ``idx0`` = the
     reference sample each robot starts its window search at (default 0, as the reference).
     """
 
     def __init__(self, route: harness.Route, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None):
-        cfg = self.cfg = route.cfg
         self.route = route
+        self._init_robots([route], np.zeros(len(starts), dtype=np.int64), starts, dyn_obs, sincos, sinus_object, idx0)
+
+    def _init_robots(self, routes, route_of, starts, dyn_obs, sincos, sinus_object, idx0):
+        cfg = self.cfg = routes[0].cfg
+        self.tab, self.route_of = _RouteTable(routes, cfg), route_of
         self.sinus_object = bool(sinus_object)     # obstacle index 2 follows the sinusoidal law (visibility.py:183-196,210-212)
         # sin / cos used by the state advance and the obstacle predictor: libm's (as the reference) unless
         # a replacement is given -- the device loop's bit-level mirror passes the kernels' own sin / cos
@@ -247,7 +288,6 @@ class VectorizedRecedingHorizon(_HostLoop):
         self.state = np.array(starts, dtype=np.float64).reshape(B, 3)
         self.traj = [self.state.copy()]
         self.last_u = np.zeros((B, cfg.nu))
-        self.has_input = False
         self.idx = np.zeros(B, dtype=np.int64) if idx0 is None else np.array(idx0, dtype=np.int64).reshape(B)
         self.t = 0
         self.dyn_obs = dyn_obs
@@ -260,11 +300,6 @@ class VectorizedRecedingHorizon(_HostLoop):
         self.dyn = d
         self.U = np.zeros((B, cfg.n_u))
         self.Y = np.zeros((B, cfg.n1))
-        self.x_ref = np.array(route.x_ref)
-        self.y_ref = np.array(route.y_ref)
-        self.th_ref = np.array(route.theta_ref)
-        self.n = len(self.x_ref)
-        self.vert = np.array(route.vertices, dtype=np.float64).reshape(-1, 2)
         self.done = np.zeros(B, dtype=bool)
 
     # dynamic-obstacle prediction for all robots: visibility.py:156-166,199-216 (linear law)
@@ -276,7 +311,7 @@ class VectorizedRecedingHorizon(_HostLoop):
         pos = s[..., None] * p1[:, :, None, :] + (1 - s[..., None]) * p2[:, :, None, :]
         if self.sinus_object and pos.shape[1] > 2:                                   # (:183-196), amplitude 1.5
             k = 2
-            ang_d = np.arctan2(p2[:, k, 1] - p1[:, k, 1], p2[:, k, 0] - p1[:, k, 0])[:, None]       # [B, 1]
+            ang_d = _atan2(p2[:, k, 1] - p1[:, k, 1], p2[:, k, 0] - p1[:, k, 0])[:, None]          # [B, 1]
             add = 1.5 * self.sincos((10 * freq[:, k, None]) * times[None, :])[1]                      # [B, H]
             sa, ca = self.sincos(ang_d)
             dx, dy = pos[:, k, :, 0] - p1[:, k, None, 0], pos[:, k, :, 1] - p1[:, k, None, 1]
@@ -299,25 +334,23 @@ class VectorizedRecedingHorizon(_HostLoop):
     def assemble(self, active=None):
         """-> P [B, n_p].  ``active`` [B] bool (default: everybody): the other robots keep everything they carry (reference sample,
         dynamic block), and their rows of P mean nothing."""
-        cfg, route, B, N, n = self.cfg, self.route, self.B, self.cfg.N_hor, self.n
+        cfg, T, rt, B, N = self.cfg, self.tab, self.route_of, self.B, self.cfg.N_hor
         s = cfg.num_steps_taken
+        n, at = T.n[rt], rt * T.width                            # each robot's route: its samples, its first row of T.ref
         x, y = self.state[:, 0], self.state[:, 1]
-        # static circles (path_generator.py:295-304 + visibility.py:141-148 with look-back 0)
-        cons = np.zeros((B, cfg.Nobs, cfg.nobs))
-        nv = len(self.vert)
-        if nv:
-            if cfg.Nobs >= nv:
-                cons[:, :nv, 0:2] = self.vert[None]
-                cons[:, :nv, 2] = route.radius
-            else:
-                dist = np.linalg.norm(self.vert[None, :, :] - self.state[:, None, 0:2], axis=2)
-                lb = np.argmin(dist, axis=1)
-                ub = min(nv, cfg.Nobs)
-                j = lb[:, None] + np.arange(cfg.Nobs)[None, :]
-                ok = j < ub
-                jj = np.minimum(j, nv - 1)
-                cons[..., 0:2] = np.where(ok[..., None], self.vert[jj], 0.0)
-                cons[..., 2] = np.where(ok, route.radius, 0.0)
+        # static circles (path_generator.py:295-304 + visibility.py:141-148 with look-back 0): the route's first Nobs vertices; on a
+        # route with more, those from the closest one on, up to slot Nobs
+        cons = T.head[rt]
+        more = np.nonzero(T.nv[rt] > cfg.Nobs)[0]
+        if len(more):
+            r, nv = rt[more, None], T.nv[rt[more], None]
+            dist = np.linalg.norm(T.vert[rt[more]] - self.state[more, None, 0:2], axis=2)
+            lb = np.argmin(np.where(np.arange(T.vert.shape[1])[None, :] < nv, dist, np.inf), axis=1)     # not the padding
+            j = lb[:, None] + np.arange(cfg.Nobs)[None, :]
+            ok = j < cfg.Nobs
+            jj = np.minimum(j, nv - 1)
+            cons[more, :, 0:2] = np.where(ok[..., None], T.vert[r, jj], 0.0)
+            cons[more, :, 2] = np.where(ok, T.radius[r], 0.0)
         # dynamic ellipses (path_generator.py:306-316)
         if self.K:
             if self.t == 0:
@@ -337,36 +370,27 @@ class VectorizedRecedingHorizon(_HostLoop):
         w = np.arange(6 * s)
         j = lb[:, None] + w[None, :]
         ok = j < ub[:, None]
-        jj = np.minimum(j, n - 1)
-        d = np.linalg.norm(np.stack([self.x_ref[jj] - x[:, None], self.y_ref[jj] - y[:, None]], axis=2), axis=2)
+        p = T.ref.take(at[:, None] + np.minimum(j, n[:, None] - 1), axis=0)
+        d = np.linalg.norm(np.stack([p[..., 0] - x[:, None], p[..., 1] - y[:, None]], axis=2), axis=2)
         d = np.where(ok, d, np.inf)
         self.idx = lb + np.argmin(d, axis=1) if active is None else np.where(active, lb + np.argmin(d, axis=1), self.idx)
         idx = self.idx
-        # horizon references and target (:326-341)
-        end = np.array(route.end, dtype=np.float64)
-        j = idx[:, None] + np.arange(N)[None, :]
-        ok = j < n
-        jj = np.minimum(j, n - 1)
-        refs = np.empty((B, N, 3))
-        refs[..., 0] = np.where(ok, self.x_ref[jj], end[0])
-        refs[..., 1] = np.where(ok, self.y_ref[jj], end[1])
-        refs[..., 2] = np.where(ok, self.th_ref[jj], end[2])
-        far = idx + N < n
-        jf = np.minimum(idx + N, n - 1)
-        xf = np.where(far[:, None], np.stack([self.x_ref[jf], self.y_ref[jf], self.th_ref[jf]], axis=1), end[None, :])
+        # horizon references and target (:326-341): beyond the route's last sample its goal pose, the table's entry n
+        refs = T.ref.take(np.minimum((at + idx)[:, None] + np.arange(N)[None, :], (at + n)[:, None]), axis=0)
+        xf = T.ref.take(np.minimum(at + idx + N, at + n), axis=0)
         # velocity reference with the braking profile (:343-361)
-        bv, bd, base = np.array(route.brake_velocities), np.array(route.brake_distances), route.base_speed
-        vel = np.full((B, N), base)
-        brake = (idx + N) >= n - bd[0] / base
+        base = T.base[rt, None]
+        brake = (idx + N) >= n - T.bd[rt, 0] / T.base[rt]
         num_base = np.minimum(n - idx - 1, N)
         k = np.arange(N)[None, :]
         nb = num_base[:, None]
-        tail = np.where(k - nb < len(bv), bv[np.clip(k - nb, 0, len(bv) - 1)], 0.0)
+        tail = T.bv.reshape(-1).take((rt * T.bv.shape[1])[:, None] + np.clip(k - nb, 0, T.bv.shape[1] - 1))     # zeros beyond a route's own
         vel_b = np.where(k < nb, base, tail)
-        vel = np.where(brake[:, None], vel_b, vel)
+        vel = np.where(brake[:, None], vel_b, base)
         for b in np.where(brake & (num_base == 0))[0]:                      # inside the last sample: distance-based (:347-351)
-            dist_to_goal = math.sqrt((self.state[b, 0] - end[0]) ** 2 + (self.state[b, 1] - end[1]) ** 2)
-            vr = [v for (v, dd) in zip(bv, bd) if dd <= dist_to_goal][:N]
+            r = rt[b]
+            dist_to_goal = math.sqrt((self.state[b, 0] - T.end[r, 0]) ** 2 + (self.state[b, 1] - T.end[r, 1]) ** 2)
+            vr = [v for (v, dd) in zip(T.bv[r, :T.nb[r]], T.bd[r, :T.nb[r]]) if dd <= dist_to_goal][:N]
             vel[b] = np.array(vr + [0.0] * (N - len(vr)))
         W = np.tile(np.array(cfg.weights()), (B, 1))
         P = np.concatenate([self.state, self.last_u, xf, self.last_u, W, vel, cons.reshape(B, -1),
@@ -392,9 +416,8 @@ class VectorizedRecedingHorizon(_HostLoop):
         self.state = st
         last_u = U[:, (s - 1) * cfg.nu:s * cfg.nu].copy()
         self.last_u = last_u if active is None else np.where(active[:, None], last_u, self.last_u)
-        self.has_input = True
-        end = self.route.end
-        done = (np.abs(st[:, 0] - end[0]) <= 0.05) & (np.abs(st[:, 1] - end[1]) <= 0.05) & (np.abs(self.last_u[:, 0]) < 0.005)
+        end = self.tab.end[self.route_of]
+        done = (np.abs(st[:, 0] - end[:, 0]) <= 0.05) & (np.abs(st[:, 1] - end[:, 1]) <= 0.05) & (np.abs(self.last_u[:, 0]) < 0.005)
         self.done = done if active is None else np.where(active, done, self.done)
         self.t += s
 
@@ -480,18 +503,17 @@ def no_clearance(B: int):
     return rec
 
 
-class FleetRecedingHorizon(_HostLoop):
+class FleetRecedingHorizon(VectorizedRecedingHorizon):
     """``VectorizedRecedingHorizon`` for a fleet on R routes: robot b follows ``routes[route_of[b]]``.
 
-    One ``VectorizedRecedingHorizon`` per route runs that route's robots (in fleet order); their rows are
-    scattered into fleet order, and one ``solve_fn(P, u0, y0) -> (U, Y, status)`` call covers the whole fleet
-    per step.  Each robot's quantities are therefore exactly those of the single-route mirror for its route.
-    ``dyn_obs``, ``sincos`` and ``sinus_object`` as in ``VectorizedRecedingHorizon``, ``dyn_obs`` in fleet
-    order; ``idx0`` = the reference sample each robot starts at, on its own route (default 0).
+    The step is ``VectorizedRecedingHorizon``'s, which reads everything of a route through ``route_of[b]``, so each robot's quantities
+    are exactly those of the single-route mirror for its route; one ``solve_fn(P, u0, y0) -> (U, Y, status)`` call covers the whole
+    fleet per step.  This class adds what is the fleet's: peers, retirement, the monitor and missions.  ``dyn_obs``, ``sincos`` and
+    ``sinus_object`` as in ``VectorizedRecedingHorizon``; ``idx0`` = the reference sample each robot starts at, on its own route
+    (default 0).
 
-    ``peers`` (a ``Peers``) lets the robots of a group see each other: ``assemble`` overlays the chosen peers on
-    the gathered parameter vectors.  Peers cross routes, so the rule lives here and not in the per-route mirrors,
-    whose carried dynamic blocks never see it.
+    ``peers`` (a ``Peers``) lets the robots of a group see each other: ``assemble`` overlays the chosen peers on the parameter
+    vectors it returns, never on the carried dynamic blocks.
 
     ``retire=True``: a robot whose terminal test holds after an advance leaves the loop for good, as the reference's
     ``while not terminal`` ends for one robot.  Everybody is ``active`` at the first step; a retired robot
@@ -506,21 +528,17 @@ class FleetRecedingHorizon(_HostLoop):
     ``missions`` (a ``Missions``, needs ``retire=True``): ``retire`` re-dispatches an active robot that is done and has another leg
     instead of retiring it: ``leg`` [B] and ``route_of`` [B] move on, ``leg_at`` [B, Lmax] takes the step count
     at which each leg ended (-1: not yet, or no such leg), the robot's reference sample, ``last_u``, ``U`` and ``Y`` rows are zeroed
-    and ``done`` cleared, and the robot moves to the mirror of its new route with its state, carried dynamic block and trajectory.
+    and ``done`` cleared, in place; its state, carried dynamic block and trajectory are not touched.
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
                  monitor=None, missions=None):
         self.routes = list(routes)
-        cfg = self.cfg = self.routes[0].cfg
-        self.B = B = len(starts)
-        self.route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
+        cfg, B = self.routes[0].cfg, len(starts)
+        route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
         assert all(r.cfg is cfg or r.cfg == cfg for r in self.routes)
-        assert ((self.route_of >= 0) & (self.route_of < len(self.routes))).all()
-        starts = np.array(starts, dtype=np.float64).reshape(B, 3)
-        self._dyn_obs, self._sincos, self._sinus_object = dyn_obs, sincos, sinus_object
-        self._traj_head = []                                      # the rows before the parts' own first (``_regroup``)
-        self._group(starts, idx0)
+        assert ((route_of >= 0) & (route_of < len(self.routes))).all()
+        self._init_robots(self.routes, route_of, starts, dyn_obs, sincos, sinus_object, idx0)
         self.missions = missions
         if missions is not None:
             if not retire:
@@ -531,11 +549,6 @@ class FleetRecedingHorizon(_HostLoop):
             self.leg = np.zeros(B, dtype=np.int32)
             self.leg_at = np.full((B, int(self.n_legs.max())), -1, dtype=np.int32)
             self.route_of = self.route_of.copy()
-        self.t = 0
-        self.U = np.zeros((B, cfg.n_u))
-        self.Y = np.zeros((B, cfg.n1))
-        self.sincos = sincos if sincos is not None else (lambda x: (np.sin(x), np.cos(x)))
-        self.K = 0 if dyn_obs is None else dyn_obs[0].shape[1]
         self.peers = peers
         if peers is not None:
             g = peers.checked(B, self.K, cfg.Ndynobs)
@@ -554,32 +567,6 @@ class FleetRecedingHorizon(_HostLoop):
             self.monitor_groups = [np.nonzero(g == v)[0] for v in np.unique(g)]   # members in ascending robot index
             self.clearance = no_clearance(B)
 
-    def _group(self, starts, idx0):
-        """``parts`` = (robots of the route in fleet order, its mirror), for every route somebody is on."""
-        B, dyn_obs = self.B, self._dyn_obs
-        self.parts = []
-        for r, route in enumerate(self.routes):
-            ids = np.nonzero(self.route_of == r)[0]
-            if not len(ids):
-                continue
-            sub = VectorizedRecedingHorizon(route, starts[ids], None if dyn_obs is None else tuple(a[ids] for a in dyn_obs),
-                                            sincos=self._sincos, sinus_object=self._sinus_object,
-                                            idx0=None if idx0 is None else np.asarray(idx0).reshape(B)[ids])
-            self.parts.append((ids, sub))
-
-    def _regroup(self, last_u, idx, done):
-        """The robots into the mirrors of ``route_of`` as it is now, each with what it carries: state, dynamic block, clock and the
-        ``last_u``, ``idx`` and ``done`` given; the trajectory so far is kept here.  The clock ``t`` and ``has_input`` are the fleet's:
-        every part advances them at every step, whoever is active, so any part's will do.  The whole trajectory is copied at every
-        step that re-dispatches somebody: fine for the fleets of the tests, quadratic for a long run of a big one."""
-        assert len({(sub.t, sub.has_input, len(sub.traj)) for _, sub in self.parts}) == 1
-        state, dyn = self.state, self._gather("dyn", self.parts[0][1].dyn.shape[1:])
-        t, has_input = self.parts[0][1].t, self.parts[0][1].has_input
-        self._traj_head = self.traj[:-1]
-        self._group(state, idx)
-        for ids, sub in self.parts:
-            sub.last_u, sub.done, sub.dyn, sub.t, sub.has_input = last_u[ids], done[ids], dyn[ids], t, has_input
-
     @property
     def n_active(self):
         return self.B if self.active is None else int(self.active.sum())
@@ -594,53 +581,16 @@ class FleetRecedingHorizon(_HostLoop):
                 self.leg[go] += 1
                 self.route_of[go] = [self.legs[b][self.leg[b]] for b in np.nonzero(go)[0]]
                 self.U[go], self.Y[go] = 0.0, 0.0
-                last_u, idx, done = self.last_u, self.idx, self.done
-                last_u[go], idx[go], done[go] = 0.0, 0, False
-                self._regroup(last_u, idx, done)
+                self.last_u[go], self.idx[go], self.done[go] = 0.0, 0, False
             now = now & ~go
         self.retired_at[now] = self.steps
         self.active &= ~now
 
-    def _gather(self, field, shape, dtype=np.float64):
-        out = np.empty((self.B,) + shape, dtype=dtype)
-        for ids, sub in self.parts:
-            out[ids] = getattr(sub, field)
-        return out
-
-    @property
-    def state(self):
-        return self._gather("state", (3,))
-
-    @property
-    def last_u(self):
-        return self._gather("last_u", (self.cfg.nu,))
-
-    @property
-    def idx(self):
-        return self._gather("idx", (), np.int64)
-
-    @property
-    def done(self):
-        return self._gather("done", (), bool)
-
-    @property
-    def traj(self):
-        rows = list(self._traj_head)
-        for k in range(len(self.parts[0][1].traj)):
-            row = np.empty((self.B, 3))
-            for ids, sub in self.parts:
-                row[ids] = sub.traj[k]
-            rows.append(row)
-        return rows
-
     def assemble(self):
-        act = self.active
-        P = np.empty((self.B, self.cfg.n_p)) if act is None else self.P
-        for ids, sub in self.parts:
-            if act is None:
-                P[ids] = sub.assemble()
-            else:
-                P[ids[act[ids]]] = sub.assemble(act[ids])[act[ids]]
+        P = super().assemble(self.active)
+        if self.active is not None:                                          # a retired robot's row stays its last step's
+            self.P[self.active] = P[self.active]
+            P = self.P
         if self.peers is not None:
             self._overlay_peers(P)
         self._P_step = P                                                     # what this step's solve reads: the monitor's p
@@ -666,7 +616,7 @@ class FleetRecedingHorizon(_HostLoop):
         return pred
 
     def _overlay_peers(self, P):
-        """The peers rule on the gathered parameter vectors, in place."""
+        """The peers rule on the parameter vectors, in place."""
         cfg, pe = self.cfg, self.peers
         N, M = cfg.N_hor, pe.slots
         per = cfg.ndynobs * N
@@ -703,11 +653,9 @@ class FleetRecedingHorizon(_HostLoop):
                     P[b, base + m * per:base + (m + 1) * per] = blk.reshape(len(b), per)
 
     def advance(self, U):
-        for ids, sub in self.parts:
-            sub.advance(U[ids], None if self.active is None else self.active[ids])
+        super().advance(U, self.active)
         if self.monitor is not None:
             self._monitor_update()
-        self.t += self.cfg.num_steps_taken
         self.steps += 1
 
     def _monitor_update(self):
@@ -735,9 +683,7 @@ class FleetRecedingHorizon(_HostLoop):
 
         for i in range(s):
             r = self.steps * s + 1 + i
-            pose = np.empty((B, 3))
-            for ids, sub in self.parts:
-                pose[ids] = sub.traj[len(sub.traj) - s + i]
+            pose = self.traj[len(self.traj) - s + i]
             x, y = pose[:, 0], pose[:, 1]
             dx, dy = x[:, None] - circ[..., 0], y[:, None] - circ[..., 1]
             v = lowest(np.sqrt(dx * dx + dy * dy) - circ[..., 2], circ[..., 2] > 0)
@@ -849,7 +795,7 @@ class DeviceRecedingHorizon:
             sinus = np.zeros((B, K))
             if sinus_object and K > 2:
                 sinus[:, 2] = 1.0                  # obstacle index 2 follows the sinusoidal law (visibility.py:210-212)
-            direction = np.arctan2(p2[..., 1] - p1[..., 1], p2[..., 0] - p1[..., 0])
+            direction = _atan2(p2[..., 1] - p1[..., 1], p2[..., 0] - p1[..., 0])
             dyn = np.ascontiguousarray(np.concatenate(
                 [p1, p2, freq[..., None], rx[..., None], ry[..., None], ang[..., None], sinus[..., None],
                  direction[..., None]], axis=2), dtype=np.float64)

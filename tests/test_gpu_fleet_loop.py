@@ -1,6 +1,6 @@
 """GPU: the receding-horizon loop on device with a fleet on many routes (nmpc_loop_new_routes) against its
-host mirror ``FleetRecedingHorizon`` -- one ``VectorizedRecedingHorizon`` per route, itself pinned to the
-reference's goldens through tests/test_harness.py -- driven by the oracle and given the kernels' sin / cos:
+host mirror ``FleetRecedingHorizon`` -- the ``VectorizedRecedingHorizon`` step with each robot's route looked up through
+``route_of[b]``, itself pinned to the reference's goldens through tests/test_harness.py and tests/test_fleet_mirror.py -- driven by the oracle and given the kernels' sin / cos:
 parameter vectors, states, reference indices, solver counters and trajectories must agree bit for bit, step
 after step, whatever route each robot is on."""
 import ctypes as C

@@ -66,11 +66,7 @@ def _twin_without_peers(fleet):
     """The same fleet at the same states, plans and carried blocks, without peers; stepping it leaves ``fleet`` alone."""
     twin = copy.copy(fleet)
     twin.peers = None
-    twin.parts = []
-    for ids, sub in fleet.parts:
-        sub2 = copy.copy(sub)
-        sub2.dyn = sub.dyn.copy()
-        twin.parts.append((ids, sub2))
+    twin.dyn = fleet.dyn.copy()
     return twin
 
 
@@ -94,8 +90,7 @@ def _run(cfg, routes, route_of, starts, i0, K, group_of, M, rng_, steps, seed=1,
         assert np.array_equal(P, want), f"step {k}: columns {np.unique(np.nonzero(P != want)[1])[:10]}"
         # everything outside the peer slots, and the block carried to the next step, are the loop's without peers
         assert np.array_equal(P[:, :lo], P0[:, :lo]) and np.array_equal(P[:, hi:], P0[:, hi:]), f"step {k}"
-        for (_, a), (_, b) in zip(fleet.parts, twin.parts):
-            assert np.array_equal(a.dyn, b.dyn), f"step {k}: the carried block saw peers"
+        assert np.array_equal(fleet.dyn, twin.dyn), f"step {k}: the carried block saw peers"
         sel = [[j for j in row if j >= 0] for row in fleet.peer_index.tolist()]
         assert sel == chosen, f"step {k}"
         out.append(chosen)

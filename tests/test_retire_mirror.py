@@ -154,11 +154,7 @@ def _twin_without_peers(fleet):
     twin = copy.copy(fleet)
     twin.peers = None
     twin.P = fleet.P.copy()
-    twin.parts = []
-    for ids, sub in fleet.parts:
-        sub2 = copy.copy(sub)
-        sub2.dyn = sub.dyn.copy()
-        twin.parts.append((ids, sub2))
+    twin.dyn = fleet.dyn.copy()
     return twin
 
 
