@@ -380,6 +380,41 @@ int nmpc_plan_batch_host(nmpc_planner *pl, int B, const double *start, const dou
 /* Kernel time (HIP events around the two launches) of the last nmpc_plan_batch_host call on this planner, in ms. */
 double nmpc_planner_last_ms(const nmpc_planner *pl);
 
+/* ---- map monitor: each robot's closest approach to the map's walls, on device ----------------------
+ * The clearance monitor sees what the solver sees in p; the map itself -- a wall between two corners, an obstacle the route merely
+ * passes, the boundary -- is kept away by soft costs only.  The map monitor is an opt-in stage of the loop that checks every pose a
+ * robot drives against the polygons of a map (the rule: DESIGN.md section 5.9).  It observes only: no p, u, y, state, status,
+ * trajectory or clearance record differs by a bit from the loop without it.  One more kernel per step, after the advance (and the
+ * clearance monitor), over the robots the step drove (those it retires at its end included).
+ *   The map: the scene's edge [n_edge][4] and poly_off [n_poly + 1], the obstacles first and the boundary LAST; the node fields are
+ *   ignored.  3 <= n_edge <= 1024, n_poly >= 1, poly_off ascending from 0 to n_edge in steps of three edges at least, every
+ *   coordinate finite.
+ * For each of the s = num_steps_taken rows r a step appends, with (x, y) the robot's pose of row r and (ax, ay) its pose of row
+ * r - 1, in unfused f64 in the order written, / correctly rounded, no sqrt:
+ *   wall distance, squared, per edge e: ex = x2 - x1, ey = y2 - y1, L2 = ex*ex + ey*ey; t = 0 unless L2 > 0, then t = ((x - x1)*ex +
+ *     (y - y1)*ey)/L2, if (t < 0) t = 0, if (t > 1) t = 1; cx = x1 + t*ex, cy = y1 + t*ey, dx = x - cx, dy = y - cy, v = dx*dx + dy*dy
+ *   containment of polygon k, even-odd: an edge with (y1 > y) != (y2 > y) and xi = x1 + ((y - y1)*(x2 - x1))/(y2 - y1) is a crossing
+ *     if xi > x; an obstacle fails on an odd count, the boundary (k = n_poly - 1) on an even one; no on-edge tolerance
+ *   crossing between the two rows: with orient(p, q, r) = (qx - px)*(ry - py) - (qy - py)*(rx - px), a = (ax, ay), b = (x, y) and the
+ *     edge (c, d), o1 = orient(a, b, c), o2 = orient(a, b, d), o3 = orient(c, d, a), o4 = orient(c, d, b): the edge is crossed if
+ *     o1*o2 < -1e-9 and o3*o4 < -1e-9, and the polygon that owns it fails
+ * A row is a hit if any polygon fails (a NaN pose fails the boundary).  The record: (wall2, wall_row, wall_edge) = the lexicographic
+ * minimum of (v, r, e) over everything seen so far (a comparison that is false keeps the record, so a NaN v is passed over), hits =
+ * the rows that were hits, hit_row the first of them, hit_poly the smallest failing polygon index in that row.  Initially +inf, -1,
+ * -1, 0, -1, -1, 0.  A robot retired earlier keeps its record, a step with nobody active updates nothing, records run across legs.
+ * To be called once, before the loop's first step, in any order with the other setters, on a loop that records its trajectory.
+ * NMPC_ERR_BAD_ARG with a message that names the function, and nothing changed or allocated, for a NULL map (a NULL loop:
+ * NMPC_ERR_BAD_ARG), a call after a step, a second call, a loop with max_steps == 0, n_edge or n_poly outside the limits, a
+ * malformed poly_off or a coordinate that is not finite.  A loop without the stage enqueues what it enqueued before this function
+ * existed. */
+typedef struct nmpc_map_clearance {      /* 32 bytes */
+    double wall2;
+    int32_t wall_row, wall_edge, hits, hit_row, hit_poly, reserved;
+} nmpc_map_clearance;
+int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map);
+/* Synchronises, then copies the records out [B]; on a loop without the stage the initial record everywhere. */
+int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out);
+
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);
 /* a/b and sqrt(a) as the device computes them: out_div/out_sqrt [n]. */

@@ -24,7 +24,7 @@ SYMBOLS = (
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
     "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run", "nmpc_loop_set_monitor", "nmpc_loop_clearance",
-    "nmpc_loop_set_missions", "nmpc_loop_legs",
+    "nmpc_loop_set_missions", "nmpc_loop_legs", "nmpc_loop_set_map_monitor", "nmpc_loop_map_clearance",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -86,6 +86,11 @@ assert STATUS_DTYPE.itemsize == 72
 CLEARANCE_DTYPE = np.dtype([("circle", "<f8"), ("ellipse", "<f8"), ("peer2", "<f8"),
                             ("circle_row", "<i4"), ("ellipse_row", "<i4"), ("peer_row", "<i4"), ("peer", "<i4")])
 assert CLEARANCE_DTYPE.itemsize == 40
+
+# nmpc_map_clearance: a robot's closest approach to the map's walls and the rows at which a polygon failed (nmpc_loop_set_map_monitor)
+MAP_CLEARANCE_DTYPE = np.dtype([("wall2", "<f8"), ("wall_row", "<i4"), ("wall_edge", "<i4"), ("hits", "<i4"),
+                                ("hit_row", "<i4"), ("hit_poly", "<i4"), ("reserved", "<i4")])
+assert MAP_CLEARANCE_DTYPE.itemsize == 32
 
 
 def _sources():
@@ -284,6 +289,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_monitor.restype = C.c_int
     lib.nmpc_loop_clearance.argtypes = [vp, vp]
     lib.nmpc_loop_clearance.restype = C.c_int
+    lib.nmpc_loop_set_map_monitor.argtypes = [vp, C.POINTER(NmpcScene)]
+    lib.nmpc_loop_set_map_monitor.restype = C.c_int
+    lib.nmpc_loop_map_clearance.argtypes = [vp, vp]
+    lib.nmpc_loop_map_clearance.restype = C.c_int
     lib.nmpc_loop_set_missions.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.nmpc_loop_set_missions.restype = C.c_int
     lib.nmpc_loop_legs.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -570,6 +570,114 @@ __global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(MonitorArgs m)
     }
 }
 
+// ---- map monitor: each robot's closest approach to the walls of a polygon map, and the rows at which it was inside an obstacle, outside
+// the boundary or went through an edge (nmpc_loop_set_map_monitor; the rule is DESIGN.md section 5.9).  It observes: the record is the
+// only thing it writes.  For the pose (x, y) of row r and (ax, ay) of row r - 1, unfused f64 in the order written, no sqrt:
+//   wall      per edge (x1, y1, x2, y2): ex = x2 - x1, ey = y2 - y1, L2 = ex*ex + ey*ey; t = 0 unless L2 > 0, then t = ((x - x1)*ex +
+//             (y - y1)*ey)/L2 clamped by `if (t < 0) t = 0; if (t > 1) t = 1`; dx = x - (x1 + t*ex), dy = y - (y1 + t*ey), v = dx*dx + dy*dy
+//   inside    polygon k, even-odd: an edge with (y1 > y) != (y2 > y) is a crossing if x1 + ((y - y1)*(x2 - x1))/(y2 - y1) > x; an obstacle
+//             fails on an odd count, the boundary (the last polygon) on an even one
+//   crossing  edge (c, d) is crossed if o1*o2 < -1e-9 && o3*o4 < -1e-9 (the planner's segment test, nmpc_plan.h); its polygon fails
+// A row is a hit if any polygon fails.  The record keeps the lexicographic minimum of (v, r, e), the number of hits, the first hit's row
+// and the smallest failing polygon of that row; a comparison that is false (a NaN) keeps what it would have replaced.
+struct MapArgs {
+    int B, s, E, n_poly;
+    const double *traj;       // the loop's trajectory table
+    int traj_row;             // the first of this step's s rows (>= 1: row traj_row - 1 is there)
+    const double *edge;       // [E][4] x1 y1 x2 y2, polygon by polygon: the obstacles first, the boundary last
+    const int *poly_off;      // [n_poly + 1]
+    const int *edge_poly;     // [E]: the polygon that owns the edge
+    nmpc_map_clearance *rec;  // [B]
+    const int *act;           // as in LoopArgs
+};
+
+// One wave per robot the step drove, after the advance (and the clearance monitor): the robot's s + 1 poses, from the row before the
+// step's first on, go to LDS.  Row by row, lanes stride over the edges (wall distance, crossing test: consecutive lanes read consecutive
+// edges, 32 bytes apart, through the cache: the table is the same for every robot), then over the polygons, each lane walking the edges
+// of its polygon for the parity; a wave minimum of the failing polygon index is the row's verdict.  Every lane keeps its lexicographic
+// minimum of (v, r, e); one wave reduction follows the rows, and lane 0 folds everything into the record.  Every loop is bounded by s, E
+// or n_poly (poly_off was checked by the setter).
+__global__ __launch_bounds__(64) void nmpc_loop_map_kernel(MapArgs m)
+{
+    __shared__ double own[2 * (NMPC_MAX_HORIZON + 1)];
+    const int b = m.act ? m.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
+    const int s = m.s, E = m.E, n_poly = m.n_poly, row0 = m.traj_row;
+    for (int i = lane; i <= s; i += 64) {
+        const double *row = m.traj + ((size_t)(row0 - 1 + i) * m.B + b) * 3;
+        own[2 * i] = row[0];
+        own[2 * i + 1] = row[1];
+    }
+    __syncthreads();
+    constexpr int NONE = 0x7fffffff;
+    double wv = __builtin_inf();
+    int wr = NONE, we = NONE;
+    int hits = 0, hit_row = NONE, hit_poly = NONE;        // the same in every lane
+    for (int i = 0; i < s; ++i) {
+        const double ax = own[2 * i], ay = own[2 * i + 1], x = own[2 * i + 2], y = own[2 * i + 3];
+        const double ux = x - ax, uy = y - ay;
+        const int r = row0 + i;
+        int fail = NONE;
+        for (int e = lane; e < E; e += 64) {
+            const double x1 = m.edge[4 * e], y1 = m.edge[4 * e + 1], x2 = m.edge[4 * e + 2], y2 = m.edge[4 * e + 3];
+            const double ex = x2 - x1, ey = y2 - y1;
+            const double L2 = ex * ex + ey * ey;
+            double t = 0.0;
+            if (L2 > 0.0) {
+                t = ((x - x1) * ex + (y - y1) * ey) / L2;
+                if (t < 0.0) t = 0.0;
+                if (t > 1.0) t = 1.0;
+            }
+            const double cx = x1 + t * ex, cy = y1 + t * ey;
+            const double dx = x - cx, dy = y - cy;
+            const double v = dx * dx + dy * dy;
+            if (v < wv) { wv = v; wr = r; we = e; }       // (rows and a lane's edges ascend: among equal values the first stays)
+            const double o1 = ux * (y1 - ay) - uy * (x1 - ax);
+            const double o2 = ux * (y2 - ay) - uy * (x2 - ax);
+            const double o3 = ex * (ay - y1) - ey * (ax - x1);
+            const double o4 = ex * (y - y1) - ey * (x - x1);
+            if (o1 * o2 < -1e-9 && o3 * o4 < -1e-9) {
+                const int k = m.edge_poly[e];
+                if (k < fail) fail = k;
+            }
+        }
+        for (int k = lane; k < n_poly; k += 64) {
+            const int lo = m.poly_off[k], hi = m.poly_off[k + 1];
+            bool odd = false;
+            for (int e = lo; e < hi; ++e) {
+                const double y1 = m.edge[4 * e + 1], y2 = m.edge[4 * e + 3];
+                if ((y1 > y) != (y2 > y)) {
+                    const double x1 = m.edge[4 * e], x2 = m.edge[4 * e + 2];
+                    const double xi = x1 + ((y - y1) * (x2 - x1)) / (y2 - y1);
+                    if (xi > x) odd = !odd;
+                }
+            }
+            const bool bad = k == n_poly - 1 ? !odd : odd;
+            if (bad && k < fail) fail = k;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const int o = __shfl_xor(fail, off);
+            if (o < fail) fail = o;
+        }
+        if (fail != NONE) {
+            if (hits == 0) { hit_row = r; hit_poly = fail; }
+            ++hits;
+        }
+    }
+    wave_argmin3(wv, wr, we);
+    if (lane == 0) {
+        nmpc_map_clearance c = m.rec[b];
+        if (wv < c.wall2 || (wv == c.wall2 && (wr < c.wall_row || (wr == c.wall_row && we < c.wall_edge)))) {
+            c.wall2 = wv; c.wall_row = wr; c.wall_edge = we;
+        }
+        if (hits > 0) {
+            if (c.hits == 0) { c.hit_row = hit_row; c.hit_poly = hit_poly; }
+            c.hits += hits;
+        }
+        m.rec[b] = c;
+    }
+}
+
 // ---- missions: a robot at its goal takes up its next route (nmpc_loop_set_missions; the rule is DESIGN.md section 5.9) ----
 struct DispatchArgs {
     int n_u, n1;

@@ -2,7 +2,7 @@
 // entry points of include/nmpc_solver.h.  Part of the one translation unit: nmpc_kernels.hip includes it inside its extern "C" block,
 // after the handle, fail, HIP_TRY and nmpc_solve_batch_device.
 //
-// A loop is its base (assemble -> solve -> advance) plus up to four stages, each a sub-struct with its device buffers and its kernels'
+// A loop is its base (assemble -> solve -> advance) plus up to five stages, each a sub-struct with its device buffers and its kernels'
 // argument block.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop
 // as it was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the
 // configuration final: loop_wire then sets every pointer one stage reads of another's, and nmpc_loop_step is ONE sequence of kernels
@@ -55,6 +55,13 @@ struct LoopMonitor {         // nmpc_loop_set_monitor: one more kernel per step,
     DevBuf<nmpc_clearance> rec;      // [B]
     bool made() const { return rec != nullptr; }
 };
+struct LoopMap {             // nmpc_loop_set_map_monitor: one more kernel per step, after the advance and the clearance monitor
+    nmpc::MapArgs a{};
+    DevBuf<double> edge;             // [E][4]
+    DevBuf<int> poly_off, edge_poly; // [n_poly + 1], [E]
+    DevBuf<nmpc_map_clearance> rec;  // [B]
+    bool made() const { return rec != nullptr; }
+};
 // nmpc_loop_set_missions: a robot at its goal takes up the next route of its mission; one more kernel per step, before the compaction
 struct LoopMissions {
     nmpc::DispatchArgs a{};
@@ -79,6 +86,7 @@ struct nmpc_loop {
     LoopPeers peers;
     LoopRetire retire;
     LoopMonitor monitor;
+    LoopMap map;
     LoopMissions missions;
 };
 
@@ -281,6 +289,46 @@ int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of)
     return NMPC_OK;
 }
 
+static const nmpc_map_clearance MAP_CLEARANCE_NONE = {__builtin_inf(), -1, -1, 0, -1, -1, 0};
+static constexpr int MAP_MAX_EDGES = 1024;
+
+int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_map_monitor", l->map.made(), "the loop has its map monitor already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopArgs &a = l->a;
+    if (!map) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: map is NULL");
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: the loop records no trajectory (max_steps == 0)");
+    const int E = map->n_edge, np = map->n_poly;
+    if (E < 3 || E > MAP_MAX_EDGES) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: n_edge outside 3 .. 1024");
+    if (np < 1 || np > E / 3) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: n_poly outside 1 .. n_edge / 3");
+    if (!map->edge || !map->poly_off) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: edge or poly_off is NULL");
+    if (map->poly_off[0] != 0 || map->poly_off[np] != E) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: poly_off does not run from 0 to n_edge");
+    for (int k = 0; k < np; ++k)
+        if (map->poly_off[k + 1] > E || map->poly_off[k] < 0 || map->poly_off[k + 1] - map->poly_off[k] < 3)
+            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_map_monitor: poly_off gives polygon " + std::to_string(k) + " fewer than three edges").c_str());
+    for (int i = 0; i < 4 * E; ++i)
+        if (!(map->edge[i] >= -DBL_MAX && map->edge[i] <= DBL_MAX))
+            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_map_monitor: a coordinate of edge " + std::to_string(i / 4) + " is not finite").c_str());
+    std::vector<int> owner(E);
+    for (int k = 0; k < np; ++k)
+        for (int e = map->poly_off[k]; e < map->poly_off[k + 1]; ++e) owner[e] = k;
+    LoopMap st;
+    const std::vector<nmpc_map_clearance> none(a.B, MAP_CLEARANCE_NONE);
+    HIP_TRY(h, st.rec.upload(none.data(), a.B));
+    HIP_TRY(h, st.edge.upload(map->edge, 4 * (size_t)E));
+    HIP_TRY(h, st.poly_off.upload(map->poly_off, (size_t)np + 1));
+    HIP_TRY(h, st.edge_poly.upload(owner.data(), E));
+    nmpc::MapArgs &m = st.a;
+    m.B = a.B; m.s = a.s; m.E = E; m.n_poly = np;
+    m.traj = l->d_traj;
+    m.edge = st.edge; m.poly_off = st.poly_off; m.edge_poly = st.edge_poly;
+    m.rec = st.rec;
+    l->map = std::move(st);
+    return NMPC_OK;
+}
+
 int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *leg_route)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
@@ -332,7 +380,7 @@ static int loop_nactive(nmpc_loop *l, int *n)
 static void loop_wire(nmpc_loop *l)
 {
     const int *act = l->retire.act;
-    l->a.act = l->peers.a.act = l->monitor.a.act = l->missions.a.act = act;
+    l->a.act = l->peers.a.act = l->monitor.a.act = l->map.a.act = l->missions.a.act = act;
     l->monitor.a.retired_at = l->retire.retired_at;
     l->retire.a.pred = l->peers.pred;
 }
@@ -386,6 +434,10 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         if (l->monitor.made()) {       // over the robots the advance ran over: the compaction comes after
             l->monitor.a.traj_row = a.traj_row;
             hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, l->monitor.a);
+        }
+        if (l->map.made()) {           // the same rows of the same robots, against the map
+            l->map.a.traj_row = a.traj_row;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, l->map.a);
         }
         if (l->missions.made()) {
             l->missions.a.step = l->steps + 1;
@@ -476,6 +528,19 @@ int nmpc_loop_clearance(nmpc_loop *l, nmpc_clearance *out)
         return NMPC_OK;
     }
     HIP_TRY(l->h, l->monitor.rec.read(out, B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out)
+{
+    if (!out) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_settle(l)) return rc;
+    const int B = l->a.B;
+    if (!l->map.made()) {
+        for (int b = 0; b < B; ++b) out[b] = MAP_CLEARANCE_NONE;
+        return NMPC_OK;
+    }
+    HIP_TRY(l->h, l->map.rec.read(out, B));
     return NMPC_OK;
 }
 

@@ -313,18 +313,29 @@ def plan_scene(planner: VisibilityPlanner) -> PlanScene:
     sc = getattr(planner, "_plan_scene", None)
     if sc is not None:
         return sc
-    polys = list(planner.obstacles) + [planner.boundary]
-    V, E = len(planner.nodes), sum(len(p) for p in polys)
+    edges, off = map_edges(planner, inflated=True)
+    V, E = len(planner.nodes), len(edges)
     if V > PLAN_MAX_NODES or E > PLAN_MAX_EDGES:
         raise ValueError(f"scene with {V} nodes and {E} edges: the batched planner takes {PLAN_MAX_NODES} and {PLAN_MAX_EDGES} at the most")
-    edges = np.array([[*poly[i], *poly[(i + 1) % len(poly)]] for poly in polys for i in range(len(poly))], dtype=np.float64).reshape(E, 4)
-    off = np.zeros(len(polys) + 1, dtype=np.int32)
-    off[1:] = np.cumsum([len(p) for p in polys])
     nodes = np.array(planner.nodes, dtype=np.float64).reshape(V, 2)
     allv = [v for o in planner.original_obstacles for v in o] + list(planner.original_boundary)
     nv = np.array([allv[harness.closest_index(c, allv)] for c in planner.nodes], dtype=np.float64).reshape(V, 2)
     sc = planner._plan_scene = PlanScene(nodes, edges, off, nv)
     return sc
+
+
+def map_edges(planner: VisibilityPlanner, inflated: bool = False):
+    """-> (edges [E, 4] = (x1, y1, x2, y2), poly_off [n_poly + 1] int32) of a planner's scene in the ``nmpc_scene`` layout, the obstacles
+    first and the boundary last: what ``trajectory.MapMonitor`` takes.  By default the ORIGINAL obstacles and boundary, the true walls;
+    ``inflated=True``: the polygons the planner plans on, where a hit means "closer than ``vehicle_width``"."""
+    if inflated:
+        polys = list(planner.obstacles) + [planner.boundary]
+    else:
+        polys = list(planner.original_obstacles) + [planner.original_boundary]
+    edges = np.array([[*poly[i], *poly[(i + 1) % len(poly)]] for poly in polys for i in range(len(poly))], dtype=np.float64).reshape(-1, 4)
+    off = np.zeros(len(polys) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(p) for p in polys])
+    return edges, off
 
 
 def _free_batch(sc: PlanScene, a, b, chunk=8192):

@@ -503,6 +503,110 @@ def no_clearance(B: int):
     return rec
 
 
+MAP_MAX_EDGES = 1024        # E of a map monitor's map (nmpc_loop_set_map_monitor)
+
+
+def no_map_clearance(B: int):
+    """-> the initial map records [B]: wall2 +inf, rows, edge and polygon -1, no hits."""
+    rec = np.zeros(B, dtype=_lib.MAP_CLEARANCE_DTYPE)
+    rec["wall2"] = np.inf
+    rec["wall_row"] = rec["wall_edge"] = rec["hit_row"] = rec["hit_poly"] = -1
+    return rec
+
+
+@dataclasses.dataclass(frozen=True)
+class MapMonitor:
+    """The map monitor, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon`` alike: per robot, the closest
+    approach to the walls of a polygon map over the poses driven so far, and the rows at which it stood inside an obstacle, outside the
+    boundary or went through an edge between two rows (``map_clearance``, a ``_lib.MAP_CLEARANCE_DTYPE`` array [B]).  It observes only.
+    ``edges`` [E, 4] = (x1, y1, x2, y2) polygon by polygon, the obstacles first and the boundary last; ``poly_off`` [n_poly + 1]: polygon
+    k owns the edges poly_off[k] .. poly_off[k + 1] (``frontend.map_edges`` gives both for a planner's scene)."""
+    edges: object
+    poly_off: object
+
+    def checked(self):
+        """-> (edges [E, 4] float64, poly_off [n_poly + 1] int32), contiguous; ValueError for what ``nmpc_loop_set_map_monitor`` refuses."""
+        edges = np.ascontiguousarray(self.edges, dtype=np.float64)
+        off = np.ascontiguousarray(self.poly_off, dtype=np.int32).reshape(-1)
+        if edges.ndim != 2 or edges.shape[1] != 4:
+            raise ValueError(f"map monitor: edges of shape {edges.shape}, not [E, 4]")
+        E, n_poly = len(edges), len(off) - 1
+        if E < 3 or E > MAP_MAX_EDGES:
+            raise ValueError(f"map monitor: {E} edges, 3 to {MAP_MAX_EDGES} are taken")
+        if n_poly < 1 or n_poly > E // 3:
+            raise ValueError(f"map monitor: {n_poly} polygons for {E} edges")
+        if off[0] != 0 or off[-1] != E or (np.diff(off) < 3).any():
+            raise ValueError("map monitor: poly_off must ascend from 0 to E in steps of three edges at least")
+        if not np.isfinite(edges).all():
+            raise ValueError("map monitor: a coordinate that is not finite")
+        return edges, off
+
+    def rows(self, ax, ay, x, y):
+        """The rule for n poses (x, y) [n], each with the pose (ax, ay) of the row before -> (v [n], e [n], poly [n]): the smallest squared
+        wall distance that is not NaN (+inf without any) and the first edge that has it, and the smallest failing polygon index, -1
+        if none fails.  Unfused f64 in the order DESIGN.md section 5.9 writes."""
+        edges, off = self.checked()
+        ax, ay, x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (ax, ay, x, y))
+        n, chunk = len(x), max(1, (1 << 20) // len(edges))
+        if n > chunk:
+            parts = [self.rows(ax[i:i + chunk], ay[i:i + chunk], x[i:i + chunk], y[i:i + chunk]) for i in range(0, n, chunk)]
+            return tuple(np.concatenate(c) for c in zip(*parts))
+        x1, y1, x2, y2 = (edges[:, k][None, :] for k in range(4))
+        X, Y, AX, AY = x[:, None], y[:, None], ax[:, None], ay[:, None]
+        at = np.arange(n)
+        with np.errstate(all="ignore"):
+            ex, ey = x2 - x1, y2 - y1
+            L2 = ex * ex + ey * ey
+            pos = L2 > 0
+            t = ((X - x1) * ex + (Y - y1) * ey) / np.where(pos, L2, 1.0)
+            t = np.where(t < 0, 0.0, t)
+            t = np.where(t > 1, 1.0, t)
+            t = np.where(pos, t, 0.0)
+            cx, cy = x1 + t * ex, y1 + t * ey
+            dx, dy = X - cx, Y - cy
+            v = dx * dx + dy * dy
+            v = np.where(np.isnan(v), np.inf, v)
+            e = np.argmin(v, axis=1)
+            # crossing between the two rows (frontend._seg_intersect_strict)
+            ux, uy = X - AX, Y - AY
+            o1 = ux * (y1 - AY) - uy * (x1 - AX)
+            o2 = ux * (y2 - AY) - uy * (x2 - AX)
+            o3 = ex * (AY - y1) - ey * (AX - x1)
+            o4 = ex * (Y - y1) - ey * (X - x1)
+            crossed = (o1 * o2 < -1e-9) & (o3 * o4 < -1e-9)
+            # containment: even-odd count per polygon
+            straddle = (y1 > Y) != (y2 > Y)
+            xi = x1 + ((Y - y1) * ex) / np.where(straddle, ey, 1.0)
+            hit = straddle & (xi > X)
+        first = off[:-1].astype(np.intp)
+        fails = (np.add.reduceat(hit.astype(np.int32), first, axis=1) & 1).astype(bool)          # [n, n_poly]: an odd count
+        fails[:, -1] = ~fails[:, -1]                                                            # the boundary fails on an even one
+        fails |= np.add.reduceat(crossed.astype(np.int32), first, axis=1) > 0
+        poly = np.where(fails.any(axis=1), np.argmax(fails, axis=1), -1).astype(np.int32)
+        return v[at, e], e.astype(np.int32), poly
+
+    def scan(self, traj):
+        """The rule over the rows >= 1 of a recorded trajectory table [rows, B, 3] (row r against row r - 1) -> the records [B] a monitor
+        would hold for robots driven over all those rows."""
+        T = np.asarray(traj, dtype=np.float64)
+        R, B = T.shape[0], T.shape[1]
+        rec = no_map_clearance(B)
+        if R < 2 or B == 0:
+            return rec
+        a, b = T[:-1].reshape(-1, 3), T[1:].reshape(-1, 3)
+        v, e, poly = (q.reshape(R - 1, B) for q in self.rows(a[:, 0], a[:, 1], b[:, 0], b[:, 1]))
+        at = np.arange(B)
+        k = np.argmin(v, axis=0)                                            # the first row with the smallest value
+        seen = v[k, at] < np.inf
+        rec["wall2"][seen], rec["wall_row"][seen], rec["wall_edge"][seen] = v[k, at][seen], k[seen] + 1, e[k, at][seen]
+        hit = poly >= 0
+        k = np.argmax(hit, axis=0)
+        some = hit.any(axis=0)
+        rec["hits"] = hit.sum(axis=0)
+        rec["hit_row"][some], rec["hit_poly"][some] = k[some] + 1, poly[k, at][some]
+        return rec
+
+
 class FleetRecedingHorizon(VectorizedRecedingHorizon):
     """``VectorizedRecedingHorizon`` for a fleet on R routes: robot b follows ``routes[route_of[b]]``.
 
@@ -525,6 +629,9 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     ``advance`` from the rows it appends to ``traj`` and the parameter vectors ``assemble`` returned for this step, for the robots
     the step drove.  Nothing else reads it.
 
+    ``map_monitor`` (a ``MapMonitor``): ``map_clearance`` [B] holds every robot's closest approach to the map's walls and its hits
+    (DESIGN.md section 5.9), updated by ``advance`` from the rows it appends to ``traj``, for the robots the step drove.
+
     ``missions`` (a ``Missions``, needs ``retire=True``): ``retire`` re-dispatches an active robot that is done and has another leg
     instead of retiring it: ``leg`` [B] and ``route_of`` [B] move on, ``leg_at`` [B, Lmax] takes the step count
     at which each leg ended (-1: not yet, or no such leg), the robot's reference sample, ``last_u``, ``U`` and ``Y`` rows are zeroed
@@ -532,7 +639,7 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None, missions=None):
+                 monitor=None, missions=None, map_monitor=None):
         self.routes = list(routes)
         cfg, B = self.routes[0].cfg, len(starts)
         route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
@@ -566,6 +673,10 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             g = np.zeros(B, dtype=np.int32) if g is None else g
             self.monitor_groups = [np.nonzero(g == v)[0] for v in np.unique(g)]   # members in ascending robot index
             self.clearance = no_clearance(B)
+        self.map_monitor = map_monitor
+        if map_monitor is not None:
+            map_monitor.checked()
+            self.map_clearance = no_map_clearance(B)
 
     @property
     def n_active(self):
@@ -656,7 +767,28 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         super().advance(U, self.active)
         if self.monitor is not None:
             self._monitor_update()
+        if self.map_monitor is not None:
+            self._map_update()
         self.steps += 1
+
+    def _map_update(self):
+        """The map monitor's rule on the s rows this step appended, each against the row before it, for the robots
+        the step drove.  The rows ascend, so a strictly smaller value is the only way to win, and ``rows`` names the first edge."""
+        s, rec = self.cfg.num_steps_taken, self.map_clearance
+        who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
+        if not len(who):
+            return
+        for i in range(s):
+            r = self.steps * s + 1 + i
+            at = len(self.traj) - s + i
+            pose, prev = self.traj[at], self.traj[at - 1]
+            v, e, poly = self.map_monitor.rows(prev[who, 0], prev[who, 1], pose[who, 0], pose[who, 1])
+            b, better = who, v < rec["wall2"][who]
+            rec["wall2"][b[better]], rec["wall_row"][b[better]], rec["wall_edge"][b[better]] = v[better], r, e[better]
+            hit = poly >= 0
+            first = hit & (rec["hits"][who] == 0)
+            rec["hit_row"][b[first]], rec["hit_poly"][b[first]] = r, poly[first]
+            rec["hits"][b[hit]] += 1
 
     def _monitor_update(self):
         """The monitor's rule on the s rows this step appended, for the robots it drove (``active`` as the
@@ -770,6 +902,11 @@ class DeviceRecedingHorizon:
     step before to have counted its active robots (an event, not the device).  Its host mirror is ``FleetRecedingHorizon`` with
     ``retire=True`` (tests/test_gpu_retire_loop.py).
 
+    ``map_monitor`` (a ``MapMonitor``, needs ``max_steps`` > 0): every robot's closest approach to the walls of a polygon map, and the rows
+    at which it was inside an obstacle, outside the boundary or went through an edge, are kept on the device
+    (``nmpc_loop_set_map_monitor``), one more kernel per step after the advance; ``map_clearance()`` reads the
+    records.  Its host mirror is ``FleetRecedingHorizon`` with the same ``map_monitor`` (tests/test_gpu_map_monitor_loop.py).
+
     ``missions`` (a ``Missions``, needs ``retire=True``): every robot drives the routes of its mission leg after leg and retires after
     the last (``nmpc_loop_set_missions``); one more kernel per step, before the active list is rebuilt.
     ``legs()`` tells where everybody is.  Its host mirror is ``FleetRecedingHorizon`` with the same ``missions``
@@ -777,7 +914,7 @@ class DeviceRecedingHorizon:
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None, retire=False, monitor=None, missions=None):
+                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -828,6 +965,15 @@ class DeviceRecedingHorizon:
         if monitor is not None:
             g = None if monitor.group_of is None else np.ascontiguousarray(monitor.group_of, dtype=np.int32).reshape(B)
             self._set(self.lib.nmpc_loop_set_monitor(h, _lib.as_i32p(g)))
+        self.map_monitor = map_monitor
+        if map_monitor is not None:
+            try:
+                edges, off = map_monitor.checked()
+            except ValueError:
+                self.close()
+                raise
+            sc = _lib.NmpcScene(0, len(edges), len(off) - 1, 0, None, _lib.as_dp(edges), _lib.as_i32p(off))
+            self._set(self.lib.nmpc_loop_set_map_monitor(h, C.byref(sc)))
         self.missions = missions
         self._leg_off = None
         if missions is not None:
@@ -899,6 +1045,13 @@ class DeviceRecedingHorizon:
         after synchronising; without a ``monitor`` the initial record everywhere."""
         rec = np.empty(self.B, dtype=_lib.CLEARANCE_DTYPE)
         self.solver._check(self.lib.nmpc_loop_clearance(self._l, rec.ctypes.data))
+        return rec
+
+    def map_clearance(self):
+        """-> the map monitor's records [B] (``_lib.MAP_CLEARANCE_DTYPE``: wall2, wall_row, wall_edge, hits, hit_row, hit_poly, reserved)
+        after synchronising; without a ``map_monitor`` the initial record everywhere."""
+        rec = np.empty(self.B, dtype=_lib.MAP_CLEARANCE_DTYPE)
+        self.solver._check(self.lib.nmpc_loop_map_clearance(self._l, rec.ctypes.data))
         return rec
 
     def read(self):

@@ -242,6 +242,14 @@ def clearance_differing(dev, host):
     return [f for f in a.dtype.names if a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes() or a[f].shape != b[f].shape]
 
 
+def map_clearance_differing(dev, host):
+    """``clearance_differing`` for the map monitor's records (``dev``: a ``DeviceRecedingHorizon`` with a map monitor or its
+    ``map_clearance()``, ``host``: its mirror or the mirror's ``map_clearance``): the fields that are not bit-equal."""
+    a = dev.map_clearance() if callable(getattr(dev, "map_clearance", None)) else dev
+    b = getattr(host, "map_clearance", host)
+    return [f for f in a.dtype.names if a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes() or a[f].shape != b[f].shape]
+
+
 def trajectory_differing(dev, host, steps, rows=None):
     """After ``steps`` steps of both: [] if the device's trajectory is [steps * num_steps_taken + 1, B, 3] and the mirror's bits
     (``rows`` as in ``step_differing``)."""

@@ -12,7 +12,9 @@ DESIGN.md section 5.9) in groups of G consecutive robots, default the --peers gr
 of robots that were inside a circle, inside a padded ellipse and closer to a groupmate than two peer radii, and the fleet's smallest value of each.
 --own-routes: every robot its own start and goal (workloads.own_route_fleet, seed 0), with --retire --legs L its own mission of L legs, each leg
 from the goal of the one before; the routes are planned on the device (frontend.DevicePlanner), and the result line
-gains plan_ms (the planner kernels' time over all batches, redraws included) and routes_planned.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+gains plan_ms (the planner kernels' time over all batches, redraws included) and routes_planned.  --map [inflated]: the map monitor
+(nmpc_loop_set_map_monitor) on the scene's original polygons, the true walls, or with "inflated" on the polygons the
+planner plans on; the result line then has map_clearance: the share of robots with a hit, the rows hit and the fleet's smallest wall distance.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -24,7 +26,7 @@ sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config                            # noqa: E402
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
-from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, MapMonitor, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
 from mpc_trajectory_generator_amd.workloads import moving_ellipses, route_fleet   # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -56,6 +58,9 @@ ap.add_argument("--own-routes", action="store_true",
 ap.add_argument("--monitor", type=int, nargs="?", const=0, default=None, metavar="G",
                 help="device loop only: keep every robot's closest approach to circles, scripted ellipses and the robots of its group of G "
                      "consecutive robots (of a sub-fleet) on the device, and report them; G defaults to the --peers groups, or 32")
+ap.add_argument("--map", nargs="?", const="original", default=None, choices=("original", "inflated"), metavar="inflated",
+                help="device loop only: keep every robot's closest approach to the scene's walls and its rows inside an obstacle, outside the "
+                     "boundary or through an edge on the device, and report them; 'inflated': against the polygons the planner plans on")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
@@ -65,6 +70,8 @@ if args.monitor is not None:
     if args.monitor < 0:
         ap.error("--monitor G: G >= 1")
     args.monitor = args.monitor or args.peers or 32
+if args.map and (args.host or args.steps < 1):
+    ap.error("--map reads the trajectory the device loop records: it needs the device loop (no --host) and --steps >= 1")
 if args.legs < 1 or (args.legs > 1 and (not args.retire or args.host)):
     ap.error("--legs L: L >= 1, and L > 1 needs --retire on the device loop")
 if args.own_routes and (args.host or args.routes != 1):
@@ -89,6 +96,11 @@ def monitor_of(n):
     """groups of --monitor consecutive robots among n"""
     return Monitor(group_of=(np.arange(n) // args.monitor).astype(np.int32)) if args.monitor else None
 
+
+map_monitor = None
+if args.map:
+    from mpc_trajectory_generator_amd.frontend import map_edges, scene_planner
+    map_monitor = MapMonitor(*map_edges(scene_planner(cfg, args.scene), inflated=args.map == "inflated"))
 
 planning = {}
 legs_of = None
@@ -159,7 +171,7 @@ if not args.host:
         sub_routes, sub_route_of = routes_of(ids)
         loops.append(DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                            route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
-                                           missions=missions_of(ids)))
+                                           missions=missions_of(ids), map_monitor=map_monitor))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -196,6 +208,10 @@ if not args.host:
             "closer_than_two_peer_radii_frac": float((rec["peer2"] < (2 * peer_radius) ** 2).mean()), "two_peer_radii_m": 2 * peer_radius,
             "min_circle_m": float(rec["circle"].min()), "min_ellipse_level": float(rec["ellipse"].min()),
             "min_peer_m": float(np.sqrt(rec["peer2"].min()))}
+    if args.map:
+        rec = np.concatenate([rh.map_clearance() for rh in loops])
+        quality["map_clearance"] = {"polygons": args.map, "edges": len(map_monitor.edges), "robots_hit_frac": float((rec["hits"] > 0).mean()),
+                                    "rows_hit": int(rec["hits"].sum()), "min_wall_m": float(np.sqrt(rec["wall2"].min()))}
     from mpc_trajectory_generator_amd import _lib
     if hasattr(_lib.load_library(), "nmpc_debug_win_stats"):        # instrumented build (-DNMPC_WIN_STATS, scripts/win_stats.py)
         buf = (ctypes.c_ulonglong * 2)()
@@ -208,6 +224,7 @@ if not args.host:
                                + (f", robots start up to {args.back} samples before the route's end" if args.back != 60 else "")
                                + (", robots retire at their goals" if args.retire else "")
                                + (f", clearance monitor in groups of {args.monitor}" if args.monitor else "")
+                               + (f", map monitor on the scene's {args.map} polygons" if args.map else "")
                                + (f", at most {args.budget} PANOC iterations per solve (NotConvergedOutOfTime beyond)" if args.budget else "")
                                + (f", fleet split into {args.split} sub-fleets on {args.split} streams" if args.split > 1 else ""),
                    "kernel": solver.kernel_name},
