@@ -251,6 +251,26 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
  * K + M > Ndynobs, a group_of[b] out of range, an rx, ry or range that is not finite and positive, a call after a step, or
  * a second call.  A loop without peers enqueues what it enqueued before this function existed. */
 int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range);
+/* Peers found through a grid: the rule and the results of nmpc_loop_set_peers, bit for bit, at a cost that grows with the robots
+ * near each other, not with the group (the rule, and why it misses nobody: DESIGN.md section 5.9).  Every step, on the device, each
+ * robot's box over its predicted positions is filed in a uniform grid of edge `cell` (metres; the edge grows where the fleet's extent
+ * would need more than 128 cells on an axis), and a robot forms its distances to the robots filed in the cells its range can reach
+ * instead of to all of its group.  group_of keeps its meaning (NULL = everybody: "avoid whoever is near").  Three kernels take the
+ * place of the all-pairs one.
+ * This is the loop's peers call: either setter after the other, a second call or a call after a step is refused.  NMPC_ERR_BAD_ARG
+ * with a message, and nothing changed, for everything nmpc_loop_set_peers refuses and for a cell that is not finite and positive. */
+int nmpc_loop_set_peers_grid(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range, double cell);
+/* The grid of the last step, for tests and reports: the minimum of the filed robots' lower box corners, the cells' edges per axis,
+ * the fleet's largest box extent per axis, the cells per axis and the robots filed (those with a stage at which both coordinates
+ * are finite). */
+typedef struct nmpc_peer_grid {      /* 64 bytes */
+    double origin[2], h[2], W[2];
+    int32_t nx, ny, filed, reserved;
+} nmpc_peer_grid;
+/* Synchronises, then copies out the last step's grid and, if asked for (NULL = skip), cell_of [B]: the cell each robot is filed
+ * under (row-major, y * nx + x), -1 for an unfiled one.  NMPC_ERR_BAD_ARG on a loop without nmpc_loop_set_peers_grid or before its
+ * first step. */
+int nmpc_loop_peer_grid(nmpc_loop *l, nmpc_peer_grid *out, int32_t *cell_of);
 /* Retirement: robots that reach their goal leave the loop, as the reference's `while not terminal` ends for one robot
  * (src/path_generator.py:290,397).  Off unless on != 0 is given here; a loop without it enqueues what it enqueued before this
  * function existed.  With it, every robot is active at the first step; after a step's advance an active robot whose terminal

@@ -25,6 +25,7 @@ SYMBOLS = (
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
     "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run", "nmpc_loop_set_monitor", "nmpc_loop_clearance",
     "nmpc_loop_set_missions", "nmpc_loop_legs", "nmpc_loop_set_map_monitor", "nmpc_loop_map_clearance",
+    "nmpc_loop_set_peers_grid", "nmpc_loop_peer_grid",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -91,6 +92,10 @@ assert CLEARANCE_DTYPE.itemsize == 40
 MAP_CLEARANCE_DTYPE = np.dtype([("wall2", "<f8"), ("wall_row", "<i4"), ("wall_edge", "<i4"), ("hits", "<i4"),
                                 ("hit_row", "<i4"), ("hit_poly", "<i4"), ("reserved", "<i4")])
 assert MAP_CLEARANCE_DTYPE.itemsize == 32
+
+# nmpc_peer_grid: the grid the peers of a step were found through (nmpc_loop_set_peers_grid)
+PEER_GRID_DTYPE = np.dtype([("origin", "<f8", 2), ("h", "<f8", 2), ("W", "<f8", 2), ("nx", "<i4"), ("ny", "<i4"), ("filed", "<i4"), ("reserved", "<i4")])
+assert PEER_GRID_DTYPE.itemsize == 64
 
 
 def _sources():
@@ -279,6 +284,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
                                          C.c_int, dp, C.c_int, C.POINTER(vp)]
     lib.nmpc_loop_set_peers.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_double, C.c_double]
     lib.nmpc_loop_set_peers.restype = C.c_int
+    lib.nmpc_loop_set_peers_grid.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]
+    lib.nmpc_loop_set_peers_grid.restype = C.c_int
+    lib.nmpc_loop_peer_grid.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    lib.nmpc_loop_peer_grid.restype = C.c_int
     lib.nmpc_loop_set_retire.argtypes = [vp, C.c_int]
     lib.nmpc_loop_set_retire.restype = C.c_int
     lib.nmpc_loop_active.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -302,6 +302,61 @@ __global__ void nmpc_loop_predict_kernel(PeerArgs a)
     }
 }
 
+// What the two peers kernels share: a lane's list of its best NDYN_MAX candidates, sorted by (D, j) and held in registers (static
+// indices); no candidate = (inf, INT_MAX), behind every real one
+constexpr int PEER_NONE = 0x7fffffff;
+
+// D(b, j) = min_k |pred[b][k] - pred[j][k]|^2, b's positions in `own` (LDS), j's row of pred in `pj`
+__device__ __forceinline__ double peer_closeness(const double *own, const double *pj, int N)
+{
+    double D = __builtin_inf();
+    for (int k = 0; k < N; ++k) {
+        const double dx = own[2 * k] - pj[3 * k], dy = own[2 * k + 1] - pj[3 * k + 1];
+        const double d = dx * dx + dy * dy;
+        if (d < D) D = d;
+    }
+    return D;
+}
+
+// candidate (cd, cj) into the lane's sorted list
+__device__ __forceinline__ void peer_keep(double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX], double cd, int cj)
+{
+#pragma unroll
+    for (int q = 0; q < NDYN_MAX; ++q) {
+        if (cd < bd[q] || (cd == bd[q] && cj < bj[q])) {
+            const double td = bd[q]; const int tj = bj[q];
+            bd[q] = cd; bj[q] = cj;
+            cd = td; cj = tj;
+        }
+    }
+}
+
+// M rounds: the wave's (D, j) minimum over the lanes' heads, written over ellipse slot K + m of p[b]; the lane that held it moves on
+// to its next
+__device__ __forceinline__ void peer_overlay(const PeerArgs &a, int b, int lane, double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX])
+{
+    const int N = a.N;
+    double *pd = a.P + (size_t)b * a.n_p + a.pdyn;
+    const int per = 5 * N;
+    for (int m = 0; m < a.M; ++m) {
+        double d = bd[0];
+        int j = bj[0];
+        wave_argmin(d, j);
+        if (j == PEER_NONE) break;            // (wave-uniform) no candidate left: the remaining slots keep what they hold
+        if (bj[0] == j) {
+#pragma unroll
+            for (int q = 0; q + 1 < NDYN_MAX; ++q) { bd[q] = bd[q + 1]; bj[q] = bj[q + 1]; }
+            bd[NDYN_MAX - 1] = __builtin_inf(); bj[NDYN_MAX - 1] = PEER_NONE;
+        }
+        const double *pj = a.pred + (size_t)j * N * 3;
+        double *slot = pd + (size_t)(a.K + m) * per;
+        for (int e = lane; e < per; e += 64) {
+            const int st = e / 5, f = e - st * 5;
+            slot[e] = f == 0 ? pj[3 * st] : (f == 1 ? pj[3 * st + 1] : (f == 2 ? a.rx : (f == 3 ? a.ry : pj[3 * st + 2])));
+        }
+    }
+}
+
 // one wave per robot: D(b, j) = min_k |pred[b][k] - pred[j][k]|^2 over the members j != b of b's group (lanes stride over them),
 // the first M of the candidates D < range^2 in (D, j) order, each written over one ellipse slot of p[b]
 __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
@@ -317,54 +372,226 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
         own[2 * k + 1] = a.pred[((size_t)b * N + k) * 3 + 1];
     }
     __syncthreads();
-    // the lane's own best NDYN_MAX candidates, sorted by (D, j); no candidate = (inf, INT_MAX), behind every real one
-    constexpr int NONE = 0x7fffffff;
     double bd[NDYN_MAX];
     int bj[NDYN_MAX];
 #pragma unroll
-    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = NONE; }
+    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = PEER_NONE; }
     for (int i = lo + lane; i < hi; i += 64) {
         const int j = a.gmem[i];
-        const double *pj = a.pred + (size_t)j * N * 3;
-        double D = __builtin_inf();
-        for (int k = 0; k < N; ++k) {
-            const double dx = own[2 * k] - pj[3 * k], dy = own[2 * k + 1] - pj[3 * k + 1];
-            const double d = dx * dx + dy * dy;
-            if (d < D) D = d;
+        const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N);
+        if (j != b && D < a.range2) peer_keep(bd, bj, D, j);
+    }
+    peer_overlay(a, b, lane, bd, bj);
+}
+
+// ---- peers through a grid (nmpc_loop_set_peers_grid; the rule, and why it misses nobody: DESIGN.md section 5.9) ----
+// The same selection over fewer candidates.  Three kernels take the place of nmpc_loop_peers_kernel: every robot's box over its
+// predicted positions, a uniform grid in which each robot is filed once, under the cell of its box's lower corner, and per robot the
+// rule of the all-pairs kernel over the robots filed in the cells its range can reach.
+constexpr int PEER_GRID_CAP = 128;      // cells per axis at the most: 16 384 cells, two per robot of the largest fleet run (8192)
+
+struct PeerGridArgs {
+    int B, N;
+    double range, cell;
+    const double *pred;       // [B][N][3]
+    double *box;              // [B][4]: lo.x, lo.y, hi.x, hi.y over the finite stages; (inf, inf, -inf, -inf) = unfiled
+    nmpc_peer_grid *hdr;      // [1]: this step's grid
+    int *cell_of;             // [B]: the robot's cell (row-major, y * nx + x), -1 = unfiled
+    int *cell_off;            // [CAP * CAP + 1]: cell c holds cell_mem[cell_off[c] .. cell_off[c + 1])
+    int *cell_cur;            // [CAP * CAP]: the scatter's cursors
+    int *cell_mem;            // [B]
+};
+
+// the cell of coordinate v on an axis of n cells of edge h from o: monotone non-decreasing in v (every operation is; t is a NaN
+// only with h = inf, where every v answers 0)
+__device__ __forceinline__ int peer_cellof(double v, double o, double h, int n)
+{
+    const double t = (v - o) / h;
+    if (!(t > 0.0)) return 0;
+    if (t >= (double)n) return n - 1;
+    return (int)t;
+}
+
+// an axis of the grid: cells of edge `cell` over the extent ex >= 0 of the lower corners, or CAP cells of edge ex / CAP
+__device__ __forceinline__ void peer_grid_axis(double ex, double cell, int &n, double &h)
+{
+    const double q = ex / cell;
+    if (q < (double)PEER_GRID_CAP) { n = (int)q + 1; h = cell; }
+    else { n = PEER_GRID_CAP; h = ex / (double)PEER_GRID_CAP; }
+}
+
+// a box's extent rounded up: never below the real hi - lo
+__device__ __forceinline__ double peer_extent_up(double hi, double lo)
+{
+    const double w = hi - lo;
+    return w < __builtin_inf() ? __longlong_as_double(__double_as_longlong(w) + 1) : w;
+}
+
+// one thread per robot, all B (a retired robot stands parked in pred): the box of its predicted positions
+__global__ void nmpc_loop_peer_box_kernel(PeerGridArgs g)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= g.B) return;
+    const double *p = g.pred + (size_t)b * g.N * 3;
+    const double inf = __builtin_inf();
+    double lx = inf, ly = inf, hx = -inf, hy = -inf;
+    for (int k = 0; k < g.N; ++k) {
+        const double x = p[3 * k], y = p[3 * k + 1];
+        if (fabs(x) < inf && fabs(y) < inf) {      // a stage with a NaN or an infinity is in nobody's D
+            lx = x < lx ? x : lx; ly = y < ly ? y : ly;
+            hx = x > hx ? x : hx; hy = y > hy ? y : hy;
         }
-        if (j != b && D < a.range2) {
-            double cd = D;
-            int cj = j;
+    }
+    double *out = g.box + 4 * (size_t)b;
+    out[0] = lx; out[1] = ly; out[2] = hx; out[3] = hy;
+}
+
+// One workgroup, thread t over the robots [t * chunk, (t + 1) * chunk) as in nmpc_loop_compact_kernel: the grid's header (minima and
+// maxima: the order of a reduction does not show), every robot's cell, the cells' populations counted with integer atomics in global
+// memory (cell_off: 64 KB at CAP = 128, more than a workgroup's static LDS), their exclusive scan, and the scatter into cell_mem.
+// The order inside a cell is the atomics' and differs from run to run; no result depends on it.  Stores, atomics and loads of the
+// same words are ordered by the device-scope fences in front of the barriers.
+__global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(PeerGridArgs g)
+{
+    __shared__ double red[16][6];
+    __shared__ int redn[16];
+    __shared__ int cnt[1024];
+    const int t = threadIdx.x, nt = blockDim.x, B = g.B;
+    const int chunk = (B + nt - 1) / nt;
+    const int lo = t * chunk < B ? t * chunk : B, hi = lo + chunk < B ? lo + chunk : B;
+    const double inf = __builtin_inf();
+    double v[6] = {inf, inf, -inf, -inf, 0.0, 0.0};       // min lo.x, min lo.y, max lo.x, max lo.y, max extent x, max extent y
+    int nf = 0;
+    for (int b = lo; b < hi; ++b) {
+        const double *bx = g.box + 4 * (size_t)b;
+        if (bx[0] <= bx[2]) {
+            const double wx = peer_extent_up(bx[2], bx[0]), wy = peer_extent_up(bx[3], bx[1]);
+            v[0] = bx[0] < v[0] ? bx[0] : v[0]; v[1] = bx[1] < v[1] ? bx[1] : v[1];
+            v[2] = bx[0] > v[2] ? bx[0] : v[2]; v[3] = bx[1] > v[3] ? bx[1] : v[3];
+            v[4] = wx > v[4] ? wx : v[4]; v[5] = wy > v[5] ? wy : v[5];
+            ++nf;
+        }
+    }
 #pragma unroll
-            for (int q = 0; q < NDYN_MAX; ++q) {
-                if (cd < bd[q] || (cd == bd[q] && cj < bj[q])) {
-                    const double td = bd[q]; const int tj = bj[q];
-                    bd[q] = cd; bj[q] = cj;
-                    cd = td; cj = tj;
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const double o = __shfl_xor(v[q], off);
+            v[q] = q < 2 ? (o < v[q] ? o : v[q]) : (o > v[q] ? o : v[q]);
+        }
+        nf += __shfl_xor(nf, off);
+    }
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) red[t >> 6][q] = v[q];
+        redn[t >> 6] = nf;
+    }
+    __syncthreads();
+    nf = 0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) v[q] = q < 2 ? inf : (q < 4 ? -inf : 0.0);
+    for (int w = 0; w < nt / 64; ++w) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const double o = red[w][q];
+            v[q] = q < 2 ? (o < v[q] ? o : v[q]) : (o > v[q] ? o : v[q]);
+        }
+        nf += redn[w];
+    }
+    // the grid: the same in every thread
+    int nx = 1, ny = 1;
+    double hx = g.cell, hy = g.cell;
+    if (nf == 0) { v[0] = 0.0; v[1] = 0.0; }
+    else {
+        peer_grid_axis(v[2] - v[0], g.cell, nx, hx);
+        peer_grid_axis(v[3] - v[1], g.cell, ny, hy);
+    }
+    const int cells = nx * ny;
+    if (t == 0) {
+        nmpc_peer_grid *h = g.hdr;
+        h->origin[0] = v[0]; h->origin[1] = v[1]; h->h[0] = hx; h->h[1] = hy; h->W[0] = v[4]; h->W[1] = v[5];
+        h->nx = nx; h->ny = ny; h->filed = nf; h->reserved = 0;
+    }
+    for (int c = t; c <= cells; c += nt) g.cell_off[c] = 0;
+    __threadfence();
+    __syncthreads();
+    for (int b = lo; b < hi; ++b) {
+        const double *bx = g.box + 4 * (size_t)b;
+        int c = -1;
+        if (bx[0] <= bx[2]) {
+            c = peer_cellof(bx[1], v[1], hy, ny) * nx + peer_cellof(bx[0], v[0], hx, nx);
+            atomicAdd(g.cell_off + c, 1);
+        }
+        g.cell_of[b] = c;
+    }
+    __threadfence();
+    __syncthreads();
+    // exclusive scan of the populations: thread t over the entries [t * cchunk, (t + 1) * cchunk), the one behind the last cell included
+    const int ncell = cells + 1;
+    const int cchunk = (ncell + nt - 1) / nt;
+    const int clo = t * cchunk < ncell ? t * cchunk : ncell, chi = clo + cchunk < ncell ? clo + cchunk : ncell;
+    int sum = 0;
+    for (int c = clo; c < chi; ++c) sum += g.cell_off[c];
+    cnt[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < nt; off <<= 1) {            // inclusive scan
+        const int o = t >= off ? cnt[t - off] : 0;
+        __syncthreads();
+        cnt[t] += o;
+        __syncthreads();
+    }
+    int run = cnt[t] - sum;
+    for (int c = clo; c < chi; ++c) {
+        const int n = g.cell_off[c];
+        g.cell_off[c] = run;
+        if (c < cells) g.cell_cur[c] = run;
+        run += n;
+    }
+    __threadfence();
+    __syncthreads();
+    for (int b = lo; b < hi; ++b) {
+        const int c = g.cell_of[b];                     // (the thread's own store above)
+        if (c >= 0) g.cell_mem[atomicAdd(g.cell_cur + c, 1)] = b;
+    }
+}
+
+// one wave per active robot: the rule of nmpc_loop_peers_kernel over the robots filed in the cells of b's window, row after row (a
+// row's cells cx0 .. cx1 are one range of cell_mem, and the lanes stride over it).  Every loop's bounds are read before it starts.
+__global__ __launch_bounds__(64) void nmpc_loop_peers_grid_kernel(PeerArgs a, PeerGridArgs g)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    const int b = a.act ? a.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
+    const int N = a.N;
+    for (int k = lane; k < N; k += 64) {
+        own[2 * k] = a.pred[((size_t)b * N + k) * 3];
+        own[2 * k + 1] = a.pred[((size_t)b * N + k) * 3 + 1];
+    }
+    __syncthreads();
+    double bd[NDYN_MAX];
+    int bj[NDYN_MAX];
+#pragma unroll
+    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = PEER_NONE; }
+    // the box, the grid and the window: the same for the whole wave
+    const double *bx = g.box + 4 * (size_t)b;
+    const nmpc_peer_grid *h = g.hdr;
+    if (bx[0] <= bx[2]) {                               // an unfiled robot finds nobody
+        const int nx = h->nx, ny = h->ny, grp = a.group_of[b];
+        const int cx0 = peer_cellof((bx[0] - g.range) - h->W[0], h->origin[0], h->h[0], nx);
+        const int cy0 = peer_cellof((bx[1] - g.range) - h->W[1], h->origin[1], h->h[1], ny);
+        const int cx1 = peer_cellof(bx[2] + g.range, h->origin[0], h->h[0], nx);
+        const int cy1 = peer_cellof(bx[3] + g.range, h->origin[1], h->h[1], ny);
+        for (int row = cy0; row <= cy1; ++row) {
+            const int i0 = g.cell_off[row * nx + cx0], i1 = g.cell_off[row * nx + cx1 + 1];
+            for (int i = i0 + lane; i < i1; i += 64) {
+                const int j = g.cell_mem[i];
+                if (j != b && a.group_of[j] == grp) {
+                    const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N);
+                    if (D < a.range2) peer_keep(bd, bj, D, j);
                 }
             }
         }
     }
-    // M rounds: the wave's (D, j) minimum over the lanes' heads; the lane that held it moves on to its next
-    double *pd = a.P + (size_t)b * a.n_p + a.pdyn;
-    const int per = 5 * N;
-    for (int m = 0; m < a.M; ++m) {
-        double d = bd[0];
-        int j = bj[0];
-        wave_argmin(d, j);
-        if (j == NONE) break;                 // (wave-uniform) no candidate left: the remaining slots keep what they hold
-        if (bj[0] == j) {
-#pragma unroll
-            for (int q = 0; q + 1 < NDYN_MAX; ++q) { bd[q] = bd[q + 1]; bj[q] = bj[q + 1]; }
-            bd[NDYN_MAX - 1] = __builtin_inf(); bj[NDYN_MAX - 1] = NONE;
-        }
-        const double *pj = a.pred + (size_t)j * N * 3;
-        double *slot = pd + (size_t)(a.K + m) * per;
-        for (int e = lane; e < per; e += 64) {
-            const int st = e / 5, f = e - st * 5;
-            slot[e] = f == 0 ? pj[3 * st] : (f == 1 ? pj[3 * st + 1] : (f == 2 ? a.rx : (f == 3 ? a.ry : pj[3 * st + 2])));
-        }
-    }
+    peer_overlay(a, b, lane, bd, bj);
 }
 
 // ---- retirement: robots that reached their goal leave the loop (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9) ----

@@ -33,7 +33,13 @@ struct LoopPeers {           // nmpc_loop_set_peers: two more kernels per step, 
     nmpc::PeerArgs a{};
     DevBuf<double> pred;     // [B][N][3]
     LoopGroups groups;
+    // nmpc_loop_set_peers_grid: the candidates come from a grid, three kernels in the place of the all-pairs one
+    nmpc::PeerGridArgs g{};
+    DevBuf<double> box;              // [B][4]
+    DevBuf<nmpc_peer_grid> hdr;      // [1]
+    DevBuf<int> cell_of, cell_off, cell_cur, cell_mem;      // [B], [CAP * CAP + 1], [CAP * CAP], [B]
     bool made() const { return pred != nullptr; }
+    bool grid() const { return box != nullptr; }
 };
 // nmpc_loop_set_retire: robots at their goal leave the loop.  A step runs over the active list, the solve over gathered rows, and
 // the host learns the list's length one step late (nmpc_loop.h)
@@ -204,18 +210,21 @@ static int loop_setter(nmpc_loop *l, const char *fn, bool has, const char *alrea
     return NMPC_OK;
 }
 
-int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range)
+// both peers setters: `cell` NULL = all pairs (nmpc_loop_set_peers), else the grid's edge
+static int loop_set_peers(nmpc_loop *l, const char *fn, const int32_t *group_of, int M, double rx, double ry, double range, const double *cell)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
-    if (const int rc = loop_setter(l, "nmpc_loop_set_peers", l->peers.made(), "the loop has its peers already")) return rc;
+    if (const int rc = loop_setter(l, fn, l->peers.made(), "the loop has its peers already")) return rc;
     nmpc_handle *h = l->h;
     const nmpc::LoopArgs &a = l->a;
     const int B = a.B;
-    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: M < 1");
-    if (a.K + M > a.ndyn) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: K + M > Ndynobs, no free ellipse slot");
+    const std::string who = std::string(fn) + ": ";
+    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, (who + "M < 1").c_str());
+    if (a.K + M > a.ndyn) return fail(h, NMPC_ERR_BAD_ARG, (who + "K + M > Ndynobs, no free ellipse slot").c_str());
     for (const double v : {rx, ry, range})
-        if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: rx, ry and range must be finite and positive");
-    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_peers: group_of out of range");
+        if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (who + "rx, ry and range must be finite and positive").c_str());
+    if (cell && (!(*cell > 0.0) || *cell > DBL_MAX)) return fail(h, NMPC_ERR_BAD_ARG, (who + "cell must be finite and positive").c_str());
+    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, (who + "group_of out of range").c_str());
     LoopPeers st;
     HIP_TRY(h, st.pred.alloc((size_t)B * a.N * 3));
     HIP_TRY(h, st.groups.upload(group_of, B));
@@ -225,8 +234,31 @@ int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx,
     p.ts = a.ts; p.rx = rx; p.ry = ry; p.range2 = range * range;
     p.state = l->d_state; p.U = l->d_U; p.pred = st.pred;
     p.group_of = st.groups.group_of; p.goff = st.groups.goff; p.gmem = st.groups.gmem; p.P = l->d_P;
+    if (cell) {
+        constexpr size_t cells = (size_t)nmpc::PEER_GRID_CAP * nmpc::PEER_GRID_CAP;
+        HIP_TRY(h, st.box.alloc(4 * (size_t)B));
+        HIP_TRY(h, st.hdr.alloc_fill(1, 0));
+        HIP_TRY(h, st.cell_of.alloc_fill(B, 0xFF));
+        HIP_TRY(h, st.cell_off.alloc_fill(cells + 1, 0));
+        HIP_TRY(h, st.cell_cur.alloc_fill(cells, 0));
+        HIP_TRY(h, st.cell_mem.alloc_fill(B, 0));
+        nmpc::PeerGridArgs &g = st.g;
+        g.B = B; g.N = a.N; g.range = range; g.cell = *cell;
+        g.pred = st.pred; g.box = st.box; g.hdr = st.hdr;
+        g.cell_of = st.cell_of; g.cell_off = st.cell_off; g.cell_cur = st.cell_cur; g.cell_mem = st.cell_mem;
+    }
     l->peers = std::move(st);
     return NMPC_OK;
+}
+
+int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range)
+{
+    return loop_set_peers(l, "nmpc_loop_set_peers", group_of, M, rx, ry, range, nullptr);
+}
+
+int nmpc_loop_set_peers_grid(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range, double cell)
+{
+    return loop_set_peers(l, "nmpc_loop_set_peers_grid", group_of, M, rx, ry, range, &cell);
 }
 
 int nmpc_loop_set_retire(nmpc_loop *l, int on)
@@ -414,7 +446,14 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         if (l->peers.made()) {
             l->peers.a.nact = n;
             hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, l->peers.a);
-            hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, l->peers.a);
+            if (l->peers.grid()) {     // the boxes and the grid over all B: a retired robot stays filed
+                const nmpc::PeerGridArgs &g = l->peers.g;
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peer_box_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, g);
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peer_grid_kernel, dim3(1), dim3(1024), 0, s, g);
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peers_grid_kernel, dim3(n), dim3(64), 0, s, l->peers.a, g);
+            } else {
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, l->peers.a);
+            }
         }
         if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, r.pack);
         HIP_TRY(h, hipGetLastError());
@@ -528,6 +567,17 @@ int nmpc_loop_clearance(nmpc_loop *l, nmpc_clearance *out)
         return NMPC_OK;
     }
     HIP_TRY(l->h, l->monitor.rec.read(out, B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_peer_grid(nmpc_loop *l, nmpc_peer_grid *out, int32_t *cell_of)
+{
+    if (!out) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_settle(l)) return rc;
+    if (!l->peers.grid()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_peer_grid: the loop has no peers grid (nmpc_loop_set_peers_grid)");
+    if (l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_peer_grid: before the loop's first step");
+    HIP_TRY(l->h, l->peers.hdr.read(out, 1));
+    HIP_TRY(l->h, l->peers.cell_of.read(cell_of, l->a.B));
     return NMPC_OK;
 }
 

@@ -439,21 +439,126 @@ class Peers:
     positions come closest to its own, closer than ``range``, take ellipse slots K .. K + slots - 1 of its
     parameter vector (K = its scripted obstacles) as ellipses of radii ``rx``, ``ry`` -- the radii the cost
     reads, nothing is added to them -- at their predicted poses.  ``group_of`` [B] = the group of each robot,
-    values in [0, B) (``None``: one group); robots of different groups never see each other."""
+    values in [0, B) (``None``: one group); robots of different groups never see each other.
+
+    ``cell`` (metres; ``None``: all pairs of a group) finds the same peers through a grid (``peer_grid``,
+    ``nmpc_loop_set_peers_grid``): a robot forms its distances to the robots filed near it only, which is what lets a whole
+    fleet be one group.  No result depends on it."""
     slots: int
     rx: float
     ry: float
     range: float
     group_of: object = None
+    cell: float = None
 
     def checked(self, B: int, K: int, Ndynobs: int):
-        """-> group_of as an int32 array or None; ValueError for what ``nmpc_loop_set_peers`` refuses."""
+        """-> group_of as an int32 array or None; ValueError for what ``nmpc_loop_set_peers`` / ``nmpc_loop_set_peers_grid`` refuses."""
         if self.slots < 1 or K + self.slots > Ndynobs:
             raise ValueError(f"peers: slots = {self.slots} with {K} scripted obstacles and Ndynobs = {Ndynobs}")
         for v in (self.rx, self.ry, self.range):
             if not (math.isfinite(v) and v > 0):
                 raise ValueError("peers: rx, ry and range must be finite and positive")
+        if self.cell is not None and not (math.isfinite(self.cell) and self.cell > 0):
+            raise ValueError("peers: cell must be finite and positive")
         return _checked_groups("peers", self.group_of, B)
+
+
+PEER_GRID_CAP = 128          # cells per axis at the most (csrc/nmpc_loop.h)
+
+
+class PeerGrid:
+    """The grid of one step (``peer_grid``): ``origin`` [2], ``h`` [2] the cells' edges, ``W`` [2] the largest box extent, ``nx``,
+    ``ny``, ``filed`` (what ``nmpc_loop_peer_grid`` returns as its header), ``cell_of`` [B] int32 (row-major, y * nx + x; -1 =
+    unfiled), the boxes ``lo``, ``hi`` [B, 2] and ``candidates(b)``."""
+
+    def header(self):
+        """-> the header as one ``_lib.PEER_GRID_DTYPE`` record, as the device reports it."""
+        rec = np.zeros((), dtype=_lib.PEER_GRID_DTYPE)
+        rec["origin"], rec["h"], rec["W"] = self.origin, self.h, self.W
+        rec["nx"], rec["ny"], rec["filed"] = self.nx, self.ny, self.filed
+        return rec
+
+    def _cellof(self, v, axis):
+        """The cell of coordinate ``v`` on ``axis``: monotone non-decreasing in ``v`` (peer_cellof of csrc/nmpc_loop.h)."""
+        n = (self.nx, self.ny)[axis]
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = (np.float64(v) - self.origin[axis]) / self.h[axis]
+        if not t > 0.0:
+            return 0
+        if t >= float(n):
+            return n - 1
+        return int(t)
+
+    def window(self, b):
+        """-> (cx0, cx1, cy0, cy1), inclusive: the cells robot b looks at; None for an unfiled robot."""
+        if self.cell_of[b] < 0:
+            return None
+        lo, hi, r = self.lo[b], self.hi[b], np.float64(self.range)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return (self._cellof((lo[0] - r) - self.W[0], 0), self._cellof(hi[0] + r, 0),
+                    self._cellof((lo[1] - r) - self.W[1], 1), self._cellof(hi[1] + r, 1))
+
+    def row_ranges(self, b):
+        """-> [(i0, i1)] per row of b's window: the row's cells are ``cell_mem[i0:i1]``."""
+        w = self.window(b)
+        if w is None:
+            return []
+        cx0, cx1, cy0, cy1 = w
+        return [(int(self.cell_off[row * self.nx + cx0]), int(self.cell_off[row * self.nx + cx1 + 1])) for row in range(cy0, cy1 + 1)]
+
+    def candidates(self, b):
+        """-> the robots filed in the cells of b's window (b itself among them), row after row, ascending inside a cell."""
+        rr = self.row_ranges(b)
+        return np.concatenate([self.cell_mem[i0:i1] for i0, i1 in rr]) if rr else np.zeros(0, dtype=np.int64)
+
+
+def peer_grid(pred, range, cell):
+    """The broad phase of the peers rule for the predictions ``pred`` [B, N, >= 2] of one step, in the device's
+    arithmetic (unfused f64, the same operations in the same order): -> a ``PeerGrid``.
+
+    A robot's box is the minimum and maximum of its positions over the stages at which both coordinates are finite; a robot without
+    such a stage is unfiled.  The grid starts at the minimum of the filed boxes' lower corners and has cells of edge ``cell``, or
+    ``PEER_GRID_CAP`` cells of edge extent / ``PEER_GRID_CAP`` on an axis that would need more; a robot is filed under the cell of its
+    box's lower corner.  Robot b looks at the cells from that of ``(lo_b - range) - W`` to that of ``hi_b + range``, ``W`` the largest
+    box extent (rounded up): every j with D(b, j) < range^2 is filed there."""
+    pred = np.asarray(pred, dtype=np.float64)
+    B = pred.shape[0]
+    g = PeerGrid()
+    g.range, g.cell = float(range), float(cell)
+    xy = pred[:, :, :2]
+    ok = np.isfinite(xy).all(axis=2)                                        # [B, N]: the stages that count
+    g.lo = np.where(ok[..., None], xy, np.inf).min(axis=1)
+    g.hi = np.where(ok[..., None], xy, -np.inf).max(axis=1)
+    filed = ok.any(axis=1)
+    g.filed = int(filed.sum())
+    g.nx = g.ny = 1
+    g.h = np.array([g.cell, g.cell])
+    g.origin, g.W = np.zeros(2), np.zeros(2)
+    g.cell_of = np.full(B, -1, dtype=np.int32)
+    if g.filed:
+        lo, hi = g.lo[filed], g.hi[filed]
+        with np.errstate(over="ignore"):
+            w = hi - lo
+            ex = lo.max(axis=0) - lo.min(axis=0)
+        up = (w.view(np.int64) + 1).view(np.float64)                       # the next double above: never below the real hi - lo
+        g.W = np.where(w < np.inf, up, w).max(axis=0)
+        g.origin = lo.min(axis=0)
+        n = [1, 1]
+        for ax in (0, 1):
+            q = ex[ax] / g.cell
+            if q < float(PEER_GRID_CAP):
+                n[ax] = int(q) + 1
+            else:
+                n[ax], g.h[ax] = PEER_GRID_CAP, ex[ax] / float(PEER_GRID_CAP)
+        g.nx, g.ny = n
+        for b in np.nonzero(filed)[0]:
+            g.cell_of[b] = g._cellof(g.lo[b, 1], 1) * g.nx + g._cellof(g.lo[b, 0], 0)
+    cells = g.nx * g.ny
+    who = np.nonzero(filed)[0]
+    order = who[np.argsort(g.cell_of[who], kind="stable")]                  # ascending robot index inside a cell
+    g.cell_mem = order.astype(np.int64)
+    g.cell_off = np.concatenate([[0], np.cumsum(np.bincount(g.cell_of[who], minlength=cells))]).astype(np.int64)
+    return g
 
 
 @dataclasses.dataclass(frozen=True)
@@ -617,7 +722,8 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     (default 0).
 
     ``peers`` (a ``Peers``) lets the robots of a group see each other: ``assemble`` overlays the chosen peers on the parameter
-    vectors it returns, never on the carried dynamic blocks.
+    vectors it returns, never on the carried dynamic blocks.  With ``peers.cell`` the distances are formed over
+    ``peer_grid(...).candidates`` only (``grid`` keeps the step's ``PeerGrid``): the same peers, at a cost that lets a fleet be one group.
 
     ``retire=True``: a robot whose terminal test holds after an advance leaves the loop for good, as the reference's
     ``while not terminal`` ends for one robot.  Everybody is ``active`` at the first step; a retired robot
@@ -660,6 +766,7 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         if peers is not None:
             g = peers.checked(B, self.K, cfg.Ndynobs)
             g = np.zeros(B, dtype=np.int32) if g is None else g
+            self.group_of = g
             self.groups = [np.nonzero(g == v)[0] for v in np.unique(g)]       # members in ascending robot index
         self.steps = 0
         if retire:
@@ -735,6 +842,9 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         pred = self.predict()
         r2 = pe.range * pe.range
         self.peer_index = np.full((self.B, M), -1)                           # who fills slot K + m of robot b at this step (-1: nobody)
+        if pe.cell is not None:
+            self._overlay_peers_grid(P, pred, base, per, r2)
+            return
         for mem in self.groups:
             G = len(mem)
             if G < 2:
@@ -762,6 +872,32 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
                     blk[..., 2], blk[..., 3] = pe.rx, pe.ry
                     self.peer_index[b, m] = src
                     P[b, base + m * per:base + (m + 1) * per] = blk.reshape(len(b), per)
+
+    def _overlay_peers_grid(self, P, pred, base, per, r2):
+        """``_overlay_peers`` with D formed over ``peer_grid(...).candidates`` only: robot by robot, the same closeness, (D, j)
+        order and overlay."""
+        cfg, pe = self.cfg, self.peers
+        N, M = cfg.N_hor, pe.slots
+        self.grid = grid = peer_grid(pred, pe.range, pe.cell)
+        px, py = pred[:, :, 0], pred[:, :, 1]
+        for b in range(self.B):
+            if self.active is not None and not self.active[b]:                # a retired robot's p is not touched
+                continue
+            c = grid.candidates(b)
+            c = c[(c != b) & (self.group_of[c] == self.group_of[b])]
+            if not len(c):
+                continue
+            with np.errstate(invalid="ignore", over="ignore"):
+                dx, dy = px[b][None, :] - px[c], py[b][None, :] - py[c]
+                d = dx * dx + dy * dy                                         # [C, N]
+            D = np.where(np.isnan(d), np.inf, d).min(axis=1)                  # min over the stages, a NaN passed over
+            c, D = c[D < r2], D[D < r2]
+            for m, j in enumerate(c[np.lexsort((c, D))][:M]):                 # (D, j)
+                blk = np.empty((N, cfg.ndynobs))
+                blk[:, 0], blk[:, 1], blk[:, 4] = pred[j, :, 0], pred[j, :, 1], pred[j, :, 2]
+                blk[:, 2], blk[:, 3] = pe.rx, pe.ry
+                self.peer_index[b, m] = j
+                P[b, base + m * per:base + (m + 1) * per] = blk.reshape(per)
 
     def advance(self, U):
         super().advance(U, self.active)
@@ -890,7 +1026,8 @@ class DeviceRecedingHorizon:
 
     ``peers`` (a ``Peers``): the robots of a group see each other (``nmpc_loop_set_peers``); two more
     kernels per step, between the assembly and the solve.  Its host mirror is ``FleetRecedingHorizon`` with the same ``peers``
-    (tests/test_gpu_peers_loop.py).
+    (tests/test_gpu_peers_loop.py).  With ``peers.cell`` the candidates come from a grid built on the device every step
+    (``nmpc_loop_set_peers_grid``): the same results, ``peer_grid()`` reads the last step's grid (tests/test_gpu_peers_grid_loop.py).
 
     ``monitor`` (a ``Monitor``, needs ``max_steps`` > 0): every robot's closest approach to circles, scripted ellipses and the robots
     of its monitor group is kept on the device (``nmpc_loop_set_monitor``), one more kernel per step after the
@@ -957,7 +1094,11 @@ class DeviceRecedingHorizon:
         self.peers = peers
         if peers is not None:
             g = None if peers.group_of is None else np.ascontiguousarray(peers.group_of, dtype=np.int32).reshape(B)
-            self._set(self.lib.nmpc_loop_set_peers(h, _lib.as_i32p(g), int(peers.slots), float(peers.rx), float(peers.ry), float(peers.range)))
+            if peers.cell is None:
+                self._set(self.lib.nmpc_loop_set_peers(h, _lib.as_i32p(g), int(peers.slots), float(peers.rx), float(peers.ry), float(peers.range)))
+            else:
+                self._set(self.lib.nmpc_loop_set_peers_grid(h, _lib.as_i32p(g), int(peers.slots), float(peers.rx), float(peers.ry),
+                                                            float(peers.range), float(peers.cell)))
         self.retire = bool(retire)
         if retire:
             self._set(self.lib.nmpc_loop_set_retire(h, 1))
@@ -1046,6 +1187,14 @@ class DeviceRecedingHorizon:
         rec = np.empty(self.B, dtype=_lib.CLEARANCE_DTYPE)
         self.solver._check(self.lib.nmpc_loop_clearance(self._l, rec.ctypes.data))
         return rec
+
+    def peer_grid(self):
+        """-> (header, cell_of [B] int32) after synchronising: the grid the last step's peers were found through (one
+        ``_lib.PEER_GRID_DTYPE`` record: origin, h, W, nx, ny, filed) and the cell each robot was filed under (-1: unfiled).  Needs
+        ``peers`` with a ``cell`` and a step taken."""
+        hdr, cell_of = np.zeros((), dtype=_lib.PEER_GRID_DTYPE), np.empty(self.B, dtype=np.int32)
+        self.solver._check(self.lib.nmpc_loop_peer_grid(self._l, hdr.ctypes.data, _lib.as_i32p(cell_of)))
+        return hdr, cell_of
 
     def map_clearance(self):
         """-> the map monitor's records [B] (``_lib.MAP_CLEARANCE_DTYPE``: wall2, wall_row, wall_edge, hits, hit_row, hit_poly, reserved)

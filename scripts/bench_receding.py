@@ -5,7 +5,8 @@ Default: the whole loop on device (nmpc_loop_*: assembly, solve and state advanc
 crosses PCIe between steps), every robot on the scene's route; --routes R > 1: the robots follow R routes
 planned between random start / goal points of the scene (frontend.random_fleet).  --peers G: the robots see each
 other in groups of G consecutive robots; --peer-slots of the Ndynobs ellipse slots go to peers, the
-rest stay scripted.  --retire: robots that reach their goal leave the loop (nmpc_loop_set_retire); the run ends when nobody is
+rest stay scripted; with --peer-cell H the peers are found through a grid of H metres built on the device every step
+(nmpc_loop_set_peers_grid: the same peers), and the result line gains peer_grid: the last step's cells, filed robots and largest cell.  --retire: robots that reach their goal leave the loop (nmpc_loop_set_retire); the run ends when nobody is
 active or after --steps steps, and reports the steps and solves it took.  --back: how close to the route's end robots may start
 (--routes 1); a small value gives a fleet whose robots arrive all through the run.  --monitor [G]: the clearance monitor (nmpc_loop_set_monitor,
 DESIGN.md section 5.9) in groups of G consecutive robots, default the --peers groups or 32; the result line then has, from its records, the shares
@@ -47,6 +48,8 @@ ap.add_argument("--peers", type=int, default=0,
                 help="G > 0: groups of G consecutive robots (of a sub-fleet, see --split) see each other; 0 = nobody sees anybody")
 ap.add_argument("--peer-slots", type=int, default=2, help="with --peers: ellipse slots given to peers (the other Ndynobs - M stay scripted)")
 ap.add_argument("--peer-range", type=float, default=10.0, help="with --peers: how far a robot sees, in metres")
+ap.add_argument("--peer-cell", type=float, default=None, metavar="H",
+                help="with --peers: find the peers through a grid with cells of H metres (device loop: nmpc_loop_set_peers_grid)")
 ap.add_argument("--retire", action="store_true",
                 help="device loop only: retire the robots that reach their goal; run until nobody is active, --steps at the most")
 ap.add_argument("--legs", type=int, default=1, metavar="L",
@@ -70,6 +73,8 @@ if args.monitor is not None:
     if args.monitor < 0:
         ap.error("--monitor G: G >= 1")
     args.monitor = args.monitor or args.peers or 32
+if args.peer_cell is not None and not args.peers:
+    ap.error("--peer-cell goes with --peers G")
 if args.map and (args.host or args.steps < 1):
     ap.error("--map reads the trajectory the device loop records: it needs the device loop (no --host) and --steps >= 1")
 if args.legs < 1 or (args.legs > 1 and (not args.retire or args.host)):
@@ -89,7 +94,7 @@ peer_radius = cfg.vehicle_width + cfg.vehicle_margin
 def peers_of(n):
     """groups of --peers consecutive robots among n"""
     return Peers(slots=args.peer_slots, rx=peer_radius, ry=peer_radius, range=args.peer_range,
-                 group_of=(np.arange(n) // args.peers).astype(np.int32)) if args.peers else None
+                 group_of=(np.arange(n) // args.peers).astype(np.int32), cell=args.peer_cell) if args.peers else None
 
 
 def monitor_of(n):
@@ -137,7 +142,8 @@ if args.own_routes:
     fleet = f", every robot its own start and goal (workloads.own_route_fleet, seed 0; {len(routes)} routes planned on the device)"
 if args.peers:
     fleet += (f", {K} scripted ellipses and {args.peer_slots} peer slots per robot, groups of {args.peers} consecutive robots, "
-              f"range {args.peer_range} m, radii {peer_radius} m")
+              f"range {args.peer_range} m, radii {peer_radius} m"
+              + (f", found through a grid of {args.peer_cell} m" if args.peer_cell is not None else ""))
 solver = BatchSolver(cfg, max_batch=B, **sopts)
 missions_of = lambda ids: None
 routes_of = lambda ids: (routes, None if route_of is None else route_of[ids])
@@ -200,6 +206,11 @@ if not args.host:
     quality = {}
     if args.legs > 1:
         quality["legs_done"] = int(sum((rh.legs()[2] >= 0).sum() for rh in loops))
+    if args.peers and args.peer_cell is not None and args.steps >= 1:
+        grids = [rh.peer_grid() for rh in loops]                  # the last step's, per sub-fleet
+        quality["peer_grid"] = {"cell_m": args.peer_cell, "cells": [[int(h["nx"]), int(h["ny"])] for h, _ in grids],
+                                "edges_m": [h["h"].tolist() for h, _ in grids], "filed": int(sum(h["filed"] for h, _ in grids)),
+                                "largest_cell": int(max(np.bincount(c[c >= 0]).max(initial=0) for _, c in grids))}
     if args.monitor:
         rec = np.concatenate([rh.clearance() for rh in loops])
         quality["clearance"] = {
