@@ -118,7 +118,6 @@ struct nmpc_handle {
     bool loop_order_prev = true;   // nmpc_loop_step: launch order from the previous step's pass counts (experiments: NMPC_LOOP_ORDER_PREV=0 switches it off)
     DevBuf<int> d_order;           // launch order (hard-looking instances first)
     bool use_order = true;
-    const nmpc_status *order_hint = nullptr;   // set by nmpc_loop_step for the duration of its solve: the previous step's statuses (launch order by their pass counts)
     DevBuf<unsigned char> d_cls;
     Staging stg;
     SmallArena small;
@@ -336,8 +335,10 @@ static void fill_args(const nmpc_handle *h, KArgs &a, int B)
     a.tl_t0 = h->tl_budget > 0 ? h->d_t0.p : nullptr;
 }
 
-int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_u, const double *d_y0,
-                            const double *d_c0, double *d_y_out, nmpc_status *d_status, void *stream)
+// the solve of nmpc_solve_batch_device.  prev: the statuses these very instances' previous solves left (nmpc_loop_step: launch order
+// by their pass counts), or NULL: the order comes from the inputs
+static int solve_launch(nmpc_handle *h, int B, const double *d_p, double *d_u, const double *d_y0, const double *d_c0, double *d_y_out,
+                        nmpc_status *d_status, const nmpc_status *prev, void *stream)
 {
     if (const int rc = check_batch(h, B, d_p, d_u); rc || B == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -352,7 +353,7 @@ int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_
     const int grid = B < h->grid_cap ? B : h->grid_cap;          // waves that take instances
     if (B > grid) {        // more instances than resident waves: hand the hard-looking ones out first
         if (h->use_order) {
-            if (h->order_hint) hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, h->order_hint, h->d_cls.p);
+            if (prev) hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, prev, h->d_cls.p);
             else hipLaunchKernelGGL(nmpc::nmpc_classify_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a, h->d_cls.p);
             hipLaunchKernelGGL(nmpc::nmpc_order_kernel, dim3(1), dim3(1024), 0, s, B, h->d_cls.p, h->d_order.p);
             a.order = h->d_order;
@@ -394,6 +395,12 @@ int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_
     }
     HIP_TRY(h, hipGetLastError());
     return NMPC_OK;
+}
+
+int nmpc_solve_batch_device(nmpc_handle *h, int B, const double *d_p, double *d_u, const double *d_y0,
+                            const double *d_c0, double *d_y_out, nmpc_status *d_status, void *stream)
+{
+    return solve_launch(h, B, d_p, d_u, d_y0, d_c0, d_y_out, d_status, nullptr, stream);
 }
 
 int nmpc_eval_batch_device(nmpc_handle *h, int B, const double *d_p, const double *d_u, const double *d_c,

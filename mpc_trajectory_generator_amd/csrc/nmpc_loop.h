@@ -23,11 +23,51 @@
 // The host sizes a step's launches by nact, which it learns one step late: the count is copied to pinned memory behind an event, and
 // the next nmpc_loop_step waits for THAT event (not for the device: a loop on another stream keeps running).  This coupling of the
 // host to the step before exists only with retirement on; without it a step enqueues what it always did and waits for nothing.
+//
+// Arguments: every kernel takes (LoopView, LoopStep, the arguments of its stage), or fewer where it needs fewer.  LoopView is what the
+// loop is -- its shape, its per-robot arrays, its active list -- fixed once the loop is configured and the same for every kernel;
+// LoopStep is what changes from step to step, all of it derived from the step count and the active count.  A stage's struct holds
+// what is the stage's own and nothing of those two.
 #pragma once
 
 namespace nmpc {
 
-// one route: where its tables sit in LoopArgs::tab (in doubles) and its constants (nmpc_route)
+constexpr int LOOP_NONE = 0x7fffffff;       // no candidate, no row, no polygon: the index behind every real one
+
+struct LoopView {
+    int B, N, nobs, ndyn, K, n_p, n_u, n1, s;
+    double ts;
+    double *state;            // [B][3]
+    double *last_u;           // [B][2]
+    int *idx;                 // [B]
+    unsigned char *done;      // [B]
+    double *P, *U, *Y;        // [B][n_p], [B][n_u], [B][n1]
+    nmpc_status *st;          // [B]
+    const int *route_of;      // [B] (written by nmpc_loop_dispatch_kernel, through its own pointer, and by nobody else)
+    double *traj;             // [(steps * s + 1)][B][3] or NULL
+    const int *act;           // the robots a step runs over, ascending; NULL: all B (no retirement), row i is robot i
+
+    __device__ int robot(int i) const { return act ? act[i] : i; }
+    __device__ double *row(int r, int b) const { return traj + ((size_t)r * B + b) * 3; }      // trajectory row r of robot b
+    // where the blocks of a parameter vector start: head [NZ] | vel_ref [N] | circles [nobs][3] | ellipses [ndyn][N][5] | references [N][3]
+    __device__ int p_vel() const { return NZ; }
+    __device__ int p_circ() const { return NZ + N; }
+    __device__ int p_dyn() const { return NZ + N + 3 * nobs; }
+    __device__ int p_ref() const { return NZ + N + 3 * nobs + 5 * ndyn * N; }
+};
+
+struct LoopStep {
+    int t;                    // controls applied before this step
+    int traj_row;             // the first of this step's s trajectory rows (>= 1: row 0 is the start)
+    int step;                 // steps taken, this one included: what retired_at and leg_at take
+    int nact;                 // the robots this step runs over (B without retirement)
+    int cur;                  // which of the two carried dynamic blocks is read; the other is written
+
+    // the step that follows `steps` others of s controls each, over n robots
+    static LoopStep after(int steps, int s, int n) { return {steps * s, steps * s + 1, steps + 1, n, steps & 1}; }
+};
+
+// one route: where its tables sit in AssembleArgs::tab (in doubles) and its constants (nmpc_route)
 struct LoopRoute {
     int xr, yr, thr, vert, bv, bd;          // x_ref | y_ref | theta_ref [n_ref], vertices [n_vert][2], brake vel / dist [n_brake]
     int n_ref, n_vert, n_brake;
@@ -36,26 +76,36 @@ struct LoopRoute {
     double w[10];
 };
 
-struct LoopArgs {
-    int B, N, nobs, ndyn, K, n_p, n_u, s, t;
-    double ts;
+struct AssembleArgs {         // (the advance reads a route's goal pose through it)
     const double *tab;        // every route's tables, packed
     const LoopRoute *routes;  // [R]
-    const int *route_of;      // [B]
     const double *dynpar;     // [B][K][10]: p1x p1y p2x p2y freq rx ry angle | sinusoidal law (0 / 1) | atan2(p2 - p1)
-    double *state;            // [B][3]
-    double *last_u;           // [B][2]
-    int *idx;                 // [B]
-    const double *dyn_in;     // [B][ndyn][N][5]
-    double *dyn_out;
-    double *P;                // [B][n_p]
-    const double *U;          // [B][n_u]
-    unsigned char *done;      // [B]
-    double *traj;             // [(steps * s + 1)][B][3] or NULL
-    int traj_row;             // rows already written
-    const int *act;           // robots this step runs over, ascending; NULL: all B (no retirement)
-    int nact;                 // their number (B without retirement)
+    double *dyn[2];           // [B][ndyn][N][5]: the carried dynamic block, read and written in turn
 };
+
+// thread t of a workgroup owns the entries [lo, hi) of n: chunks of ceil(n / threads), the last ones short or empty
+__device__ __forceinline__ void block_chunk(int n, int &lo, int &hi)
+{
+    const int t = threadIdx.x, nt = blockDim.x;
+    const int chunk = (n + nt - 1) / nt;
+    lo = t * chunk < n ? t * chunk : n;
+    hi = lo + chunk < n ? lo + chunk : n;
+}
+
+// inclusive scan over the workgroup's threads of one value each, through cnt [threads] in LDS; the last thread's result is the total
+__device__ __forceinline__ int block_scan(int *cnt, int c)
+{
+    const int t = threadIdx.x, nt = blockDim.x;
+    cnt[t] = c;
+    __syncthreads();
+    for (int off = 1; off < nt; off <<= 1) {
+        const int v = t >= off ? cnt[t - off] : 0;
+        __syncthreads();
+        cnt[t] += v;
+        __syncthreads();
+    }
+    return cnt[t];
+}
 
 // (d, j) lexicographic minimum over the wave, result in every lane: the FIRST minimal index, like np.argmin
 __device__ __forceinline__ void wave_argmin(double &d, int &j)
@@ -79,27 +129,26 @@ __device__ __forceinline__ double linspace_at(double t0, double ts, int H, int i
 }
 
 // one wave per robot: fills p[b] and the rotated dynamic block
-__global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
+__global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopView L, LoopStep stp, AssembleArgs g)
 {
-    const int b = a.act ? a.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
     // the robot's route: the same for the whole wave (read before any store, so that the loads can be scalar)
-    const LoopRoute &rt = a.routes[a.route_of[b]];
-    const double *xr = a.tab + rt.xr, *yr = a.tab + rt.yr, *thr = a.tab + rt.thr, *vert = a.tab + rt.vert;
-    const double *bv = a.tab + rt.bv, *bd = a.tab + rt.bd;
-    const int N = a.N, n = rt.n_ref, s = a.s, n_vert = rt.n_vert, n_brake = rt.n_brake;
+    const LoopRoute &rt = g.routes[L.route_of[b]];
+    const double *xr = g.tab + rt.xr, *yr = g.tab + rt.yr, *thr = g.tab + rt.thr, *vert = g.tab + rt.vert;
+    const double *bv = g.tab + rt.bv, *bd = g.tab + rt.bd;
+    const int N = L.N, n = rt.n_ref, s = L.s, t = stp.t, n_vert = rt.n_vert, n_brake = rt.n_brake;
     const double base = rt.base, radius = rt.radius, pad = rt.pad, ex = rt.end[0], ey = rt.end[1], eth = rt.end[2];
-    const double x = a.state[3 * b], y = a.state[3 * b + 1], th = a.state[3 * b + 2];
-    double *p = a.P + (size_t)b * a.n_p;
-    constexpr int NZ_ = 20;
+    const double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
+    double *p = L.P + (size_t)b * L.n_p;
 
     // ---- static circles (path_generator.py:295-304 + visibility.py:141-148, look-back 0)
     {
-        double *pc = p + NZ_ + N;
+        double *pc = p + L.p_circ();
         const int nv = n_vert;
         int lb = 0, ub = nv;
-        if (nv > a.nobs) {
+        if (nv > L.nobs) {
             double best = __builtin_inf();
-            int bj = 0x7fffffff;
+            int bj = LOOP_NONE;
             for (int j = lane; j < nv; j += 64) {
                 const double dx = vert[2 * j] - x, dy = vert[2 * j + 1] - y;
                 double d = sqrt(dx * dx + dy * dy);
@@ -108,9 +157,9 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
             }
             wave_argmin(best, bj);
             lb = bj;
-            ub = a.nobs;          // (sic: the reference's window is [lb, min(nv, Nobs)) )
+            ub = L.nobs;          // (sic: the reference's window is [lb, min(nv, Nobs)) )
         }
-        for (int k = lane; k < a.nobs; k += 64) {
+        for (int k = lane; k < L.nobs; k += 64) {
             const int j = lb + k;
             const bool ok = nv > 0 && j < ub;
             const int jj = j < nv ? j : (nv > 0 ? nv - 1 : 0);
@@ -121,20 +170,20 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
     }
     // ---- dynamic ellipses (path_generator.py:306-316; visibility.py:156-166,199-216)
     {
-        const int per = N * 5, tot = a.ndyn * per;
-        const double *din = a.dyn_in + (size_t)b * tot;
-        double *dout = a.dyn_out + (size_t)b * tot;
-        double *pd = p + NZ_ + N + 3 * a.nobs;
+        const int per = N * 5, tot = L.ndyn * per;
+        const double *din = g.dyn[stp.cur] + (size_t)b * tot;
+        double *dout = g.dyn[stp.cur ^ 1] + (size_t)b * tot;
+        double *pd = p + L.p_dyn();
         for (int e = lane; e < tot; e += 64) {
             const int k = e / per, r = e - k * per, st = r / 5, f = r - st * 5;
             double v;
-            const bool fresh = k < a.K && (a.t == 0 || st >= N - s);
+            const bool fresh = k < L.K && (t == 0 || st >= N - s);
             if (fresh) {
-                const double *q = a.dynpar + ((size_t)b * a.K + k) * 10;
+                const double *q = g.dynpar + ((size_t)b * L.K + k) * 10;
                 if (f < 2) {
-                    const int H = a.t == 0 ? N : s, i = a.t == 0 ? st : st - (N - s);
-                    const double t0 = a.t == 0 ? 0.0 : (double)(a.t + N - s) * a.ts;
-                    const double tm = linspace_at(t0, a.ts, H, i);
+                    const int H = t == 0 ? N : s, i = t == 0 ? st : st - (N - s);
+                    const double t0 = t == 0 ? 0.0 : (double)(t + N - s) * L.ts;
+                    const double tm = linspace_at(t0, L.ts, H, i);
                     double sn, cs;
                     sincos_cw(q[4] * tm, sn, cs);
                     const double w = fabs(sn);
@@ -156,7 +205,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
                 } else {
                     v = f == 2 ? q[5] + pad : (f == 3 ? q[6] + pad : q[7]);
                 }
-            } else if (a.t == 0) {
+            } else if (t == 0) {
                 v = din[e];                                    // padding block as initialised
             } else {
                 // the reference rotates the WHOLE flat list left by 5 s entries (path_generator.py:312): a shift by s
@@ -172,10 +221,10 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
     // ---- closest reference sample in the sliding window (:320-325)
     int idx;
     {
-        const int i0 = a.idx[b];
+        const int i0 = L.idx[b];
         const int lb = i0 - s > 0 ? i0 - s : 0, ub = i0 + 5 * s < n ? i0 + 5 * s : n;
         double best = __builtin_inf();
-        int bj = 0x7fffffff;
+        int bj = LOOP_NONE;
         for (int j = lb + lane; j < ub; j += 64) {
             const double dx = xr[j] - x, dy = yr[j] - y;
             double d = sqrt(dx * dx + dy * dy);
@@ -184,24 +233,24 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
         }
         wave_argmin(best, bj);
         idx = bj;
-        if (lane == 0) a.idx[b] = idx;
+        if (lane == 0) L.idx[b] = idx;
     }
     // ---- head: state, last_u, target, last_u again, weights (:378-379)
     {
         const bool far = idx + N < n;
         const int jf = far ? idx + N : n - 1;
         if (lane < 3) p[lane] = lane == 0 ? x : (lane == 1 ? y : th);
-        if (lane >= 3 && lane < 5) p[lane] = a.last_u[2 * b + lane - 3];
+        if (lane >= 3 && lane < 5) p[lane] = L.last_u[2 * b + lane - 3];
         if (lane >= 5 && lane < 8) {
             const int f = lane - 5;
             p[lane] = far ? (f == 0 ? xr[jf] : (f == 1 ? yr[jf] : thr[jf])) : (f == 0 ? ex : (f == 1 ? ey : eth));
         }
-        if (lane >= 8 && lane < 10) p[lane] = a.last_u[2 * b + lane - 8];
+        if (lane >= 8 && lane < 10) p[lane] = L.last_u[2 * b + lane - 8];
         if (lane >= 10 && lane < 20) p[lane] = rt.w[lane - 10];
     }
     // ---- horizon references (:326-341) and velocity reference with the braking profile (:343-361)
     {
-        double *pv = p + NZ_, *pr = p + NZ_ + N + 3 * a.nobs + 5 * a.ndyn * N;
+        double *pv = p + L.p_vel(), *pr = p + L.p_ref();
         const bool brake = (double)(idx + N) >= (double)n - bd[0] / base;
         const int nbase = n - idx - 1 < N ? n - idx - 1 : N;
         const double ddx = x - ex, ddy = y - ey;
@@ -235,76 +284,73 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopArgs a)
 }
 
 // one thread per robot: Euler advance over the steps taken (mpc_generator.py:225-235), terminal test (:397)
-__global__ void nmpc_loop_advance_kernel(LoopArgs a)
+__global__ void nmpc_loop_advance_kernel(LoopView L, LoopStep stp, AssembleArgs g)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.nact) return;
-    const int b = a.act ? a.act[i] : i;
-    const double *u = a.U + (size_t)b * a.n_u;
-    double x = a.state[3 * b], y = a.state[3 * b + 1], th = a.state[3 * b + 2];
-    for (int i = 0; i < a.s; ++i) {
+    if (i >= stp.nact) return;
+    const int b = L.robot(i);
+    const double *u = L.U + (size_t)b * L.n_u;
+    double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
+    for (int i = 0; i < L.s; ++i) {
         const double v = u[2 * i], w = u[2 * i + 1];
         double sn, cs;
         sincos_cw(th, sn, cs);
-        x = x + a.ts * (v * cs);
-        y = y + a.ts * (v * sn);
-        th = th + a.ts * w;
-        if (a.traj) {
-            double *row = a.traj + ((size_t)(a.traj_row + i) * a.B + b) * 3;
+        x = x + L.ts * (v * cs);
+        y = y + L.ts * (v * sn);
+        th = th + L.ts * w;
+        if (L.traj) {
+            double *row = L.row(stp.traj_row + i, b);
             row[0] = x; row[1] = y; row[2] = th;
         }
     }
-    a.state[3 * b] = x; a.state[3 * b + 1] = y; a.state[3 * b + 2] = th;
-    const double lv = u[2 * (a.s - 1)], lw = u[2 * (a.s - 1) + 1];
-    a.last_u[2 * b] = lv; a.last_u[2 * b + 1] = lw;
-    const double *end = a.routes[a.route_of[b]].end;
-    a.done[b] = (fabs(x - end[0]) <= 0.05 && fabs(y - end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
+    L.state[3 * b] = x; L.state[3 * b + 1] = y; L.state[3 * b + 2] = th;
+    const double lv = u[2 * (L.s - 1)], lw = u[2 * (L.s - 1) + 1];
+    L.last_u[2 * b] = lv; L.last_u[2 * b + 1] = lw;
+    const double *end = g.routes[L.route_of[b]].end;
+    L.done[b] = (fabs(x - end[0]) <= 0.05 && fabs(y - end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
 }
 
 // ---- peers: the robots of a group see each other (nmpc_loop_set_peers; the rule is DESIGN.md section 5.9) ----
 // Two kernels between the assembly and the solve: every robot's predicted poses over the horizon, then per robot the M closest
 // peers of its group written into the ellipse slots [K, K + M) of p.  The carried block (dyn_in / dyn_out) never sees them.
-struct PeerArgs {
-    int B, N, n_p, n_u, s, K, M;
-    int pdyn;                 // where the dynamic block starts in p
-    double ts, rx, ry, range2;
-    const double *state;      // [B][3]
-    const double *U;          // [B][n_u]: the previous plan
-    double *pred;             // [B][N][3]
+struct GroupLists {          // the groups 0 .. B - 1 (most of them empty)
     const int *group_of;      // [B]
     const int *goff;          // [groups + 1]: a group's members are gmem[goff[g] .. goff[g + 1])
     const int *gmem;          // [B], ascending robot index inside a group
-    double *P;                // [B][n_p]
-    const int *act;           // as in LoopArgs
-    int nact;
+};
+
+struct PeerArgs {
+    int M;
+    double rx, ry, range2;
+    double *pred;             // [B][N][3]
+    GroupLists grp;
 };
 
 // one thread per robot: pred[b][k] = the pose after k + 1 Euler steps (the expression of nmpc_loop_advance_kernel) under the
 // previous plan shifted by the s controls already applied, its last control held beyond the plan's end
 // (a retired robot's row is not computed here: nmpc_loop_compact_kernel parked it)
-__global__ void nmpc_loop_predict_kernel(PeerArgs a)
+__global__ void nmpc_loop_predict_kernel(LoopView L, LoopStep stp, PeerArgs a)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.nact) return;
-    const int b = a.act ? a.act[i] : i;
-    const double *u = a.U + (size_t)b * a.n_u;
-    double *out = a.pred + (size_t)b * a.N * 3;
-    double x = a.state[3 * b], y = a.state[3 * b + 1], th = a.state[3 * b + 2];
-    for (int k = 0; k < a.N; ++k) {
-        const int c = a.s + k < a.N ? a.s + k : a.N - 1;
+    if (i >= stp.nact) return;
+    const int b = L.robot(i);
+    const double *u = L.U + (size_t)b * L.n_u;      // the previous plan
+    double *out = a.pred + (size_t)b * L.N * 3;
+    double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
+    for (int k = 0; k < L.N; ++k) {
+        const int c = L.s + k < L.N ? L.s + k : L.N - 1;
         const double v = u[2 * c], w = u[2 * c + 1];
         double sn, cs;
         sincos_cw(th, sn, cs);
-        x = x + a.ts * (v * cs);
-        y = y + a.ts * (v * sn);
-        th = th + a.ts * w;
+        x = x + L.ts * (v * cs);
+        y = y + L.ts * (v * sn);
+        th = th + L.ts * w;
         out[3 * k] = x; out[3 * k + 1] = y; out[3 * k + 2] = th;
     }
 }
 
 // What the two peers kernels share: a lane's list of its best NDYN_MAX candidates, sorted by (D, j) and held in registers (static
-// indices); no candidate = (inf, INT_MAX), behind every real one
-constexpr int PEER_NONE = 0x7fffffff;
+// indices); no candidate = (inf, LOOP_NONE), behind every real one
 
 // D(b, j) = min_k |pred[b][k] - pred[j][k]|^2, b's positions in `own` (LDS), j's row of pred in `pj`
 __device__ __forceinline__ double peer_closeness(const double *own, const double *pj, int N)
@@ -333,23 +379,23 @@ __device__ __forceinline__ void peer_keep(double (&bd)[NDYN_MAX], int (&bj)[NDYN
 
 // M rounds: the wave's (D, j) minimum over the lanes' heads, written over ellipse slot K + m of p[b]; the lane that held it moves on
 // to its next
-__device__ __forceinline__ void peer_overlay(const PeerArgs &a, int b, int lane, double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX])
+__device__ __forceinline__ void peer_overlay(const LoopView &L, const PeerArgs &a, int b, int lane, double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX])
 {
-    const int N = a.N;
-    double *pd = a.P + (size_t)b * a.n_p + a.pdyn;
+    const int N = L.N;
+    double *pd = L.P + (size_t)b * L.n_p + L.p_dyn();
     const int per = 5 * N;
     for (int m = 0; m < a.M; ++m) {
         double d = bd[0];
         int j = bj[0];
         wave_argmin(d, j);
-        if (j == PEER_NONE) break;            // (wave-uniform) no candidate left: the remaining slots keep what they hold
+        if (j == LOOP_NONE) break;            // (wave-uniform) no candidate left: the remaining slots keep what they hold
         if (bj[0] == j) {
 #pragma unroll
             for (int q = 0; q + 1 < NDYN_MAX; ++q) { bd[q] = bd[q + 1]; bj[q] = bj[q + 1]; }
-            bd[NDYN_MAX - 1] = __builtin_inf(); bj[NDYN_MAX - 1] = PEER_NONE;
+            bd[NDYN_MAX - 1] = __builtin_inf(); bj[NDYN_MAX - 1] = LOOP_NONE;
         }
         const double *pj = a.pred + (size_t)j * N * 3;
-        double *slot = pd + (size_t)(a.K + m) * per;
+        double *slot = pd + (size_t)(L.K + m) * per;
         for (int e = lane; e < per; e += 64) {
             const int st = e / 5, f = e - st * 5;
             slot[e] = f == 0 ? pj[3 * st] : (f == 1 ? pj[3 * st + 1] : (f == 2 ? a.rx : (f == 3 ? a.ry : pj[3 * st + 2])));
@@ -359,14 +405,14 @@ __device__ __forceinline__ void peer_overlay(const PeerArgs &a, int b, int lane,
 
 // one wave per robot: D(b, j) = min_k |pred[b][k] - pred[j][k]|^2 over the members j != b of b's group (lanes stride over them),
 // the first M of the candidates D < range^2 in (D, j) order, each written over one ellipse slot of p[b]
-__global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
+__global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(LoopView L, PeerArgs a)
 {
     __shared__ double own[2 * NMPC_MAX_HORIZON];
-    const int b = a.act ? a.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
-    const int N = a.N;
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int N = L.N;
     // the group's member range: the same for the whole wave
-    const int g = a.group_of[b];
-    const int lo = a.goff[g], hi = a.goff[g + 1];
+    const int g = a.grp.group_of[b];
+    const int lo = a.grp.goff[g], hi = a.grp.goff[g + 1];
     for (int k = lane; k < N; k += 64) {
         own[2 * k] = a.pred[((size_t)b * N + k) * 3];
         own[2 * k + 1] = a.pred[((size_t)b * N + k) * 3 + 1];
@@ -375,13 +421,13 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
     double bd[NDYN_MAX];
     int bj[NDYN_MAX];
 #pragma unroll
-    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = PEER_NONE; }
+    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
     for (int i = lo + lane; i < hi; i += 64) {
-        const int j = a.gmem[i];
+        const int j = a.grp.gmem[i];
         const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N);
         if (j != b && D < a.range2) peer_keep(bd, bj, D, j);
     }
-    peer_overlay(a, b, lane, bd, bj);
+    peer_overlay(L, a, b, lane, bd, bj);
 }
 
 // ---- peers through a grid (nmpc_loop_set_peers_grid; the rule, and why it misses nobody: DESIGN.md section 5.9) ----
@@ -391,9 +437,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(PeerArgs a)
 constexpr int PEER_GRID_CAP = 128;      // cells per axis at the most: 16 384 cells, two per robot of the largest fleet run (8192)
 
 struct PeerGridArgs {
-    int B, N;
     double range, cell;
-    const double *pred;       // [B][N][3]
     double *box;              // [B][4]: lo.x, lo.y, hi.x, hi.y over the finite stages; (inf, inf, -inf, -inf) = unfiled
     nmpc_peer_grid *hdr;      // [1]: this step's grid
     int *cell_of;             // [B]: the robot's cell (row-major, y * nx + x), -1 = unfiled
@@ -428,14 +472,14 @@ __device__ __forceinline__ double peer_extent_up(double hi, double lo)
 }
 
 // one thread per robot, all B (a retired robot stands parked in pred): the box of its predicted positions
-__global__ void nmpc_loop_peer_box_kernel(PeerGridArgs g)
+__global__ void nmpc_loop_peer_box_kernel(LoopView L, PeerArgs a, PeerGridArgs g)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= g.B) return;
-    const double *p = g.pred + (size_t)b * g.N * 3;
+    if (b >= L.B) return;
+    const double *p = a.pred + (size_t)b * L.N * 3;
     const double inf = __builtin_inf();
     double lx = inf, ly = inf, hx = -inf, hy = -inf;
-    for (int k = 0; k < g.N; ++k) {
+    for (int k = 0; k < L.N; ++k) {
         const double x = p[3 * k], y = p[3 * k + 1];
         if (fabs(x) < inf && fabs(y) < inf) {      // a stage with a NaN or an infinity is in nobody's D
             lx = x < lx ? x : lx; ly = y < ly ? y : ly;
@@ -446,19 +490,19 @@ __global__ void nmpc_loop_peer_box_kernel(PeerGridArgs g)
     out[0] = lx; out[1] = ly; out[2] = hx; out[3] = hy;
 }
 
-// One workgroup, thread t over the robots [t * chunk, (t + 1) * chunk) as in nmpc_loop_compact_kernel: the grid's header (minima and
+// One workgroup, thread t over its chunk of the robots (block_chunk) as in nmpc_loop_compact_kernel: the grid's header (minima and
 // maxima: the order of a reduction does not show), every robot's cell, the cells' populations counted with integer atomics in global
 // memory (cell_off: 64 KB at CAP = 128, more than a workgroup's static LDS), their exclusive scan, and the scatter into cell_mem.
 // The order inside a cell is the atomics' and differs from run to run; no result depends on it.  Stores, atomics and loads of the
 // same words are ordered by the device-scope fences in front of the barriers.
-__global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(PeerGridArgs g)
+__global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(LoopView L, PeerGridArgs g)
 {
     __shared__ double red[16][6];
     __shared__ int redn[16];
     __shared__ int cnt[1024];
-    const int t = threadIdx.x, nt = blockDim.x, B = g.B;
-    const int chunk = (B + nt - 1) / nt;
-    const int lo = t * chunk < B ? t * chunk : B, hi = lo + chunk < B ? lo + chunk : B;
+    const int t = threadIdx.x, nt = blockDim.x;
+    int lo, hi;
+    block_chunk(L.B, lo, hi);
     const double inf = __builtin_inf();
     double v[6] = {inf, inf, -inf, -inf, 0.0, 0.0};       // min lo.x, min lo.y, max lo.x, max lo.y, max extent x, max extent y
     int nf = 0;
@@ -526,21 +570,12 @@ __global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(PeerGridArgs 
     }
     __threadfence();
     __syncthreads();
-    // exclusive scan of the populations: thread t over the entries [t * cchunk, (t + 1) * cchunk), the one behind the last cell included
-    const int ncell = cells + 1;
-    const int cchunk = (ncell + nt - 1) / nt;
-    const int clo = t * cchunk < ncell ? t * cchunk : ncell, chi = clo + cchunk < ncell ? clo + cchunk : ncell;
+    // exclusive scan of the populations: thread t over its chunk of the entries, the one behind the last cell included
+    int clo, chi;
+    block_chunk(cells + 1, clo, chi);
     int sum = 0;
     for (int c = clo; c < chi; ++c) sum += g.cell_off[c];
-    cnt[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < nt; off <<= 1) {            // inclusive scan
-        const int o = t >= off ? cnt[t - off] : 0;
-        __syncthreads();
-        cnt[t] += o;
-        __syncthreads();
-    }
-    int run = cnt[t] - sum;
+    int run = block_scan(cnt, sum) - sum;
     for (int c = clo; c < chi; ++c) {
         const int n = g.cell_off[c];
         g.cell_off[c] = run;
@@ -557,11 +592,11 @@ __global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(PeerGridArgs 
 
 // one wave per active robot: the rule of nmpc_loop_peers_kernel over the robots filed in the cells of b's window, row after row (a
 // row's cells cx0 .. cx1 are one range of cell_mem, and the lanes stride over it).  Every loop's bounds are read before it starts.
-__global__ __launch_bounds__(64) void nmpc_loop_peers_grid_kernel(PeerArgs a, PeerGridArgs g)
+__global__ __launch_bounds__(64) void nmpc_loop_peers_grid_kernel(LoopView L, PeerArgs a, PeerGridArgs g)
 {
     __shared__ double own[2 * NMPC_MAX_HORIZON];
-    const int b = a.act ? a.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
-    const int N = a.N;
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int N = L.N;
     for (int k = lane; k < N; k += 64) {
         own[2 * k] = a.pred[((size_t)b * N + k) * 3];
         own[2 * k + 1] = a.pred[((size_t)b * N + k) * 3 + 1];
@@ -570,12 +605,12 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_grid_kernel(PeerArgs a, Pe
     double bd[NDYN_MAX];
     int bj[NDYN_MAX];
 #pragma unroll
-    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = PEER_NONE; }
+    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
     // the box, the grid and the window: the same for the whole wave
     const double *bx = g.box + 4 * (size_t)b;
     const nmpc_peer_grid *h = g.hdr;
     if (bx[0] <= bx[2]) {                               // an unfiled robot finds nobody
-        const int nx = h->nx, ny = h->ny, grp = a.group_of[b];
+        const int nx = h->nx, ny = h->ny, grp = a.grp.group_of[b];
         const int cx0 = peer_cellof((bx[0] - g.range) - h->W[0], h->origin[0], h->h[0], nx);
         const int cy0 = peer_cellof((bx[1] - g.range) - h->W[1], h->origin[1], h->h[1], ny);
         const int cx1 = peer_cellof(bx[2] + g.range, h->origin[0], h->h[0], nx);
@@ -584,83 +619,61 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_grid_kernel(PeerArgs a, Pe
             const int i0 = g.cell_off[row * nx + cx0], i1 = g.cell_off[row * nx + cx1 + 1];
             for (int i = i0 + lane; i < i1; i += 64) {
                 const int j = g.cell_mem[i];
-                if (j != b && a.group_of[j] == grp) {
+                if (j != b && a.grp.group_of[j] == grp) {
                     const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N);
                     if (D < a.range2) peer_keep(bd, bj, D, j);
                 }
             }
         }
     }
-    peer_overlay(a, b, lane, bd, bj);
+    peer_overlay(L, a, b, lane, bd, bj);
 }
 
 // ---- retirement: robots that reached their goal leave the loop (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9) ----
 struct RetireArgs {
-    int B, N, s;
-    int step;                 // steps taken, this one included: what retired_at takes
-    const unsigned char *done;   // [B], of this step's advance for the robots it ran over, 1 for every robot retired before
-    const double *state;      // [B][3]
     int *retired_at;          // [B]: -1 = active
-    int *act;                 // [B]: out, the robots still active in ascending index
-    int *nact;                // [1]: out, their number
-    double *pred;             // [B][N][3] or NULL (no peers)
-    double *traj;             // as in LoopArgs
-    int traj_row;             // the first of this step's s rows
+    int *list;                // [B]: LoopView::act as the compaction writes it, the robots still active in ascending index
+    int *count;               // [1]: their number
+    double *sP, *sU, *sY;     // [count][n_p], [count][n_u], [count][n1]: the rows the solve reads and writes, row i = robot act[i]
+    nmpc_status *sst;         // [count]
 };
 
-// One workgroup, after the advance: thread t takes the robots [t * chunk, (t + 1) * chunk), so that an exclusive scan of the threads'
-// counts gives each its place in the ascending list.  An active robot that is done is retired at this step: retired_at latches, and
-// with peers its row of pred becomes its final pose at every stage, a copy, for as long as the others look at it.  A robot retired
-// earlier repeats its final pose in this step's trajectory rows.
-__global__ __launch_bounds__(1024) void nmpc_loop_compact_kernel(RetireArgs r)
+// One workgroup, after the advance: thread t takes its chunk of the robots (block_chunk), so that an exclusive scan of the threads'
+// counts gives each its place in the ascending list.  An active robot that is done (done[b] is of this step's advance for the robots
+// it ran over, 1 for every robot retired before) is retired at this step: retired_at latches, and with peers (pred, theirs, else NULL)
+// its row of pred becomes its final pose at every stage, a copy, for as long as the others look at it.  A robot retired earlier
+// repeats its final pose in this step's trajectory rows.
+__global__ __launch_bounds__(1024) void nmpc_loop_compact_kernel(LoopView L, LoopStep stp, RetireArgs r, double *pred)
 {
     __shared__ int cnt[1024];
-    const int t = threadIdx.x, nt = blockDim.x;
-    const int chunk = (r.B + nt - 1) / nt;
-    const int lo = t * chunk < r.B ? t * chunk : r.B, hi = lo + chunk < r.B ? lo + chunk : r.B;
+    int lo, hi;
+    block_chunk(L.B, lo, hi);
     int c = 0;
     for (int b = lo; b < hi; ++b) {
-        const double x = r.state[3 * b], y = r.state[3 * b + 1], th = r.state[3 * b + 2];
+        const double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
         if (r.retired_at[b] >= 0) {
-            if (r.traj) {
-                for (int i = 0; i < r.s; ++i) {
-                    double *row = r.traj + ((size_t)(r.traj_row + i) * r.B + b) * 3;
+            if (L.traj) {
+                for (int i = 0; i < L.s; ++i) {
+                    double *row = L.row(stp.traj_row + i, b);
                     row[0] = x; row[1] = y; row[2] = th;
                 }
             }
-        } else if (r.done[b]) {
-            r.retired_at[b] = r.step;
-            if (r.pred) {
-                double *out = r.pred + (size_t)b * r.N * 3;
-                for (int k = 0; k < r.N; ++k) { out[3 * k] = x; out[3 * k + 1] = y; out[3 * k + 2] = th; }
+        } else if (L.done[b]) {
+            r.retired_at[b] = stp.step;
+            if (pred) {
+                double *out = pred + (size_t)b * L.N * 3;
+                for (int k = 0; k < L.N; ++k) { out[3 * k] = x; out[3 * k + 1] = y; out[3 * k + 2] = th; }
             }
         } else {
             ++c;
         }
     }
-    cnt[t] = c;
-    __syncthreads();
-    for (int off = 1; off < nt; off <<= 1) {            // inclusive scan
-        const int v = t >= off ? cnt[t - off] : 0;
-        __syncthreads();
-        cnt[t] += v;
-        __syncthreads();
-    }
-    int pos = cnt[t] - c;
+    const int end = block_scan(cnt, c);
+    int pos = end - c;
     for (int b = lo; b < hi; ++b)
-        if (r.retired_at[b] < 0) r.act[pos++] = b;      // (the thread's own stores above)
-    if (t == nt - 1) *r.nact = cnt[t];
+        if (r.retired_at[b] < 0) r.list[pos++] = b;     // (the thread's own stores above)
+    if (threadIdx.x == blockDim.x - 1) *r.count = end;
 }
-
-// the rows the solve reads and writes, of the robots in act, to and from contiguous buffers: row i = robot act[i]
-struct PackArgs {
-    int n_p, n_u, n1;
-    const int *act;
-    double *P, *U, *Y;        // [B][n_p], [B][n_u], [B][n1]: the loop's
-    nmpc_status *st;          // [B]
-    double *sP, *sU, *sY;     // [nact][..]: the solve's
-    nmpc_status *sst;
-};
 
 __device__ __forceinline__ void copy_row(double *dst, const double *src, int n)
 {
@@ -668,38 +681,28 @@ __device__ __forceinline__ void copy_row(double *dst, const double *src, int n)
 }
 
 // one workgroup per active robot.  The status row goes along: it is the launch-order hint of the solve (the same robot's previous pass count)
-__global__ __launch_bounds__(256) void nmpc_loop_gather_kernel(PackArgs g)
+__global__ __launch_bounds__(256) void nmpc_loop_gather_kernel(LoopView L, RetireArgs r)
 {
-    const size_t i = blockIdx.x, b = (size_t)g.act[blockIdx.x];
-    copy_row(g.sP + i * g.n_p, g.P + b * g.n_p, g.n_p);
-    copy_row(g.sU + i * g.n_u, g.U + b * g.n_u, g.n_u);
-    copy_row(g.sY + i * g.n1, g.Y + b * g.n1, g.n1);
-    if (threadIdx.x == 0) g.sst[i] = g.st[b];
+    const size_t i = blockIdx.x, b = (size_t)L.act[blockIdx.x];
+    copy_row(r.sP + i * L.n_p, L.P + b * L.n_p, L.n_p);
+    copy_row(r.sU + i * L.n_u, L.U + b * L.n_u, L.n_u);
+    copy_row(r.sY + i * L.n1, L.Y + b * L.n1, L.n1);
+    if (threadIdx.x == 0) r.sst[i] = L.st[b];
 }
 
-__global__ __launch_bounds__(256) void nmpc_loop_scatter_kernel(PackArgs g)
+__global__ __launch_bounds__(256) void nmpc_loop_scatter_kernel(LoopView L, RetireArgs r)
 {
-    const size_t i = blockIdx.x, b = (size_t)g.act[blockIdx.x];
-    copy_row(g.U + b * g.n_u, g.sU + i * g.n_u, g.n_u);
-    copy_row(g.Y + b * g.n1, g.sY + i * g.n1, g.n1);
-    if (threadIdx.x == 0) g.st[b] = g.sst[i];
+    const size_t i = blockIdx.x, b = (size_t)L.act[blockIdx.x];
+    copy_row(L.U + b * L.n_u, r.sU + i * L.n_u, L.n_u);
+    copy_row(L.Y + b * L.n1, r.sY + i * L.n1, L.n1);
+    if (threadIdx.x == 0) L.st[b] = r.sst[i];
 }
 
 // ---- clearance monitor: each robot's closest approach to circles, scripted ellipses and groupmates (nmpc_loop_set_monitor; the
 // rule is DESIGN.md section 5.9).  It observes: the record is the only thing it writes.
 struct MonitorArgs {
-    int B, N, nobs, K, n_p, s;
-    int pcirc, pdyn;          // where the circle slots and the dynamic block start in p
-    const double *P;          // [B][n_p]: this step's parameter vectors as the solve read them
-    const double *state;      // [B][3]: where a robot retired before this step stands
-    const double *traj;       // the loop's trajectory table
-    int traj_row;             // the first of this step's s rows
-    const int *retired_at;    // [B] as the step found it (the compaction has not run yet), or NULL: nobody retires
-    const int *group_of;      // [B]: the monitor's own groups, lists as in PeerArgs
-    const int *goff;
-    const int *gmem;
+    GroupLists grp;           // the monitor's own groups
     nmpc_clearance *rec;      // [B]
-    const int *act;           // as in LoopArgs
 };
 
 // (v, r, j) lexicographic minimum over the wave, result in every lane
@@ -717,30 +720,30 @@ __device__ __forceinline__ void wave_argmin3(double &d, int &r, int &j)
 // One wave per robot the step drove, after the advance: the robot's s new poses go to LDS; lanes stride over the (pose, circle slot)
 // and (pose, scripted ellipse) pairs of its p, then over the members of its group, each lane walking the s rows of its member (a
 // robot retired earlier stands at its state: the compaction writes its rows later); every lane keeps its lexicographic minimum, three
-// wave reductions follow, and lane 0 folds them into the record.  A lane that saw nothing holds (inf, INT_MAX): behind every value.
-__global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(MonitorArgs m)
+// wave reductions follow, and lane 0 folds them into the record.  A lane that saw nothing holds (inf, LOOP_NONE): behind every value.
+// P is this step's parameter vectors as the solve read them; retired_at is retirement's (NULL: nobody retires), as the step found it.
+__global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(LoopView L, LoopStep stp, MonitorArgs m, const int *retired_at)
 {
     __shared__ double own[2 * NMPC_MAX_HORIZON];
-    const int b = m.act ? m.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
-    const int s = m.s, N = m.N, row0 = m.traj_row;
-    const int g = m.group_of[b];
-    const int lo = m.goff[g], hi = m.goff[g + 1];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int s = L.s, N = L.N, nobs = L.nobs, K = L.K, row0 = stp.traj_row;
+    const int g = m.grp.group_of[b];
+    const int lo = m.grp.goff[g], hi = m.grp.goff[g + 1];
     for (int i = lane; i < s; i += 64) {
-        const double *row = m.traj + ((size_t)(row0 + i) * m.B + b) * 3;
+        const double *row = L.row(row0 + i, b);
         own[2 * i] = row[0];
         own[2 * i + 1] = row[1];
     }
     __syncthreads();
-    constexpr int NONE = 0x7fffffff;
-    const double *p = m.P + (size_t)b * m.n_p;
+    const double *p = L.P + (size_t)b * L.n_p;
     // ---- static circles: sqrt(dx^2 + dy^2) - r over the slots with r > 0
     double cv = __builtin_inf();
-    int cr = NONE;
+    int cr = LOOP_NONE;
     {
-        const double *pc = p + m.pcirc;
-        const int tot = s * m.nobs;
+        const double *pc = p + L.p_circ();
+        const int tot = s * nobs;
         for (int e = lane; e < tot; e += 64) {
-            const int i = e / m.nobs, c = e - i * m.nobs;
+            const int i = e / nobs, c = e - i * nobs;
             const double rc = pc[3 * c + 2];
             if (rc > 0.0) {
                 const double dx = own[2 * i] - pc[3 * c], dy = own[2 * i + 1] - pc[3 * c + 1];
@@ -753,12 +756,12 @@ __global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(MonitorArgs m)
     }
     // ---- scripted ellipses: the cost's level (a/rx)^2 + (c/ry)^2 at entry i of slot k, for the pose after control i
     double ev = __builtin_inf();
-    int er = NONE;
+    int er = LOOP_NONE;
     {
-        const double *pd = p + m.pdyn;
-        const int tot = s * m.K;
+        const double *pd = p + L.p_dyn();
+        const int tot = s * K;
         for (int e = lane; e < tot; e += 64) {
-            const int i = e / m.K, k = e - i * m.K;
+            const int i = e / K, k = e - i * K;
             const double *q = pd + ((size_t)k * N + i) * 5;
             const double dx = own[2 * i] - q[0], dy = own[2 * i + 1] - q[1];
             double sn, cs;
@@ -772,13 +775,13 @@ __global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(MonitorArgs m)
     }
     // ---- groupmates: squared distance between centres, in the same row
     double pv = __builtin_inf();
-    int pr = NONE, pj = NONE;
+    int pr = LOOP_NONE, pj = LOOP_NONE;
     for (int at = lo + lane; at < hi; at += 64) {
-        const int j = m.gmem[at];
+        const int j = m.grp.gmem[at];
         if (j == b) continue;
-        const bool parked = m.retired_at && m.retired_at[j] >= 0;
+        const bool parked = retired_at && retired_at[j] >= 0;
         for (int i = 0; i < s; ++i) {
-            const double *q = parked ? m.state + 3 * (size_t)j : m.traj + ((size_t)(row0 + i) * m.B + j) * 3;
+            const double *q = parked ? L.state + 3 * (size_t)j : L.row(row0 + i, j);
             const double dx = own[2 * i] - q[0], dy = own[2 * i + 1] - q[1];
             const double v = dx * dx + dy * dy;
             const int r = row0 + i;
@@ -808,14 +811,11 @@ __global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(MonitorArgs m)
 // A row is a hit if any polygon fails.  The record keeps the lexicographic minimum of (v, r, e), the number of hits, the first hit's row
 // and the smallest failing polygon of that row; a comparison that is false (a NaN) keeps what it would have replaced.
 struct MapArgs {
-    int B, s, E, n_poly;
-    const double *traj;       // the loop's trajectory table
-    int traj_row;             // the first of this step's s rows (>= 1: row traj_row - 1 is there)
+    int E, n_poly;
     const double *edge;       // [E][4] x1 y1 x2 y2, polygon by polygon: the obstacles first, the boundary last
     const int *poly_off;      // [n_poly + 1]
     const int *edge_poly;     // [E]: the polygon that owns the edge
     nmpc_map_clearance *rec;  // [B]
-    const int *act;           // as in LoopArgs
 };
 
 // One wave per robot the step drove, after the advance (and the clearance monitor): the robot's s + 1 poses, from the row before the
@@ -824,26 +824,25 @@ struct MapArgs {
 // of its polygon for the parity; a wave minimum of the failing polygon index is the row's verdict.  Every lane keeps its lexicographic
 // minimum of (v, r, e); one wave reduction follows the rows, and lane 0 folds everything into the record.  Every loop is bounded by s, E
 // or n_poly (poly_off was checked by the setter).
-__global__ __launch_bounds__(64) void nmpc_loop_map_kernel(MapArgs m)
+__global__ __launch_bounds__(64) void nmpc_loop_map_kernel(LoopView L, LoopStep stp, MapArgs m)
 {
     __shared__ double own[2 * (NMPC_MAX_HORIZON + 1)];
-    const int b = m.act ? m.act[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
-    const int s = m.s, E = m.E, n_poly = m.n_poly, row0 = m.traj_row;
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int s = L.s, E = m.E, n_poly = m.n_poly, row0 = stp.traj_row;      // (row0 >= 1: the row before it is there)
     for (int i = lane; i <= s; i += 64) {
-        const double *row = m.traj + ((size_t)(row0 - 1 + i) * m.B + b) * 3;
+        const double *row = L.row(row0 - 1 + i, b);
         own[2 * i] = row[0];
         own[2 * i + 1] = row[1];
     }
     __syncthreads();
-    constexpr int NONE = 0x7fffffff;
     double wv = __builtin_inf();
-    int wr = NONE, we = NONE;
-    int hits = 0, hit_row = NONE, hit_poly = NONE;        // the same in every lane
+    int wr = LOOP_NONE, we = LOOP_NONE;
+    int hits = 0, hit_row = LOOP_NONE, hit_poly = LOOP_NONE;        // the same in every lane
     for (int i = 0; i < s; ++i) {
         const double ax = own[2 * i], ay = own[2 * i + 1], x = own[2 * i + 2], y = own[2 * i + 3];
         const double ux = x - ax, uy = y - ay;
         const int r = row0 + i;
-        int fail = NONE;
+        int fail = LOOP_NONE;
         for (int e = lane; e < E; e += 64) {
             const double x1 = m.edge[4 * e], y1 = m.edge[4 * e + 1], x2 = m.edge[4 * e + 2], y2 = m.edge[4 * e + 3];
             const double ex = x2 - x1, ey = y2 - y1;
@@ -886,7 +885,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(MapArgs m)
             const int o = __shfl_xor(fail, off);
             if (o < fail) fail = o;
         }
-        if (fail != NONE) {
+        if (fail != LOOP_NONE) {
             if (hits == 0) { hit_row = r; hit_poly = fail; }
             ++hits;
         }
@@ -907,42 +906,37 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(MapArgs m)
 
 // ---- missions: a robot at its goal takes up its next route (nmpc_loop_set_missions; the rule is DESIGN.md section 5.9) ----
 struct DispatchArgs {
-    int n_u, n1;
-    int step;                 // steps taken, this one included: what leg_at takes
-    const int *act;           // the robots this step's advance ran over (the compaction comes after)
-    unsigned char *done;      // [B], of this step's advance; cleared for a robot that goes on, so that the compaction keeps it
     const int *leg_off;       // [B + 1]: robot b drives the routes leg_route[leg_off[b] .. leg_off[b + 1]) in turn
     const int *leg_route;     // [leg_off[B]]
     int *leg;                 // [B]: the leg a robot is on, counted inside its mission
     int *leg_at;              // [leg_off[B]]: the steps at which each leg ended, -1 = not yet
-    int *route_of;            // [B]: LoopArgs::route_of, written here and nowhere else
-    int *idx;                 // [B]
-    double *last_u;           // [B][2]
-    double *U, *Y;            // [B][n_u], [B][n1]: the loop's (the scatter has run)
+    int *route_of;            // [B]: LoopView::route_of, written here and nowhere else
 };
 
 // One wave per robot the step drove, after the advance (and the monitor) and before the compaction.  A robot whose terminal test holds
 // ends its leg at this step; if its mission has another leg it starts that route as a loop started anew from where it stands: window
-// search from sample 0, no previous control, a cold solve.  Its state, carried dynamic block, p, status and clearance record stay.
-__global__ __launch_bounds__(64) void nmpc_loop_dispatch_kernel(DispatchArgs d)
+// search from sample 0, no previous control, a cold solve (the scatter has run: U and Y are the loop's), and done[b] cleared, so that
+// the compaction keeps it.  Its state, carried dynamic block, p, status and clearance record stay.  The list is there: missions need
+// retirement.
+__global__ __launch_bounds__(64) void nmpc_loop_dispatch_kernel(LoopView L, LoopStep stp, DispatchArgs d)
 {
-    const int b = d.act[blockIdx.x], lane = threadIdx.x;
+    const int b = L.act[blockIdx.x], lane = threadIdx.x;
     // the same for the whole wave (read before any store, so that the loads can be scalar)
-    const int fin = d.done[b], leg = d.leg[b], lo = d.leg_off[b], hi = d.leg_off[b + 1];
+    const int fin = L.done[b], leg = d.leg[b], lo = d.leg_off[b], hi = d.leg_off[b + 1];
     if (!fin) return;
     const bool more = lo + leg + 1 < hi;
     const int next = more ? d.leg_route[lo + leg + 1] : 0;
-    if (lane == 0) d.leg_at[lo + leg] = d.step;
+    if (lane == 0) d.leg_at[lo + leg] = stp.step;
     if (!more) return;                        // the last leg: the compaction retires the robot
-    double *u = d.U + (size_t)b * d.n_u, *y = d.Y + (size_t)b * d.n1;
-    for (int e = lane; e < d.n_u; e += 64) u[e] = 0.0;
-    for (int e = lane; e < d.n1; e += 64) y[e] = 0.0;
+    double *u = L.U + (size_t)b * L.n_u, *y = L.Y + (size_t)b * L.n1;
+    for (int e = lane; e < L.n_u; e += 64) u[e] = 0.0;
+    for (int e = lane; e < L.n1; e += 64) y[e] = 0.0;
     if (lane == 0) {
         d.leg[b] = leg + 1;
         d.route_of[b] = next;
-        d.idx[b] = 0;
-        d.last_u[2 * b] = 0.0; d.last_u[2 * b + 1] = 0.0;
-        d.done[b] = 0;
+        L.idx[b] = 0;
+        L.last_u[2 * b] = 0.0; L.last_u[2 * b + 1] = 0.0;
+        L.done[b] = 0;
     }
 }
 

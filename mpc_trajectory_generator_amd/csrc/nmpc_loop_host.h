@@ -1,17 +1,21 @@
 // nmpc_loop_host.h -- host side of the receding-horizon loop on device (its kernels: nmpc_loop.h): struct nmpc_loop and the nmpc_loop_*
 // entry points of include/nmpc_solver.h.  Part of the one translation unit: nmpc_kernels.hip includes it inside its extern "C" block,
-// after the handle, fail, HIP_TRY and nmpc_solve_batch_device.
+// after the handle, fail, HIP_TRY and solve_launch.
 //
-// A loop is its base (assemble -> solve -> advance) plus up to five stages, each a sub-struct with its device buffers and its kernels'
-// argument block.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop
-// as it was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the
-// configuration final: loop_wire then sets every pointer one stage reads of another's, and nmpc_loop_step is ONE sequence of kernels
-// in which a stage adds its own.
+// A loop is its view (nmpc::LoopView: the shape, the per-robot arrays and the active list, the same for every kernel), its base
+// (assemble -> solve -> advance) and up to five stages, each a sub-struct with its device buffers and the argument block of its own
+// kernels.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop as it
+// was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the configuration
+// final.  The loop keeps ONE counter, `steps`: nmpc_loop_step derives everything that changes per step from it and the active count
+// (nmpc::LoopStep, on its stack), hands view, step and a stage's block to each kernel, and writes to no argument block.  It is ONE
+// sequence of kernels in which a stage adds its own; the two pointers that cross stages (the peers' pred for the compaction,
+// retirement's retired_at for the monitor) are passed at the launch, from the stage that owns them.
 #pragma once
 
-// member lists of the groups 0 .. B - 1 (most of them empty), each group's robots in ascending index (PeerArgs, MonitorArgs)
+// member lists of the groups 0 .. B - 1 (most of them empty), each group's robots in ascending index
 struct LoopGroups {
     DevBuf<int> group_of, goff, gmem;      // [B], [B + 1], [B]
+    nmpc::GroupLists lists() const { return {group_of, goff, gmem}; }
     // group_of NULL: everybody in group 0
     hipError_t upload(const int32_t *of, int B)
     {
@@ -46,7 +50,6 @@ struct LoopPeers {           // nmpc_loop_set_peers: two more kernels per step, 
 struct LoopRetire {
     bool called = false;         // the setter has been taken, with on = 0 too
     nmpc::RetireArgs a{};
-    nmpc::PackArgs pack{};
     DevBuf<int> act, nact, retired_at;
     DevBuf<double> sP, sU, sY;
     DevBuf<nmpc_status> sst;
@@ -78,8 +81,9 @@ struct LoopMissions {
 
 struct nmpc_loop {
     nmpc_handle *h = nullptr;
-    nmpc::LoopArgs a{};          // device pointers and constants; t / dyn_in / dyn_out / traj_row / nact change per step
-    int steps = 0, max_steps = 0;
+    nmpc::LoopView v{};          // what every kernel sees of the loop; act is the retirement setter's, the rest final at creation
+    nmpc::AssembleArgs a{};
+    int steps = 0, max_steps = 0;        // steps taken: the loop's one counter (nmpc::LoopStep::after)
     int R = 1;
     std::vector<int> h_route_of;         // [B] as given at creation
     DevBuf<double> d_tab;        // every route's tables, one allocation
@@ -135,12 +139,12 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
     l->h = h;
     l->max_steps = max_steps;
     l->R = R;
-    nmpc::LoopArgs &a = l->a;
-    a.B = B; a.N = h->pb.N; a.nobs = h->pb.nobs; a.ndyn = h->pb.ndyn; a.K = K;
-    a.n_p = nmpc_n_p(&h->pb); a.n_u = nmpc_n_u(&h->pb);
-    a.s = routes[0].num_steps_taken; a.t = 0;
-    a.ts = h->pb.ts;
-    const size_t n1 = nmpc_n1(&h->pb), ndynrow = (size_t)a.ndyn * a.N * 5;
+    nmpc::LoopView &v = l->v;
+    v.B = B; v.N = h->pb.N; v.nobs = h->pb.nobs; v.ndyn = h->pb.ndyn; v.K = K;
+    v.n_p = nmpc_n_p(&h->pb); v.n_u = nmpc_n_u(&h->pb); v.n1 = nmpc_n1(&h->pb);
+    v.s = routes[0].num_steps_taken;
+    v.ts = h->pb.ts;
+    const size_t ndynrow = (size_t)v.ndyn * v.N * 5;
     // route tables, route after route: x_ref | y_ref | theta_ref | vertices | brake velocities | brake distances
     std::vector<double> tab(ntab);
     std::vector<nmpc::LoopRoute> desc(R);
@@ -167,13 +171,13 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
     else HIP_TRY(h, l->d_dynpar.alloc(10 * (size_t)B));
     HIP_TRY(h, l->d_state.upload(starts, (size_t)B * 3));
     if (max_steps > 0) {
-        HIP_TRY(h, l->d_traj.alloc(((size_t)max_steps * a.s + 1) * B * 3));
+        HIP_TRY(h, l->d_traj.alloc(((size_t)max_steps * v.s + 1) * B * 3));
         HIP_TRY(h, hipMemcpy(l->d_traj, starts, (size_t)B * 3 * 8, hipMemcpyHostToDevice));
     }
     HIP_TRY(h, l->d_last_u.alloc_fill((size_t)B * 2, 0));
-    HIP_TRY(h, l->d_P.alloc((size_t)B * a.n_p));
-    HIP_TRY(h, l->d_U.alloc_fill((size_t)B * a.n_u, 0));
-    HIP_TRY(h, l->d_Y.alloc_fill((size_t)B * n1, 0));
+    HIP_TRY(h, l->d_P.alloc((size_t)B * v.n_p));
+    HIP_TRY(h, l->d_U.alloc_fill((size_t)B * v.n_u, 0));
+    HIP_TRY(h, l->d_Y.alloc_fill((size_t)B * v.n1, 0));
     if (idx0) HIP_TRY(h, l->d_idx.upload(idx0, B));
     else HIP_TRY(h, l->d_idx.alloc_fill(B, 0));
     HIP_TRY(h, l->d_done.alloc_fill(B, 0));
@@ -184,10 +188,10 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
         HIP_TRY(h, l->d_dyn[0].upload(pad.data(), pad.size()));
         HIP_TRY(h, l->d_dyn[1].alloc(pad.size()));
     }
-    a.tab = l->d_tab; a.routes = l->d_routes; a.route_of = l->d_route_of;
-    a.dynpar = l->d_dynpar; a.state = l->d_state; a.last_u = l->d_last_u; a.idx = l->d_idx;
-    a.P = l->d_P; a.U = l->d_U; a.done = l->d_done; a.traj = l->d_traj; a.traj_row = 1;
-    a.act = nullptr; a.nact = B;
+    v.state = l->d_state; v.last_u = l->d_last_u; v.idx = l->d_idx; v.done = l->d_done;
+    v.P = l->d_P; v.U = l->d_U; v.Y = l->d_Y; v.st = l->d_st; v.route_of = l->d_route_of; v.traj = l->d_traj;
+    nmpc::AssembleArgs &a = l->a;
+    a.tab = l->d_tab; a.routes = l->d_routes; a.dynpar = l->d_dynpar; a.dyn[0] = l->d_dyn[0]; a.dyn[1] = l->d_dyn[1];
     *out = l.release();
     return NMPC_OK;
 }
@@ -216,24 +220,21 @@ static int loop_set_peers(nmpc_loop *l, const char *fn, const int32_t *group_of,
     if (!l) return NMPC_ERR_BAD_ARG;
     if (const int rc = loop_setter(l, fn, l->peers.made(), "the loop has its peers already")) return rc;
     nmpc_handle *h = l->h;
-    const nmpc::LoopArgs &a = l->a;
-    const int B = a.B;
+    const nmpc::LoopView &v = l->v;
+    const int B = v.B;
     const std::string who = std::string(fn) + ": ";
     if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, (who + "M < 1").c_str());
-    if (a.K + M > a.ndyn) return fail(h, NMPC_ERR_BAD_ARG, (who + "K + M > Ndynobs, no free ellipse slot").c_str());
+    if (v.K + M > v.ndyn) return fail(h, NMPC_ERR_BAD_ARG, (who + "K + M > Ndynobs, no free ellipse slot").c_str());
     for (const double v : {rx, ry, range})
         if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (who + "rx, ry and range must be finite and positive").c_str());
     if (cell && (!(*cell > 0.0) || *cell > DBL_MAX)) return fail(h, NMPC_ERR_BAD_ARG, (who + "cell must be finite and positive").c_str());
     if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, (who + "group_of out of range").c_str());
     LoopPeers st;
-    HIP_TRY(h, st.pred.alloc((size_t)B * a.N * 3));
+    HIP_TRY(h, st.pred.alloc((size_t)B * v.N * 3));
     HIP_TRY(h, st.groups.upload(group_of, B));
     nmpc::PeerArgs &p = st.a;
-    p.B = B; p.N = a.N; p.n_p = a.n_p; p.n_u = a.n_u; p.s = a.s; p.K = a.K; p.M = M;
-    p.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
-    p.ts = a.ts; p.rx = rx; p.ry = ry; p.range2 = range * range;
-    p.state = l->d_state; p.U = l->d_U; p.pred = st.pred;
-    p.group_of = st.groups.group_of; p.goff = st.groups.goff; p.gmem = st.groups.gmem; p.P = l->d_P;
+    p.M = M; p.rx = rx; p.ry = ry; p.range2 = range * range;
+    p.pred = st.pred; p.grp = st.groups.lists();
     if (cell) {
         constexpr size_t cells = (size_t)nmpc::PEER_GRID_CAP * nmpc::PEER_GRID_CAP;
         HIP_TRY(h, st.box.alloc(4 * (size_t)B));
@@ -243,8 +244,8 @@ static int loop_set_peers(nmpc_loop *l, const char *fn, const int32_t *group_of,
         HIP_TRY(h, st.cell_cur.alloc_fill(cells, 0));
         HIP_TRY(h, st.cell_mem.alloc_fill(B, 0));
         nmpc::PeerGridArgs &g = st.g;
-        g.B = B; g.N = a.N; g.range = range; g.cell = *cell;
-        g.pred = st.pred; g.box = st.box; g.hdr = st.hdr;
+        g.range = range; g.cell = *cell;
+        g.box = st.box; g.hdr = st.hdr;
         g.cell_of = st.cell_of; g.cell_off = st.cell_off; g.cell_cur = st.cell_cur; g.cell_mem = st.cell_mem;
     }
     l->peers = std::move(st);
@@ -266,33 +267,29 @@ int nmpc_loop_set_retire(nmpc_loop *l, int on)
     if (!l) return NMPC_ERR_BAD_ARG;
     if (const int rc = loop_setter(l, "nmpc_loop_set_retire", l->retire.called, "called already")) return rc;
     nmpc_handle *h = l->h;
-    const nmpc::LoopArgs &a = l->a;
-    const size_t B = (size_t)a.B, n1 = (size_t)nmpc_n1(&h->pb);
+    const nmpc::LoopView &v = l->v;
+    const size_t B = (size_t)v.B;
     LoopRetire st;
     st.called = true;
     if (on) {
         std::vector<int> all(B);
         for (size_t b = 0; b < B; ++b) all[b] = (int)b;
         HIP_TRY(h, st.act.upload(all.data(), B));                  // everybody is active at step 0
-        HIP_TRY(h, st.nact.upload(&a.B, 1));
+        HIP_TRY(h, st.nact.upload(&v.B, 1));
         HIP_TRY(h, st.retired_at.alloc_fill(B, 0xFF));             // retired_at = -1
-        HIP_TRY(h, st.sP.alloc(B * a.n_p));
-        HIP_TRY(h, st.sU.alloc(B * a.n_u));
-        HIP_TRY(h, st.sY.alloc(B * n1));
+        HIP_TRY(h, st.sP.alloc(B * v.n_p));
+        HIP_TRY(h, st.sU.alloc(B * v.n_u));
+        HIP_TRY(h, st.sY.alloc(B * v.n1));
         HIP_TRY(h, st.sst.alloc(B));
         HIP_TRY(h, st.h_nact.alloc(sizeof(int)));
         HIP_TRY(h, st.ev_nact.create(hipEventDisableTiming));
-        *(int *)st.h_nact.p = a.B;
+        *(int *)st.h_nact.p = v.B;
         nmpc::RetireArgs &r = st.a;
-        r.B = a.B; r.N = a.N; r.s = a.s;
-        r.done = l->d_done; r.state = l->d_state; r.retired_at = st.retired_at; r.act = st.act; r.nact = st.nact;
-        r.traj = l->d_traj;
-        nmpc::PackArgs &g = st.pack;
-        g.n_p = a.n_p; g.n_u = a.n_u; g.n1 = (int)n1;
-        g.act = st.act; g.P = l->d_P; g.U = l->d_U; g.Y = l->d_Y; g.st = l->d_st;
-        g.sP = st.sP; g.sU = st.sU; g.sY = st.sY; g.sst = st.sst;
+        r.retired_at = st.retired_at; r.list = st.act; r.count = st.nact;
+        r.sP = st.sP; r.sU = st.sU; r.sY = st.sY; r.sst = st.sst;
     }
     l->retire = std::move(st);
+    l->v.act = l->retire.act;      // the robots every kernel runs over from now on (NULL with on = 0: everybody)
     return NMPC_OK;
 }
 
@@ -303,20 +300,14 @@ int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of)
     if (!l) return NMPC_ERR_BAD_ARG;
     if (const int rc = loop_setter(l, "nmpc_loop_set_monitor", l->monitor.made(), "the loop has its monitor already")) return rc;
     nmpc_handle *h = l->h;
-    const nmpc::LoopArgs &a = l->a;
-    const int B = a.B;
+    const int B = l->v.B;
     if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: the loop records no trajectory (max_steps == 0)");
     if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_monitor: group_of out of range");
     LoopMonitor st;
     const std::vector<nmpc_clearance> none(B, CLEARANCE_NONE);
     HIP_TRY(h, st.rec.upload(none.data(), B));
     HIP_TRY(h, st.groups.upload(group_of, B));
-    nmpc::MonitorArgs &m = st.a;
-    m.B = B; m.N = a.N; m.nobs = a.nobs; m.K = a.K; m.n_p = a.n_p; m.s = a.s;
-    m.pcirc = nmpc::NZ + a.N; m.pdyn = nmpc::NZ + a.N + 3 * a.nobs;
-    m.P = l->d_P; m.state = l->d_state; m.traj = l->d_traj;
-    m.group_of = st.groups.group_of; m.goff = st.groups.goff; m.gmem = st.groups.gmem;
-    m.rec = st.rec;
+    st.a.grp = st.groups.lists(); st.a.rec = st.rec;
     l->monitor = std::move(st);
     return NMPC_OK;
 }
@@ -329,7 +320,7 @@ int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map)
     if (!l) return NMPC_ERR_BAD_ARG;
     if (const int rc = loop_setter(l, "nmpc_loop_set_map_monitor", l->map.made(), "the loop has its map monitor already")) return rc;
     nmpc_handle *h = l->h;
-    const nmpc::LoopArgs &a = l->a;
+    const int B = l->v.B;
     if (!map) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: map is NULL");
     if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: the loop records no trajectory (max_steps == 0)");
     const int E = map->n_edge, np = map->n_poly;
@@ -347,14 +338,13 @@ int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map)
     for (int k = 0; k < np; ++k)
         for (int e = map->poly_off[k]; e < map->poly_off[k + 1]; ++e) owner[e] = k;
     LoopMap st;
-    const std::vector<nmpc_map_clearance> none(a.B, MAP_CLEARANCE_NONE);
-    HIP_TRY(h, st.rec.upload(none.data(), a.B));
+    const std::vector<nmpc_map_clearance> none(B, MAP_CLEARANCE_NONE);
+    HIP_TRY(h, st.rec.upload(none.data(), B));
     HIP_TRY(h, st.edge.upload(map->edge, 4 * (size_t)E));
     HIP_TRY(h, st.poly_off.upload(map->poly_off, (size_t)np + 1));
     HIP_TRY(h, st.edge_poly.upload(owner.data(), E));
     nmpc::MapArgs &m = st.a;
-    m.B = a.B; m.s = a.s; m.E = E; m.n_poly = np;
-    m.traj = l->d_traj;
+    m.E = E; m.n_poly = np;
     m.edge = st.edge; m.poly_off = st.poly_off; m.edge_poly = st.edge_poly;
     m.rec = st.rec;
     l->map = std::move(st);
@@ -366,8 +356,7 @@ int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *
     if (!l) return NMPC_ERR_BAD_ARG;
     if (const int rc = loop_setter(l, "nmpc_loop_set_missions", l->missions.made(), "the loop has its missions already")) return rc;
     nmpc_handle *h = l->h;
-    const nmpc::LoopArgs &a = l->a;
-    const int B = a.B;
+    const int B = l->v.B;
     if (!leg_off || !leg_route) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off or leg_route is NULL");
     if (!l->retire.made()) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: the loop does not retire its robots (nmpc_loop_set_retire first)");
     if (leg_off[0] != 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_missions: leg_off[0] != 0");
@@ -386,10 +375,8 @@ int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *
     HIP_TRY(h, st.leg_at.alloc_fill(T, 0xFF));                     // leg_at = -1
     st.n_legs = T;
     nmpc::DispatchArgs &d = st.a;
-    d.n_u = a.n_u; d.n1 = nmpc_n1(&h->pb);
-    d.done = l->d_done;
     d.leg_off = st.leg_off; d.leg_route = st.leg_route; d.leg = st.leg; d.leg_at = st.leg_at;
-    d.route_of = l->d_route_of; d.idx = l->d_idx; d.last_u = l->d_last_u; d.U = l->d_U; d.Y = l->d_Y;
+    d.route_of = l->d_route_of;
     l->missions = std::move(st);
     return NMPC_OK;
 }
@@ -406,17 +393,6 @@ static int loop_nactive(nmpc_loop *l, int *n)
     return NMPC_OK;
 }
 
-// Run by step 0, when no setter can follow: the pointers that cross stages.  The robots a step runs over are the retirement's active
-// list (NULL without: everybody, row i is robot i), for the base and for every stage; the monitor reads retired_at as the step
-// found it, and the compaction parks a retired robot's predictions for the peers.  A stage that is not made has nothing to give (NULL).
-static void loop_wire(nmpc_loop *l)
-{
-    const int *act = l->retire.act;
-    l->a.act = l->peers.a.act = l->monitor.a.act = l->map.a.act = l->missions.a.act = act;
-    l->monitor.a.retired_at = l->retire.retired_at;
-    l->retire.a.pred = l->peers.pred;
-}
-
 // One step: assemble -> solve -> advance over the n robots still active, every stage's kernels where they belong.  Without retirement
 // n = B and the host waits for nothing; with it the step waits for the count of the step before (an event), solves on gathered rows
 // and rebuilds the active list behind the advance.
@@ -428,75 +404,58 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     if (l->max_steps > 0 && l->steps >= l->max_steps) return fail(h, NMPC_ERR_BAD_ARG, "trajectory buffer is full");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (l->steps == 0) loop_wire(l);
-    nmpc::LoopArgs &a = l->a;
+    const nmpc::LoopView &v = l->v;
     LoopRetire &r = l->retire;
     const bool retiring = r.made();
-    int n = a.B;
+    int n = v.B;
     if (retiring) {
         if (const int rc = loop_nactive(l, &n)) return rc;
-        if (n < 0 || n > a.B) return fail(h, NMPC_ERR_HIP, "nmpc_loop_step: active count out of range");
+        if (n < 0 || n > v.B) return fail(h, NMPC_ERR_HIP, "nmpc_loop_step: active count out of range");
     }
-    a.nact = n;
+    const nmpc::LoopStep stp = nmpc::LoopStep::after(l->steps, v.s, n);
     if (n > 0) {
-        const int cur = l->steps & 1;
-        a.dyn_in = l->d_dyn[cur];
-        a.dyn_out = l->d_dyn[cur ^ 1];
-        hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, v, stp, l->a);
         if (l->peers.made()) {
-            l->peers.a.nact = n;
-            hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, l->peers.a);
+            const nmpc::PeerArgs &p = l->peers.a;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, p);
             if (l->peers.grid()) {     // the boxes and the grid over all B: a retired robot stays filed
                 const nmpc::PeerGridArgs &g = l->peers.g;
-                hipLaunchKernelGGL(nmpc::nmpc_loop_peer_box_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, g);
-                hipLaunchKernelGGL(nmpc::nmpc_loop_peer_grid_kernel, dim3(1), dim3(1024), 0, s, g);
-                hipLaunchKernelGGL(nmpc::nmpc_loop_peers_grid_kernel, dim3(n), dim3(64), 0, s, l->peers.a, g);
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peer_box_kernel, dim3((v.B + 255) / 256), dim3(256), 0, s, v, p, g);
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peer_grid_kernel, dim3(1), dim3(1024), 0, s, v, g);
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peers_grid_kernel, dim3(n), dim3(64), 0, s, v, p, g);
             } else {
-                hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, l->peers.a);
+                hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, v, p);
             }
         }
-        if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, r.pack);
+        if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, v, r.a);
         HIP_TRY(h, hipGetLastError());
         // warm start: previous controls and multipliers, penalty back to its initial value (the server's behaviour).  The solve runs on
         // the loop's own rows, or on the gathered ones: rows 0 .. n - 1 are then the active robots
-        double *P = l->d_P, *U = l->d_U, *Y = l->d_Y;
-        nmpc_status *st = l->d_st;
-        if (retiring) { P = r.sP; U = r.sU; Y = r.sY; st = r.sst; }
+        double *P = v.P, *U = v.U, *Y = v.Y;
+        nmpc_status *st = v.st;
+        if (retiring) { P = r.a.sP; U = r.a.sU; Y = r.a.sY; st = r.a.sst; }
         // launch order: from the second step on, by the pass counts of these very robots' solves of the step before (read by the
         // classification kernel ahead of the solve, which then overwrites them); the first step has only the inputs to go by
-        h->order_hint = (l->steps > 0 && h->loop_order_prev) ? st : nullptr;
-        const int rc = nmpc_solve_batch_device(h, n, P, U, Y, nullptr, Y, st, stream);
-        h->order_hint = nullptr;
-        if (rc) return rc;
-        if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, r.pack);
-        hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
-        if (l->monitor.made()) {       // over the robots the advance ran over: the compaction comes after
-            l->monitor.a.traj_row = a.traj_row;
-            hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, l->monitor.a);
-        }
-        if (l->map.made()) {           // the same rows of the same robots, against the map
-            l->map.a.traj_row = a.traj_row;
-            hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, l->map.a);
-        }
-        if (l->missions.made()) {
-            l->missions.a.step = l->steps + 1;
-            hipLaunchKernelGGL(nmpc::nmpc_loop_dispatch_kernel, dim3(n), dim3(64), 0, s, l->missions.a);
-        }
+        const nmpc_status *hint = (l->steps > 0 && h->loop_order_prev) ? st : nullptr;
+        if (const int rc = solve_launch(h, n, P, U, Y, nullptr, Y, st, hint, stream)) return rc;
+        if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, v, r.a);
+        hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->a);
+        // the monitors and the dispatch run over the robots the advance ran over: the compaction comes after.  The monitor reads
+        // retired_at as the step found it (NULL without retirement)
+        if (l->monitor.made())
+            hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, l->monitor.a, r.retired_at);
+        if (l->map.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, v, stp, l->map.a);
+        if (l->missions.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_dispatch_kernel, dim3(n), dim3(64), 0, s, v, stp, l->missions.a);
     }
-    if (retiring) {
-        // (with nobody active the step still counts: the clock advances and the trajectory rows repeat)
-        r.a.step = l->steps + 1;
-        r.a.traj_row = a.traj_row;
-        hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, r.a);
-    }
+    // (with nobody active the step still counts: the clock advances and the trajectory rows repeat).  The compaction parks a retired
+    // robot's predictions for the peers (NULL without them)
+    if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, v, stp, r.a, l->peers.pred);
     HIP_TRY(h, hipGetLastError());
     if (retiring) {
         HIP_TRY(h, hipMemcpyAsync(r.h_nact.p, r.nact.p, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipEventRecord(r.ev_nact, s));
         r.nact_pending = true;
     }
-    a.t += a.s;
-    a.traj_row += a.s;
     l->steps++;
     return NMPC_OK;
 }
@@ -532,7 +491,7 @@ static int loop_settle(nmpc_loop *l)
 int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at)
 {
     if (const int rc = loop_settle(l)) return rc;
-    const int B = l->a.B;
+    const int B = l->v.B;
     if (!l->retire.made()) {
         if (n_active) *n_active = B;
         if (retired_at) for (int b = 0; b < B; ++b) retired_at[b] = -1;
@@ -546,7 +505,7 @@ int nmpc_loop_active(nmpc_loop *l, int32_t *n_active, int32_t *retired_at)
 int nmpc_loop_legs(nmpc_loop *l, int32_t *leg, int32_t *route_of, int32_t *leg_at)
 {
     if (const int rc = loop_settle(l)) return rc;
-    const size_t B = (size_t)l->a.B;
+    const size_t B = (size_t)l->v.B;
     HIP_TRY(l->h, l->d_route_of.read(route_of, B));
     if (!l->missions.made()) {
         if (leg) for (size_t b = 0; b < B; ++b) leg[b] = 0;
@@ -561,7 +520,7 @@ int nmpc_loop_clearance(nmpc_loop *l, nmpc_clearance *out)
 {
     if (!out) return NMPC_ERR_BAD_ARG;
     if (const int rc = loop_settle(l)) return rc;
-    const int B = l->a.B;
+    const int B = l->v.B;
     if (!l->monitor.made()) {
         for (int b = 0; b < B; ++b) out[b] = CLEARANCE_NONE;
         return NMPC_OK;
@@ -577,7 +536,7 @@ int nmpc_loop_peer_grid(nmpc_loop *l, nmpc_peer_grid *out, int32_t *cell_of)
     if (!l->peers.grid()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_peer_grid: the loop has no peers grid (nmpc_loop_set_peers_grid)");
     if (l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_peer_grid: before the loop's first step");
     HIP_TRY(l->h, l->peers.hdr.read(out, 1));
-    HIP_TRY(l->h, l->peers.cell_of.read(cell_of, l->a.B));
+    HIP_TRY(l->h, l->peers.cell_of.read(cell_of, l->v.B));
     return NMPC_OK;
 }
 
@@ -585,7 +544,7 @@ int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out)
 {
     if (!out) return NMPC_ERR_BAD_ARG;
     if (const int rc = loop_settle(l)) return rc;
-    const int B = l->a.B;
+    const int B = l->v.B;
     if (!l->map.made()) {
         for (int b = 0; b < B; ++b) out[b] = MAP_CLEARANCE_NONE;
         return NMPC_OK;
@@ -598,7 +557,7 @@ int nmpc_loop_read(nmpc_loop *l, double *state, double *last_u, int32_t *idx, ui
 {
     if (const int rc = loop_settle(l)) return rc;
     nmpc_handle *h = l->h;
-    const size_t B = (size_t)l->a.B;
+    const size_t B = (size_t)l->v.B;
     HIP_TRY(h, l->d_state.read(state, B * 3));
     HIP_TRY(h, l->d_last_u.read(last_u, B * 2));
     HIP_TRY(h, l->d_idx.read(idx, B));
@@ -611,10 +570,10 @@ int nmpc_loop_params(nmpc_loop *l, double *p, double *u, double *y)
 {
     if (const int rc = loop_settle(l)) return rc;
     nmpc_handle *h = l->h;
-    const size_t B = (size_t)l->a.B;
-    HIP_TRY(h, l->d_P.read(p, B * l->a.n_p));
-    HIP_TRY(h, l->d_U.read(u, B * l->a.n_u));
-    HIP_TRY(h, l->d_Y.read(y, B * (size_t)nmpc_n1(&h->pb)));
+    const size_t B = (size_t)l->v.B;
+    HIP_TRY(h, l->d_P.read(p, B * l->v.n_p));
+    HIP_TRY(h, l->d_U.read(u, B * l->v.n_u));
+    HIP_TRY(h, l->d_Y.read(y, B * l->v.n1));
     return NMPC_OK;
 }
 
@@ -623,9 +582,9 @@ int nmpc_loop_trajectory(nmpc_loop *l, double *rows, int max_rows)
     if (!l || !rows) return NMPC_ERR_BAD_ARG;
     nmpc_handle *h = l->h;
     if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "the loop was created without a trajectory buffer");
-    const int nrows = l->steps * l->a.s + 1;
+    const int nrows = l->steps * l->v.s + 1;
     if (max_rows < nrows) return fail(h, NMPC_ERR_BAD_ARG, "trajectory does not fit");
     if (const int rc = loop_settle(l)) return rc;
-    HIP_TRY(h, l->d_traj.read(rows, (size_t)nrows * l->a.B * 3));
+    HIP_TRY(h, l->d_traj.read(rows, (size_t)nrows * l->v.B * 3));
     return nrows;
 }
