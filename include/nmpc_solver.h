@@ -47,7 +47,8 @@ extern "C" {
 
 typedef enum nmpc_error {
     NMPC_OK = 0,
-    NMPC_ERR_BAD_PROBLEM = -1,      /* unsupported dims / non-positive ts                     */
+    NMPC_ERR_BAD_PROBLEM = -1,      /* unsupported dims; ts not finite and > 0; a bound that is NaN or infinite;
+                                       vmin > vmax, amin > amax, wmax < 0 or awmax < 0 (equal bounds are accepted) */
     NMPC_ERR_BAD_OPTS = -2,
     NMPC_ERR_BAD_ARG = -3,          /* NULL pointer, B < 0, B > max_batch                     */
     NMPC_ERR_NO_DEVICE = -4,        /* no HIP device / wrong architecture                     */
@@ -159,6 +160,9 @@ int nmpc_abi_version(void);
 int nmpc_experiments_build(void);
 /* Diagnostic: the solve kernel this handle launches (the name a rocprofv3 kernel trace shows). */
 const char *nmpc_kernel_name(const nmpc_handle *h);
+/* Diagnostic: the radius in metres of the circle culling this handle's solves use, 1.1 * N * ts * max(|vmin|, |vmax|): what the
+ * bounds let a robot travel in a horizon, plus a margin.  Any value gives the same results; 0 for a NULL handle. */
+double nmpc_cull_radius(const nmpc_handle *h);
 
 /* Device path: every pointer is device memory on the handle's device; the launch is enqueued on
  * `stream` (a hipStream_t, NULL = default stream) and the call returns without synchronising.

@@ -19,7 +19,7 @@ BUILD_INFO = os.path.join(_CSRC, "build_info.json")      # written by build_libr
 # every symbol include/nmpc_solver.h declares
 SYMBOLS = (
     "nmpc_default_opts", "nmpc_n_u", "nmpc_n_p", "nmpc_n1", "nmpc_n2", "nmpc_new", "nmpc_free",
-    "nmpc_ping", "nmpc_last_error", "nmpc_abi_version", "nmpc_experiments_build", "nmpc_kernel_name", "nmpc_solve_batch_device",
+    "nmpc_ping", "nmpc_last_error", "nmpc_abi_version", "nmpc_experiments_build", "nmpc_kernel_name", "nmpc_cull_radius", "nmpc_solve_batch_device",
     "nmpc_solve_batch_host", "nmpc_last_batch_ms", "nmpc_set_time_limits", "nmpc_eval_batch_device", "nmpc_eval_batch_host",
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
@@ -268,6 +268,8 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_last_error.restype = C.c_char_p
     lib.nmpc_kernel_name.argtypes = [vp]
     lib.nmpc_kernel_name.restype = C.c_char_p
+    lib.nmpc_cull_radius.argtypes = [vp]
+    lib.nmpc_cull_radius.restype = C.c_double
     lib.nmpc_last_batch_ms.argtypes = [vp]
     lib.nmpc_last_batch_ms.restype = C.c_double
     lib.nmpc_solve_batch_device.argtypes = [vp, C.c_int] + [vp] * 7

@@ -215,8 +215,13 @@ static void read_knobs([[maybe_unused]] nmpc_handle *h)
 int nmpc_new(const nmpc_problem *pb, const nmpc_opts *opts, int device_id, int max_batch, nmpc_handle **out)
 {
     if (!pb || !out || max_batch < 1) return NMPC_ERR_BAD_ARG;
-    if (pb->N < 2 || pb->N > NMPC_MAX_HORIZON || pb->nobs < 0 || pb->nobs > 64 || pb->ndyn < 0 || pb->ndyn > nmpc::NDYN_MAX ||
-        !(pb->ts > 0.0))
+    if (pb->N < 2 || pb->N > NMPC_MAX_HORIZON || pb->nobs < 0 || pb->nobs > 64 || pb->ndyn < 0 || pb->ndyn > nmpc::NDYN_MAX)
+        return NMPC_ERR_BAD_PROBLEM;
+    // ts and the boxes U and C (ranges stated in include/nmpc_solver.h); written so that a NaN fails every test
+    auto finite = [](double x) { return x >= -DBL_MAX && x <= DBL_MAX; };
+    if (!(pb->ts > 0.0 && pb->ts <= DBL_MAX) || !finite(pb->vmin) || !finite(pb->vmax) || !(pb->vmin <= pb->vmax) ||
+        !finite(pb->amin) || !finite(pb->amax) || !(pb->amin <= pb->amax) ||
+        !(pb->wmax >= 0.0 && pb->wmax <= DBL_MAX) || !(pb->awmax >= 0.0 && pb->awmax <= DBL_MAX))
         return NMPC_ERR_BAD_PROBLEM;
     nmpc_opts op;
     if (opts) op = *opts; else nmpc_default_opts(&op);
@@ -287,6 +292,7 @@ const char *nmpc_last_error(const nmpc_handle *h) { return h ? h->err.c_str() : 
 double nmpc_last_batch_ms(const nmpc_handle *h) { return h ? h->last_ms : 0.0; }
 static bool timed(const nmpc_handle *h) { return h->tl_dur > 0 || h->tl_budget > 0; }
 const char *nmpc_kernel_name(const nmpc_handle *h) { return h ? h->kernel[timed(h)]->name : ""; }
+double nmpc_cull_radius(const nmpc_handle *h) { return h ? h->cull_radius : 0.0; }
 
 // a limit in ms -> ticks of the 100 MHz clock: 0 stays 0 (off), anything above it is at least one tick, and at most 2^52 ticks (16 months)
 static long long ms_to_ticks(double ms)

@@ -102,6 +102,11 @@ class BatchSolver:
         return self.lib.nmpc_kernel_name(self._h).decode()
 
     @property
+    def cull_radius(self) -> float:
+        """The circle-culling radius in metres this handle's solves use (diagnostic; any value gives the same results)."""
+        return float(self.lib.nmpc_cull_radius(self._h))
+
+    @property
     def last_batch_ms(self) -> float:
         """Kernel time (HIP events) of the last host-path ``solve`` on this handle; per-instance times are in
         ``status["solve_time_ms"]``."""

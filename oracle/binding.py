@@ -72,6 +72,9 @@ class Oracle:
     def __init__(self, N, nobs, ndyn, ts, vmin, vmax, wmax, amin, amax, awmax, **opts):
         self.lib = C.CDLL(build_oracle())
         self.pb = OrcProblem(N, nobs, ndyn, 0, ts, vmin, vmax, wmax, amin, amax, awmax)
+        if not self.lib.orc_problem_valid(C.byref(self.pb)):
+            raise RuntimeError(f"oracle problem outside what include/nmpc_solver.h accepts: N={N} nobs={nobs} ndyn={ndyn} ts={ts!r} "
+                               f"v=[{vmin!r}, {vmax!r}] wmax={wmax!r} a=[{amin!r}, {amax!r}] awmax={awmax!r}")
         self.opts = OrcOpts()
         self.lib.orc_default_opts(C.byref(self.opts))
         for k, v in opts.items():

@@ -288,9 +288,15 @@ static int check_problem(const orc_problem *pb)
     if (pb->N < 2 || pb->N > MAXN) return -1;
     if (pb->nobs < 0 || pb->nobs > MAXOBS) return -2;
     if (pb->ndyn < 0 || pb->ndyn > MAXDYN) return -3;
-    if (!(pb->ts > 0.0)) return -4;
+    if (!finite_pos(pb->ts)) return -4;
+    /* the boxes U and C, as nmpc_new checks them; a NaN fails every comparison */
+    if (!(pb->vmin >= -DBL_MAX && pb->vmax <= DBL_MAX && pb->vmin <= pb->vmax)) return -4;
+    if (!(pb->amin >= -DBL_MAX && pb->amax <= DBL_MAX && pb->amin <= pb->amax)) return -4;
+    if (!(pb->wmax >= 0.0 && pb->wmax <= DBL_MAX && pb->awmax >= 0.0 && pb->awmax <= DBL_MAX)) return -4;
     return 0;
 }
+
+int orc_problem_valid(const orc_problem *pb) { return check_problem(pb) == 0; }
 
 static void prepare(const orc_problem *pb, const double *p, inst_t *I)
 {

@@ -87,6 +87,8 @@ int orc_n2(const orc_problem *pb);
 void orc_default_opts(orc_opts *o);
 /* 1 if the ALM knobs lie in the ranges of include/nmpc_solver.h, else 0 (orc_solve then returns -6) */
 int orc_opts_valid(const orc_opts *o);
+/* 1 if sizes, ts and the boxes U and C are what nmpc_new accepts, else 0 (orc_eval and orc_solve then return < 0) */
+int orc_problem_valid(const orc_problem *pb);
 
 /* psi(u; c, y, p), grad_u psi, F1, F2.  c = 0, y = NULL gives f and grad f.
  * grad / F1 / F2 may be NULL.  Returns 0, or <0 on a bad descriptor. */

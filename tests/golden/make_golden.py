@@ -16,7 +16,10 @@ OpEn code generator would have built (OpEn ALM documentation
 
 and differentiates that too.
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [variant ...]
+
+Without arguments every variant is written; with arguments only the ones named (``fast slow fwd``: the three sets of
+vehicle constants of tests/vehicle_sets.py, which leave the four BASELINE files as they are).
 """
 import math
 import os
@@ -151,6 +154,8 @@ sys.modules["opengen"] = og
 sys.dont_write_bytecode = True
 sys.path.insert(0, os.path.join(REF, "src"))
 from mpc.mpc_generator import MpcModule  # noqa: E402  (the reference, unmodified)
+sys.path.insert(0, os.path.dirname(OUT))
+from vehicle_sets import VEHICLE_GOLDENS, VEHICLE_SETS  # noqa: E402
 
 
 class dotdict(dict):
@@ -166,7 +171,8 @@ def load_cfg(name, **over):
 
 
 def variants():
-    """The four problem shapes of BASELINE.md section 4 (overrides per SURVEY.md App. E)."""
+    """The four problem shapes of BASELINE.md section 4 (overrides per SURVEY.md App. E), then default.yaml with each of the three
+    sets of vehicle constants of tests/vehicle_sets.py at the shape named there."""
     d = load_cfg("default.yaml")
     yield "default", d
     yield "n40", load_cfg("jconf_3.yaml", N_hor=40)
@@ -174,6 +180,8 @@ def variants():
     s = load_cfg("smooth_velocity.yaml")
     s.update(N_hor=20, nz=20, qv=d.qv, vel_red_steps=d.vel_red_steps, Ndynobs=d.Ndynobs)
     yield "smooth", s
+    for stem, (vset, shape) in VEHICLE_GOLDENS.items():
+        yield stem, load_cfg("default.yaml", **VEHICLE_SETS[vset], **shape)
 
 
 def reference_eval(cfg, u, p):
@@ -261,8 +269,12 @@ def realistic_case(cfg, rng, all_weights):
     return u, np.array(p, dtype=np.float64)
 
 
-def main():
+def main(only=()):
+    unknown = set(only) - {name for name, _ in variants()}
+    assert not unknown, f"unknown variants {sorted(unknown)}"
     for name, cfg in variants():
+        if only and name not in only:
+            continue
         N = cfg.N_hor
         n_u = cfg.nu * N
         n_p = cfg.nz + N + cfg.Nobs * cfg.nobs + cfg.Ndynobs * cfg.ndynobs * N + cfg.nx * N
@@ -315,4 +327,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
