@@ -439,6 +439,78 @@ int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map);
 /* Synchronises, then copies the records out [B]; on a loop without the stage the initial record everywhere. */
 int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out);
 
+/* ---- drive log: each robot's applied controls and solve outcomes, on device -----------------------
+ * The reference's PathGenerator.run gives back the path, the controls that were applied and how long each solve took, and reports a
+ * bad exit status at the step where it occurs (src/path_generator.py:385-394,431-437).  The drive log is an opt-in stage of the loop
+ * that keeps all of that on the device (the rule: DESIGN.md section 5.9).  It observes only: no p, u, y, state, status, trajectory,
+ * clearance or map record differs by a bit from the loop without it.  Two more kernels per step, after the advance and the monitors
+ * and before the missions' dispatch: one over the robots the step drove (those it retires at its end included), one workgroup for
+ * the step's fleet totals.  With s = num_steps_taken and `step` the loop's step count, this step included (1-based, as retired_at):
+ *   ctrl [max_steps * s][B][2]  row step_before * s + i = the (v, w) applied between trajectory rows step_before * s + i and the next:
+ *                               the first s control pairs of the robot's u, as the advance read them.  +0.0 where a robot was not driven.
+ *   rec  [max_steps][B]         nmpc_step_record of row step - 1: the fields of the step's nmpc_status after the solve, and the leg the
+ *                               solve belonged to (before the step's dispatch; 0 without missions).  A robot the step did not drive
+ *                               keeps exit_status = -1 and zeros.
+ *   sum  [B]                    nmpc_drive_summary, cumulative; a retired robot keeps its summary, and it runs on across legs:
+ *     steps, rows               + 1, + s
+ *     exits[e]                  + 1 for e = the solve's exit_status (0 .. 4)
+ *     inner_total               + num_inner_iterations; inner_max / inner_max_step: the largest count and the step it occurred at
+ *     length                    length = length + sqrt(dx*dx + dy*dy) over the step's rows in order, (dx, dy) from trajectory row r - 1 to
+ *                               row r, unfused f64
+ *     v_abs_max, w_abs_max      fabs of the applied controls
+ *     acc_*, wacc_*             a = (v_i - v_prev) / ts (IEEE division), v_prev = p[3] for the step's first control -- the very v_-1 the
+ *                               solve formed F1 from; 0 after a mission's re-dispatch -- and the control before for the others; w likewise
+ *                               with p[4].  *_abs_max takes fabs(a), *_sq_sum = *_sq_sum + a*a, sequential, no fma
+ *     f2_max / f2_max_step      the largest f2_norm and the step it occurred at
+ *     Every maximum is updated by `if (x > m) m = x` from +0.0: a comparison that is false (a NaN) keeps the record, and among equal
+ *     values the earliest step stays.  The two *_step fields start at -1.
+ *   tot  [max_steps]            nmpc_step_totals of row step - 1, over the robots the step drove: their number, their solves per exit
+ *                               status, the sum of their num_inner_iterations, the largest one and the smallest robot index that has it,
+ *                               and the largest solve_time_ms.  A step with nobody active writes zeros.
+ * To be called once, before the loop's first step, in any order with the other setters, on a loop that records its trajectory
+ * (max_steps > 0: that is the log's length, and `length` reads the trajectory's rows).  NMPC_ERR_BAD_ARG with a message that names the
+ * function, and nothing changed or allocated, for a call after a step, a second call or a loop with max_steps == 0 (a NULL loop:
+ * NMPC_ERR_BAD_ARG).  A loop without the stage enqueues what it enqueued before this function existed. */
+typedef struct nmpc_step_record {        /* 40 bytes */
+    int32_t  exit_status;            /* nmpc_exit; -1: the robot was not solved in this step */
+    int32_t  leg;                    /* the leg this solve belonged to (before the step's dispatch); 0 without missions */
+    uint32_t num_inner_iterations, num_outer_iterations;
+    double   cost, f2_norm, solve_time_ms;
+} nmpc_step_record;
+typedef struct nmpc_drive_summary {      /* 112 bytes */
+    int32_t  steps, rows;            /* solves taken, controls applied */
+    uint32_t exits[5];               /* solves per nmpc_exit value */
+    uint32_t inner_max;
+    uint64_t inner_total;
+    int32_t  inner_max_step, f2_max_step;
+    double   length;
+    double   v_abs_max, w_abs_max;
+    double   acc_abs_max, wacc_abs_max, acc_sq_sum, wacc_sq_sum;
+    double   f2_max;
+} nmpc_drive_summary;
+typedef struct nmpc_step_totals {        /* 48 bytes */
+    int32_t  solved;                 /* the step's active count */
+    uint32_t exits[5];
+    uint32_t inner_max;
+    int32_t  inner_max_robot;        /* among the robots with the largest count, the smallest index */
+    uint64_t inner_total;
+    double   solve_ms_max;
+} nmpc_step_totals;
+#ifdef __cplusplus
+static_assert(sizeof(nmpc_step_record) == 40 && sizeof(nmpc_drive_summary) == 112 && sizeof(nmpc_step_totals) == 48, "drive log layouts");
+#else
+_Static_assert(sizeof(nmpc_step_record) == 40 && sizeof(nmpc_drive_summary) == 112 && sizeof(nmpc_step_totals) == 48, "drive log layouts");
+#endif
+int nmpc_loop_set_log(nmpc_loop *l);
+/* Synchronises, then copies what is asked for (NULL = skip) of the steps taken so far: ctrl [steps * s][B][2] and rec [steps][B].
+ * Returns the step count (or < 0); NMPC_ERR_BAD_ARG if max_steps, the steps the caller's buffers hold, is smaller.  A loop without a
+ * log reports 0 steps and writes nothing. */
+int nmpc_loop_log(nmpc_loop *l, double *ctrl, nmpc_step_record *rec, int max_steps);
+/* Synchronises, then copies the summaries out [B]; on a loop without a log the initial summary everywhere. */
+int nmpc_loop_drive_summary(nmpc_loop *l, nmpc_drive_summary *out);
+/* Synchronises, then copies the totals of the steps taken so far out [steps] and returns the step count (or < 0), as nmpc_loop_log. */
+int nmpc_loop_step_totals(nmpc_loop *l, nmpc_step_totals *out, int max_steps);
+
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);
 /* a/b and sqrt(a) as the device computes them: out_div/out_sqrt [n]. */

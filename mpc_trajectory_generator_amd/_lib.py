@@ -26,6 +26,7 @@ SYMBOLS = (
     "nmpc_loop_trajectory", "nmpc_loop_set_retire", "nmpc_loop_active", "nmpc_loop_run", "nmpc_loop_set_monitor", "nmpc_loop_clearance",
     "nmpc_loop_set_missions", "nmpc_loop_legs", "nmpc_loop_set_map_monitor", "nmpc_loop_map_clearance",
     "nmpc_loop_set_peers_grid", "nmpc_loop_peer_grid",
+    "nmpc_loop_set_log", "nmpc_loop_log", "nmpc_loop_drive_summary", "nmpc_loop_step_totals",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -96,6 +97,19 @@ assert MAP_CLEARANCE_DTYPE.itemsize == 32
 # nmpc_peer_grid: the grid the peers of a step were found through (nmpc_loop_set_peers_grid)
 PEER_GRID_DTYPE = np.dtype([("origin", "<f8", 2), ("h", "<f8", 2), ("W", "<f8", 2), ("nx", "<i4"), ("ny", "<i4"), ("filed", "<i4"), ("reserved", "<i4")])
 assert PEER_GRID_DTYPE.itemsize == 64
+
+# the drive log (nmpc_loop_set_log): nmpc_step_record, one per robot and step; nmpc_drive_summary, one per robot; nmpc_step_totals, one per step
+STEP_RECORD_DTYPE = np.dtype([("exit_status", "<i4"), ("leg", "<i4"), ("num_inner_iterations", "<u4"), ("num_outer_iterations", "<u4"),
+                              ("cost", "<f8"), ("f2_norm", "<f8"), ("solve_time_ms", "<f8")])
+assert STEP_RECORD_DTYPE.itemsize == 40
+DRIVE_SUMMARY_DTYPE = np.dtype([("steps", "<i4"), ("rows", "<i4"), ("exits", "<u4", 5), ("inner_max", "<u4"), ("inner_total", "<u8"),
+                                ("inner_max_step", "<i4"), ("f2_max_step", "<i4"), ("length", "<f8"), ("v_abs_max", "<f8"),
+                                ("w_abs_max", "<f8"), ("acc_abs_max", "<f8"), ("wacc_abs_max", "<f8"), ("acc_sq_sum", "<f8"),
+                                ("wacc_sq_sum", "<f8"), ("f2_max", "<f8")])
+assert DRIVE_SUMMARY_DTYPE.itemsize == 112
+STEP_TOTALS_DTYPE = np.dtype([("solved", "<i4"), ("exits", "<u4", 5), ("inner_max", "<u4"), ("inner_max_robot", "<i4"),
+                              ("inner_total", "<u8"), ("solve_ms_max", "<f8")])
+assert STEP_TOTALS_DTYPE.itemsize == 48
 
 
 def _sources():
@@ -308,6 +322,14 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_missions.restype = C.c_int
     lib.nmpc_loop_legs.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.nmpc_loop_legs.restype = C.c_int
+    lib.nmpc_loop_set_log.argtypes = [vp]
+    lib.nmpc_loop_set_log.restype = C.c_int
+    lib.nmpc_loop_log.argtypes = [vp, dp, vp, C.c_int]
+    lib.nmpc_loop_log.restype = C.c_int
+    lib.nmpc_loop_drive_summary.argtypes = [vp, vp]
+    lib.nmpc_loop_drive_summary.restype = C.c_int
+    lib.nmpc_loop_step_totals.argtypes = [vp, vp, C.c_int]
+    lib.nmpc_loop_step_totals.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]

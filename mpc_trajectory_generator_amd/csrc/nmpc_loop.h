@@ -904,6 +904,130 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(LoopView L, LoopStep 
     }
 }
 
+// ---- drive log: each robot's applied controls and solve outcomes (nmpc_loop_set_log; the rule is DESIGN.md section 5.9).  It observes:
+// its four tables are the only things it writes.
+struct LogArgs {
+    double *ctrl;             // [max_steps * s][B][2]
+    nmpc_step_record *rec;    // [max_steps][B]
+    nmpc_drive_summary *sum;  // [B]
+    nmpc_step_totals *tot;    // [max_steps]
+};
+
+// One thread per robot the step drove, after the advance and the monitors and before the dispatch: U is what the advance applied, st the
+// step's statuses (scattered), P the parameter vectors as the solve read them (p[3], p[4]: the controls before this step's first) and
+// `leg` the missions' array as the solve found it (NULL: no missions).  The thread copies the s control pairs and the record, walks the
+// step's s + 1 trajectory rows for the length and folds everything into the robot's summary, field by field in global memory (exits is
+// indexed by the status).  Unfused f64; a comparison that is false keeps a maximum.
+__global__ __launch_bounds__(256) void nmpc_loop_log_kernel(LoopView L, LoopStep stp, LogArgs g, const int *leg)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= stp.nact) return;
+    const int b = L.robot(i), s = L.s;
+    const double *u = L.U + (size_t)b * L.n_u, *p = L.P + (size_t)b * L.n_p;
+    const nmpc_status st = L.st[b];
+    nmpc_step_record r;
+    r.exit_status = st.exit_status; r.leg = leg ? leg[b] : 0;
+    r.num_inner_iterations = st.num_inner_iterations; r.num_outer_iterations = st.num_outer_iterations;
+    r.cost = st.cost; r.f2_norm = st.f2_norm; r.solve_time_ms = st.solve_time_ms;
+    g.rec[(size_t)(stp.step - 1) * L.B + b] = r;
+    nmpc_drive_summary *m = g.sum + b;
+    m->steps = m->steps + 1;
+    m->rows = m->rows + s;
+    if ((unsigned)st.exit_status < 5u) m->exits[st.exit_status] += 1u;
+    m->inner_total = m->inner_total + st.num_inner_iterations;
+    if (st.num_inner_iterations > m->inner_max) { m->inner_max = st.num_inner_iterations; m->inner_max_step = stp.step; }
+    if (st.f2_norm > m->f2_max) { m->f2_max = st.f2_norm; m->f2_max_step = stp.step; }
+    double len = m->length, vm = m->v_abs_max, wm = m->w_abs_max;
+    double am = m->acc_abs_max, wam = m->wacc_abs_max, as = m->acc_sq_sum, was = m->wacc_sq_sum;
+    double vp = p[3], wp = p[4];
+    const double *at = L.row(stp.traj_row - 1, b);           // (traj_row >= 1: the row before the step's first is there)
+    double ax = at[0], ay = at[1];
+    for (int c = 0; c < s; ++c) {
+        const double v = u[2 * c], w = u[2 * c + 1];
+        double *out = g.ctrl + ((size_t)(stp.t + c) * L.B + b) * 2;
+        out[0] = v; out[1] = w;
+        const double *row = L.row(stp.traj_row + c, b);
+        const double x = row[0], y = row[1];
+        const double dx = x - ax, dy = y - ay;
+        len = len + sqrt(dx * dx + dy * dy);
+        ax = x; ay = y;
+        const double fv = fabs(v), fw = fabs(w);
+        if (fv > vm) vm = fv;
+        if (fw > wm) wm = fw;
+        const double a = (v - vp) / L.ts, wa = (w - wp) / L.ts;
+        const double fa = fabs(a), fwa = fabs(wa);
+        if (fa > am) am = fa;
+        if (fwa > wam) wam = fwa;
+        as = as + a * a;
+        was = was + wa * wa;
+        vp = v; wp = w;
+    }
+    m->length = len; m->v_abs_max = vm; m->w_abs_max = wm;
+    m->acc_abs_max = am; m->wacc_abs_max = wam; m->acc_sq_sum = as; m->wacc_sq_sum = was;
+}
+
+// One workgroup, behind nmpc_loop_log_kernel: thread t strides over the rows of the step's active list; a wave reduction, then the
+// waves' results through LDS, and thread 0 writes the step's totals.  Every field is independent of the order: integer sums, one
+// maximum over the key (inner << 32) | (0xffffffff - b) -- the largest count, and among equals the smallest robot -- and a maximum of
+// non-negative finite times.  With nobody active (nact == 0) the row is written as zeros.
+__global__ __launch_bounds__(1024) void nmpc_loop_log_totals_kernel(LoopView L, LoopStep stp, LogArgs g)
+{
+    __shared__ unsigned long long rkey[16], rsum[16];
+    __shared__ double rms[16];
+    __shared__ unsigned rex[16][5];
+    const int t = threadIdx.x, nt = blockDim.x;
+    unsigned e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;
+    unsigned long long key = 0, sum = 0;
+    double ms = 0.0;
+    for (int i = t; i < stp.nact; i += nt) {
+        const int b = L.robot(i);
+        const nmpc_status *st = L.st + b;
+        const int e = st->exit_status;
+        const unsigned inner = st->num_inner_iterations;
+        const double tm = st->solve_time_ms;
+        e0 += e == 0; e1 += e == 1; e2 += e == 2; e3 += e == 3; e4 += e == 4;
+        sum += inner;
+        const unsigned long long k = ((unsigned long long)inner << 32) | (0xffffffffu - (unsigned)b);
+        if (k > key) key = k;
+        if (tm > ms) ms = tm;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        e0 += __shfl_xor(e0, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off);
+        e3 += __shfl_xor(e3, off); e4 += __shfl_xor(e4, off);
+        sum += __shfl_xor(sum, off);
+        const unsigned long long ok = __shfl_xor(key, off);
+        if (ok > key) key = ok;
+        const double om = __shfl_xor(ms, off);
+        if (om > ms) ms = om;
+    }
+    if ((t & 63) == 0) {
+        const int w = t >> 6;
+        rkey[w] = key; rsum[w] = sum; rms[w] = ms;
+        rex[w][0] = e0; rex[w][1] = e1; rex[w][2] = e2; rex[w][3] = e3; rex[w][4] = e4;
+    }
+    __syncthreads();
+    if (t == 0) {
+        nmpc_step_totals o;
+        o.solved = stp.nact;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) o.exits[q] = 0;
+        key = 0; sum = 0; ms = 0.0;
+        for (int w = 0; w < nt / 64; ++w) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) o.exits[q] += rex[w][q];
+            sum += rsum[w];
+            if (rkey[w] > key) key = rkey[w];
+            if (rms[w] > ms) ms = rms[w];
+        }
+        o.inner_max = (unsigned)(key >> 32);
+        o.inner_max_robot = stp.nact > 0 ? (int)(0xffffffffu - (unsigned)(key & 0xffffffffu)) : 0;
+        o.inner_total = sum;
+        o.solve_ms_max = ms;
+        g.tot[stp.step - 1] = o;
+    }
+}
+
 // ---- missions: a robot at its goal takes up its next route (nmpc_loop_set_missions; the rule is DESIGN.md section 5.9) ----
 struct DispatchArgs {
     const int *leg_off;       // [B + 1]: robot b drives the routes leg_route[leg_off[b] .. leg_off[b + 1]) in turn

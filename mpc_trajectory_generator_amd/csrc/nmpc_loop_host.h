@@ -3,13 +3,13 @@
 // after the handle, fail, HIP_TRY and solve_launch.
 //
 // A loop is its view (nmpc::LoopView: the shape, the per-robot arrays and the active list, the same for every kernel), its base
-// (assemble -> solve -> advance) and up to five stages, each a sub-struct with its device buffers and the argument block of its own
+// (assemble -> solve -> advance) and up to six stages, each a sub-struct with its device buffers and the argument block of its own
 // kernels.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop as it
 // was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the configuration
 // final.  The loop keeps ONE counter, `steps`: nmpc_loop_step derives everything that changes per step from it and the active count
 // (nmpc::LoopStep, on its stack), hands view, step and a stage's block to each kernel, and writes to no argument block.  It is ONE
-// sequence of kernels in which a stage adds its own; the two pointers that cross stages (the peers' pred for the compaction,
-// retirement's retired_at for the monitor) are passed at the launch, from the stage that owns them.
+// sequence of kernels in which a stage adds its own; the pointers that cross stages (the peers' pred for the compaction,
+// retirement's retired_at for the monitor, the missions' leg for the log) are passed at the launch, from the stage that owns them.
 #pragma once
 
 // member lists of the groups 0 .. B - 1 (most of them empty), each group's robots in ascending index
@@ -78,6 +78,15 @@ struct LoopMissions {
     int n_legs = 0;                  // leg_off[B]
     bool made() const { return leg_off != nullptr; }
 };
+// nmpc_loop_set_log: two more kernels per step, after the advance and the monitors and before the dispatch
+struct LoopLog {
+    nmpc::LogArgs a{};
+    DevBuf<double> ctrl;             // [max_steps * s][B][2]
+    DevBuf<nmpc_step_record> rec;    // [max_steps][B]
+    DevBuf<nmpc_drive_summary> sum;  // [B]
+    DevBuf<nmpc_step_totals> tot;    // [max_steps]
+    bool made() const { return sum != nullptr; }
+};
 
 struct nmpc_loop {
     nmpc_handle *h = nullptr;
@@ -98,6 +107,7 @@ struct nmpc_loop {
     LoopMonitor monitor;
     LoopMap map;
     LoopMissions missions;
+    LoopLog log;
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -381,6 +391,30 @@ int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *
     return NMPC_OK;
 }
 
+static const nmpc_step_record STEP_RECORD_NONE = {-1, 0, 0, 0, 0.0, 0.0, 0.0};
+static const nmpc_drive_summary DRIVE_SUMMARY_NONE = {0, 0, {0, 0, 0, 0, 0}, 0, 0, -1, -1, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+
+int nmpc_loop_set_log(nmpc_loop *l)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_log", l->log.made(), "the loop has its log already")) return rc;
+    nmpc_handle *h = l->h;
+    const size_t B = (size_t)l->v.B, steps = (size_t)l->max_steps;
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_log: the loop records no trajectory (max_steps == 0)");
+    LoopLog st;
+    HIP_TRY(h, st.ctrl.alloc_fill(steps * l->v.s * B * 2, 0));
+    {
+        const std::vector<nmpc_step_record> none(steps * B, STEP_RECORD_NONE);
+        HIP_TRY(h, st.rec.upload(none.data(), none.size()));
+    }
+    const std::vector<nmpc_drive_summary> none(B, DRIVE_SUMMARY_NONE);
+    HIP_TRY(h, st.sum.upload(none.data(), B));
+    HIP_TRY(h, st.tot.alloc_fill(steps, 0));
+    st.a.ctrl = st.ctrl; st.a.rec = st.rec; st.a.sum = st.sum; st.a.tot = st.tot;
+    l->log = std::move(st);
+    return NMPC_OK;
+}
+
 // a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
 static int loop_nactive(nmpc_loop *l, int *n)
 {
@@ -445,7 +479,14 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         if (l->monitor.made())
             hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, l->monitor.a, r.retired_at);
         if (l->map.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, v, stp, l->map.a);
+        // the log sees the leg and the p the solve belonged to: the dispatch comes after (leg: the missions', NULL without them)
+        if (l->log.made()) {
+            hipLaunchKernelGGL(nmpc::nmpc_loop_log_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->log.a, l->missions.leg.p);
+            hipLaunchKernelGGL(nmpc::nmpc_loop_log_totals_kernel, dim3(1), dim3(1024), 0, s, v, stp, l->log.a);
+        }
         if (l->missions.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_dispatch_kernel, dim3(n), dim3(64), 0, s, v, stp, l->missions.a);
+    } else if (l->log.made()) {    // nobody active: the step's totals are a row of zeros
+        hipLaunchKernelGGL(nmpc::nmpc_loop_log_totals_kernel, dim3(1), dim3(1024), 0, s, v, stp, l->log.a);
     }
     // (with nobody active the step still counts: the clock advances and the trajectory rows repeat).  The compaction parks a retired
     // robot's predictions for the peers (NULL without them)
@@ -551,6 +592,41 @@ int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out)
     }
     HIP_TRY(l->h, l->map.rec.read(out, B));
     return NMPC_OK;
+}
+
+int nmpc_loop_log(nmpc_loop *l, double *ctrl, nmpc_step_record *rec, int max_steps)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (!l->log.made()) return 0;
+    if (max_steps < l->steps) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_log: max_steps is smaller than the steps taken, the log does not fit");
+    if (const int rc = loop_settle(l)) return rc;
+    const size_t B = (size_t)l->v.B, steps = (size_t)l->steps;
+    HIP_TRY(l->h, l->log.ctrl.read(ctrl, steps * l->v.s * B * 2));
+    HIP_TRY(l->h, l->log.rec.read(rec, steps * B));
+    return l->steps;
+}
+
+int nmpc_loop_drive_summary(nmpc_loop *l, nmpc_drive_summary *out)
+{
+    if (!out) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_settle(l)) return rc;
+    const int B = l->v.B;
+    if (!l->log.made()) {
+        for (int b = 0; b < B; ++b) out[b] = DRIVE_SUMMARY_NONE;
+        return NMPC_OK;
+    }
+    HIP_TRY(l->h, l->log.sum.read(out, B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_step_totals(nmpc_loop *l, nmpc_step_totals *out, int max_steps)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (!l->log.made()) return 0;
+    if (max_steps < l->steps) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_step_totals: max_steps is smaller than the steps taken, the totals do not fit");
+    if (const int rc = loop_settle(l)) return rc;
+    HIP_TRY(l->h, l->log.tot.read(out, (size_t)l->steps));
+    return l->steps;
 }
 
 int nmpc_loop_read(nmpc_loop *l, double *state, double *last_u, int32_t *idx, uint8_t *done, nmpc_status *status)

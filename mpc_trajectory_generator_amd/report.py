@@ -49,3 +49,54 @@ def batch_summary(status) -> dict:
             "p99_inner_iters": float(np.percentile(it, 99)), "max_inner_iters": int(it.max()),
             "mean_outer_iters": float(status["num_outer_iterations"].mean()),
             "exit_status_counts": {int(k): int(v) for k, v in zip(*np.unique(status["exit_status"], return_counts=True))}}
+
+
+def _logged(loop):
+    """-> (trajectory [rows, B, 3], controls, step_records, drive_summary, step_totals) of a loop that keeps a drive log: a
+    ``DeviceRecedingHorizon`` or its host mirror ``FleetRecedingHorizon``, either with ``log=DriveLog()``."""
+    if getattr(loop, "log", None) is None:
+        raise ValueError("the loop keeps no drive log (log=DriveLog())")
+    get = lambda name: (lambda v: v() if callable(v) else v)(getattr(loop, name))      # noqa: E731
+    traj = loop.trajectory() if callable(getattr(loop, "trajectory", None)) else np.stack(loop.traj)
+    return traj, get("controls"), get("step_records"), get("drive_summary"), get("step_totals")
+
+
+def fleet_runs(loop):
+    """What the reference's ``PathGenerator.run`` returns (src/path_generator.py:431-437), per robot of a logged loop: -> a list [B] of
+    ``(xx, xy, uv, uomega, solver_times)``, cut at the robot's last driven row: ``rows`` controls, ``rows + 1`` poses and ``steps``
+    solve times (ms), ``rows`` and ``steps`` the robot's summary's.  A robot that retired is cut where it stopped."""
+    traj, ctrl, rec, summary, _ = _logged(loop)
+    out = []
+    for b in range(traj.shape[1]):
+        rows, steps = int(summary["rows"][b]), int(summary["steps"][b])
+        out.append((traj[:rows + 1, b, 0].tolist(), traj[:rows + 1, b, 1].tolist(), ctrl[:rows, b, 0].tolist(), ctrl[:rows, b, 1].tolist(),
+                    rec["solve_time_ms"][:steps, b].tolist()))
+    return out
+
+
+def fleet_runtime_text(loop, file_name: str = "") -> str:
+    """``runtime_analysis`` over the fleet of a logged loop, from its totals and summaries: the solver times are the steps' slowest solves
+    (``solve_ms_max``: what a control period has to wait for), followed by the fleet's solves per exit status, its PANOC iterations and
+    the largest acceleration any robot used."""
+    from ._lib import EXIT_STATUS
+    _, _, _, summary, tot = _logged(loop)
+    ms = tot["solve_ms_max"][tot["solved"] > 0]
+    text = runtime_analysis({"solver_time": float(ms.sum())}, ms)
+    solves = int(tot["solved"].sum())
+    lines = ["-" * 44, f"{'Robots':<30}{len(summary):>12d}", f"{'Steps':<30}{len(tot):>12d}", f"{'Solves':<30}{solves:>12d}"]
+    for e, n in enumerate(tot["exits"].sum(axis=0).tolist()):
+        if n:
+            lines.append(f"{'  ' + EXIT_STATUS[e]:<30}{n:>12d}")
+    lines.append(f"{'PANOC iterations':<30}{int(tot['inner_total'].sum()):>12d}")
+    if len(tot):
+        k = int(np.argmax(tot["inner_max"]))
+        lines.append(f"{'  most in one solve':<30}{int(tot['inner_max'][k]):>12d}  (step {k + 1}, robot {int(tot['inner_max_robot'][k])})")
+    if len(summary):
+        lines += [f"{'Longest path':<30}{float(summary['length'].max()):>12.3f} m",
+                  f"{'Largest |acceleration|':<30}{float(summary['acc_abs_max'].max()):>12.3f} m/s^2",
+                  f"{'Largest |angular acc.|':<30}{float(summary['wacc_abs_max'].max()):>12.3f} rad/s^2"]
+    more = "\n".join(lines) + "\n"
+    if file_name:
+        with open(file_name, "a") as fh:
+            fh.write(more)
+    return text + more

@@ -176,6 +176,7 @@ class _HostLoop:
         P = self.assemble()
         if self.active is None:
             self.U, self.Y, st = solve_fn(P, self.U, self.Y)
+            self._st_step = st                                               # this step's statuses: the drive log's
             self.advance(self.U)
             return P, st
         rows = np.nonzero(self.active)[0]
@@ -184,6 +185,7 @@ class _HostLoop:
             if self.status is None:
                 self.status = np.zeros(len(self.active), dtype=st.dtype)
             self.U[rows], self.Y[rows], self.status[rows] = U, Y, st
+        self._st_step = self.status
         self.advance(self.U)
         self.retire()
         return P, self.status
@@ -712,6 +714,32 @@ class MapMonitor:
         return rec
 
 
+@dataclasses.dataclass(frozen=True)
+class DriveLog:
+    """The drive log, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon`` alike: the controls every robot
+    applied, one record per robot and step of how its solve ended, a cumulative summary per robot and the fleet's totals per step
+    (``controls``, ``step_records``, ``drive_summary``, ``step_totals``).  It observes only."""
+
+
+def no_step_records(steps: int, B: int):
+    """-> the initial records [steps, B]: exit_status -1, everything else 0."""
+    rec = np.zeros((steps, B), dtype=_lib.STEP_RECORD_DTYPE)
+    rec["exit_status"] = -1
+    return rec
+
+
+def no_drive_summary(B: int):
+    """-> the initial summaries [B]: zeros, the two ``*_step`` fields -1."""
+    rec = np.zeros(B, dtype=_lib.DRIVE_SUMMARY_DTYPE)
+    rec["inner_max_step"] = rec["f2_max_step"] = -1
+    return rec
+
+
+def no_step_totals(steps: int):
+    """-> the totals of ``steps`` steps with nobody active: zeros."""
+    return np.zeros(steps, dtype=_lib.STEP_TOTALS_DTYPE)
+
+
 class FleetRecedingHorizon(VectorizedRecedingHorizon):
     """``VectorizedRecedingHorizon`` for a fleet on R routes: robot b follows ``routes[route_of[b]]``.
 
@@ -742,10 +770,15 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     instead of retiring it: ``leg`` [B] and ``route_of`` [B] move on, ``leg_at`` [B, Lmax] takes the step count
     at which each leg ended (-1: not yet, or no such leg), the robot's reference sample, ``last_u``, ``U`` and ``Y`` rows are zeroed
     and ``done`` cleared, in place; its state, carried dynamic block and trajectory are not touched.
+
+    ``log`` (a ``DriveLog``): ``controls`` [steps * s, B, 2], ``step_records`` [steps, B], ``drive_summary`` [B] and ``step_totals``
+    [steps] (the ``_lib.*_DTYPE`` records of the device), updated by ``advance`` -- before ``retire``, so a
+    record names the leg its solve belonged to -- from the controls it applied, the statuses ``step`` got from its ``solve_fn``, the
+    rows it appended to ``traj`` and the parameter vectors ``assemble`` returned for this step, for the robots the step drove.
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None, missions=None, map_monitor=None):
+                 monitor=None, missions=None, map_monitor=None, log=None):
         self.routes = list(routes)
         cfg, B = self.routes[0].cfg, len(starts)
         route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
@@ -784,6 +817,23 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         if map_monitor is not None:
             map_monitor.checked()
             self.map_clearance = no_map_clearance(B)
+        self.log = log
+        if log is not None:
+            self._ctrl, self._rec, self._tot = [], [], []                     # per step: [s, B, 2], [B], one record
+            self.drive_summary = no_drive_summary(B)
+
+    @property
+    def controls(self):
+        """-> [steps * s, B, 2]: the (v, omega) applied between trajectory rows c and c + 1; +0.0 where a robot was not driven."""
+        return np.concatenate(self._ctrl) if self._ctrl else np.zeros((0, self.B, 2))
+
+    @property
+    def step_records(self):
+        return np.stack(self._rec) if self._rec else no_step_records(0, self.B)
+
+    @property
+    def step_totals(self):
+        return np.concatenate(self._tot) if self._tot else no_step_totals(0)
 
     @property
     def n_active(self):
@@ -905,7 +955,67 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._monitor_update()
         if self.map_monitor is not None:
             self._map_update()
+        if self.log is not None:
+            self._log_update(U)
         self.steps += 1
+
+    def _log_update(self, U):
+        """The drive log's rule for the robots this step drove (``active`` as the step found it: ``retire``
+        comes after, so ``leg`` is the leg the solve belonged to).  Unfused f64, sequential sums, and maxima that a false comparison
+        (a NaN) leaves alone."""
+        cfg, B, st, P = self.cfg, self.B, self._st_step, self._P_step
+        s, nu, step = cfg.num_steps_taken, cfg.nu, self.steps + 1
+        drove = np.ones(B, dtype=bool) if self.active is None else self.active.copy()
+        who = np.nonzero(drove)[0]
+        ctrl, rec, tot = np.zeros((s, B, 2)), no_step_records(1, B)[0], no_step_totals(1)
+        self._ctrl.append(ctrl)
+        self._rec.append(rec)
+        self._tot.append(tot)
+        if not len(who):
+            return
+        st = st[who]
+        ctrl[:, who] = U[who, :s * nu].reshape(len(who), s, nu).transpose(1, 0, 2)
+        for f in ("exit_status", "num_inner_iterations", "num_outer_iterations", "cost", "f2_norm", "solve_time_ms"):
+            rec[f][who] = st[f]
+        rec["leg"][who] = self.leg[who] if self.missions is not None else 0
+        m = self.drive_summary
+        m["steps"][who] += 1
+        m["rows"][who] += s
+        e, inner, f2 = st["exit_status"], st["num_inner_iterations"], st["f2_norm"]
+        ok = (e >= 0) & (e < 5)
+        np.add.at(m["exits"], (who[ok], e[ok]), 1)
+        m["inner_total"][who] += inner.astype(np.uint64)
+
+        def raise_to(field, x, at=None):
+            """``if (x > m) m = x`` on the robots driven, with the step where ``at`` names a field"""
+            b = who[x > m[field][who]]
+            m[field][b] = x[x > m[field][who]]
+            if at is not None:
+                m[at][b] = step
+
+        raise_to("inner_max", inner, "inner_max_step")
+        raise_to("f2_max", f2, "f2_max_step")
+        vp, wp = P[who, 3], P[who, 4]
+        with np.errstate(all="ignore"):
+            for i in range(s):
+                a, b = self.traj[len(self.traj) - s - 1 + i][who], self.traj[len(self.traj) - s + i][who]
+                dx, dy = b[:, 0] - a[:, 0], b[:, 1] - a[:, 1]
+                m["length"][who] = m["length"][who] + np.sqrt(dx * dx + dy * dy)
+                v, w = U[who, i * nu], U[who, i * nu + 1]
+                raise_to("v_abs_max", np.abs(v))
+                raise_to("w_abs_max", np.abs(w))
+                acc, wacc = (v - vp) / cfg.ts, (w - wp) / cfg.ts
+                raise_to("acc_abs_max", np.abs(acc))
+                raise_to("wacc_abs_max", np.abs(wacc))
+                m["acc_sq_sum"][who] = m["acc_sq_sum"][who] + acc * acc
+                m["wacc_sq_sum"][who] = m["wacc_sq_sum"][who] + wacc * wacc
+                vp, wp = v, w
+        tot["solved"] = len(who)
+        tot["exits"] = np.bincount(e[ok], minlength=5)
+        tot["inner_max"], tot["inner_max_robot"] = inner.max(), who[np.argmax(inner)]      # the first maximum: the smallest robot index
+        tot["inner_total"] = inner.astype(np.uint64).sum()
+        ms = st["solve_time_ms"]
+        tot["solve_ms_max"] = np.where(ms > 0, ms, 0.0).max()
 
     def _map_update(self):
         """The map monitor's rule on the s rows this step appended, each against the row before it, for the robots
@@ -1048,10 +1158,15 @@ class DeviceRecedingHorizon:
     the last (``nmpc_loop_set_missions``); one more kernel per step, before the active list is rebuilt.
     ``legs()`` tells where everybody is.  Its host mirror is ``FleetRecedingHorizon`` with the same ``missions``
     (tests/test_gpu_missions_loop.py).
+
+    ``log`` (a ``DriveLog``, needs ``max_steps`` > 0): the controls every robot applied, a record of every solve, a summary per robot and
+    the fleet's totals per step are kept on the device (``nmpc_loop_set_log``), two more kernels per step after
+    the advance; ``controls()``, ``step_records()``, ``drive_summary()`` and ``step_totals()`` read them.  Its host mirror is
+    ``FleetRecedingHorizon`` with the same ``log`` (tests/test_gpu_log_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None):
+                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -1115,6 +1230,9 @@ class DeviceRecedingHorizon:
                 raise
             sc = _lib.NmpcScene(0, len(edges), len(off) - 1, 0, None, _lib.as_dp(edges), _lib.as_i32p(off))
             self._set(self.lib.nmpc_loop_set_map_monitor(h, C.byref(sc)))
+        self.log = log
+        if log is not None:
+            self._set(self.lib.nmpc_loop_set_log(h))
         self.missions = missions
         self._leg_off = None
         if missions is not None:
@@ -1202,6 +1320,39 @@ class DeviceRecedingHorizon:
         rec = np.empty(self.B, dtype=_lib.MAP_CLEARANCE_DTYPE)
         self.solver._check(self.lib.nmpc_loop_map_clearance(self._l, rec.ctypes.data))
         return rec
+
+    def _log(self, want_ctrl):
+        ctrl = np.zeros((self.steps * self.cfg.num_steps_taken, self.B, 2)) if want_ctrl else None
+        rec = None if want_ctrl else no_step_records(self.steps, self.B)
+        n = self.lib.nmpc_loop_log(self._l, _lib.as_dp(ctrl), None if rec is None else rec.ctypes.data, self.steps)
+        if n < 0:
+            self.solver._check(n)
+        return ctrl[:n * self.cfg.num_steps_taken] if want_ctrl else rec[:n]
+
+    def controls(self):
+        """-> [steps * s, B, 2] after synchronising: the (v, omega) applied between trajectory rows c and c + 1, +0.0 where a robot was
+        not driven (``log=DriveLog()``; without it no rows)."""
+        return self._log(True)
+
+    def step_records(self):
+        """-> [steps, B] (``_lib.STEP_RECORD_DTYPE``: exit_status, leg, num_inner_iterations, num_outer_iterations, cost, f2_norm,
+        solve_time_ms) after synchronising: how each robot's solve of each step ended, exit_status -1 where it was not solved
+        (``log=DriveLog()``; without it no steps)."""
+        return self._log(False)
+
+    def drive_summary(self):
+        """-> the drive log's summaries [B] (``_lib.DRIVE_SUMMARY_DTYPE``) after synchronising; without a ``log`` the initial one everywhere."""
+        rec = np.empty(self.B, dtype=_lib.DRIVE_SUMMARY_DTYPE)
+        self.solver._check(self.lib.nmpc_loop_drive_summary(self._l, rec.ctypes.data))
+        return rec
+
+    def step_totals(self):
+        """-> the fleet's totals per step [steps] (``_lib.STEP_TOTALS_DTYPE``) after synchronising (``log=DriveLog()``; without it no steps)."""
+        tot = no_step_totals(self.steps)
+        n = self.lib.nmpc_loop_step_totals(self._l, tot.ctypes.data, self.steps)
+        if n < 0:
+            self.solver._check(n)
+        return tot[:n]
 
     def read(self):
         """-> (state [B,3], last_u [B,2], idx [B], done [B] bool, status [B]) after synchronising."""

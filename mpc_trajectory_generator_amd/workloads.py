@@ -250,6 +250,33 @@ def map_clearance_differing(dev, host):
     return [f for f in a.dtype.names if a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes() or a[f].shape != b[f].shape]
 
 
+LOG_PRODUCTS = ("controls", "step_records", "drive_summary", "step_totals")
+LOG_CLOCK_FIELDS = ("solve_time_ms", "solve_ms_max")      # read from a clock: no two runs agree on them
+
+
+def log_differing(dev, host):
+    """The drive log's four products (``dev``: a ``DeviceRecedingHorizon`` with a log or a dict of its ``controls()``, ``step_records()``,
+    ``drive_summary()`` and ``step_totals()``; ``host``: its mirror, or such a dict) -> the names, "product.field", that are not
+    bit-equal: a value compares by its bytes, so -0.0 is not 0.0 and a NaN equals itself.  Every field but the two a clock gives."""
+    def product(x, name):
+        if isinstance(x, dict):
+            return x[name]
+        v = getattr(x, name)
+        return v() if callable(v) else v
+    bad = []
+    for name in LOG_PRODUCTS:
+        a, b = np.asarray(product(dev, name)), np.asarray(product(host, name))
+        if a.shape != b.shape:
+            bad.append(f"{name} of shape {a.shape}, not {b.shape}")
+        elif a.dtype.names is None:
+            if a.tobytes() != np.asarray(b, dtype=a.dtype).tobytes():
+                bad.append(name)
+        else:
+            bad += [f"{name}.{f}" for f in a.dtype.names
+                    if f not in LOG_CLOCK_FIELDS and a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes()]
+    return bad
+
+
 def trajectory_differing(dev, host, steps, rows=None):
     """After ``steps`` steps of both: [] if the device's trajectory is [steps * num_steps_taken + 1, B, 3] and the mirror's bits
     (``rows`` as in ``step_differing``)."""

@@ -15,7 +15,9 @@ of robots that were inside a circle, inside a padded ellipse and closer to a gro
 from the goal of the one before; the routes are planned on the device (frontend.DevicePlanner), and the result line
 gains plan_ms (the planner kernels' time over all batches, redraws included) and routes_planned.  --map [inflated]: the map monitor
 (nmpc_loop_set_map_monitor) on the scene's original polygons, the true walls, or with "inflated" on the polygons the
-planner plans on; the result line then has map_clearance: the share of robots with a hit, the rows hit and the fleet's smallest wall distance.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+planner plans on; the result line then has map_clearance: the share of robots with a hit, the rows hit and the fleet's smallest wall distance.
+--log: the drive log (nmpc_loop_set_log): the result line then has drive_log: the share of non-converged solves per exit
+status, the worst step's slowest solve and the fleet's largest acceleration.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -27,7 +29,7 @@ sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config                            # noqa: E402
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
-from mpc_trajectory_generator_amd.trajectory import FleetRecedingHorizon, MapMonitor, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.trajectory import DriveLog, FleetRecedingHorizon, MapMonitor, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
 from mpc_trajectory_generator_amd.workloads import moving_ellipses, route_fleet   # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -64,6 +66,9 @@ ap.add_argument("--monitor", type=int, nargs="?", const=0, default=None, metavar
 ap.add_argument("--map", nargs="?", const="original", default=None, choices=("original", "inflated"), metavar="inflated",
                 help="device loop only: keep every robot's closest approach to the scene's walls and its rows inside an obstacle, outside the "
                      "boundary or through an edge on the device, and report them; 'inflated': against the polygons the planner plans on")
+ap.add_argument("--log", action="store_true",
+                help="device loop only: keep every robot's applied controls, a record of every solve, a summary per robot and the fleet's "
+                     "totals per step on the device, and report from them")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
@@ -77,6 +82,8 @@ if args.peer_cell is not None and not args.peers:
     ap.error("--peer-cell goes with --peers G")
 if args.map and (args.host or args.steps < 1):
     ap.error("--map reads the trajectory the device loop records: it needs the device loop (no --host) and --steps >= 1")
+if args.log and (args.host or args.steps < 1):
+    ap.error("--log is the device loop's, and its length is --steps: it needs the device loop (no --host) and --steps >= 1")
 if args.legs < 1 or (args.legs > 1 and (not args.retire or args.host)):
     ap.error("--legs L: L >= 1, and L > 1 needs --retire on the device loop")
 if args.own_routes and (args.host or args.routes != 1):
@@ -177,7 +184,7 @@ if not args.host:
         sub_routes, sub_route_of = routes_of(ids)
         loops.append(DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                            route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
-                                           missions=missions_of(ids), map_monitor=map_monitor))
+                                           missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -224,6 +231,19 @@ if not args.host:
         quality["map_clearance"] = {"polygons": args.map, "edges": len(map_monitor.edges), "robots_hit_frac": float((rec["hits"] > 0).mean()),
                                     "rows_hit": int(rec["hits"].sum()), "min_wall_m": float(np.sqrt(rec["wall2"].min()))}
     from mpc_trajectory_generator_amd import _lib
+    if args.log:
+        tot = [rh.step_totals() for rh in loops]
+        summ = np.concatenate([rh.drive_summary() for rh in loops])
+        exits = sum(t["exits"].sum(axis=0) for t in tot)
+        worst = max(tot, key=lambda t: t["solve_ms_max"].max(initial=0.0))
+        quality["drive_log"] = {
+            "solves": int(exits.sum()),
+            "not_converged_frac": {_lib.EXIT_STATUS[e]: float(exits[e] / max(exits.sum(), 1)) for e in range(1, 5)},
+            "worst_step": int(np.argmax(worst["solve_ms_max"])) + 1 if len(worst) else 0,
+            "worst_step_solve_ms_max": float(worst["solve_ms_max"].max(initial=0.0)),
+            "max_acc_abs": float(summ["acc_abs_max"].max()), "max_wacc_abs": float(summ["wacc_abs_max"].max()),
+            "device_bytes": int(sum(rh.max_steps * rh.B * (rh.cfg.num_steps_taken * 16 + _lib.STEP_RECORD_DTYPE.itemsize)
+                                    + rh.B * _lib.DRIVE_SUMMARY_DTYPE.itemsize + rh.max_steps * _lib.STEP_TOTALS_DTYPE.itemsize for rh in loops))}
     if hasattr(_lib.load_library(), "nmpc_debug_win_stats"):        # instrumented build (-DNMPC_WIN_STATS, scripts/win_stats.py)
         buf = (ctypes.c_ulonglong * 2)()
         _lib.load_library().nmpc_debug_win_stats(buf, 0)
@@ -236,6 +256,7 @@ if not args.host:
                                + (", robots retire at their goals" if args.retire else "")
                                + (f", clearance monitor in groups of {args.monitor}" if args.monitor else "")
                                + (f", map monitor on the scene's {args.map} polygons" if args.map else "")
+                               + (", drive log" if args.log else "")
                                + (f", at most {args.budget} PANOC iterations per solve (NotConvergedOutOfTime beyond)" if args.budget else "")
                                + (f", fleet split into {args.split} sub-fleets on {args.split} streams" if args.split > 1 else ""),
                    "kernel": solver.kernel_name},
