@@ -253,7 +253,8 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
  *   rx, ry        the ellipse's radii as the cost reads them (no padding is added), range: all finite and > 0
  * To be called once, before the loop's first step.  NMPC_ERR_BAD_ARG with a message, and nothing changed, for M < 1,
  * K + M > Ndynobs, a group_of[b] out of range, an rx, ry or range that is not finite and positive, a call after a step, or
- * a second call.  A loop without peers enqueues what it enqueued before this function existed. */
+ * a second call.  A loop without peers enqueues what it enqueued before this function existed.  On a loop with a crowd
+ * (nmpc_loop_set_crowd, Mc slots) the peers' slots are K + Mc .. K + Mc + M - 1, and K + Mc + M > Ndynobs is refused. */
 int nmpc_loop_set_peers(nmpc_loop *l, const int32_t *group_of, int M, double rx, double ry, double range);
 /* Peers found through a grid: the rule and the results of nmpc_loop_set_peers, bit for bit, at a cost that grows with the robots
  * near each other, not with the group (the rule, and why it misses nobody: DESIGN.md section 5.9).  Every step, on the device, each
@@ -510,6 +511,48 @@ int nmpc_loop_log(nmpc_loop *l, double *ctrl, nmpc_step_record *rec, int max_ste
 int nmpc_loop_drive_summary(nmpc_loop *l, nmpc_drive_summary *out);
 /* Synchronises, then copies the totals of the steps taken so far out [steps] and returns the step count (or < 0), as nmpc_loop_log. */
 int nmpc_loop_step_totals(nmpc_loop *l, nmpc_step_totals *out, int max_steps);
+/* Crowd: D moving obstacles that belong to the world and are shared by the whole fleet (the rule: DESIGN.md section 5.9), where
+ * nmpc_loop_new* gives every robot a private copy of at most Ndynobs.  One table [D][N][5] of every obstacle's ellipses over the horizon is
+ * advanced on the device once per step -- every step, whoever is active, across mission legs: all stages fresh at the first step, later a
+ * shift by the s stages taken inside each obstacle's row and the last s stages fresh -- by the arithmetic of the scripted ellipses, so that
+ * row d equals, bit for bit, the block a loop carries for a scripted obstacle with the same ten parameters.  Every step, between the assembly
+ * of p and the solve, each active robot's predicted poses (those of nmpc_loop_set_peers) are compared with this step's table: C(b, d) = min
+ * over the stages k of |pred[b][k] - table[d][k]|^2 (unfused f64; a comparison that is false because of a NaN neither lowers the minimum nor
+ * makes a candidate), and the first M obstacles with C < range^2 in (C, d) order are copied, row by row, over the ellipse slots K .. K + M - 1
+ * of its p.  A slot that finds no obstacle keeps what the assembly put there; the block the loop carries never sees the crowd; a retired
+ * robot keeps its p and its seen.  With a crowd the peers' slots follow the crowd's: scripted [0, K), crowd [K, K + M), peers from K + M on.
+ *   obst [D][10]  (p1x, p1y, p2x, p2y, freq, rx, ry, angle, sinus, direction) per obstacle, as dyn of nmpc_loop_new.  The values are not
+ *                 checked: an obstacle with a NaN is never a candidate, and no loop's bounds depend on them.
+ *   pad           added to both radii (nmpc_route.dyn_pad of the scripted ellipses), finite
+ *   M             ellipse slots given to the crowd, M >= 1 and K + M (+ the peers' M) <= Ndynobs
+ *   range         finite and > 0
+ * To be called once, before the loop's first step, in any order with the other setters; whichever of this and the peers setters comes second
+ * checks that all three kinds fit.  NMPC_ERR_BAD_ARG with a message, nothing changed and nothing allocated, for D < 1 or D > 16384, obst NULL,
+ * M < 1, K + M (+ the peers' M) > Ndynobs, a pad that is not finite, a range that is not finite and positive, a call after a step, or a
+ * second call.  A loop without a crowd enqueues what it enqueued before this function existed. */
+int nmpc_loop_set_crowd(nmpc_loop *l, int D, const double *obst, double pad, int M, double range);
+/* Synchronises, then copies what is asked for (NULL = skip): table [D][N][5] as the last step wrote it, and seen [B][M], the obstacle in
+ * slot K + m of each robot's p at its last step, -1 for none.  NMPC_ERR_BAD_ARG on a loop without a crowd or before its first step. */
+int nmpc_loop_crowd(nmpc_loop *l, double *table, int32_t *seen);
+/* Crowd observer: each robot's closest approach to ANY obstacle of the crowd, in a slot of its p or not.  One more kernel per step, after the
+ * advance, over the robots the step drove: for each of the step's s trajectory rows r = first + i and every d < D, the cost's level
+ * (a*a)/(rx*rx) + (c*c)/(ry*ry) of the pose of row r against entry i of obstacle d's row of this step's table ((a, c) as nmpc_clearance's
+ * ellipse).  The record is the lexicographic minimum of (level, row, obstacle) from (+inf, -1, -1); a comparison that is false keeps it, and a
+ * retired robot keeps its record.  It observes only.  To be called once, before the first step and after nmpc_loop_set_crowd, on a loop that
+ * records its trajectory.  NMPC_ERR_BAD_ARG with a message, nothing changed and nothing allocated, for a loop without a crowd, a loop with
+ * max_steps == 0, a call after a step, or a second call. */
+typedef struct nmpc_crowd_clearance {    /* 16 bytes */
+    double  level;
+    int32_t row, obstacle;
+} nmpc_crowd_clearance;
+#ifdef __cplusplus
+static_assert(sizeof(nmpc_crowd_clearance) == 16, "nmpc_crowd_clearance layout");
+#else
+_Static_assert(sizeof(nmpc_crowd_clearance) == 16, "nmpc_crowd_clearance layout");
+#endif
+int nmpc_loop_set_crowd_monitor(nmpc_loop *l);
+/* Synchronises, then copies the records out [B]; on a loop without the observer the initial record everywhere. */
+int nmpc_loop_crowd_clearance(nmpc_loop *l, nmpc_crowd_clearance *out);
 
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);

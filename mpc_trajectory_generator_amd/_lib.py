@@ -27,6 +27,7 @@ SYMBOLS = (
     "nmpc_loop_set_missions", "nmpc_loop_legs", "nmpc_loop_set_map_monitor", "nmpc_loop_map_clearance",
     "nmpc_loop_set_peers_grid", "nmpc_loop_peer_grid",
     "nmpc_loop_set_log", "nmpc_loop_log", "nmpc_loop_drive_summary", "nmpc_loop_step_totals",
+    "nmpc_loop_set_crowd", "nmpc_loop_crowd", "nmpc_loop_set_crowd_monitor", "nmpc_loop_crowd_clearance",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -110,6 +111,10 @@ assert DRIVE_SUMMARY_DTYPE.itemsize == 112
 STEP_TOTALS_DTYPE = np.dtype([("solved", "<i4"), ("exits", "<u4", 5), ("inner_max", "<u4"), ("inner_max_robot", "<i4"),
                               ("inner_total", "<u8"), ("solve_ms_max", "<f8")])
 assert STEP_TOTALS_DTYPE.itemsize == 48
+
+# nmpc_crowd_clearance: a robot's closest approach to any obstacle of the crowd (nmpc_loop_set_crowd_monitor)
+CROWD_CLEARANCE_DTYPE = np.dtype([("level", "<f8"), ("row", "<i4"), ("obstacle", "<i4")])
+assert CROWD_CLEARANCE_DTYPE.itemsize == 16
 
 
 def _sources():
@@ -330,6 +335,14 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_drive_summary.restype = C.c_int
     lib.nmpc_loop_step_totals.argtypes = [vp, vp, C.c_int]
     lib.nmpc_loop_step_totals.restype = C.c_int
+    lib.nmpc_loop_set_crowd.argtypes = [vp, C.c_int, dp, C.c_double, C.c_int, C.c_double]
+    lib.nmpc_loop_set_crowd.restype = C.c_int
+    lib.nmpc_loop_crowd.argtypes = [vp, dp, C.POINTER(C.c_int32)]
+    lib.nmpc_loop_crowd.restype = C.c_int
+    lib.nmpc_loop_set_crowd_monitor.argtypes = [vp]
+    lib.nmpc_loop_set_crowd_monitor.restype = C.c_int
+    lib.nmpc_loop_crowd_clearance.argtypes = [vp, vp]
+    lib.nmpc_loop_crowd_clearance.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]

@@ -118,6 +118,18 @@ __device__ __forceinline__ void wave_argmin(double &d, int &j)
     }
 }
 
+// (v, r, j) lexicographic minimum over the wave, result in every lane
+__device__ __forceinline__ void wave_argmin3(double &d, int &r, int &j)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double od = __shfl_xor(d, off);
+        const int orow = __shfl_xor(r, off);
+        const int oj = __shfl_xor(j, off);
+        if (od < d || (od == d && (orow < r || (orow == r && oj < j)))) { d = od; r = orow; j = oj; }
+    }
+}
+
 // times = numpy.linspace(t0, t0 + H * ts, H)[i]   (visibility.py:204)
 __device__ __forceinline__ double linspace_at(double t0, double ts, int H, int i)
 {
@@ -126,6 +138,35 @@ __device__ __forceinline__ double linspace_at(double t0, double ts, int H, int i
     if (i == H - 1) return stop;
     const double step = (stop - t0) / (double)(H - 1);
     return (double)i * step + t0;
+}
+
+// Field f of stage st of a scripted ellipse q [10] (AssembleArgs::dynpar) where the step computes it anew: every stage at t == 0, the
+// last s stages afterwards (visibility.py:156-166,199-216).  The assembly's carried block and the crowd's table share it.
+__device__ __forceinline__ double ellipse_fresh(const double *q, double pad, int f, int st, int t, int N, int s, double ts)
+{
+    if (f >= 2) return f == 2 ? q[5] + pad : (f == 3 ? q[6] + pad : q[7]);
+    const int H = t == 0 ? N : s, i = t == 0 ? st : st - (N - s);
+    const double t0 = t == 0 ? 0.0 : (double)(t + N - s) * ts;
+    const double tm = linspace_at(t0, ts, H, i);
+    double sn, cs;
+    sincos_cw(q[4] * tm, sn, cs);
+    const double w = fabs(sn);
+    double v = w * q[f] + (1.0 - w) * q[2 + f];
+    if (q[8] != 0.0) {
+        // sinusoidal law (visibility.py:177-196): offset across the p1 -> p2 line, amplitude 1.5
+        const double p3x = w * q[0] + (1.0 - w) * q[2], p3y = w * q[1] + (1.0 - w) * q[3];
+        double s10, c10, sa_, ca_;
+        sincos_cw((10.0 * q[4]) * tm, s10, c10);
+        sincos_cw(q[9], sa_, ca_);
+        const double add = 1.5 * c10;
+        const double dx = p3x - q[0], dy = p3y - q[1];
+        const double rx = ca_ * dx - sa_ * dy;
+        double ry = sa_ * dx + ca_ * dy;
+        ry = ry + add;
+        const double qx = ca_ * rx - (-sa_) * ry, qy = (-sa_) * rx + ca_ * ry;      // rotate back by -angle
+        v = f == 0 ? qx + q[0] : qy + q[1];
+    }
+    return v;
 }
 
 // one wave per robot: fills p[b] and the rotated dynamic block
@@ -179,32 +220,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopView L, Loop
             double v;
             const bool fresh = k < L.K && (t == 0 || st >= N - s);
             if (fresh) {
-                const double *q = g.dynpar + ((size_t)b * L.K + k) * 10;
-                if (f < 2) {
-                    const int H = t == 0 ? N : s, i = t == 0 ? st : st - (N - s);
-                    const double t0 = t == 0 ? 0.0 : (double)(t + N - s) * L.ts;
-                    const double tm = linspace_at(t0, L.ts, H, i);
-                    double sn, cs;
-                    sincos_cw(q[4] * tm, sn, cs);
-                    const double w = fabs(sn);
-                    v = w * q[f] + (1.0 - w) * q[2 + f];
-                    if (q[8] != 0.0) {
-                        // sinusoidal law (visibility.py:177-196): offset across the p1 -> p2 line, amplitude 1.5
-                        const double p3x = w * q[0] + (1.0 - w) * q[2], p3y = w * q[1] + (1.0 - w) * q[3];
-                        double s10, c10, sa_, ca_;
-                        sincos_cw((10.0 * q[4]) * tm, s10, c10);
-                        sincos_cw(q[9], sa_, ca_);
-                        const double add = 1.5 * c10;
-                        const double dx = p3x - q[0], dy = p3y - q[1];
-                        const double rx = ca_ * dx - sa_ * dy;
-                        double ry = sa_ * dx + ca_ * dy;
-                        ry = ry + add;
-                        const double qx = ca_ * rx - (-sa_) * ry, qy = (-sa_) * rx + ca_ * ry;      // rotate back by -angle
-                        v = f == 0 ? qx + q[0] : qy + q[1];
-                    }
-                } else {
-                    v = f == 2 ? q[5] + pad : (f == 3 ? q[6] + pad : q[7]);
-                }
+                v = ellipse_fresh(g.dynpar + ((size_t)b * L.K + k) * 10, pad, f, st, t, N, s, L.ts);
             } else if (t == 0) {
                 v = din[e];                                    // padding block as initialised
             } else {
@@ -312,7 +328,8 @@ __global__ void nmpc_loop_advance_kernel(LoopView L, LoopStep stp, AssembleArgs 
 
 // ---- peers: the robots of a group see each other (nmpc_loop_set_peers; the rule is DESIGN.md section 5.9) ----
 // Two kernels between the assembly and the solve: every robot's predicted poses over the horizon, then per robot the M closest
-// peers of its group written into the ellipse slots [K, K + M) of p.  The carried block (dyn_in / dyn_out) never sees them.
+// peers of its group written into the ellipse slots [first, first + M) of p, first = K + the crowd's slots.  The carried block
+// (dyn_in / dyn_out) never sees them.
 struct GroupLists {          // the groups 0 .. B - 1 (most of them empty)
     const int *group_of;      // [B]
     const int *goff;          // [groups + 1]: a group's members are gmem[goff[g] .. goff[g + 1])
@@ -320,22 +337,22 @@ struct GroupLists {          // the groups 0 .. B - 1 (most of them empty)
 };
 
 struct PeerArgs {
-    int M;
+    int M, first;             // the peers' ellipse slots: [first, first + M)
     double rx, ry, range2;
-    double *pred;             // [B][N][3]
+    double *pred;             // [B][N][3]: the loop's predicted poses (nmpc_loop_predict_kernel)
     GroupLists grp;
 };
 
 // one thread per robot: pred[b][k] = the pose after k + 1 Euler steps (the expression of nmpc_loop_advance_kernel) under the
 // previous plan shifted by the s controls already applied, its last control held beyond the plan's end
 // (a retired robot's row is not computed here: nmpc_loop_compact_kernel parked it)
-__global__ void nmpc_loop_predict_kernel(LoopView L, LoopStep stp, PeerArgs a)
+__global__ void nmpc_loop_predict_kernel(LoopView L, LoopStep stp, double *pred)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= stp.nact) return;
     const int b = L.robot(i);
     const double *u = L.U + (size_t)b * L.n_u;      // the previous plan
-    double *out = a.pred + (size_t)b * L.N * 3;
+    double *out = pred + (size_t)b * L.N * 3;
     double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
     for (int k = 0; k < L.N; ++k) {
         const int c = L.s + k < L.N ? L.s + k : L.N - 1;
@@ -349,15 +366,16 @@ __global__ void nmpc_loop_predict_kernel(LoopView L, LoopStep stp, PeerArgs a)
     }
 }
 
-// What the two peers kernels share: a lane's list of its best NDYN_MAX candidates, sorted by (D, j) and held in registers (static
-// indices); no candidate = (inf, LOOP_NONE), behind every real one
+// What the peers kernels and the crowd's share: a lane's list of its best NDYN_MAX candidates, sorted by (D, j) and held in registers
+// (static indices); no candidate = (inf, LOOP_NONE), behind every real one
 
-// D(b, j) = min_k |pred[b][k] - pred[j][k]|^2, b's positions in `own` (LDS), j's row of pred in `pj`
-__device__ __forceinline__ double peer_closeness(const double *own, const double *pj, int N)
+// D(b, j) = min_k |pred[b][k] - pj[k]|^2, b's positions in `own` (LDS), j's positions stage by stage in `pj`, `stride` doubles apart
+// (3: a row of pred, 5: a row of the crowd's table)
+__device__ __forceinline__ double peer_closeness(const double *own, const double *pj, int N, int stride)
 {
     double D = __builtin_inf();
     for (int k = 0; k < N; ++k) {
-        const double dx = own[2 * k] - pj[3 * k], dy = own[2 * k + 1] - pj[3 * k + 1];
+        const double dx = own[2 * k] - pj[stride * k], dy = own[2 * k + 1] - pj[stride * k + 1];
         const double d = dx * dx + dy * dy;
         if (d < D) D = d;
     }
@@ -377,14 +395,17 @@ __device__ __forceinline__ void peer_keep(double (&bd)[NDYN_MAX], int (&bj)[NDYN
     }
 }
 
-// M rounds: the wave's (D, j) minimum over the lanes' heads, written over ellipse slot K + m of p[b]; the lane that held it moves on
-// to its next
-__device__ __forceinline__ void peer_overlay(const LoopView &L, const PeerArgs &a, int b, int lane, double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX])
+// M rounds: the wave's (D, j) minimum over the lanes' heads, written over ellipse slot first + m of p[b]; the lane that held it moves
+// on to its next.  entry(j, e) = entry e of candidate j's ellipse row [N][5]; seen [M] (NULL: nobody asks) gets j, or -1 where no
+// candidate was left
+template <class Entry>
+__device__ __forceinline__ void peer_overlay(const LoopView &L, int b, int lane, double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX], int first, int M,
+                                             int *seen, Entry entry)
 {
-    const int N = L.N;
     double *pd = L.P + (size_t)b * L.n_p + L.p_dyn();
-    const int per = 5 * N;
-    for (int m = 0; m < a.M; ++m) {
+    const int per = 5 * L.N;
+    int m = 0;
+    for (; m < M; ++m) {
         double d = bd[0];
         int j = bj[0];
         wave_argmin(d, j);
@@ -394,13 +415,22 @@ __device__ __forceinline__ void peer_overlay(const LoopView &L, const PeerArgs &
             for (int q = 0; q + 1 < NDYN_MAX; ++q) { bd[q] = bd[q + 1]; bj[q] = bj[q + 1]; }
             bd[NDYN_MAX - 1] = __builtin_inf(); bj[NDYN_MAX - 1] = LOOP_NONE;
         }
-        const double *pj = a.pred + (size_t)j * N * 3;
-        double *slot = pd + (size_t)(L.K + m) * per;
-        for (int e = lane; e < per; e += 64) {
-            const int st = e / 5, f = e - st * 5;
-            slot[e] = f == 0 ? pj[3 * st] : (f == 1 ? pj[3 * st + 1] : (f == 2 ? a.rx : (f == 3 ? a.ry : pj[3 * st + 2])));
-        }
+        double *slot = pd + (size_t)(first + m) * per;
+        for (int e = lane; e < per; e += 64) slot[e] = entry(j, e);
+        if (seen && lane == 0) seen[m] = j;
     }
+    if (seen) for (int q = m + lane; q < M; q += 64) seen[q] = -1;
+}
+
+// a peer's ellipse row: its predicted poses as (x, y, rx, ry, theta)
+__device__ __forceinline__ void peers_overlay(const LoopView &L, const PeerArgs &a, int b, int lane, double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX])
+{
+    const int N = L.N;
+    peer_overlay(L, b, lane, bd, bj, a.first, a.M, nullptr, [&](int j, int e) {
+        const double *pj = a.pred + (size_t)j * N * 3;
+        const int st = e / 5, f = e - st * 5;
+        return f == 0 ? pj[3 * st] : (f == 1 ? pj[3 * st + 1] : (f == 2 ? a.rx : (f == 3 ? a.ry : pj[3 * st + 2])));
+    });
 }
 
 // one wave per robot: D(b, j) = min_k |pred[b][k] - pred[j][k]|^2 over the members j != b of b's group (lanes stride over them),
@@ -424,10 +454,10 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(LoopView L, PeerArg
     for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
     for (int i = lo + lane; i < hi; i += 64) {
         const int j = a.grp.gmem[i];
-        const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N);
+        const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N, 3);
         if (j != b && D < a.range2) peer_keep(bd, bj, D, j);
     }
-    peer_overlay(L, a, b, lane, bd, bj);
+    peers_overlay(L, a, b, lane, bd, bj);
 }
 
 // ---- peers through a grid (nmpc_loop_set_peers_grid; the rule, and why it misses nobody: DESIGN.md section 5.9) ----
@@ -620,13 +650,103 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_grid_kernel(LoopView L, Pe
             for (int i = i0 + lane; i < i1; i += 64) {
                 const int j = g.cell_mem[i];
                 if (j != b && a.grp.group_of[j] == grp) {
-                    const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N);
+                    const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N, 3);
                     if (D < a.range2) peer_keep(bd, bj, D, j);
                 }
             }
         }
     }
-    peer_overlay(L, a, b, lane, bd, bj);
+    peers_overlay(L, a, b, lane, bd, bj);
+}
+
+// ---- crowd: D moving obstacles of the world, shared by the fleet (nmpc_loop_set_crowd; the rule is DESIGN.md section 5.9) ----
+// One table of every obstacle's ellipses over the horizon, advanced once per step whoever is active; between the assembly and the solve
+// each active robot's M closest obstacles are written into the ellipse slots [K, K + M) of p.  The carried block never sees them.  An
+// optional observer keeps each robot's closest approach to any obstacle of the crowd.
+struct CrowdArgs {
+    int D, M;
+    double pad, range2;
+    const double *obst;       // [D][10]: the fields of AssembleArgs::dynpar
+    double *tab[2];           // [D][N][5]: read and written in turn with LoopStep::cur, as AssembleArgs::dyn
+    const double *pred;       // [B][N][3]: the loop's predicted poses (nmpc_loop_predict_kernel)
+    int *seen;                // [B][M]: the obstacle in slot K + m of p[b], -1 = none
+    nmpc_crowd_clearance *rec;    // [B], NULL without the observer
+};
+
+// One thread per entry (d, stage, field) of the table: what the assembly does to a scripted slot, obstacle by obstacle.  A stage that is
+// not fresh takes stage st + s of the SAME obstacle (st + s < N): the assembly's flat rotation carries a neighbour's stages only into
+// stages that a scripted obstacle then refreshes.
+__global__ __launch_bounds__(256) void nmpc_loop_crowd_advance_kernel(LoopView L, LoopStep stp, CrowdArgs c)
+{
+    const int per = L.N * 5, tot = c.D * per;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= tot) return;
+    const int d = e / per, r = e - d * per, st = r / 5, f = r - st * 5;
+    const bool fresh = stp.t == 0 || st >= L.N - L.s;
+    c.tab[stp.cur ^ 1][e] = fresh ? ellipse_fresh(c.obst + (size_t)d * 10, c.pad, f, st, stp.t, L.N, L.s, L.ts) : c.tab[stp.cur][e + 5 * L.s];
+}
+
+// one wave per active robot: C(b, d) = min_k |pred[b][k] - tab[d][k]|^2 over the table as this step wrote it (lanes stride over d, each
+// reading its obstacle's row through the cache), the first M of the candidates C < range^2 in (C, d) order, each obstacle's row copied
+// over one ellipse slot of p[b].  No loop's bounds depend on the table's values.
+__global__ __launch_bounds__(64) void nmpc_loop_crowd_kernel(LoopView L, LoopStep stp, CrowdArgs c)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int N = L.N, per = 5 * N;
+    const double *tab = c.tab[stp.cur ^ 1];
+    for (int k = lane; k < N; k += 64) {
+        own[2 * k] = c.pred[((size_t)b * N + k) * 3];
+        own[2 * k + 1] = c.pred[((size_t)b * N + k) * 3 + 1];
+    }
+    __syncthreads();
+    double bd[NDYN_MAX];
+    int bj[NDYN_MAX];
+#pragma unroll
+    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
+    for (int d = lane; d < c.D; d += 64) {
+        const double C = peer_closeness(own, tab + (size_t)d * per, N, 5);
+        if (C < c.range2) peer_keep(bd, bj, C, d);
+    }
+    peer_overlay(L, b, lane, bd, bj, L.K, c.M, c.seen + (size_t)b * c.M, [&](int d, int e) { return tab[(size_t)d * per + e]; });
+}
+
+// One wave per robot the step drove, after the advance: the robot's s new poses go to LDS; row by row, lanes stride over ALL D obstacles,
+// the pose of row traj_row + i against entry i of the obstacle's row of this step's table (the pairing of nmpc_loop_monitor_kernel's
+// scripted ellipses, and its level).  A lane's rows and obstacles ascend, so among equal values its first stays; one wave reduction, and
+// lane 0 folds the lexicographic minimum of (level, row, d) into the record.  It observes: the record is the only thing it writes.
+__global__ __launch_bounds__(64) void nmpc_loop_crowd_monitor_kernel(LoopView L, LoopStep stp, CrowdArgs c)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int s = L.s, N = L.N, row0 = stp.traj_row;
+    const double *tab = c.tab[stp.cur ^ 1];
+    for (int i = lane; i < s; i += 64) {
+        const double *row = L.row(row0 + i, b);
+        own[2 * i] = row[0];
+        own[2 * i + 1] = row[1];
+    }
+    __syncthreads();
+    double bv = __builtin_inf();
+    int br = LOOP_NONE, bo = LOOP_NONE;
+    for (int i = 0; i < s; ++i) {
+        const double x = own[2 * i], y = own[2 * i + 1];
+        for (int d = lane; d < c.D; d += 64) {
+            const double *q = tab + ((size_t)d * N + i) * 5;
+            const double dx = x - q[0], dy = y - q[1];
+            double sn, cs;
+            sincos_cw(q[4], sn, cs);
+            const double al = dx * cs + dy * sn, ac = dx * sn - dy * cs;
+            const double v = (al * al) / (q[2] * q[2]) + (ac * ac) / (q[3] * q[3]);
+            if (v < bv) { bv = v; br = row0 + i; bo = d; }
+        }
+    }
+    wave_argmin3(bv, br, bo);
+    if (lane == 0) {
+        nmpc_crowd_clearance r = c.rec[b];
+        if (bv < r.level || (bv == r.level && (br < r.row || (br == r.row && bo < r.obstacle)))) { r.level = bv; r.row = br; r.obstacle = bo; }
+        c.rec[b] = r;
+    }
 }
 
 // ---- retirement: robots that reached their goal leave the loop (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9) ----
@@ -704,18 +824,6 @@ struct MonitorArgs {
     GroupLists grp;           // the monitor's own groups
     nmpc_clearance *rec;      // [B]
 };
-
-// (v, r, j) lexicographic minimum over the wave, result in every lane
-__device__ __forceinline__ void wave_argmin3(double &d, int &r, int &j)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double od = __shfl_xor(d, off);
-        const int orow = __shfl_xor(r, off);
-        const int oj = __shfl_xor(j, off);
-        if (od < d || (od == d && (orow < r || (orow == r && oj < j)))) { d = od; r = orow; j = oj; }
-    }
-}
 
 // One wave per robot the step drove, after the advance: the robot's s new poses go to LDS; lanes stride over the (pose, circle slot)
 // and (pose, scripted ellipse) pairs of its p, then over the members of its group, each lane walking the s rows of its member (a

@@ -3,13 +3,14 @@
 // after the handle, fail, HIP_TRY and solve_launch.
 //
 // A loop is its view (nmpc::LoopView: the shape, the per-robot arrays and the active list, the same for every kernel), its base
-// (assemble -> solve -> advance) and up to six stages, each a sub-struct with its device buffers and the argument block of its own
+// (assemble -> solve -> advance) and up to seven stages, each a sub-struct with its device buffers and the argument block of its own
 // kernels.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop as it
 // was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the configuration
 // final.  The loop keeps ONE counter, `steps`: nmpc_loop_step derives everything that changes per step from it and the active count
 // (nmpc::LoopStep, on its stack), hands view, step and a stage's block to each kernel, and writes to no argument block.  It is ONE
-// sequence of kernels in which a stage adds its own; the pointers that cross stages (the peers' pred for the compaction,
-// retirement's retired_at for the monitor, the missions' leg for the log) are passed at the launch, from the stage that owns them.
+// sequence of kernels in which a stage adds its own; the pointers that cross stages (the predicted poses, which peers and crowd share
+// and the loop owns, for the compaction; retirement's retired_at for the monitor; the missions' leg for the log) are passed at the
+// launch, from the stage that owns them.
 #pragma once
 
 // member lists of the groups 0 .. B - 1 (most of them empty), each group's robots in ascending index
@@ -35,15 +36,24 @@ struct LoopGroups {
 };
 struct LoopPeers {           // nmpc_loop_set_peers: two more kernels per step, between the assembly and the solve
     nmpc::PeerArgs a{};
-    DevBuf<double> pred;     // [B][N][3]
     LoopGroups groups;
     // nmpc_loop_set_peers_grid: the candidates come from a grid, three kernels in the place of the all-pairs one
     nmpc::PeerGridArgs g{};
     DevBuf<double> box;              // [B][4]
     DevBuf<nmpc_peer_grid> hdr;      // [1]
     DevBuf<int> cell_of, cell_off, cell_cur, cell_mem;      // [B], [CAP * CAP + 1], [CAP * CAP], [B]
-    bool made() const { return pred != nullptr; }
+    bool made() const { return groups.group_of != nullptr; }
     bool grid() const { return box != nullptr; }
+};
+// nmpc_loop_set_crowd: one kernel per step that advances the world's table, one between the assembly and the solve; with the observer
+// (nmpc_loop_set_crowd_monitor) one more after the advance
+struct LoopCrowd {
+    nmpc::CrowdArgs a{};
+    DevBuf<double> obst, tab[2];     // [D][10], [D][N][5] twice
+    DevBuf<int> seen;                // [B][M]
+    DevBuf<nmpc_crowd_clearance> rec;    // [B]: the observer's
+    bool made() const { return obst != nullptr; }
+    bool watched() const { return rec != nullptr; }
 };
 // nmpc_loop_set_retire: robots at their goal leave the loop.  A step runs over the active list, the solve over gathered rows, and
 // the host learns the list's length one step late (nmpc_loop.h)
@@ -102,7 +112,9 @@ struct nmpc_loop {
     DevBuf<int> d_idx;
     DevBuf<unsigned char> d_done;
     DevBuf<nmpc_status> d_st;
+    DevBuf<double> d_pred;       // [B][N][3]: every robot's predicted poses, made by the first of the peers and crowd setters
     LoopPeers peers;
+    LoopCrowd crowd;
     LoopRetire retire;
     LoopMonitor monitor;
     LoopMap map;
@@ -234,17 +246,19 @@ static int loop_set_peers(nmpc_loop *l, const char *fn, const int32_t *group_of,
     const int B = v.B;
     const std::string who = std::string(fn) + ": ";
     if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, (who + "M < 1").c_str());
-    if (v.K + M > v.ndyn) return fail(h, NMPC_ERR_BAD_ARG, (who + "K + M > Ndynobs, no free ellipse slot").c_str());
+    const int Mc = l->crowd.a.M;       // the crowd's slots come first (0 without a crowd)
+    if (v.K + Mc + M > v.ndyn) return fail(h, NMPC_ERR_BAD_ARG, (who + (Mc ? "K + the crowd's M + M > Ndynobs, no free ellipse slot" : "K + M > Ndynobs, no free ellipse slot")).c_str());
     for (const double v : {rx, ry, range})
         if (!(v > 0.0) || v > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (who + "rx, ry and range must be finite and positive").c_str());
     if (cell && (!(*cell > 0.0) || *cell > DBL_MAX)) return fail(h, NMPC_ERR_BAD_ARG, (who + "cell must be finite and positive").c_str());
     if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= B) return fail(h, NMPC_ERR_BAD_ARG, (who + "group_of out of range").c_str());
     LoopPeers st;
-    HIP_TRY(h, st.pred.alloc((size_t)B * v.N * 3));
+    DevBuf<double> pred;           // the loop's, unless the crowd has made it
+    if (!l->d_pred) HIP_TRY(h, pred.alloc((size_t)B * v.N * 3));
     HIP_TRY(h, st.groups.upload(group_of, B));
     nmpc::PeerArgs &p = st.a;
-    p.M = M; p.rx = rx; p.ry = ry; p.range2 = range * range;
-    p.pred = st.pred; p.grp = st.groups.lists();
+    p.M = M; p.first = v.K + Mc; p.rx = rx; p.ry = ry; p.range2 = range * range;
+    p.pred = l->d_pred.p ? l->d_pred.p : pred.p; p.grp = st.groups.lists();
     if (cell) {
         constexpr size_t cells = (size_t)nmpc::PEER_GRID_CAP * nmpc::PEER_GRID_CAP;
         HIP_TRY(h, st.box.alloc(4 * (size_t)B));
@@ -259,6 +273,58 @@ static int loop_set_peers(nmpc_loop *l, const char *fn, const int32_t *group_of,
         g.cell_of = st.cell_of; g.cell_off = st.cell_off; g.cell_cur = st.cell_cur; g.cell_mem = st.cell_mem;
     }
     l->peers = std::move(st);
+    if (pred) l->d_pred = std::move(pred);
+    return NMPC_OK;
+}
+
+static constexpr int CROWD_MAX = 16384;
+static const nmpc_crowd_clearance CROWD_CLEARANCE_NONE = {__builtin_inf(), -1, -1};
+
+int nmpc_loop_set_crowd(nmpc_loop *l, int D, const double *obst, double pad, int M, double range)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_crowd", l->crowd.made(), "the loop has its crowd already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopView &v = l->v;
+    const size_t B = (size_t)v.B;
+    if (D < 1 || D > CROWD_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: D outside 1 .. 16384");
+    if (!obst) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: obst is NULL");
+    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: M < 1");
+    const int Mp = l->peers.made() ? l->peers.a.M : 0;
+    if (v.K + M + Mp > v.ndyn)
+        return fail(h, NMPC_ERR_BAD_ARG, Mp ? "nmpc_loop_set_crowd: K + M + the peers' M > Ndynobs, no free ellipse slot" : "nmpc_loop_set_crowd: K + M > Ndynobs, no free ellipse slot");
+    if (!(pad >= -DBL_MAX && pad <= DBL_MAX)) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: pad must be finite");
+    if (!(range > 0.0) || range > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: range must be finite and positive");
+    LoopCrowd st;
+    DevBuf<double> pred;           // the loop's, unless the peers have made it
+    if (!l->d_pred) HIP_TRY(h, pred.alloc(B * v.N * 3));
+    const size_t ntab = (size_t)D * v.N * 5;
+    HIP_TRY(h, st.obst.upload(obst, (size_t)D * 10));
+    HIP_TRY(h, st.tab[0].alloc_fill(ntab, 0));
+    HIP_TRY(h, st.tab[1].alloc_fill(ntab, 0));
+    HIP_TRY(h, st.seen.alloc_fill(B * M, 0xFF));                   // seen = -1
+    nmpc::CrowdArgs &c = st.a;
+    c.D = D; c.M = M; c.pad = pad; c.range2 = range * range;
+    c.obst = st.obst; c.tab[0] = st.tab[0]; c.tab[1] = st.tab[1];
+    c.pred = l->d_pred.p ? l->d_pred.p : pred.p; c.seen = st.seen; c.rec = nullptr;
+    l->crowd = std::move(st);
+    if (pred) l->d_pred = std::move(pred);
+    if (l->peers.made()) l->peers.a.first = v.K + M;       // the peers' slots follow the crowd's
+    return NMPC_OK;
+}
+
+int nmpc_loop_set_crowd_monitor(nmpc_loop *l)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_crowd_monitor", l->crowd.watched(), "the loop has its crowd observer already")) return rc;
+    nmpc_handle *h = l->h;
+    if (!l->crowd.made()) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd_monitor: the loop has no crowd (nmpc_loop_set_crowd first)");
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd_monitor: the loop records no trajectory (max_steps == 0)");
+    DevBuf<nmpc_crowd_clearance> rec;
+    const std::vector<nmpc_crowd_clearance> none(l->v.B, CROWD_CLEARANCE_NONE);
+    HIP_TRY(h, rec.upload(none.data(), none.size()));
+    l->crowd.rec = std::move(rec);
+    l->crowd.a.rec = l->crowd.rec;
     return NMPC_OK;
 }
 
@@ -447,11 +513,16 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         if (n < 0 || n > v.B) return fail(h, NMPC_ERR_HIP, "nmpc_loop_step: active count out of range");
     }
     const nmpc::LoopStep stp = nmpc::LoopStep::after(l->steps, v.s, n);
+    const LoopCrowd &cr = l->crowd;
+    // the crowd's table belongs to the world: it advances with nobody active too
+    if (cr.made())
+        hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_advance_kernel, dim3((cr.a.D * v.N * 5 + 255) / 256), dim3(256), 0, s, v, stp, cr.a);
     if (n > 0) {
         hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, v, stp, l->a);
+        if (l->d_pred) hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->d_pred.p);
+        if (cr.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a);
         if (l->peers.made()) {
             const nmpc::PeerArgs &p = l->peers.a;
-            hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, p);
             if (l->peers.grid()) {     // the boxes and the grid over all B: a retired robot stays filed
                 const nmpc::PeerGridArgs &g = l->peers.g;
                 hipLaunchKernelGGL(nmpc::nmpc_loop_peer_box_kernel, dim3((v.B + 255) / 256), dim3(256), 0, s, v, p, g);
@@ -479,6 +550,7 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         if (l->monitor.made())
             hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, l->monitor.a, r.retired_at);
         if (l->map.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, v, stp, l->map.a);
+        if (cr.watched()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a);
         // the log sees the leg and the p the solve belonged to: the dispatch comes after (leg: the missions', NULL without them)
         if (l->log.made()) {
             hipLaunchKernelGGL(nmpc::nmpc_loop_log_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->log.a, l->missions.leg.p);
@@ -489,8 +561,8 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         hipLaunchKernelGGL(nmpc::nmpc_loop_log_totals_kernel, dim3(1), dim3(1024), 0, s, v, stp, l->log.a);
     }
     // (with nobody active the step still counts: the clock advances and the trajectory rows repeat).  The compaction parks a retired
-    // robot's predictions for the peers (NULL without them)
-    if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, v, stp, r.a, l->peers.pred);
+    // robot's predictions for the peers (NULL without them: the crowd reads the active robots' only)
+    if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, v, stp, r.a, l->peers.made() ? l->d_pred.p : nullptr);
     HIP_TRY(h, hipGetLastError());
     if (retiring) {
         HIP_TRY(h, hipMemcpyAsync(r.h_nact.p, r.nact.p, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -578,6 +650,31 @@ int nmpc_loop_peer_grid(nmpc_loop *l, nmpc_peer_grid *out, int32_t *cell_of)
     if (l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_peer_grid: before the loop's first step");
     HIP_TRY(l->h, l->peers.hdr.read(out, 1));
     HIP_TRY(l->h, l->peers.cell_of.read(cell_of, l->v.B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_crowd(nmpc_loop *l, double *table, int32_t *seen)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    const LoopCrowd &c = l->crowd;
+    if (!c.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_crowd: the loop has no crowd (nmpc_loop_set_crowd)");
+    if (l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_crowd: before the loop's first step");
+    // step k (k = 0, 1, ...) wrote buffer (k & 1) ^ 1
+    HIP_TRY(l->h, c.tab[((l->steps - 1) & 1) ^ 1].read(table, (size_t)c.a.D * l->v.N * 5));
+    HIP_TRY(l->h, c.seen.read(seen, (size_t)l->v.B * c.a.M));
+    return NMPC_OK;
+}
+
+int nmpc_loop_crowd_clearance(nmpc_loop *l, nmpc_crowd_clearance *out)
+{
+    if (!out) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_settle(l)) return rc;
+    const int B = l->v.B;
+    if (!l->crowd.watched()) {
+        for (int b = 0; b < B; ++b) out[b] = CROWD_CLEARANCE_NONE;
+        return NMPC_OK;
+    }
+    HIP_TRY(l->h, l->crowd.rec.read(out, B));
     return NMPC_OK;
 }
 

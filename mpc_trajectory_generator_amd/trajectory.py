@@ -234,6 +234,38 @@ def _atan2(y, x):
     return np.array([math.atan2(a, b) for a, b in zip(y.ravel(), x.ravel())], dtype=np.float64).reshape(y.shape)
 
 
+def _predict_ellipses(cfg, sincos, obs, sinus, t0, horizon):
+    """The closed-form obstacle predictor (visibility.py:156-166,199-216) for any number of obstacles at once: ``obs`` =
+    ``(p1 [..., 2], p2 [..., 2], freq [...], rx [...], ry [...], angle [...])``, ``sinus`` [...] bool = who follows the sinusoidal law
+    (:183-196, amplitude 1.5) -> [..., horizon, 5] = (x, y, rx + pad, ry + pad, angle) at ``linspace(t0, t0 + horizon ts, horizon)``."""
+    p1, p2, freq, rx, ry, ang = obs
+    times = np.linspace(t0, t0 + horizon * cfg.ts, horizon)                       # (:204)
+    s = np.abs(sincos(freq[..., None] * times)[0])                                 # [..., H]
+    pos = s[..., None] * p1[..., None, :] + (1 - s[..., None]) * p2[..., None, :]
+    if sinus.any():
+        a, b, f, at = p1[sinus], p2[sinus], freq[sinus], pos[sinus]                # [n, 2], [n, 2], [n], [n, H, 2]
+        ang_d = _atan2(b[:, 1] - a[:, 1], b[:, 0] - a[:, 0])[:, None]              # [n, 1]
+        add = 1.5 * sincos((10 * f[:, None]) * times[None, :])[1]                  # [n, H]
+        sa, ca = sincos(ang_d)
+        dx, dy = at[:, :, 0] - a[:, None, 0], at[:, :, 1] - a[:, None, 1]
+        ex = ca * dx - sa * dy
+        ey = sa * dx + ca * dy
+        ey = ey + add
+        sm, cm = sincos(-ang_d)
+        qx = cm * (ex - 0.0) - sm * (ey - 0.0)
+        qy = sm * (ex - 0.0) + cm * (ey - 0.0)
+        at[:, :, 0] = qx + a[:, None, 0]
+        at[:, :, 1] = qy + a[:, None, 1]
+        pos[sinus] = at
+    pad = cfg.vehicle_width / 2 + cfg.vehicle_margin
+    out = np.empty(pos.shape[:-1] + (5,))
+    out[..., 0:2] = pos
+    out[..., 2] = (rx + pad)[..., None]
+    out[..., 3] = (ry + pad)[..., None]
+    out[..., 4] = ang[..., None]
+    return out
+
+
 class _RouteTable:
     """What a step reads of R routes, side by side (the device's ``LoopRoute`` table, csrc/nmpc_loop_host.h): row r = route r, padded to
     the longest route's, with each route's own lengths ``n``, ``nv``, ``nb`` [R]; ``end`` [R, 3], ``base`` (speed) and ``radius`` [R].
@@ -306,32 +338,10 @@ class VectorizedRecedingHorizon(_HostLoop):
 
     # dynamic-obstacle prediction for all robots: visibility.py:156-166,199-216 (linear law)
     def _predict(self, t0, horizon):
-        cfg = self.cfg
-        p1, p2, freq, rx, ry, ang = self.dyn_obs
-        times = np.linspace(t0, t0 + horizon * cfg.ts, horizon)                       # (:204)
-        s = np.abs(self.sincos(freq[:, :, None] * times[None, None, :])[0])        # [B, K, H]
-        pos = s[..., None] * p1[:, :, None, :] + (1 - s[..., None]) * p2[:, :, None, :]
-        if self.sinus_object and pos.shape[1] > 2:                                   # (:183-196), amplitude 1.5
-            k = 2
-            ang_d = _atan2(p2[:, k, 1] - p1[:, k, 1], p2[:, k, 0] - p1[:, k, 0])[:, None]          # [B, 1]
-            add = 1.5 * self.sincos((10 * freq[:, k, None]) * times[None, :])[1]                      # [B, H]
-            sa, ca = self.sincos(ang_d)
-            dx, dy = pos[:, k, :, 0] - p1[:, k, None, 0], pos[:, k, :, 1] - p1[:, k, None, 1]
-            ex = ca * dx - sa * dy
-            ey = sa * dx + ca * dy
-            ey = ey + add
-            sm, cm = self.sincos(-ang_d)
-            qx = cm * (ex - 0.0) - sm * (ey - 0.0)
-            qy = sm * (ex - 0.0) + cm * (ey - 0.0)
-            pos[:, k, :, 0] = qx + p1[:, k, None, 0]
-            pos[:, k, :, 1] = qy + p1[:, k, None, 1]
-        pad = cfg.vehicle_width / 2 + cfg.vehicle_margin
-        out = np.empty(pos.shape[:3] + (5,))
-        out[..., 0:2] = pos
-        out[..., 2] = (rx + pad)[:, :, None]
-        out[..., 3] = (ry + pad)[:, :, None]
-        out[..., 4] = ang[:, :, None]
-        return out
+        sinus = np.zeros(self.dyn_obs[2].shape, dtype=bool)
+        if self.sinus_object and sinus.shape[1] > 2:
+            sinus[:, 2] = True
+        return _predict_ellipses(self.cfg, self.sincos, self.dyn_obs, sinus, t0, horizon)
 
     def assemble(self, active=None):
         """-> P [B, n_p].  ``active`` [B] bool (default: everybody): the other robots keep everything they carry (reference sample,
@@ -463,6 +473,46 @@ class Peers:
         if self.cell is not None and not (math.isfinite(self.cell) and self.cell > 0):
             raise ValueError("peers: cell must be finite and positive")
         return _checked_groups("peers", self.group_of, B)
+
+
+CROWD_MAX = 16384            # D of a crowd at the most (nmpc_loop_set_crowd)
+
+
+@dataclasses.dataclass(frozen=True)
+class Crowd:
+    """D moving obstacles that belong to the world and are shared by the whole fleet, for
+    ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon`` alike: one table of every obstacle's ellipses over the horizon is advanced
+    once per step, and every step the ``slots`` obstacles that come closest to a robot's predicted positions, closer than ``range``,
+    take ellipse slots K .. K + slots - 1 of its parameter vector (K = its scripted obstacles; peers follow from K + slots on).
+    ``obstacles`` = ``(p1 [D, 2], p2 [D, 2], freq [D], rx [D], ry [D], angle [D])`` as one robot's ``dyn_obs``; ``sinus`` [D] bool =
+    who follows the sinusoidal law (``None``: nobody).  The values are not checked: an obstacle with a NaN is never chosen.
+    ``watch=True`` (the device needs ``max_steps`` > 0): ``crowd_clearance`` [B] keeps every robot's closest approach to ANY obstacle
+    of the crowd, chosen or not (a ``_lib.CROWD_CLEARANCE_DTYPE`` array).  It observes only."""
+    obstacles: object
+    slots: int
+    range: float
+    sinus: object = None
+    watch: bool = False
+
+    def checked(self, B: int, K: int, Ndynobs: int, Mp: int = 0):
+        """-> (obstacles as six contiguous float64 arrays, sinus [D] bool); ValueError for what ``nmpc_loop_set_crowd`` refuses
+        (``Mp``: the slots of the loop's peers)."""
+        if len(self.obstacles) != 6:
+            raise ValueError("crowd: obstacles = (p1, p2, freq, rx, ry, angle)")
+        p1, p2, freq, rx, ry, ang = (np.ascontiguousarray(a, dtype=np.float64) for a in self.obstacles)
+        D = len(freq)
+        if D < 1 or D > CROWD_MAX:
+            raise ValueError(f"crowd: {D} obstacles, 1 to {CROWD_MAX} are taken")
+        if p1.shape != (D, 2) or p2.shape != (D, 2) or any(a.shape != (D,) for a in (freq, rx, ry, ang)):
+            raise ValueError("crowd: obstacles of shapes other than [D, 2], [D, 2], [D], [D], [D], [D]")
+        if self.slots < 1 or K + self.slots + Mp > Ndynobs:
+            raise ValueError(f"crowd: slots = {self.slots} with {K} scripted obstacles, {Mp} peer slots and Ndynobs = {Ndynobs}")
+        if not (math.isfinite(self.range) and self.range > 0):
+            raise ValueError("crowd: range must be finite and positive")
+        sinus = np.zeros(D, dtype=bool) if self.sinus is None else np.ascontiguousarray(self.sinus, dtype=bool)
+        if sinus.shape != (D,):
+            raise ValueError("crowd: sinus of a shape other than [D]")
+        return (p1, p2, freq, rx, ry, ang), sinus
 
 
 PEER_GRID_CAP = 128          # cells per axis at the most (csrc/nmpc_loop.h)
@@ -607,6 +657,14 @@ def no_clearance(B: int):
     rec = np.empty(B, dtype=_lib.CLEARANCE_DTYPE)
     rec["circle"] = rec["ellipse"] = rec["peer2"] = np.inf
     rec["circle_row"] = rec["ellipse_row"] = rec["peer_row"] = rec["peer"] = -1
+    return rec
+
+
+def no_crowd_clearance(B: int):
+    """-> the crowd observer's initial records [B]: +inf, row -1, obstacle -1."""
+    rec = np.empty(B, dtype=_lib.CROWD_CLEARANCE_DTYPE)
+    rec["level"] = np.inf
+    rec["row"] = rec["obstacle"] = -1
     return rec
 
 
@@ -775,10 +833,15 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     [steps] (the ``_lib.*_DTYPE`` records of the device), updated by ``advance`` -- before ``retire``, so a
     record names the leg its solve belonged to -- from the controls it applied, the statuses ``step`` got from its ``solve_fn``, the
     rows it appended to ``traj`` and the parameter vectors ``assemble`` returned for this step, for the robots the step drove.
+
+    ``crowd`` (a ``Crowd``): D moving obstacles of the world.  ``assemble`` advances their table
+    (``crowd_table()`` [D, N, 5]), every step and whoever is active, and overlays each active robot's closest ones on the parameter
+    vectors it returns, in front of the peers and never on the carried dynamic blocks; ``crowd_seen`` [B, slots] names them (a retired
+    robot keeps its last).  With ``crowd.watch``, ``advance`` updates ``crowd_clearance()`` [B] for the robots the step drove.
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None, missions=None, map_monitor=None, log=None):
+                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None):
         self.routes = list(routes)
         cfg, B = self.routes[0].cfg, len(starts)
         route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
@@ -795,9 +858,16 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self.leg = np.zeros(B, dtype=np.int32)
             self.leg_at = np.full((B, int(self.n_legs.max())), -1, dtype=np.int32)
             self.route_of = self.route_of.copy()
+        self.crowd = crowd
+        self._Mc = 0 if crowd is None else crowd.slots                        # the peers' slots follow the crowd's
+        if crowd is not None:
+            self._crowd_obs, self._crowd_sinus = crowd.checked(B, self.K, cfg.Ndynobs, 0 if peers is None else peers.slots)
+            self._crowd_tab = None                                            # [D, N, 5] as the last step wrote it
+            self.crowd_seen = np.full((B, crowd.slots), -1, dtype=np.int32)   # the obstacle in slot K + m of robot b's p (-1: none)
+            self._crowd_rec = no_crowd_clearance(B)
         self.peers = peers
         if peers is not None:
-            g = peers.checked(B, self.K, cfg.Ndynobs)
+            g = peers.checked(B, self.K + self._Mc, cfg.Ndynobs)
             g = np.zeros(B, dtype=np.int32) if g is None else g
             self.group_of = g
             self.groups = [np.nonzero(g == v)[0] for v in np.unique(g)]       # members in ascending robot index
@@ -859,10 +929,89 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         if self.active is not None:                                          # a retired robot's row stays its last step's
             self.P[self.active] = P[self.active]
             P = self.P
+        if self.crowd is not None:
+            self._crowd_advance()
+            self._overlay_crowd(P)
         if self.peers is not None:
             self._overlay_peers(P)
         self._P_step = P                                                     # what this step's solve reads: the monitor's p
         return P
+
+    def crowd_table(self):
+        """-> [D, N, 5]: every obstacle of the crowd over the horizon as the last step wrote it (a step taken)."""
+        return self._crowd_tab
+
+    def crowd_clearance(self):
+        """-> the crowd observer's records [B] (``_lib.CROWD_CLEARANCE_DTYPE``); without ``watch`` the initial record everywhere."""
+        return self._crowd_rec if self.crowd is not None else no_crowd_clearance(self.B)
+
+    def _crowd_advance(self):
+        """The world's table, once per step whoever is active: all stages fresh at the first step, later every obstacle's row
+        shifted by the s stages taken and its last s stages fresh -- what ``VectorizedRecedingHorizon.assemble`` does to a
+        scripted slot."""
+        cfg = self.cfg
+        N, s = cfg.N_hor, cfg.num_steps_taken
+        if self.t == 0:
+            self._crowd_tab = _predict_ellipses(cfg, self.sincos, self._crowd_obs, self._crowd_sinus, 0.0, N)
+        else:
+            fresh = _predict_ellipses(cfg, self.sincos, self._crowd_obs, self._crowd_sinus, (self.t + N - s) * cfg.ts, s)
+            self._crowd_tab = np.concatenate([self._crowd_tab[:, s:], fresh], axis=1)
+
+    def _overlay_crowd(self, P):
+        """The crowd's rule on the parameter vectors of the active robots, in place: C(b, d) = the smallest
+        squared distance over the stages between b's predicted positions and obstacle d's (a NaN never lowers it), the first
+        ``slots`` of the obstacles with C < range^2 in (C, d) order, each one's row of the table over one ellipse slot."""
+        cfg, cr, tab = self.cfg, self.crowd, self._crowd_tab
+        N, M, D = cfg.N_hor, cr.slots, len(tab)
+        per = cfg.ndynobs * N
+        base = cfg.n_p - cfg.nx * N - cfg.Ndynobs * per + self.K * per       # slot K of the dynamic block
+        who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
+        if not len(who):
+            return
+        pred = self.predict()
+        r2 = cr.range * cr.range
+        self.crowd_seen[who] = -1
+        rows = max(1, (1 << 22) // D)                                        # robots per pass: bounds the [rows, D] tables
+        for r0 in range(0, len(who), rows):
+            me = who[r0:r0 + rows]
+            C = np.full((len(me), D), np.inf)
+            with np.errstate(invalid="ignore", over="ignore"):
+                for k in range(N):                                           # min over the stages, in order
+                    dx, dy = pred[me, None, k, 0] - tab[None, :, k, 0], pred[me, None, k, 1] - tab[None, :, k, 1]
+                    d = dx * dx + dy * dy
+                    C = np.where(d < C, d, C)
+                ok = C < r2
+            order = np.argsort(np.where(ok, C, np.inf), axis=1, kind="stable")       # (C, d)
+            for m in range(min(M, D)):
+                j = order[:, m]
+                got = ok[np.arange(len(me)), j]
+                b, src = me[got], j[got]
+                self.crowd_seen[b, m] = src
+                P[b, base + m * per:base + (m + 1) * per] = tab[src].reshape(len(b), per)
+
+    def _crowd_update(self):
+        """The crowd observer's rule on the s rows this step appended, for the robots it drove: row
+        ``first + i`` against entry i of every obstacle's row of this step's table.  Rows ascend and ``argmin`` names the first
+        obstacle, so a strictly smaller level is the only way to win; a NaN level is passed over."""
+        s, rec, tab = self.cfg.num_steps_taken, self._crowd_rec, self._crowd_tab
+        who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
+        if not len(who):
+            return
+        for i in range(s):
+            r = self.steps * s + 1 + i
+            pose = self.traj[len(self.traj) - s + i]
+            e = tab[:, i, :]                                                 # [D, 5]
+            with np.errstate(all="ignore"):
+                dx, dy = pose[who, None, 0] - e[None, :, 0], pose[who, None, 1] - e[None, :, 1]
+                sn, cs = self.sincos(np.ascontiguousarray(e[:, 4]))
+                a, c = dx * cs + dy * sn, dx * sn - dy * cs
+                v = (a * a) / (e[:, 2] * e[:, 2]) + (c * c) / (e[:, 3] * e[:, 3])
+            v = np.where(np.isnan(v), np.inf, v)
+            d = np.argmin(v, axis=1)
+            v = v[np.arange(len(who)), d]
+            better = v < rec["level"][who]
+            b = who[better]
+            rec["level"][b], rec["row"][b], rec["obstacle"][b] = v[better], r, d[better]
 
     def predict(self):
         """-> pred [B, N, 3]: pred[j, k] = robot j's pose after k + 1 Euler steps (the expression of ``advance``) from
@@ -888,7 +1037,7 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         cfg, pe = self.cfg, self.peers
         N, M = cfg.N_hor, pe.slots
         per = cfg.ndynobs * N
-        base = cfg.n_p - cfg.nx * N - cfg.Ndynobs * per + self.K * per       # slot K of the dynamic block
+        base = cfg.n_p - cfg.nx * N - cfg.Ndynobs * per + (self.K + self._Mc) * per      # the peers' first slot: behind the crowd's
         pred = self.predict()
         r2 = pe.range * pe.range
         self.peer_index = np.full((self.B, M), -1)                           # who fills slot K + m of robot b at this step (-1: nobody)
@@ -955,6 +1104,8 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._monitor_update()
         if self.map_monitor is not None:
             self._map_update()
+        if self.crowd is not None and self.crowd.watch:
+            self._crowd_update()
         if self.log is not None:
             self._log_update(U)
         self.steps += 1
@@ -1163,10 +1314,15 @@ class DeviceRecedingHorizon:
     the fleet's totals per step are kept on the device (``nmpc_loop_set_log``), two more kernels per step after
     the advance; ``controls()``, ``step_records()``, ``drive_summary()`` and ``step_totals()`` read them.  Its host mirror is
     ``FleetRecedingHorizon`` with the same ``log`` (tests/test_gpu_log_loop.py).
+
+    ``crowd`` (a ``Crowd``): D moving obstacles of the world, one table on the device advanced once per step, and every step each
+    active robot's closest ones in ellipse slots of its own (``nmpc_loop_set_crowd``): two more kernels per step,
+    three with ``crowd.watch`` (needs ``max_steps`` > 0).  ``crowd_table()``, ``crowd_seen()`` and ``crowd_clearance()`` read the
+    results.  Its host mirror is ``FleetRecedingHorizon`` with the same ``crowd`` (tests/test_gpu_crowd_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None):
+                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None, crowd=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -1206,6 +1362,21 @@ class DeviceRecedingHorizon:
         solver._check(rc)
         self._l = h
         self.max_steps = int(max_steps)
+        self.crowd = crowd
+        if crowd is not None:
+            try:
+                (p1, p2, freq, rx, ry, ang), sinus = crowd.checked(B, K, cfg.Ndynobs, 0 if peers is None else peers.slots)
+            except ValueError:
+                self.close()
+                raise
+            direction = _atan2(p2[:, 1] - p1[:, 1], p2[:, 0] - p1[:, 0])
+            obst = np.ascontiguousarray(np.concatenate([p1, p2, freq[:, None], rx[:, None], ry[:, None], ang[:, None],
+                                                        sinus.astype(np.float64)[:, None], direction[:, None]], axis=1))
+            self._crowd_D = len(obst)
+            self._set(self.lib.nmpc_loop_set_crowd(h, self._crowd_D, _lib.as_dp(obst), cfg.vehicle_width / 2 + cfg.vehicle_margin,
+                                                   int(crowd.slots), float(crowd.range)))
+            if crowd.watch:
+                self._set(self.lib.nmpc_loop_set_crowd_monitor(h))
         self.peers = peers
         if peers is not None:
             g = None if peers.group_of is None else np.ascontiguousarray(peers.group_of, dtype=np.int32).reshape(B)
@@ -1313,6 +1484,27 @@ class DeviceRecedingHorizon:
         hdr, cell_of = np.zeros((), dtype=_lib.PEER_GRID_DTYPE), np.empty(self.B, dtype=np.int32)
         self.solver._check(self.lib.nmpc_loop_peer_grid(self._l, hdr.ctypes.data, _lib.as_i32p(cell_of)))
         return hdr, cell_of
+
+    def crowd_table(self):
+        """-> [D, N, 5] after synchronising: every obstacle of the crowd over the horizon as the last step wrote it.  Needs a ``crowd``
+        and a step taken."""
+        tab = np.empty((self._crowd_D, self.cfg.N_hor, 5))
+        self.solver._check(self.lib.nmpc_loop_crowd(self._l, _lib.as_dp(tab), None))
+        return tab
+
+    def crowd_seen(self):
+        """-> [B, slots] int32 after synchronising: the obstacle in ellipse slot K + m of each robot's parameter vector at its last
+        step, -1 for none.  Needs a ``crowd`` and a step taken."""
+        seen = np.empty((self.B, self.crowd.slots), dtype=np.int32)
+        self.solver._check(self.lib.nmpc_loop_crowd(self._l, None, _lib.as_i32p(seen)))
+        return seen
+
+    def crowd_clearance(self):
+        """-> the crowd observer's records [B] (``_lib.CROWD_CLEARANCE_DTYPE``: level, row, obstacle) after synchronising; without
+        a watched ``crowd`` the initial record everywhere."""
+        rec = np.empty(self.B, dtype=_lib.CROWD_CLEARANCE_DTYPE)
+        self.solver._check(self.lib.nmpc_loop_crowd_clearance(self._l, rec.ctypes.data))
+        return rec
 
     def map_clearance(self):
         """-> the map monitor's records [B] (``_lib.MAP_CLEARANCE_DTYPE``: wall2, wall_row, wall_edge, hits, hit_row, hit_poly, reserved)

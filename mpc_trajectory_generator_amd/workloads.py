@@ -135,6 +135,18 @@ def free_point_sampler(pl, rng):
     return sample
 
 
+def crowd_ellipses(cfg, scene, D, seed):
+    """-> the six arrays ``trajectory.Crowd`` takes as ``obstacles``: D moving ellipses of the scene's world, each going back and forth
+    between two collision-free points drawn as ``random_routes`` draws its end points (obstacle by obstacle, p1 then p2), with a
+    frequency, two radii and an angle drawn as ``moving_ellipses`` draws them, from one stream seeded with ``seed``."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sample = free_point_sampler(scene_planner(cfg, scene), rng)
+    ends = np.array([[sample(), sample()] for _ in range(D)], dtype=np.float64).reshape(D, 2, 2)
+    s = (D,)
+    return (ends[:, 0].copy(), ends[:, 1].copy(), rng.uniform(0.05, 0.1, s), rng.uniform(0.3, 1.0, s), rng.uniform(0.3, 1.0, s),
+            rng.uniform(0, np.pi, s))
+
+
 def own_route_fleet(cfg, scene, B, seed, legs=1, plan=None, min_length=12.0):
     """-> (routes, route_of, starts, idx0, legs): every robot its own start and goal, and ``legs`` legs each: B * legs routes, robot b's
     the routes b * legs .. b * legs + legs - 1, a leg starting at the goal of the leg before.  ``route_of`` [B] is each robot's first

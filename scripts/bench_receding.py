@@ -17,7 +17,11 @@ gains plan_ms (the planner kernels' time over all batches, redraws included) and
 (nmpc_loop_set_map_monitor) on the scene's original polygons, the true walls, or with "inflated" on the polygons the
 planner plans on; the result line then has map_clearance: the share of robots with a hit, the rows hit and the fleet's smallest wall distance.
 --log: the drive log (nmpc_loop_set_log): the result line then has drive_log: the share of non-converged solves per exit
-status, the worst step's slowest solve and the fleet's largest acceleration.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+status, the worst step's slowest solve and the fleet's largest acceleration.  --crowd D: a crowd of D moving obstacles shared by the whole fleet
+(nmpc_loop_set_crowd; workloads.crowd_ellipses, seed 2): --crowd-slots of the Ndynobs ellipse slots go to the closest
+ones within --crowd-range metres, the result line gains crowd: the share of those slots filled at the last step; with --crowd-watch also the
+observer (nmpc_loop_set_crowd_monitor): the robots whose level against some obstacle fell below 1, and how many of those closest approaches
+were to an obstacle the robot did not have in a slot at that step (found by an untimed second run that reads the slots after every step).  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -69,6 +73,11 @@ ap.add_argument("--map", nargs="?", const="original", default=None, choices=("or
 ap.add_argument("--log", action="store_true",
                 help="device loop only: keep every robot's applied controls, a record of every solve, a summary per robot and the fleet's "
                      "totals per step on the device, and report from them")
+ap.add_argument("--crowd", type=int, default=0, metavar="D",
+                help="device loop only: D > 0 moving obstacles of the scene, shared by the whole fleet (every sub-fleet sees the same crowd)")
+ap.add_argument("--crowd-slots", type=int, default=2, help="with --crowd: ellipse slots given to the crowd (the others stay scripted, or go to peers)")
+ap.add_argument("--crowd-range", type=float, default=10.0, help="with --crowd: how far a robot sees an obstacle of the crowd, in metres")
+ap.add_argument("--crowd-watch", action="store_true", help="with --crowd: keep every robot's closest approach to any obstacle of the crowd on the device")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
@@ -88,11 +97,17 @@ if args.legs < 1 or (args.legs > 1 and (not args.retire or args.host)):
     ap.error("--legs L: L >= 1, and L > 1 needs --retire on the device loop")
 if args.own_routes and (args.host or args.routes != 1):
     ap.error("--own-routes: on the device loop, and in place of --routes")
+if args.crowd and (args.host or args.steps < 1):
+    ap.error("--crowd is the device loop's: it needs the device loop (no --host) and --steps >= 1")
+if (args.crowd_watch or args.crowd < 0) and args.crowd < 1:
+    ap.error("--crowd D: D >= 1, and --crowd-watch goes with it")
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
 cfg = named_config("cfg4")
-K = cfg.Ndynobs - (args.peer_slots if args.peers else 0)
+K = cfg.Ndynobs - (args.peer_slots if args.peers else 0) - (args.crowd_slots if args.crowd else 0)
+if K < 0:
+    ap.error(f"--peer-slots and --crowd-slots together take more than the {cfg.Ndynobs} ellipse slots")
 B = args.batch
 # a peer's ellipse: its half width, this robot's half width and the margin
 peer_radius = cfg.vehicle_width + cfg.vehicle_margin
@@ -113,6 +128,12 @@ map_monitor = None
 if args.map:
     from mpc_trajectory_generator_amd.frontend import map_edges, scene_planner
     map_monitor = MapMonitor(*map_edges(scene_planner(cfg, args.scene), inflated=args.map == "inflated"))
+
+crowd = None
+if args.crowd:
+    from mpc_trajectory_generator_amd.trajectory import Crowd
+    from mpc_trajectory_generator_amd.workloads import crowd_ellipses
+    crowd = Crowd(crowd_ellipses(cfg, args.scene, args.crowd, 2), args.crowd_slots, args.crowd_range, watch=args.crowd_watch)
 
 planning = {}
 legs_of = None
@@ -151,6 +172,9 @@ if args.peers:
     fleet += (f", {K} scripted ellipses and {args.peer_slots} peer slots per robot, groups of {args.peers} consecutive robots, "
               f"range {args.peer_range} m, radii {peer_radius} m"
               + (f", found through a grid of {args.peer_cell} m" if args.peer_cell is not None else ""))
+if args.crowd:
+    fleet += (f", a crowd of {args.crowd} moving obstacles (workloads.crowd_ellipses, seed 2), {args.crowd_slots} crowd slots per robot, "
+              f"range {args.crowd_range} m" + (", crowd observer" if args.crowd_watch else "") + ("" if args.peers else f", {K} scripted ellipses"))
 solver = BatchSolver(cfg, max_batch=B, **sopts)
 missions_of = lambda ids: None
 routes_of = lambda ids: (routes, None if route_of is None else route_of[ids])
@@ -179,12 +203,16 @@ if not args.host:
     hip = ctypes.CDLL("libamdhip64.so")
     parts = np.array_split(np.arange(B), args.split)
     loops, streams = [], []
+
+    def make_loop(sv, ids):
+        sub_routes, sub_route_of = routes_of(ids)
+        return DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
+                                     route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
+                                     missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None, crowd=crowd)
+
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
-        sub_routes, sub_route_of = routes_of(ids)
-        loops.append(DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
-                                           route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
-                                           missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None))
+        loops.append(make_loop(sv, ids))
         strm = ctypes.c_void_p()
         assert hip.hipStreamCreate(ctypes.byref(strm)) == 0
         streams.append(strm)
@@ -230,6 +258,27 @@ if not args.host:
         rec = np.concatenate([rh.map_clearance() for rh in loops])
         quality["map_clearance"] = {"polygons": args.map, "edges": len(map_monitor.edges), "robots_hit_frac": float((rec["hits"] > 0).mean()),
                                     "rows_hit": int(rec["hits"].sum()), "min_wall_m": float(np.sqrt(rec["wall2"].min()))}
+    if args.crowd:
+        seen = np.concatenate([rh.crowd_seen() for rh in loops])          # the last step's
+        quality["crowd"] = {"obstacles": args.crowd, "slots": args.crowd_slots, "range_m": args.crowd_range,
+                            "slots_filled_frac": float((seen >= 0).mean())}
+        if args.crowd_watch:
+            # a second, untimed run of the same loops (bit for bit the same) that reads the slots after every step
+            recs = [rh.crowd_clearance() for rh in loops]
+            unseen = below = 0
+            for first, ids, rec in zip(loops, parts, recs):
+                rh, hist = make_loop(first.solver, ids), []
+                for k in range(first.steps):
+                    rh.step()
+                    hist.append(rh.crowd_seen())
+                assert rh.crowd_clearance().tobytes() == rec.tobytes(), "the second run is not the first"
+                rh.close()
+                hit = np.nonzero(rec["level"] < 1)[0]
+                step = (rec["row"][hit] - 1) // cfg.num_steps_taken
+                below += len(hit)
+                unseen += sum(int(rec["obstacle"][b] not in hist[k][b]) for b, k in zip(hit, step))
+            quality["crowd"].update({"robots_below_level_1": int(below), "of_those_obstacle_not_in_a_slot": int(unseen),
+                                     "min_level": float(min(r["level"].min() for r in recs))})
     from mpc_trajectory_generator_amd import _lib
     if args.log:
         tot = [rh.step_totals() for rh in loops]
