@@ -449,6 +449,8 @@ int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out);
  * the step's fleet totals.  With s = num_steps_taken and `step` the loop's step count, this step included (1-based, as retired_at):
  *   ctrl [max_steps * s][B][2]  row step_before * s + i = the (v, w) applied between trajectory rows step_before * s + i and the next:
  *                               the first s control pairs of the robot's u, as the advance read them.  +0.0 where a robot was not driven.
+ *                               With a plant (below) these stay the COMMANDED controls; what acted is the plant's `applied`, and `length`
+ *                               and the monitors see the true rows.
  *   rec  [max_steps][B]         nmpc_step_record of row step - 1: the fields of the step's nmpc_status after the solve, and the leg the
  *                               solve belonged to (before the step's dispatch; 0 without missions).  A robot the step did not drive
  *                               keeps exit_status = -1 and zeros.
@@ -553,6 +555,51 @@ _Static_assert(sizeof(nmpc_crowd_clearance) == 16, "nmpc_crowd_clearance layout"
 int nmpc_loop_set_crowd_monitor(nmpc_loop *l);
 /* Synchronises, then copies the records out [B]; on a loop without the observer the initial record everywhere. */
 int nmpc_loop_crowd_clearance(nmpc_loop *l, nmpc_crowd_clearance *out);
+
+/* ---- plant: seeded actuation, process and measurement noise, drawn on the device ------------------
+ * A loop closes on its own model: the advance applies exactly the controls the solve returned, by exactly the Euler step the solver
+ * predicts with.  The plant is an opt-in stage that stands where the advance stands and disturbs what the robot does, where that takes
+ * it and what the controller is told (the rule: DESIGN.md section 5.9).  Disturbances are xi(id, r, c): Philox4x32-10 on the counter
+ * (id, r, c, 0) under the key (seed & 0xffffffff, seed >> 32), the four output words summed to S, xi = double(S + 2 - 2^33) * C with
+ * C = 0x1.bb67ae8584caap-32, the double nearest sqrt(3) * 2^-32: symmetric, mean 0, variance 1, |xi| <= 2 sqrt(3), and the same double
+ * on every machine.  id = ids[b] (NULL: b), r = a trajectory row, c = a channel: a robot's disturbances do not depend on who else is
+ * active, on how a fleet is split over loops, or on any launch order.  Unfused f64, the statements in the order written:
+ *   measurement, at the start of a step, for every active robot, m = the row of its pose (step_before * s; row 0 is the start):
+ *       meas_x = x + meas[0]*xi(id, m, 5), y and theta likewise with channels 6 and 7; a channel whose sigma is 0 copies the value.
+ *       The assembly of p and the predicted poses (peers, crowd) start from the measured pose; nothing else reads it.
+ *   plant, in the place of the advance, for control i of the step, r = step_before * s + 1 + i, (v, w) the pair the solve returned:
+ *       t = act_gain[0]*v;  t = t + act_add[0];  va = v + t*xi(id, r, 0)      (skipped, va = v, if act_gain[0] == 0 and act_add[0] == 0)
+ *       wa likewise with index 1 and channel 1
+ *       x  = x + ts*(va*cos th);  x  = x  + proc[0]*xi(id, r, 2)              (the second statement skipped if proc[0] == 0)
+ *       y  = y + ts*(va*sin th);  y  = y  + proc[1]*xi(id, r, 3)
+ *       th = th + ts*wa;          th = th + proc[2]*xi(id, r, 4)
+ * The trajectory, the state, the monitors, the drive log's path length, retirement and the missions see the true pose; last_u, p[3],
+ * p[4] and the drive log's controls are the COMMANDED controls, what the controller knows it sent, and the terminal test reads the true
+ * pose and the commanded v.  A plant whose sigmas are all 0 executes the advance's operations and no others: the loop's bits are those
+ * of the loop without it.  With keep_applied the pairs (va, wa) are kept, applied [max_steps * s][B][2], +0.0 where a robot was not driven.
+ * To be called once, before the loop's first step, in any order with the other setters.  NMPC_ERR_BAD_ARG with a message that names the
+ * function, and nothing changed or allocated, for plant NULL, a sigma that is negative, infinite or a NaN, keep_applied on a loop with
+ * max_steps == 0, a call after a step, or a second call (a NULL loop: NMPC_ERR_BAD_ARG).  A loop without a plant enqueues what it
+ * enqueued before this function existed. */
+typedef struct nmpc_plant {              /* 96 bytes */
+    uint64_t seed;
+    double   act_gain[2], act_add[2];    /* v, w: sigma of the actuation noise = act_gain * control + act_add */
+    double   proc[3];                    /* x, y, theta: sigma per applied control */
+    double   meas[3];                    /* x, y, theta */
+    int32_t  keep_applied, reserved;
+} nmpc_plant;
+#ifdef __cplusplus
+static_assert(sizeof(nmpc_plant) == 96, "nmpc_plant layout");
+#else
+_Static_assert(sizeof(nmpc_plant) == 96, "nmpc_plant layout");
+#endif
+int nmpc_loop_set_plant(nmpc_loop *l, const nmpc_plant *plant, const uint32_t *ids);
+/* Synchronises, then copies the controls that acted so far out [steps * s][B][2] and returns their number of rows (or < 0);
+ * NMPC_ERR_BAD_ARG if `rows`, the rows the caller's buffer holds, is smaller.  A loop that keeps none reports 0 rows and writes nothing. */
+int nmpc_loop_plant_applied(nmpc_loop *l, double *out, int rows);
+/* Synchronises, then copies out [B][3] what the last step's solves were given as poses: the measured poses on a loop whose plant has a
+ * meas > 0 (a retired robot's: of its last step), else p[0 .. 3) of every robot; before the first step the start states. */
+int nmpc_loop_plant_measured(nmpc_loop *l, double *out);
 
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);

@@ -28,6 +28,7 @@ SYMBOLS = (
     "nmpc_loop_set_peers_grid", "nmpc_loop_peer_grid",
     "nmpc_loop_set_log", "nmpc_loop_log", "nmpc_loop_drive_summary", "nmpc_loop_step_totals",
     "nmpc_loop_set_crowd", "nmpc_loop_crowd", "nmpc_loop_set_crowd_monitor", "nmpc_loop_crowd_clearance",
+    "nmpc_loop_set_plant", "nmpc_loop_plant_applied", "nmpc_loop_plant_measured",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -76,6 +77,13 @@ class NmpcScene(C.Structure):
     _fields_ = [("n_node", C.c_int32), ("n_edge", C.c_int32), ("n_poly", C.c_int32), ("reserved", C.c_int32),
                 ("node_xy", C.POINTER(C.c_double)), ("edge", C.POINTER(C.c_double)), ("poly_off", C.POINTER(C.c_int32))]
 
+
+class NmpcPlant(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("act_gain", C.c_double * 2), ("act_add", C.c_double * 2), ("proc", C.c_double * 3),
+                ("meas", C.c_double * 3), ("keep_applied", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(NmpcPlant) == 96
 
 STATUS_DTYPE = np.dtype([("exit_status", "<i4"), ("num_outer_iterations", "<u4"),
                          ("num_inner_iterations", "<u4"), ("num_cost_evals", "<u4"),
@@ -343,6 +351,12 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_crowd_monitor.restype = C.c_int
     lib.nmpc_loop_crowd_clearance.argtypes = [vp, vp]
     lib.nmpc_loop_crowd_clearance.restype = C.c_int
+    lib.nmpc_loop_set_plant.argtypes = [vp, C.POINTER(NmpcPlant), C.POINTER(C.c_uint32)]
+    lib.nmpc_loop_set_plant.restype = C.c_int
+    lib.nmpc_loop_plant_applied.argtypes = [vp, dp, C.c_int]
+    lib.nmpc_loop_plant_applied.restype = C.c_int
+    lib.nmpc_loop_plant_measured.argtypes = [vp, dp]
+    lib.nmpc_loop_plant_measured.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]

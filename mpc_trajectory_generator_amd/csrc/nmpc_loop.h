@@ -27,7 +27,9 @@
 // Arguments: every kernel takes (LoopView, LoopStep, the arguments of its stage), or fewer where it needs fewer.  LoopView is what the
 // loop is -- its shape, its per-robot arrays, its active list -- fixed once the loop is configured and the same for every kernel;
 // LoopStep is what changes from step to step, all of it derived from the step count and the active count.  A stage's struct holds
-// what is the stage's own and nothing of those two.
+// what is the stage's own and nothing of those two.  The one place where two kernels of a step see different views: with a plant that
+// measures (nmpc_loop_set_plant, meas > 0) the assembly and nmpc_loop_predict_kernel get a copy of the view whose `state` is the measured
+// poses, built by nmpc_loop_step on its stack; every other kernel of the step keeps the true `state`.
 #pragma once
 
 namespace nmpc {
@@ -1025,7 +1027,8 @@ struct LogArgs {
 // step's statuses (scattered), P the parameter vectors as the solve read them (p[3], p[4]: the controls before this step's first) and
 // `leg` the missions' array as the solve found it (NULL: no missions).  The thread copies the s control pairs and the record, walks the
 // step's s + 1 trajectory rows for the length and folds everything into the robot's summary, field by field in global memory (exits is
-// indexed by the status).  Unfused f64; a comparison that is false keeps a maximum.
+// indexed by the status).  Unfused f64; a comparison that is false keeps a maximum.  With a plant (below) the controls logged stay the
+// COMMANDED ones, U as the solve returned it (what acted is the plant's `applied`), and the length walks the true rows.
 __global__ __launch_bounds__(256) void nmpc_loop_log_kernel(LoopView L, LoopStep stp, LogArgs g, const int *leg)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1134,6 +1137,103 @@ __global__ __launch_bounds__(1024) void nmpc_loop_log_totals_kernel(LoopView L, 
         o.solve_ms_max = ms;
         g.tot[stp.step - 1] = o;
     }
+}
+
+// ---- plant: the world does not do what the model says (nmpc_loop_set_plant; the rule is DESIGN.md section 5.9) ----
+// Seeded disturbances on what the robot does (actuation), on where that takes it (process) and on what the controller is told
+// (measurement).  xi(id, r, c) = nmpc::plant_xi(seed, id, r, c) (nmpc_rng.h): a robot's draws depend on (seed, its id, the trajectory
+// row, the channel) and on nothing else.  Unfused f64, the statements in the order written:
+//   measurement, at the start of a step, m = traj_row - 1 (the row of the pose being measured; row 0 is the start):
+//     meas_x = x + meas[0]*xi(id, m, 5), y and theta likewise with channels 6 and 7; a channel whose sigma is 0 copies the value and
+//     draws nothing.  The assembly and nmpc_loop_predict_kernel read the measured pose (a view whose `state` is `meas_state`), nothing
+//     else does.
+//   plant, in the place of the advance, for control i of the step, r = traj_row + i, (v, w) the commanded pair:
+//     t = act_gain[0]*v;  t = t + act_add[0];  va = v + t*xi(id, r, 0)        (skipped, va = v, if act_gain[0] == 0 and act_add[0] == 0)
+//     wa likewise with index 1 and channel 1
+//     sincos_cw(th)
+//     x  = x + ts*(va*cs);  x  = x  + proc[0]*xi(id, r, 2)                    (the second statement skipped if proc[0] == 0)
+//     y  = y + ts*(va*sn);  y  = y  + proc[1]*xi(id, r, 3)
+//     th = th + ts*wa;      th = th + proc[2]*xi(id, r, 4)
+// The trajectory row and `state` are the true pose; last_u is the COMMANDED last control, what the controller knows it sent; the
+// terminal test is the advance's, on the true pose and the commanded v; (va, wa) go to applied[t + i][b] if kept.  The sigmas are
+// kernel arguments, so a skip is uniform over the launch, and a plant of zeros executes the advance's operations and no others.
+struct PlantArgs {
+    unsigned long long seed;
+    double act_gain[2], act_add[2];       // for v and w
+    double proc[3], meas[3];              // x, y, theta
+    const unsigned *ids;      // [B]; NULL: robot b has id b
+    double *meas_state;       // [B][3]: the measured poses, what the last step's solves were given
+    double *applied;          // [max_steps * s][B][2]: the controls that acted, or NULL
+
+    __device__ unsigned id(int b) const { return ids ? ids[b] : (unsigned)b; }
+};
+
+// value + sigma * xi, or the value itself where the sigma is 0
+__device__ __forceinline__ double plant_add(double value, double sigma, const PlantArgs &p, unsigned id, unsigned row, unsigned channel)
+{
+    return sigma != 0.0 ? value + sigma * plant_xi(p.seed, id, row, channel) : value;
+}
+
+// one thread per active robot, in front of the assembly (launched only if some meas > 0): the pose as the controller is told it
+__global__ __launch_bounds__(256) void nmpc_loop_measure_kernel(LoopView L, LoopStep stp, PlantArgs p)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= stp.nact) return;
+    const int b = L.robot(i);
+    const unsigned id = p.id(b), m = (unsigned)(stp.traj_row - 1);
+    const double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
+    double *out = p.meas_state + 3 * (size_t)b;
+    out[0] = plant_add(x, p.meas[0], p, id, m, 5u);
+    out[1] = plant_add(y, p.meas[1], p, id, m, 6u);
+    out[2] = plant_add(th, p.meas[2], p, id, m, 7u);
+}
+
+// one thread per active robot, in the place of nmpc_loop_advance_kernel: its shape, its terminal test, the rule above
+__global__ __launch_bounds__(256) void nmpc_loop_plant_kernel(LoopView L, LoopStep stp, AssembleArgs g, PlantArgs p)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= stp.nact) return;
+    const int b = L.robot(i);
+    const unsigned id = p.id(b);
+    const bool act_v = p.act_gain[0] != 0.0 || p.act_add[0] != 0.0, act_w = p.act_gain[1] != 0.0 || p.act_add[1] != 0.0;
+    const double *u = L.U + (size_t)b * L.n_u;
+    double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
+    for (int i = 0; i < L.s; ++i) {
+        const unsigned r = (unsigned)(stp.traj_row + i);
+        const double v = u[2 * i], w = u[2 * i + 1];
+        double va = v, wa = w;
+        if (act_v) {
+            double t = p.act_gain[0] * v;
+            t = t + p.act_add[0];
+            va = v + t * plant_xi(p.seed, id, r, 0u);
+        }
+        if (act_w) {
+            double t = p.act_gain[1] * w;
+            t = t + p.act_add[1];
+            wa = w + t * plant_xi(p.seed, id, r, 1u);
+        }
+        double sn, cs;
+        sincos_cw(th, sn, cs);
+        x = x + L.ts * (va * cs);
+        x = plant_add(x, p.proc[0], p, id, r, 2u);
+        y = y + L.ts * (va * sn);
+        y = plant_add(y, p.proc[1], p, id, r, 3u);
+        th = th + L.ts * wa;
+        th = plant_add(th, p.proc[2], p, id, r, 4u);
+        if (L.traj) {
+            double *row = L.row(stp.traj_row + i, b);
+            row[0] = x; row[1] = y; row[2] = th;
+        }
+        if (p.applied) {
+            double *out = p.applied + ((size_t)(stp.t + i) * L.B + b) * 2;
+            out[0] = va; out[1] = wa;
+        }
+    }
+    L.state[3 * b] = x; L.state[3 * b + 1] = y; L.state[3 * b + 2] = th;
+    const double lv = u[2 * (L.s - 1)], lw = u[2 * (L.s - 1) + 1];
+    L.last_u[2 * b] = lv; L.last_u[2 * b + 1] = lw;
+    const double *end = g.routes[L.route_of[b]].end;
+    L.done[b] = (fabs(x - end[0]) <= 0.05 && fabs(y - end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
 }
 
 // ---- missions: a robot at its goal takes up its next route (nmpc_loop_set_missions; the rule is DESIGN.md section 5.9) ----

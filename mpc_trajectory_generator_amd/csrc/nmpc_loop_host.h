@@ -3,7 +3,7 @@
 // after the handle, fail, HIP_TRY and solve_launch.
 //
 // A loop is its view (nmpc::LoopView: the shape, the per-robot arrays and the active list, the same for every kernel), its base
-// (assemble -> solve -> advance) and up to seven stages, each a sub-struct with its device buffers and the argument block of its own
+// (assemble -> solve -> advance) and up to eight stages, each a sub-struct with its device buffers and the argument block of its own
 // kernels.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop as it
 // was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the configuration
 // final.  The loop keeps ONE counter, `steps`: nmpc_loop_step derives everything that changes per step from it and the active count
@@ -97,6 +97,16 @@ struct LoopLog {
     DevBuf<nmpc_step_totals> tot;    // [max_steps]
     bool made() const { return sum != nullptr; }
 };
+// nmpc_loop_set_plant: the plant kernel in the place of the advance, and with measurement noise one more kernel in front of the assembly
+struct LoopPlant {
+    bool on = false;
+    nmpc::PlantArgs a{};
+    DevBuf<double> meas;             // [B][3]: the measured poses, the start states until a step measures
+    DevBuf<unsigned> ids;            // [B], or none: robot b has id b
+    DevBuf<double> applied;          // [max_steps * s][B][2] if kept
+    bool made() const { return on; }
+    bool measures() const { return a.meas[0] > 0.0 || a.meas[1] > 0.0 || a.meas[2] > 0.0; }
+};
 
 struct nmpc_loop {
     nmpc_handle *h = nullptr;
@@ -120,6 +130,7 @@ struct nmpc_loop {
     LoopMap map;
     LoopMissions missions;
     LoopLog log;
+    LoopPlant plant;
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -481,6 +492,34 @@ int nmpc_loop_set_log(nmpc_loop *l)
     return NMPC_OK;
 }
 
+int nmpc_loop_set_plant(nmpc_loop *l, const nmpc_plant *plant, const uint32_t *ids)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_plant", l->plant.made(), "the loop has its plant already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopView &v = l->v;
+    const size_t B = (size_t)v.B;
+    if (!plant) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_plant: plant is NULL");
+    for (const double g : {plant->act_gain[0], plant->act_gain[1], plant->act_add[0], plant->act_add[1], plant->proc[0], plant->proc[1],
+                           plant->proc[2], plant->meas[0], plant->meas[1], plant->meas[2]})
+        if (!(g >= 0.0) || g > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_plant: every sigma must be finite and >= 0");
+    if (plant->keep_applied && !l->d_traj)
+        return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_plant: keep_applied on a loop that records no trajectory (max_steps == 0)");
+    LoopPlant st;
+    st.on = true;
+    HIP_TRY(h, st.meas.alloc(B * 3));
+    HIP_TRY(h, hipMemcpy(st.meas, l->d_state, B * 3 * sizeof(double), hipMemcpyDeviceToDevice));      // (no step yet: the start states)
+    if (ids) HIP_TRY(h, st.ids.upload(ids, B));
+    if (plant->keep_applied) HIP_TRY(h, st.applied.alloc_fill((size_t)l->max_steps * v.s * B * 2, 0));
+    nmpc::PlantArgs &a = st.a;
+    a.seed = plant->seed;
+    for (int k = 0; k < 2; ++k) { a.act_gain[k] = plant->act_gain[k]; a.act_add[k] = plant->act_add[k]; }
+    for (int k = 0; k < 3; ++k) { a.proc[k] = plant->proc[k]; a.meas[k] = plant->meas[k]; }
+    a.ids = st.ids; a.meas_state = st.meas; a.applied = st.applied;
+    l->plant = std::move(st);
+    return NMPC_OK;
+}
+
 // a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
 static int loop_nactive(nmpc_loop *l, int *n)
 {
@@ -514,12 +553,17 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     }
     const nmpc::LoopStep stp = nmpc::LoopStep::after(l->steps, v.s, n);
     const LoopCrowd &cr = l->crowd;
+    const LoopPlant &pl = l->plant;
+    // what the controller is told: with a plant that measures, the assembly and the prediction (and nobody else) see the measured poses
+    nmpc::LoopView told = v;
+    if (pl.made() && pl.measures()) told.state = pl.meas;
     // the crowd's table belongs to the world: it advances with nobody active too
     if (cr.made())
         hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_advance_kernel, dim3((cr.a.D * v.N * 5 + 255) / 256), dim3(256), 0, s, v, stp, cr.a);
     if (n > 0) {
-        hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, v, stp, l->a);
-        if (l->d_pred) hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->d_pred.p);
+        if (pl.made() && pl.measures()) hipLaunchKernelGGL(nmpc::nmpc_loop_measure_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, pl.a);
+        hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, told, stp, l->a);
+        if (l->d_pred) hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, told, stp, l->d_pred.p);
         if (cr.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a);
         if (l->peers.made()) {
             const nmpc::PeerArgs &p = l->peers.a;
@@ -544,7 +588,8 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         const nmpc_status *hint = (l->steps > 0 && h->loop_order_prev) ? st : nullptr;
         if (const int rc = solve_launch(h, n, P, U, Y, nullptr, Y, st, hint, stream)) return rc;
         if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_scatter_kernel, dim3(n), dim3(256), 0, s, v, r.a);
-        hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->a);
+        if (pl.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_plant_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->a, pl.a);
+        else hipLaunchKernelGGL(nmpc::nmpc_loop_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->a);
         // the monitors and the dispatch run over the robots the advance ran over: the compaction comes after.  The monitor reads
         // retired_at as the step found it (NULL without retirement)
         if (l->monitor.made())
@@ -724,6 +769,31 @@ int nmpc_loop_step_totals(nmpc_loop *l, nmpc_step_totals *out, int max_steps)
     if (const int rc = loop_settle(l)) return rc;
     HIP_TRY(l->h, l->log.tot.read(out, (size_t)l->steps));
     return l->steps;
+}
+
+int nmpc_loop_plant_applied(nmpc_loop *l, double *out, int rows)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (!l->plant.applied) return 0;
+    const int taken = l->steps * l->v.s;
+    if (rows < taken) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_plant_applied: rows is smaller than the controls applied, they do not fit");
+    if (const int rc = loop_settle(l)) return rc;
+    HIP_TRY(l->h, l->plant.applied.read(out, (size_t)taken * l->v.B * 2));
+    return taken;
+}
+
+int nmpc_loop_plant_measured(nmpc_loop *l, double *out)
+{
+    if (!out) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_settle(l)) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopView &v = l->v;
+    const size_t B = (size_t)v.B;
+    // what the solves were given is p[0 .. 3): the measured poses where the plant measures, else the poses themselves
+    if (l->plant.made() && l->plant.measures()) HIP_TRY(h, l->plant.meas.read(out, B * 3));
+    else if (l->steps == 0) HIP_TRY(h, l->d_state.read(out, B * 3));
+    else HIP_TRY(h, hipMemcpy2D(out, 3 * sizeof(double), v.P, (size_t)v.n_p * sizeof(double), 3 * sizeof(double), B, hipMemcpyDeviceToHost));
+    return NMPC_OK;
 }
 
 int nmpc_loop_read(nmpc_loop *l, double *state, double *last_u, int32_t *idx, uint8_t *done, nmpc_status *status)

@@ -779,6 +779,82 @@ class DriveLog:
     (``controls``, ``step_records``, ``drive_summary``, ``step_totals``).  It observes only."""
 
 
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_U32, _SH32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+PLANT_XI_SCALE = float.fromhex("0x1.bb67ae8584caap-32")       # the double nearest sqrt(3), scaled exactly by 2^-32
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 as published (csrc/nmpc_rng.h), vectorised: ``counter`` [..., 4] and ``key`` [..., 2] of 32-bit words (broadcast
+    against each other) -> the four output words [..., 4] uint32.  The words are carried in uint64, so that a product keeps its high
+    half."""
+    c = np.asarray(counter, dtype=np.uint64)
+    k = np.asarray(key, dtype=np.uint64)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape) for i in range(2))
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> _SH32) ^ c1 ^ k0, p1 & _U32, (p0 >> _SH32) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def plant_xi(seed, ids, row, channel):
+    """One disturbance per entry of ``ids`` (csrc/nmpc_rng.h): the counter is (id, row, channel, 0), the key
+    (seed & 0xffffffff, seed >> 32), S the sum of the four output words and xi = float(S + 2 - 2^33) * ``PLANT_XI_SCALE``.  Everything
+    before the one multiplication is exact: the device's double, bit for bit.  Mean 0, variance 1, |xi| <= 2 sqrt(3)."""
+    ids = np.asarray(ids, dtype=np.uint64)
+    counter = np.zeros(ids.shape + (4,), dtype=np.uint64)
+    counter[..., 0], counter[..., 1], counter[..., 2] = ids, np.uint64(row), np.uint64(channel)
+    words = philox4x32_10(counter, [int(seed) & 0xFFFFFFFF, int(seed) >> 32])
+    S = words.astype(np.int64).sum(axis=-1)
+    return (S + np.int64(2 - 2 ** 33)).astype(np.float64) * PLANT_XI_SCALE
+
+
+@dataclasses.dataclass(frozen=True)
+class Plant:
+    """A disturbed plant, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon`` alike: the world does not
+    do what the model says.  Every disturbance is ``sigma * plant_xi(seed, id, row, channel)``, so a robot's depend on the seed, its
+    id and the trajectory row, never on who else is active or on how a fleet is split.
+    ``act_gain``, ``act_add`` (v, omega): the control that acts is ``u + (act_gain * u + act_add) * xi``; ``proc`` (x, y, theta): added
+    to the pose after every control; ``meas`` (x, y, theta): added to the pose the assembly and the predictions start from, the true
+    pose untouched.  ``ids`` [B] uint32 (``None``: robot b has id b).  ``keep_applied`` (the device needs ``max_steps`` > 0):
+    ``applied()`` keeps the controls that acted.  ``last_u`` and the drive log hold the commanded controls; the trajectory, the
+    monitors and retirement see the true pose.  A plant of zeros changes no bit."""
+    seed: int = 0
+    act_gain: tuple = (0.0, 0.0)
+    act_add: tuple = (0.0, 0.0)
+    proc: tuple = (0.0, 0.0, 0.0)
+    meas: tuple = (0.0, 0.0, 0.0)
+    ids: object = None
+    keep_applied: bool = False
+
+    def checked(self, B: int):
+        """-> (act_gain [2], act_add [2], proc [3], meas [3] as float64 arrays, ids [B] uint32 or None); ValueError for what
+        ``nmpc_loop_set_plant`` refuses, a seed outside 64 bits and ``ids`` of another length."""
+        if not 0 <= int(self.seed) < 2 ** 64:
+            raise ValueError("plant: the seed is an unsigned 64-bit integer")
+        out = []
+        for name, n in (("act_gain", 2), ("act_add", 2), ("proc", 3), ("meas", 3)):
+            v = np.array(getattr(self, name), dtype=np.float64).reshape(-1)
+            if v.shape != (n,):
+                raise ValueError(f"plant: {name} takes {n} values")
+            if not (np.isfinite(v) & (v >= 0)).all():
+                raise ValueError(f"plant: {name} must be finite and >= 0")
+            out.append(v)
+        ids = None
+        if self.ids is not None:
+            ids = np.asarray(self.ids).reshape(-1)
+            if ids.shape != (B,):
+                raise ValueError(f"plant: {len(ids)} ids for {B} robots")
+            if not np.issubdtype(ids.dtype, np.integer) or ((ids < 0) | (ids > 0xFFFFFFFF)).any():
+                raise ValueError("plant: ids are unsigned 32-bit integers")
+            ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        return (*out, ids)
+
+
 def no_step_records(steps: int, B: int):
     """-> the initial records [steps, B]: exit_status -1, everything else 0."""
     rec = np.zeros((steps, B), dtype=_lib.STEP_RECORD_DTYPE)
@@ -838,10 +914,15 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     (``crowd_table()`` [D, N, 5]), every step and whoever is active, and overlays each active robot's closest ones on the parameter
     vectors it returns, in front of the peers and never on the carried dynamic blocks; ``crowd_seen`` [B, slots] names them (a retired
     robot keeps its last).  With ``crowd.watch``, ``advance`` updates ``crowd_clearance()`` [B] for the robots the step drove.
+
+    ``plant`` (a ``Plant``): seeded actuation, process and measurement noise.  ``assemble`` and ``predict``
+    start from the measured poses (``measured()`` [B, 3]) and nothing else does; ``advance`` applies the disturbed controls and adds
+    the process noise, ``state`` and ``traj`` are the true poses, ``last_u`` and the drive log the commanded controls;
+    ``applied()`` [steps * s, B, 2] = the controls that acted, with ``plant.keep_applied``.
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None):
+                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None):
         self.routes = list(routes)
         cfg, B = self.routes[0].cfg, len(starts)
         route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
@@ -891,6 +972,12 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         if log is not None:
             self._ctrl, self._rec, self._tot = [], [], []                     # per step: [s, B, 2], [B], one record
             self.drive_summary = no_drive_summary(B)
+        self.plant = plant
+        if plant is not None:
+            self._act_gain, self._act_add, self._proc, self._meas, ids = plant.checked(B)
+            self._ids = np.arange(B, dtype=np.uint32) if ids is None else ids
+            self._told = self.state.copy()                                    # [B, 3]: the measured poses, the start states at first
+            self._applied = []                                                # per trajectory row: [B, 2]
 
     @property
     def controls(self):
@@ -925,6 +1012,44 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         self.active &= ~now
 
     def assemble(self):
+        """With a plant that measures, everything below -- the parameter vectors and the predictions of crowd and peers -- starts
+        from the measured poses: they stand in ``state`` for the length of the call."""
+        if self.plant is None or not (self._meas > 0).any():
+            return self._assemble()
+        true = self.state
+        self.state = self._measure()
+        try:
+            return self._assemble()
+        finally:
+            self.state = true
+
+    def _measure(self):
+        """The measurement rule for the active robots, m = the row of the pose measured -> what the step is
+        told [B, 3]: a retired robot's true pose (its row of ``measured()`` stays its last measurement)."""
+        who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
+        m = self.steps * self.cfg.num_steps_taken
+        told = self.state.copy()
+        for c in range(3):
+            if self._meas[c] != 0:
+                told[who, c] = self.state[who, c] + self._meas[c] * plant_xi(self.plant.seed, self._ids[who], m, 5 + c)
+        self._told[who] = told[who]
+        return told
+
+    def measured(self):
+        """-> [B, 3]: what the last step's solves were given as poses (``nmpc_loop_plant_measured``): the measured poses where the plant
+        has a ``meas`` > 0 (a retired robot's: of its last step), else columns 0 .. 2 of the parameter vectors; the start states before
+        the first step."""
+        if self.plant is not None and (self._meas > 0).any():
+            return self._told.copy()
+        return self._P_step[:, 0:3].copy() if self.steps else self.state.copy()
+
+    def applied(self):
+        """-> [steps * s, B, 2]: the controls that acted, +0.0 where a robot was not driven; no rows without ``plant.keep_applied``."""
+        if self.plant is None or not self.plant.keep_applied or not self._applied:
+            return np.zeros((0, self.B, 2))
+        return np.stack(self._applied)
+
+    def _assemble(self):
         P = super().assemble(self.active)
         if self.active is not None:                                          # a retired robot's row stays its last step's
             self.P[self.active] = P[self.active]
@@ -1098,8 +1223,50 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
                 self.peer_index[b, m] = j
                 P[b, base + m * per:base + (m + 1) * per] = blk.reshape(per)
 
+    def _plant_advance(self, U):
+        """``VectorizedRecedingHorizon.advance`` with the plant rule in the place of its Euler step: unfused, in
+        the rule's order; a statement whose sigmas are 0 is skipped, so a plant of zeros is that advance.  Draws are pure functions of
+        (seed, id, row, channel): taken for everybody, kept for the active."""
+        cfg, active, seed, ids = self.cfg, self.active, self.plant.seed, self._ids
+        s, gain, add, proc = cfg.num_steps_taken, self._act_gain, self._act_add, self._proc
+        st = self.state.copy()
+        for i in range(s):
+            r = self.steps * s + 1 + i
+            va, wa = U[:, i * cfg.nu], U[:, 1 + i * cfg.nu]
+            if gain[0] != 0 or add[0] != 0:
+                t = gain[0] * va
+                t = t + add[0]
+                va = va + t * plant_xi(seed, ids, r, 0)
+            if gain[1] != 0 or add[1] != 0:
+                t = gain[1] * wa
+                t = t + add[1]
+                wa = wa + t * plant_xi(seed, ids, r, 1)
+            th = st[:, 2]
+            sn, cs = self.sincos(np.ascontiguousarray(th))
+            x, y, tn = st[:, 0] + cfg.ts * (va * cs), st[:, 1] + cfg.ts * (va * sn), th + cfg.ts * wa
+            if proc[0] != 0:
+                x = x + proc[0] * plant_xi(seed, ids, r, 2)
+            if proc[1] != 0:
+                y = y + proc[1] * plant_xi(seed, ids, r, 3)
+            if proc[2] != 0:
+                tn = tn + proc[2] * plant_xi(seed, ids, r, 4)
+            new, acted = np.stack([x, y, tn], axis=1), np.stack([va, wa], axis=1)
+            st = new if active is None else np.where(active[:, None], new, st)
+            self.traj.append(st.copy())
+            self._applied.append(acted if active is None else np.where(active[:, None], acted, 0.0))
+        self.state = st
+        last_u = U[:, (s - 1) * cfg.nu:s * cfg.nu].copy()                     # the commanded control: what the controller knows it sent
+        self.last_u = last_u if active is None else np.where(active[:, None], last_u, self.last_u)
+        end = self.tab.end[self.route_of]
+        done = (np.abs(st[:, 0] - end[:, 0]) <= 0.05) & (np.abs(st[:, 1] - end[:, 1]) <= 0.05) & (np.abs(self.last_u[:, 0]) < 0.005)
+        self.done = done if active is None else np.where(active, done, self.done)
+        self.t += s
+
     def advance(self, U):
-        super().advance(U, self.active)
+        if self.plant is None:
+            super().advance(U, self.active)
+        else:
+            self._plant_advance(U)
         if self.monitor is not None:
             self._monitor_update()
         if self.map_monitor is not None:
@@ -1319,10 +1486,15 @@ class DeviceRecedingHorizon:
     active robot's closest ones in ellipse slots of its own (``nmpc_loop_set_crowd``): two more kernels per step,
     three with ``crowd.watch`` (needs ``max_steps`` > 0).  ``crowd_table()``, ``crowd_seen()`` and ``crowd_clearance()`` read the
     results.  Its host mirror is ``FleetRecedingHorizon`` with the same ``crowd`` (tests/test_gpu_crowd_loop.py).
+
+    ``plant`` (a ``Plant``): seeded actuation, process and measurement noise drawn on the device (``nmpc_loop_set_plant``, DESIGN.md
+    section 5.9): ``nmpc_loop_plant_kernel`` in the place of the advance and, with a ``meas`` > 0, ``nmpc_loop_measure_kernel`` in front of
+    the assembly.  ``applied()`` (with ``plant.keep_applied``, needs ``max_steps`` > 0) and ``measured()`` read the results.  Its host
+    mirror is ``FleetRecedingHorizon`` with the same ``plant`` (tests/test_gpu_plant_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None, crowd=None):
+                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -1404,6 +1576,16 @@ class DeviceRecedingHorizon:
         self.log = log
         if log is not None:
             self._set(self.lib.nmpc_loop_set_log(h))
+        self.plant = plant
+        if plant is not None:
+            try:
+                gain, add, proc, meas, ids = plant.checked(B)
+            except ValueError:
+                self.close()
+                raise
+            pl = _lib.NmpcPlant(int(plant.seed), (C.c_double * 2)(*gain), (C.c_double * 2)(*add), (C.c_double * 3)(*proc),
+                                (C.c_double * 3)(*meas), int(bool(plant.keep_applied)), 0)
+            self._set(self.lib.nmpc_loop_set_plant(h, C.byref(pl), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint32))))
         self.missions = missions
         self._leg_off = None
         if missions is not None:
@@ -1545,6 +1727,23 @@ class DeviceRecedingHorizon:
         if n < 0:
             self.solver._check(n)
         return tot[:n]
+
+    def applied(self):
+        """-> [steps * s, B, 2] after synchronising: the controls that acted under the plant, +0.0 where a robot was not driven
+        (``plant.keep_applied``; without it no rows)."""
+        rows = self.steps * self.cfg.num_steps_taken
+        out = np.zeros((rows, self.B, 2))
+        n = self.lib.nmpc_loop_plant_applied(self._l, _lib.as_dp(out), rows)
+        if n < 0:
+            self.solver._check(n)
+        return out[:n]
+
+    def measured(self):
+        """-> [B, 3] after synchronising: what the last step's solves were given as poses: the measured poses under a plant with a
+        ``meas`` > 0, else columns 0 .. 2 of the parameter vectors; the start states before the first step."""
+        out = np.empty((self.B, 3))
+        self.solver._check(self.lib.nmpc_loop_plant_measured(self._l, _lib.as_dp(out)))
+        return out
 
     def read(self):
         """-> (state [B,3], last_u [B,2], idx [B], done [B] bool, status [B]) after synchronising."""

@@ -200,6 +200,14 @@ def tiled_fleet(routes, route_of, starts, idx0, copies):
         np.asarray(idx0)[rows].astype(np.int32)
 
 
+def ensemble_fleet(route, start, B, idx0=0):
+    """-> (routes, route_of, starts, idx0): B copies of one robot on ``route``, at the pose ``start`` and reference sample ``idx0``.
+    Without a plant every row of a loop over it is the same; under a ``trajectory.Plant`` robot b draws the disturbances of id b: the
+    Monte-Carlo study of one controller in one run."""
+    starts = np.tile(np.array(start, dtype=np.float64).reshape(1, 3), (B, 1))
+    return [route], np.zeros(B, dtype=np.int32), starts, np.full(B, int(idx0), dtype=np.int32)
+
+
 def stale_idx0(idx0, behind):
     """-> the start indices moved back by ``behind`` samples, clipped at 0: robots whose window search starts that far behind where
     they stand, so that the closest sample lies deep inside the first window."""
@@ -260,6 +268,19 @@ def map_clearance_differing(dev, host):
     a = dev.map_clearance() if callable(getattr(dev, "map_clearance", None)) else dev
     b = getattr(host, "map_clearance", host)
     return [f for f in a.dtype.names if a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes() or a[f].shape != b[f].shape]
+
+
+def plant_differing(dev, host):
+    """What a plant keeps (``dev``: a ``DeviceRecedingHorizon``, ``host``: its mirror, both with ``applied()`` and ``measured()``) -> the
+    names that are not bit-equal: a value compares by its bytes, so -0.0 is not 0.0 and a NaN equals itself."""
+    bad = []
+    for name in ("applied", "measured"):
+        a, b = getattr(dev, name)(), getattr(host, name)()
+        if a.shape != b.shape:
+            bad.append(f"{name} of shape {a.shape}, not {b.shape}")
+        elif a.tobytes() != np.ascontiguousarray(b, dtype=a.dtype).tobytes():
+            bad.append(name)
+    return bad
 
 
 LOG_PRODUCTS = ("controls", "step_records", "drive_summary", "step_totals")

@@ -21,7 +21,12 @@ status, the worst step's slowest solve and the fleet's largest acceleration.  --
 (nmpc_loop_set_crowd; workloads.crowd_ellipses, seed 2): --crowd-slots of the Ndynobs ellipse slots go to the closest
 ones within --crowd-range metres, the result line gains crowd: the share of those slots filled at the last step; with --crowd-watch also the
 observer (nmpc_loop_set_crowd_monitor): the robots whose level against some obstacle fell below 1, and how many of those closest approaches
-were to an obstacle the robot did not have in a slot at that step (found by an untimed second run that reads the slots after every step).  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+were to an obstacle the robot did not have in a slot at that step (found by an untimed second run that reads the slots after every step).
+--plant-act G, --plant-proc P, --plant-meas M, --plant-seed S: a disturbed plant (nmpc_loop_set_plant): actuation noise of
+relative sigma G on both controls, process noise of sigma P metres (and radians) per applied control, measurement noise of sigma M metres (and
+radians), seed S; a robot's id is its index in the whole fleet, so --split does not change its disturbances.  --ensemble (--routes 1): B copies of
+the fleet's robot 0, its start, reference sample and ellipses (workloads.ensemble_fleet), the Monte-Carlo study of one controller; the result line gains
+plant: the sigmas, and with --ensemble the spread of the final poses.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -78,6 +83,11 @@ ap.add_argument("--crowd", type=int, default=0, metavar="D",
 ap.add_argument("--crowd-slots", type=int, default=2, help="with --crowd: ellipse slots given to the crowd (the others stay scripted, or go to peers)")
 ap.add_argument("--crowd-range", type=float, default=10.0, help="with --crowd: how far a robot sees an obstacle of the crowd, in metres")
 ap.add_argument("--crowd-watch", action="store_true", help="with --crowd: keep every robot's closest approach to any obstacle of the crowd on the device")
+ap.add_argument("--plant-act", type=float, default=0.0, metavar="G", help="device loop only: actuation noise, sigma = G * |control| on v and omega")
+ap.add_argument("--plant-proc", type=float, default=0.0, metavar="P", help="device loop only: process noise on x, y (metres) and theta (radians) per applied control")
+ap.add_argument("--plant-meas", type=float, default=0.0, metavar="M", help="device loop only: measurement noise on x, y (metres) and theta (radians)")
+ap.add_argument("--plant-seed", type=int, default=0, metavar="S", help="the seed of the plant's disturbances")
+ap.add_argument("--ensemble", action="store_true", help="--routes 1: B copies of the fleet's robot 0 (a Monte-Carlo study under the plant)")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
@@ -101,6 +111,11 @@ if args.crowd and (args.host or args.steps < 1):
     ap.error("--crowd is the device loop's: it needs the device loop (no --host) and --steps >= 1")
 if (args.crowd_watch or args.crowd < 0) and args.crowd < 1:
     ap.error("--crowd D: D >= 1, and --crowd-watch goes with it")
+planted = args.plant_act > 0 or args.plant_proc > 0 or args.plant_meas > 0
+if min(args.plant_act, args.plant_proc, args.plant_meas) < 0 or (planted and args.host):
+    ap.error("--plant-act, --plant-proc, --plant-meas: >= 0, on the device loop (no --host)")
+if args.ensemble and (args.routes != 1 or args.own_routes or args.host):
+    ap.error("--ensemble: copies of one robot on the scene's route, on the device loop")
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
@@ -154,6 +169,10 @@ if args.own_routes:
 elif args.routes == 1:
     route = harness.scene_route(cfg, args.scene)
     i0, starts, dyn = route_fleet(route, B, 0, K, back=args.back)
+    if args.ensemble:      # everybody a copy of the fleet's robot 0: its start, its reference sample, its ellipses
+        from mpc_trajectory_generator_amd.workloads import ensemble_fleet
+        _, _, starts, i0 = ensemble_fleet(route, starts[0], B, i0[0])
+        dyn = dyn and tuple(np.repeat(a[:1], B, axis=0) for a in dyn)
     routes, route_of = route, None
 else:
     from mpc_trajectory_generator_amd.frontend import random_fleet
@@ -168,6 +187,10 @@ else:
 fleet = f", {args.routes} routes (frontend.random_fleet, seed 0)" if args.routes > 1 else ""
 if args.own_routes:
     fleet = f", every robot its own start and goal (workloads.own_route_fleet, seed 0; {len(routes)} routes planned on the device)"
+if args.ensemble:
+    fleet += ", an ensemble: every robot a copy of the fleet's robot 0"
+if planted:
+    fleet += (f", disturbed plant (actuation {args.plant_act}, process {args.plant_proc}, measurement {args.plant_meas}, seed {args.plant_seed})")
 if args.peers:
     fleet += (f", {K} scripted ellipses and {args.peer_slots} peer slots per robot, groups of {args.peers} consecutive robots, "
               f"range {args.peer_range} m, radii {peer_radius} m"
@@ -204,11 +227,18 @@ if not args.host:
     parts = np.array_split(np.arange(B), args.split)
     loops, streams = [], []
 
+    def plant_of(ids):
+        """the fleet's plant for the robots ``ids``: a robot keeps its id, its index in the whole fleet"""
+        from mpc_trajectory_generator_amd.trajectory import Plant
+        return Plant(seed=args.plant_seed, act_gain=(args.plant_act,) * 2, proc=(args.plant_proc,) * 3, meas=(args.plant_meas,) * 3,
+                     ids=np.asarray(ids, dtype=np.uint32)) if planted else None
+
     def make_loop(sv, ids):
         sub_routes, sub_route_of = routes_of(ids)
         return DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                      route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
-                                     missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None, crowd=crowd)
+                                     missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None, crowd=crowd,
+                                     plant=plant_of(ids))
 
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
@@ -279,6 +309,11 @@ if not args.host:
                 unseen += sum(int(rec["obstacle"][b] not in hist[k][b]) for b, k in zip(hit, step))
             quality["crowd"].update({"robots_below_level_1": int(below), "of_those_obstacle_not_in_a_slot": int(unseen),
                                      "min_level": float(min(r["level"].min() for r in recs))})
+    if planted or args.ensemble:
+        quality["plant"] = {"act_gain": args.plant_act, "proc": args.plant_proc, "meas": args.plant_meas, "seed": args.plant_seed}
+        if args.ensemble:
+            pose = np.concatenate([o[0] for o in outs])
+            quality["plant"].update({"final_pose_mean": pose.mean(axis=0).tolist(), "final_pose_std": pose.std(axis=0).tolist()})
     from mpc_trajectory_generator_amd import _lib
     if args.log:
         tot = [rh.step_totals() for rh in loops]
