@@ -601,6 +601,55 @@ int nmpc_loop_plant_applied(nmpc_loop *l, double *out, int rows);
  * meas > 0 (a retired robot's: of its last step), else p[0 .. 3) of every robot; before the first step the start states. */
 int nmpc_loop_plant_measured(nmpc_loop *l, double *out);
 
+/* ---- ensemble: per-group pose statistics after every step, on device -----------------------------
+ * B copies of one robot under a plant are a Monte-Carlo study of one controller, G routes or tunings x M seeded copies a comparison of
+ * G controllers; what such a run is asked for is where the copies are on average, how far they have spread and how many have arrived,
+ * step by step.  The ensemble is an opt-in stage of the loop that keeps one nmpc_ensemble_stat per group and step on the device,
+ * ens [max_steps][G] (the rule: DESIGN.md section 5.9).  It observes only: no p, u, y, state, status, trajectory or other record
+ * differs by a bit from the loop without it.  One more kernel per step, one workgroup per group, the step's LAST: behind the drive
+ * log, the missions' dispatch and, on a retiring loop, the compaction.  Unfused f64 in the order written:
+ *   members   of group g: the robots b with group_of[b] == g in ascending b, m_0 < ... < m_{n-1} (group_of NULL: one group of
+ *             everybody).  Every member counts, active, retired or re-dispatched; the pose read is the true `state` (under a plant
+ *             never the measured one), a retired robot's the pose it was parked at.  A group may be empty.
+ *   when      at the end of step k (1-based, the step retired_at takes), row k - 1; also in a step in which nobody is active any more.
+ *   n         the member count.
+ *   arrived   on a retiring loop the members with retired_at[b] >= 0, this step's retirements included (a mission robot between legs
+ *             is not counted); otherwise the members with done[b] != 0: this row's terminal test, not a latch.
+ *   SUM(v)    of one value per member, a fixed tree: slot t of 256 starts at +0.0 and takes acc = acc + v[m_i] for i = t, t + 256, ...
+ *             in ascending i; within each block of 64 slots, for off = 32, 16, 8, 4, 2, 1: a[l] = a[l] + a[l + off] for l < off (what an
+ *             xor butterfly leaves in every lane, IEEE addition being commutative); the four block sums w0 .. w3 give
+ *             ((w0 + w1) + w2) + w3.
+ *   mean      S = (SUM x, SUM y, SUM theta); mean = S / double(n), one IEEE division each.
+ *   cov       against the mean just formed, dx = x - mean_x, dy and dth likewise:
+ *             (SUM dx*dx, SUM dx*dy, SUM dy*dy, SUM dth*dth) / double(n).  Each product is rounded before it enters the tree; a
+ *             population covariance; theta as the loop keeps it, not wrapped.
+ *   far2, far_robot   the largest r2 = dx*dx + dy*dy over the members and the smallest robot index that has it: the lexicographic
+ *             extreme of (r2, b) by `r2 > far2 || (r2 == far2 && b < far_robot)` from (-1.0, -1).  A comparison that is false because
+ *             of a NaN keeps the record.
+ *   an empty group: n = 0, arrived = 0, every double +0.0, far2 = -1.0, far_robot = -1.
+ * To be called once, before the loop's first step, in any order with the other setters, on a loop with max_steps > 0 (the table's
+ * length).  NMPC_ERR_BAD_ARG with a message that names the function, and nothing changed or allocated, for max_steps == 0, a call
+ * after a step, a second call, G < 1 or G > 65536, group_of NULL with G != 1 or a group_of[b] outside [0, G) (a NULL loop:
+ * NMPC_ERR_BAD_ARG).  A loop without the stage enqueues what it enqueued before this function existed. */
+typedef struct nmpc_ensemble_stat {      /* 80 bytes */
+    int32_t n, arrived, far_robot, reserved;     /* reserved: 0 */
+    double  mean[3];                     /* x, y, theta */
+    double  cov[4];                      /* xx, xy, yy, theta-theta */
+    double  far2;
+} nmpc_ensemble_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nmpc_ensemble_stat) == 80, "nmpc_ensemble_stat layout");
+#else
+_Static_assert(sizeof(nmpc_ensemble_stat) == 80, "nmpc_ensemble_stat layout");
+#endif
+int nmpc_loop_set_ensemble(nmpc_loop *l, const int32_t *group_of, int G);
+/* Synchronises, then copies the records of the steps taken so far out [steps][G] and returns the step count (or < 0);
+ * NMPC_ERR_BAD_ARG if max_steps, the steps the caller's buffer holds, is smaller.  A loop without the stage reports 0 steps and writes
+ * nothing. */
+int nmpc_loop_ensemble(nmpc_loop *l, nmpc_ensemble_stat *out, int max_steps);
+/* G, or 0 on a loop without the stage. */
+int nmpc_loop_ensemble_groups(nmpc_loop *l);
+
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);
 /* a/b and sqrt(a) as the device computes them: out_div/out_sqrt [n]. */

@@ -29,6 +29,7 @@ SYMBOLS = (
     "nmpc_loop_set_log", "nmpc_loop_log", "nmpc_loop_drive_summary", "nmpc_loop_step_totals",
     "nmpc_loop_set_crowd", "nmpc_loop_crowd", "nmpc_loop_set_crowd_monitor", "nmpc_loop_crowd_clearance",
     "nmpc_loop_set_plant", "nmpc_loop_plant_applied", "nmpc_loop_plant_measured",
+    "nmpc_loop_set_ensemble", "nmpc_loop_ensemble", "nmpc_loop_ensemble_groups",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -123,6 +124,11 @@ assert STEP_TOTALS_DTYPE.itemsize == 48
 # nmpc_crowd_clearance: a robot's closest approach to any obstacle of the crowd (nmpc_loop_set_crowd_monitor)
 CROWD_CLEARANCE_DTYPE = np.dtype([("level", "<f8"), ("row", "<i4"), ("obstacle", "<i4")])
 assert CROWD_CLEARANCE_DTYPE.itemsize == 16
+
+# nmpc_ensemble_stat: a group's pose statistics after one step (nmpc_loop_set_ensemble)
+ENSEMBLE_DTYPE = np.dtype([("n", "<i4"), ("arrived", "<i4"), ("far_robot", "<i4"), ("reserved", "<i4"),
+                           ("mean", "<f8", 3), ("cov", "<f8", 4), ("far2", "<f8")])
+assert ENSEMBLE_DTYPE.itemsize == 80
 
 
 def _sources():
@@ -357,6 +363,12 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_plant_applied.restype = C.c_int
     lib.nmpc_loop_plant_measured.argtypes = [vp, dp]
     lib.nmpc_loop_plant_measured.restype = C.c_int
+    lib.nmpc_loop_set_ensemble.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
+    lib.nmpc_loop_set_ensemble.restype = C.c_int
+    lib.nmpc_loop_ensemble.argtypes = [vp, vp, C.c_int]
+    lib.nmpc_loop_ensemble.restype = C.c_int
+    lib.nmpc_loop_ensemble_groups.argtypes = [vp]
+    lib.nmpc_loop_ensemble_groups.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]

@@ -1272,4 +1272,110 @@ __global__ __launch_bounds__(64) void nmpc_loop_dispatch_kernel(LoopView L, Loop
     }
 }
 
+// ---- ensemble: per-group pose statistics after every step (nmpc_loop_set_ensemble; the rule is DESIGN.md section 5.9).  It observes:
+// its table is the only thing it writes.
+// Group g's members m_0 < ... < m_{n-1} are gmem[goff[g] .. goff[g + 1]); every member counts, whoever is active.  Unfused f64:
+//   SUM(v): slot t of 256 starts at +0.0 and takes acc = acc + v[m_i] for i = t, t + 256, ... ascending; within each block of 64 slots
+//           a[l] = a[l] + a[l + off] for l < off, off = 32, 16, 8, 4, 2, 1 (an xor butterfly leaves that in every lane: IEEE addition
+//           commutes); the four block sums give ((w0 + w1) + w2) + w3
+//   mean = (SUM x, SUM y, SUM theta) / double(n), one division each
+//   dx = x - mean_x, dy, dth likewise; cov = (SUM dx*dx, SUM dx*dy, SUM dy*dy, SUM dth*dth) / double(n), each product rounded first
+//   (far2, far_robot): the extreme of (r2, b), r2 = dx*dx + dy*dy, by `r2 > far2 || (r2 == far2 && b < far_robot)` from (-1.0, -1)
+//   arrived: retired_at[b] >= 0 on a retiring loop, else done[b] != 0
+//   an empty group: zeros, far2 = -1.0, far_robot = -1
+struct EnsembleArgs {
+    int G;
+    const int *goff;          // [G + 1]
+    const int *gmem;          // [B]: the groups' members, group after group, ascending inside a group
+    nmpc_ensemble_stat *ens;  // [max_steps][G]
+};
+
+// the tree's halving inside a block of 64 slots, result in every lane
+__device__ __forceinline__ double wave_sum(double a)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) a = a + __shfl_xor(a, off);
+    return a;
+}
+
+// One workgroup per group, the step's last kernel: behind the log, the dispatch and the compaction (retired_at: the retirement's, this
+// step's retirements in it; NULL without retirement).  Thread t is slot t.  Two passes over the members' true poses, the second from
+// the cache; each a wave reduction, the four waves' results through LDS, combined by thread 0, which hands the mean back through LDS
+// and writes the record.  No group is staged: its size is bounded by B only.
+__global__ __launch_bounds__(256) void nmpc_loop_ensemble_kernel(LoopView L, LoopStep stp, EnsembleArgs e, const int *retired_at)
+{
+    __shared__ double red[4][5], mean[3];
+    __shared__ int rint[4];
+    const int g = blockIdx.x, t = threadIdx.x, w = t >> 6;
+    const int lo = e.goff[g], n = e.goff[g + 1] - lo;
+    const int *mem = e.gmem + lo;
+    nmpc_ensemble_stat *out = e.ens + (size_t)(stp.step - 1) * e.G + g;
+    if (n == 0) {              // (the same for the whole workgroup)
+        if (t == 0) {
+            nmpc_ensemble_stat o;
+            o.n = 0; o.arrived = 0; o.far_robot = -1; o.reserved = 0;
+            o.mean[0] = o.mean[1] = o.mean[2] = 0.0;
+            o.cov[0] = o.cov[1] = o.cov[2] = o.cov[3] = 0.0;
+            o.far2 = -1.0;
+            *out = o;
+        }
+        return;
+    }
+    const double dn = (double)n;
+    double sx = 0.0, sy = 0.0, sth = 0.0;
+    int arrived = 0;
+    for (int i = t; i < n; i += 256) {
+        const int b = mem[i];
+        const double *p = L.state + 3 * (size_t)b;
+        sx = sx + p[0]; sy = sy + p[1]; sth = sth + p[2];
+        arrived += retired_at ? retired_at[b] >= 0 : L.done[b] != 0;
+    }
+    sx = wave_sum(sx); sy = wave_sum(sy); sth = wave_sum(sth);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) arrived += __shfl_xor(arrived, off);
+    if ((t & 63) == 0) { red[w][0] = sx; red[w][1] = sy; red[w][2] = sth; rint[w] = arrived; }
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) mean[q] = (((red[0][q] + red[1][q]) + red[2][q]) + red[3][q]) / dn;
+        arrived = ((rint[0] + rint[1]) + rint[2]) + rint[3];
+    }
+    __syncthreads();
+    const double mx = mean[0], my = mean[1], mth = mean[2];
+    double cxx = 0.0, cxy = 0.0, cyy = 0.0, ctt = 0.0, far2 = -1.0;
+    int far = -1;
+    for (int i = t; i < n; i += 256) {
+        const int b = mem[i];
+        const double *p = L.state + 3 * (size_t)b;
+        const double dx = p[0] - mx, dy = p[1] - my, dth = p[2] - mth;
+        const double xx = dx * dx, xy = dx * dy, yy = dy * dy, tt = dth * dth;
+        cxx = cxx + xx; cxy = cxy + xy; cyy = cyy + yy; ctt = ctt + tt;
+        const double r2 = xx + yy;
+        if (r2 > far2 || (r2 == far2 && b < far)) { far2 = r2; far = b; }
+    }
+    cxx = wave_sum(cxx); cxy = wave_sum(cxy); cyy = wave_sum(cyy); ctt = wave_sum(ctt);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double o2 = __shfl_xor(far2, off);
+        const int ob = __shfl_xor(far, off);
+        if (o2 > far2 || (o2 == far2 && ob < far)) { far2 = o2; far = ob; }
+    }
+    // (red and rint are free again: thread 0 read them in front of the barrier that published the mean)
+    if ((t & 63) == 0) { red[w][0] = cxx; red[w][1] = cxy; red[w][2] = cyy; red[w][3] = ctt; red[w][4] = far2; rint[w] = far; }
+    __syncthreads();
+    if (t == 0) {
+        nmpc_ensemble_stat o;
+        o.n = n; o.arrived = arrived; o.reserved = 0;
+        o.mean[0] = mx; o.mean[1] = my; o.mean[2] = mth;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o.cov[q] = (((red[0][q] + red[1][q]) + red[2][q]) + red[3][q]) / dn;
+        far2 = -1.0; far = -1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (red[k][4] > far2 || (red[k][4] == far2 && rint[k] < far)) { far2 = red[k][4]; far = rint[k]; }
+        o.far2 = far2; o.far_robot = far;
+        *out = o;
+    }
+}
+
 }  // namespace nmpc

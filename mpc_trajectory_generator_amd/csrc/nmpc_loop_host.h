@@ -3,13 +3,13 @@
 // after the handle, fail, HIP_TRY and solve_launch.
 //
 // A loop is its view (nmpc::LoopView: the shape, the per-robot arrays and the active list, the same for every kernel), its base
-// (assemble -> solve -> advance) and up to eight stages, each a sub-struct with its device buffers and the argument block of its own
+// (assemble -> solve -> advance) and up to nine stages, each a sub-struct with its device buffers and the argument block of its own
 // kernels.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop as it
 // was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the configuration
 // final.  The loop keeps ONE counter, `steps`: nmpc_loop_step derives everything that changes per step from it and the active count
 // (nmpc::LoopStep, on its stack), hands view, step and a stage's block to each kernel, and writes to no argument block.  It is ONE
 // sequence of kernels in which a stage adds its own; the pointers that cross stages (the predicted poses, which peers and crowd share
-// and the loop owns, for the compaction; retirement's retired_at for the monitor; the missions' leg for the log) are passed at the
+// and the loop owns, for the compaction; retirement's retired_at for the monitor and the ensemble; the missions' leg for the log) are passed at the
 // launch, from the stage that owns them.
 #pragma once
 
@@ -107,6 +107,12 @@ struct LoopPlant {
     bool made() const { return on; }
     bool measures() const { return a.meas[0] > 0.0 || a.meas[1] > 0.0 || a.meas[2] > 0.0; }
 };
+struct LoopEnsemble {        // nmpc_loop_set_ensemble: one more kernel per step, the step's last
+    nmpc::EnsembleArgs a{};
+    DevBuf<int> goff, gmem;              // [G + 1], [B]: the groups' members, ascending inside a group
+    DevBuf<nmpc_ensemble_stat> ens;      // [max_steps][G]
+    bool made() const { return ens != nullptr; }
+};
 
 struct nmpc_loop {
     nmpc_handle *h = nullptr;
@@ -131,6 +137,7 @@ struct nmpc_loop {
     LoopMissions missions;
     LoopLog log;
     LoopPlant plant;
+    LoopEnsemble ensemble;
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -520,6 +527,35 @@ int nmpc_loop_set_plant(nmpc_loop *l, const nmpc_plant *plant, const uint32_t *i
     return NMPC_OK;
 }
 
+static constexpr int ENSEMBLE_MAX_GROUPS = 65536;
+
+int nmpc_loop_set_ensemble(nmpc_loop *l, const int32_t *group_of, int G)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_ensemble", l->ensemble.made(), "the loop has its ensemble already")) return rc;
+    nmpc_handle *h = l->h;
+    const int B = l->v.B;
+    if (l->max_steps == 0) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_ensemble: the loop keeps no table per step (max_steps == 0)");
+    if (G < 1 || G > ENSEMBLE_MAX_GROUPS) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_ensemble: G outside 1 .. 65536");
+    if (!group_of && G != 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_ensemble: group_of == NULL with G != 1");
+    if (group_of) for (int b = 0; b < B; ++b) if (group_of[b] < 0 || group_of[b] >= G) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_ensemble: group_of out of range");
+    // the members group after group, each group's in ascending index (as LoopGroups::upload files its own)
+    std::vector<int> off((size_t)G + 1, 0), mem(B);
+    for (int b = 0; b < B; ++b) off[(group_of ? group_of[b] : 0) + 1]++;
+    for (int g = 0; g < G; ++g) off[g + 1] += off[g];
+    {
+        std::vector<int> at(off.begin(), off.end() - 1);
+        for (int b = 0; b < B; ++b) mem[at[group_of ? group_of[b] : 0]++] = b;
+    }
+    LoopEnsemble st;
+    HIP_TRY(h, st.goff.upload(off.data(), off.size()));
+    HIP_TRY(h, st.gmem.upload(mem.data(), B));
+    HIP_TRY(h, st.ens.alloc_fill((size_t)l->max_steps * G, 0));
+    st.a.G = G; st.a.goff = st.goff; st.a.gmem = st.gmem; st.a.ens = st.ens;
+    l->ensemble = std::move(st);
+    return NMPC_OK;
+}
+
 // a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
 static int loop_nactive(nmpc_loop *l, int *n)
 {
@@ -608,6 +644,9 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     // (with nobody active the step still counts: the clock advances and the trajectory rows repeat).  The compaction parks a retired
     // robot's predictions for the peers (NULL without them: the crowd reads the active robots' only)
     if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_compact_kernel, dim3(1), dim3(1024), 0, s, v, stp, r.a, l->peers.made() ? l->d_pred.p : nullptr);
+    // the ensemble sees the step as it ends: everybody's true pose, retired_at with this step's retirements (NULL without retirement)
+    if (l->ensemble.made())
+        hipLaunchKernelGGL(nmpc::nmpc_loop_ensemble_kernel, dim3(l->ensemble.a.G), dim3(256), 0, s, v, stp, l->ensemble.a, r.retired_at.p);
     HIP_TRY(h, hipGetLastError());
     if (retiring) {
         HIP_TRY(h, hipMemcpyAsync(r.h_nact.p, r.nact.p, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -769,6 +808,21 @@ int nmpc_loop_step_totals(nmpc_loop *l, nmpc_step_totals *out, int max_steps)
     if (const int rc = loop_settle(l)) return rc;
     HIP_TRY(l->h, l->log.tot.read(out, (size_t)l->steps));
     return l->steps;
+}
+
+int nmpc_loop_ensemble(nmpc_loop *l, nmpc_ensemble_stat *out, int max_steps)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (!l->ensemble.made()) return 0;
+    if (max_steps < l->steps) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_ensemble: max_steps is smaller than the steps taken, the records do not fit");
+    if (const int rc = loop_settle(l)) return rc;
+    HIP_TRY(l->h, l->ensemble.ens.read(out, (size_t)l->steps * l->ensemble.a.G));
+    return l->steps;
+}
+
+int nmpc_loop_ensemble_groups(nmpc_loop *l)
+{
+    return l && l->ensemble.made() ? l->ensemble.a.G : 0;
 }
 
 int nmpc_loop_plant_applied(nmpc_loop *l, double *out, int rows)

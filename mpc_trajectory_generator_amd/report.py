@@ -100,3 +100,26 @@ def fleet_runtime_text(loop, file_name: str = "") -> str:
         with open(file_name, "a") as fh:
             fh.write(more)
     return text + more
+
+
+def ensemble_text(stats, group: int = 0) -> str:
+    """One line per step for group ``group`` of an ensemble's records (``ensemble_stats()`` [steps, G] of a ``DeviceRecedingHorizon`` or
+    its host mirror): the mean position, the semi-axes of the position's covariance ellipse (the square roots of the eigenvalues of
+    [[xx, xy], [xy, yy]], the larger first), the standard deviation of the heading, the distance of the member furthest from the mean
+    with its robot index, and the share of the members that have arrived."""
+    st = np.asarray(stats)
+    if st.ndim != 2 or not 0 <= group < st.shape[1]:
+        raise ValueError(f"ensemble records of shape {st.shape} have no group {group}")
+    lines = [f"Ensemble group {group}", f"{'step':>5}{'mean x':>10}{'mean y':>10}{'axis a':>10}{'axis b':>10}{'sd theta':>10}{'furthest':>10}{'robot':>7}{'arrived':>9}",
+             "-" * 81]
+    for k, r in enumerate(st[:, group]):
+        n = int(r["n"])
+        if n == 0:
+            lines.append(f"{k + 1:>5}{'(no members)':>76}")
+            continue
+        xx, xy, yy, tt = (float(v) for v in r["cov"])
+        half, det = (xx + yy) / 2, np.hypot((xx - yy) / 2, xy)
+        a, b = np.sqrt(max(half + det, 0.0)), np.sqrt(max(half - det, 0.0))
+        lines.append(f"{k + 1:>5}{float(r['mean'][0]):>10.4f}{float(r['mean'][1]):>10.4f}{a:>10.4f}{b:>10.4f}{np.sqrt(max(tt, 0.0)):>10.4f}"
+                     f"{np.sqrt(max(float(r['far2']), 0.0)):>10.4f}{int(r['far_robot']):>7d}{int(r['arrived']) / n:>9.1%}")
+    return "\n".join(lines) + "\n"

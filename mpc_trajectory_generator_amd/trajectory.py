@@ -855,6 +855,73 @@ class Plant:
         return (*out, ids)
 
 
+ENSEMBLE_MAX_GROUPS = 65536  # G of an ensemble at the most (nmpc_loop_set_ensemble)
+
+
+@dataclasses.dataclass(frozen=True)
+class Ensemble:
+    """Per-group pose statistics after every step, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon``
+    alike: the robots are partitioned into ``groups`` groups, ``group_of`` [B] = the group of each robot (``None``: one group of
+    everybody; ``groups`` defaults to ``max(group_of) + 1``, or 1), and after every step one ``_lib.ENSEMBLE_DTYPE`` record per group
+    holds the member count, how many have arrived, the mean pose, the population covariance of the position and the variance of the
+    heading against that mean, and the member furthest from the mean position (``ensemble_stats()`` [steps, G]).  Every member counts,
+    active or retired, with its true pose; sums are taken by the fixed tree of ``ensemble_sum``.  A group may be empty.  It observes
+    only."""
+    group_of: object = None
+    groups: int = None
+
+    def checked(self, B: int):
+        """-> (group_of [B] as an int32 array or None, G); ValueError for what ``nmpc_loop_set_ensemble`` refuses and for a
+        ``group_of`` of another length."""
+        g = None
+        if self.group_of is not None:
+            g = np.ascontiguousarray(self.group_of, dtype=np.int32).reshape(-1)
+            if g.shape != (B,):
+                raise ValueError(f"ensemble: {len(g)} group ids for {B} robots")
+        G = self.groups
+        if G is None:
+            G = 1 if g is None or not len(g) else int(g.max()) + 1
+        G = int(G)
+        if G < 1 or G > ENSEMBLE_MAX_GROUPS:
+            raise ValueError(f"ensemble: {G} groups, 1 to {ENSEMBLE_MAX_GROUPS} are taken")
+        if g is None and G != 1:
+            raise ValueError("ensemble: groups != 1 without group_of")
+        if g is not None and ((g < 0) | (g >= G)).any():
+            raise ValueError("ensemble: group_of out of range")
+        return g, G
+
+
+def ensemble_sum(v):
+    """The ensemble's sum of one value per member, ``v`` [n] -> a float, or ``v`` [n, k] -> [k], column by
+    column: slot t of 256 starts at +0.0 and takes ``acc = acc + v[i]`` for i = t, t + 256, ... in ascending i; within each block of
+    64 slots, for off = 32, 16, 8, 4, 2, 1, ``a[l] = a[l] + a[l + off]`` for l < off; the four block sums give ``((w0 + w1) + w2) + w3``.
+    The device's bits: its workgroup of 256 threads and its wave reductions add in this order."""
+    v = np.asarray(v, dtype=np.float64)
+    flat = v.ndim == 1
+    v = v[:, None] if flat else v
+    n, k = v.shape
+    acc = np.zeros((256, k))
+    with np.errstate(all="ignore"):
+        for i in range(0, n, 256):
+            m = min(256, n - i)
+            acc[:m] = acc[:m] + v[i:i + m]
+        a = acc.reshape(4, 64, k)
+        off = 32
+        while off >= 1:
+            a[:, :off] = a[:, :off] + a[:, off:2 * off]
+            off >>= 1
+        w = a[:, 0]
+        out = ((w[0] + w[1]) + w[2]) + w[3]
+    return float(out[0]) if flat else out
+
+
+def no_ensemble_stats(steps: int, G: int):
+    """-> the records [steps, G] of empty groups: zeros, ``far2`` -1.0 and ``far_robot`` -1."""
+    rec = np.zeros((steps, G), dtype=_lib.ENSEMBLE_DTYPE)
+    rec["far2"], rec["far_robot"] = -1.0, -1
+    return rec
+
+
 def no_step_records(steps: int, B: int):
     """-> the initial records [steps, B]: exit_status -1, everything else 0."""
     rec = np.zeros((steps, B), dtype=_lib.STEP_RECORD_DTYPE)
@@ -919,10 +986,14 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     start from the measured poses (``measured()`` [B, 3]) and nothing else does; ``advance`` applies the disturbed controls and adds
     the process noise, ``state`` and ``traj`` are the true poses, ``last_u`` and the drive log the commanded controls;
     ``applied()`` [steps * s, B, 2] = the controls that acted, with ``plant.keep_applied``.
+
+    ``ensemble`` (an ``Ensemble``): ``ensemble_stats()`` [steps, G] holds one ``_lib.ENSEMBLE_DTYPE`` record per group and step
+    (DESIGN.md section 5.9), appended by ``step`` when everything else of the step is over -- behind ``advance`` and, on a retiring
+    fleet, ``retire`` -- from the true poses of all members, ``retired_at`` (a retiring fleet) or ``done``.  Nothing else reads it.
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None):
+                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None, ensemble=None):
         self.routes = list(routes)
         cfg, B = self.routes[0].cfg, len(starts)
         route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
@@ -978,6 +1049,44 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._ids = np.arange(B, dtype=np.uint32) if ids is None else ids
             self._told = self.state.copy()                                    # [B, 3]: the measured poses, the start states at first
             self._applied = []                                                # per trajectory row: [B, 2]
+        self.ensemble = ensemble
+        if ensemble is not None:
+            g, self._ens_G = ensemble.checked(B)
+            g = np.zeros(B, dtype=np.int32) if g is None else g
+            self._ens_members = [(int(v), np.nonzero(g == v)[0]) for v in np.unique(g)]      # members in ascending robot index
+            self._ens = []                                                    # per step: [G] records
+
+    def step(self, solve_fn):
+        out = super().step(solve_fn)
+        if self.ensemble is not None:
+            self._ensemble_update()
+        return out
+
+    def _ensemble_update(self):
+        """The ensemble's rule at the end of a step, for every group with a member: unfused f64, the sums by
+        ``ensemble_sum``, each product rounded before it enters the tree, and a furthest member that a false comparison (a NaN)
+        leaves alone; the members ascend, so the first largest r2 is the smallest robot index."""
+        rec = no_ensemble_stats(1, self._ens_G)[0]
+        arrived = self.done != 0 if self.active is None else self.retired_at >= 0
+        with np.errstate(all="ignore"):
+            for g, mem in self._ens_members:
+                n, pose = len(mem), self.state[mem]
+                mean = ensemble_sum(pose) / float(n)
+                d = pose - mean
+                dx, dy, dth = d[:, 0], d[:, 1], d[:, 2]
+                prod = np.stack([dx * dx, dx * dy, dy * dy, dth * dth], axis=1)
+                rec["n"][g], rec["arrived"][g] = n, int(arrived[mem].sum())
+                rec["mean"][g], rec["cov"][g] = mean, ensemble_sum(prod) / float(n)
+                r2 = prod[:, 0] + prod[:, 2]
+                seen = ~np.isnan(r2)
+                if seen.any():
+                    k = int(np.argmax(np.where(seen, r2, -1.0)))
+                    rec["far2"][g], rec["far_robot"][g] = r2[k], mem[k]
+        self._ens.append(rec)
+
+    def ensemble_stats(self):
+        """-> [steps, G] (``_lib.ENSEMBLE_DTYPE``): every group's record after every step taken; no steps without an ``ensemble``."""
+        return np.stack(self._ens) if self.ensemble is not None and self._ens else no_ensemble_stats(0, getattr(self, "_ens_G", 1))
 
     @property
     def controls(self):
@@ -1491,10 +1600,17 @@ class DeviceRecedingHorizon:
     section 5.9): ``nmpc_loop_plant_kernel`` in the place of the advance and, with a ``meas`` > 0, ``nmpc_loop_measure_kernel`` in front of
     the assembly.  ``applied()`` (with ``plant.keep_applied``, needs ``max_steps`` > 0) and ``measured()`` read the results.  Its host
     mirror is ``FleetRecedingHorizon`` with the same ``plant`` (tests/test_gpu_plant_loop.py).
+
+    ``ensemble`` (an ``Ensemble``, needs ``max_steps`` > 0): after every step one record per group -- member count, arrivals, mean pose,
+    covariance of the position, variance of the heading, the member furthest from the mean -- is kept on the device
+    (``nmpc_loop_set_ensemble``): ``nmpc_loop_ensemble_kernel``, one workgroup per group, the step's last kernel.
+    ``ensemble_stats()`` reads the table.  Its host mirror is ``FleetRecedingHorizon`` with the same ``ensemble``
+    (tests/test_gpu_ensemble_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
-                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None):
+                 route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None,
+                 ensemble=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -1586,6 +1702,14 @@ class DeviceRecedingHorizon:
             pl = _lib.NmpcPlant(int(plant.seed), (C.c_double * 2)(*gain), (C.c_double * 2)(*add), (C.c_double * 3)(*proc),
                                 (C.c_double * 3)(*meas), int(bool(plant.keep_applied)), 0)
             self._set(self.lib.nmpc_loop_set_plant(h, C.byref(pl), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self.ensemble = ensemble
+        if ensemble is not None:
+            try:
+                g, G = ensemble.checked(B)
+            except ValueError:
+                self.close()
+                raise
+            self._set(self.lib.nmpc_loop_set_ensemble(h, _lib.as_i32p(g), G))
         self.missions = missions
         self._leg_off = None
         if missions is not None:
@@ -1744,6 +1868,15 @@ class DeviceRecedingHorizon:
         out = np.empty((self.B, 3))
         self.solver._check(self.lib.nmpc_loop_plant_measured(self._l, _lib.as_dp(out)))
         return out
+
+    def ensemble_stats(self):
+        """-> [steps, G] (``_lib.ENSEMBLE_DTYPE``: n, arrived, far_robot, reserved, mean [3], cov [4], far2) after synchronising: every
+        group's record after every step taken (``ensemble=Ensemble(...)``; without it no steps)."""
+        rec = no_ensemble_stats(self.steps, max(1, self.lib.nmpc_loop_ensemble_groups(self._l)))      # (the loop's G: 0 without the stage)
+        n = self.lib.nmpc_loop_ensemble(self._l, rec.ctypes.data, self.steps)
+        if n < 0:
+            self.solver._check(n)
+        return rec[:n]
 
     def read(self):
         """-> (state [B,3], last_u [B,2], idx [B], done [B] bool, status [B]) after synchronising."""

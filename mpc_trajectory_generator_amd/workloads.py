@@ -208,6 +208,16 @@ def ensemble_fleet(route, start, B, idx0=0):
     return [route], np.zeros(B, dtype=np.int32), starts, np.full(B, int(idx0), dtype=np.int32)
 
 
+def grouped_ensemble(routes, route_of, starts, idx0, copies):
+    """-> (routes, route_of, starts, idx0, group_of): every robot of a base fleet of m repeated ``copies`` times, robot b a copy of base
+    robot b % m (as ``tiled_fleet``) and ``group_of[b]`` = that base robot, so the copies of one robot are interleaved with everybody
+    else's and no group's members are contiguous.  Under a ``trajectory.Plant`` with ``trajectory.Ensemble(group_of, groups=m)`` each
+    group is the Monte-Carlo study of one robot -- one route, one tuning -- and the loop compares m of them in one run."""
+    m = len(starts)
+    routes, route_of, starts, idx0 = tiled_fleet(routes, route_of, starts, idx0, int(copies))
+    return routes, route_of, starts, idx0, (np.arange(len(starts)) % m).astype(np.int32)
+
+
 def stale_idx0(idx0, behind):
     """-> the start indices moved back by ``behind`` samples, clipped at 0: robots whose window search starts that far behind where
     they stand, so that the closest sample lies deep inside the first window."""
@@ -281,6 +291,17 @@ def plant_differing(dev, host):
         elif a.tobytes() != np.ascontiguousarray(b, dtype=a.dtype).tobytes():
             bad.append(name)
     return bad
+
+
+def ensemble_differing(dev, host):
+    """``clearance_differing`` for the ensemble's records (``dev``: a ``DeviceRecedingHorizon`` with an ensemble or its
+    ``ensemble_stats()``, ``host``: its mirror or the mirror's ``ensemble_stats()``): the fields that are not byte-equal, or the shapes
+    if they differ."""
+    a = dev.ensemble_stats() if callable(getattr(dev, "ensemble_stats", None)) else np.asarray(dev)
+    b = host.ensemble_stats() if callable(getattr(host, "ensemble_stats", None)) else np.asarray(host)
+    if a.shape != b.shape:
+        return [f"ensemble_stats of shape {a.shape}, not {b.shape}"]
+    return [f for f in a.dtype.names if a[f].tobytes() != np.ascontiguousarray(b[f], dtype=a[f].dtype).tobytes()]
 
 
 LOG_PRODUCTS = ("controls", "step_records", "drive_summary", "step_totals")

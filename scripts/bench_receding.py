@@ -26,7 +26,12 @@ were to an obstacle the robot did not have in a slot at that step (found by an u
 relative sigma G on both controls, process noise of sigma P metres (and radians) per applied control, measurement noise of sigma M metres (and
 radians), seed S; a robot's id is its index in the whole fleet, so --split does not change its disturbances.  --ensemble (--routes 1): B copies of
 the fleet's robot 0, its start, reference sample and ellipses (workloads.ensemble_fleet), the Monte-Carlo study of one controller; the result line gains
-plant: the sigmas, and with --ensemble the spread of the final poses.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+plant: the sigmas, and with --ensemble the spread of the final poses.  --ensemble-stats [M]: the ensemble stage (nmpc_loop_set_ensemble, DESIGN.md
+section 5.9): without M the whole fleet is one group (with --ensemble: the study's result, on the device); with M every robot of the fleet --routes
+gives is repeated M times (workloads.grouped_ensemble: --batch x M robots, the copies of a robot one group, interleaved) and, under the plant, each
+group is the Monte-Carlo study of one robot.  The result line gains ensemble: from the device's records of the last step, per group (the first 8)
+the members, the mean pose, the standard deviations of x, y and the heading and the arrived count -- the records of the --split sub-fleets pooled
+on the host -- and with --ensemble the largest relative difference of those standard deviations from the host-side spread beside them.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -38,7 +43,7 @@ sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config                            # noqa: E402
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
-from mpc_trajectory_generator_amd.trajectory import DriveLog, FleetRecedingHorizon, MapMonitor, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.trajectory import DriveLog, Ensemble, FleetRecedingHorizon, MapMonitor, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
 from mpc_trajectory_generator_amd.workloads import moving_ellipses, route_fleet   # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -88,6 +93,9 @@ ap.add_argument("--plant-proc", type=float, default=0.0, metavar="P", help="devi
 ap.add_argument("--plant-meas", type=float, default=0.0, metavar="M", help="device loop only: measurement noise on x, y (metres) and theta (radians)")
 ap.add_argument("--plant-seed", type=int, default=0, metavar="S", help="the seed of the plant's disturbances")
 ap.add_argument("--ensemble", action="store_true", help="--routes 1: B copies of the fleet's robot 0 (a Monte-Carlo study under the plant)")
+ap.add_argument("--ensemble-stats", type=int, nargs="?", const=0, default=None, metavar="M",
+                help="device loop only: per-group pose statistics after every step, kept on the device; without M one group of everybody, with M "
+                     "every robot of the fleet M times (--batch x M robots), the copies of a robot one group")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
@@ -116,6 +124,11 @@ if min(args.plant_act, args.plant_proc, args.plant_meas) < 0 or (planted and arg
     ap.error("--plant-act, --plant-proc, --plant-meas: >= 0, on the device loop (no --host)")
 if args.ensemble and (args.routes != 1 or args.own_routes or args.host):
     ap.error("--ensemble: copies of one robot on the scene's route, on the device loop")
+if args.ensemble_stats is not None:
+    if args.host or args.steps < 1 or args.ensemble_stats < 0:
+        ap.error("--ensemble-stats [M]: M >= 1, on the device loop (no --host) with --steps >= 1")
+    if args.ensemble_stats and (args.ensemble or args.own_routes or args.legs > 1 or args.peers):
+        ap.error("--ensemble-stats M repeats the fleet --routes gives: not with --ensemble, --own-routes, --legs or --peers")
 sopts = {"max_total_inner": args.budget} if args.budget > 0 else {}
 if args.experiments:
     sopts["experiments"] = True
@@ -184,11 +197,23 @@ else:
     xs, ys = np.concatenate([r.x_ref for r in routes]), np.concatenate([r.y_ref for r in routes])
     jj = first[:, None] + np.minimum(n[:, None] - 1, i0[:, None] + rng.integers(0, 30, (B, K)))
     dyn = moving_ellipses(np.stack([xs[jj], ys[jj]], axis=2), rng)
+ens_group_of, ens_G = None, 0           # with --ensemble-stats: the group of every robot of the whole fleet, and their number
+if args.ensemble_stats is not None:
+    ens_group_of, ens_G = np.zeros(B, dtype=np.int32), 1
+    if args.ensemble_stats:
+        from mpc_trajectory_generator_amd.workloads import grouped_ensemble
+        routes, route_of, starts, i0, ens_group_of = grouped_ensemble([routes] if route_of is None else routes,
+                                                                     np.zeros(B, dtype=np.int32) if route_of is None else route_of,
+                                                                     starts, i0, args.ensemble_stats)
+        dyn = dyn and tuple(a[ens_group_of] for a in dyn)
+        B, ens_G = len(starts), B
 fleet = f", {args.routes} routes (frontend.random_fleet, seed 0)" if args.routes > 1 else ""
 if args.own_routes:
     fleet = f", every robot its own start and goal (workloads.own_route_fleet, seed 0; {len(routes)} routes planned on the device)"
 if args.ensemble:
     fleet += ", an ensemble: every robot a copy of the fleet's robot 0"
+if args.ensemble_stats:
+    fleet += f", every robot {args.ensemble_stats} times (workloads.grouped_ensemble: {ens_G} groups)"
 if planted:
     fleet += (f", disturbed plant (actuation {args.plant_act}, process {args.plant_proc}, measurement {args.plant_meas}, seed {args.plant_seed})")
 if args.peers:
@@ -233,12 +258,24 @@ if not args.host:
         return Plant(seed=args.plant_seed, act_gain=(args.plant_act,) * 2, proc=(args.plant_proc,) * 3, meas=(args.plant_meas,) * 3,
                      ids=np.asarray(ids, dtype=np.uint32)) if planted else None
 
+    def pooled(recs):
+        """the sub-fleets' records of one step [G] each -> the whole fleet's (n, arrived, mean [G, 3], cov [G, 4]): counts add, means weigh by
+        n, and a sub-fleet's second moments move from its own mean to the fleet's"""
+        n, arrived = sum(r["n"] for r in recs), sum(r["arrived"] for r in recs)
+        w = [r["n"] / np.maximum(n, 1) for r in recs]
+        mean = sum(wi[:, None] * r["mean"] for wi, r in zip(w, recs))
+        cov = 0.0
+        for wi, r in zip(w, recs):
+            d = r["mean"] - mean
+            cov = cov + wi[:, None] * (r["cov"] + np.stack([d[:, 0] * d[:, 0], d[:, 0] * d[:, 1], d[:, 1] * d[:, 1], d[:, 2] * d[:, 2]], axis=1))
+        return n, arrived, mean, cov
+
     def make_loop(sv, ids):
         sub_routes, sub_route_of = routes_of(ids)
         return DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                      route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
                                      missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None, crowd=crowd,
-                                     plant=plant_of(ids))
+                                     plant=plant_of(ids), ensemble=None if ens_group_of is None else Ensemble(ens_group_of[ids], groups=ens_G))
 
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
@@ -315,6 +352,15 @@ if not args.host:
             pose = np.concatenate([o[0] for o in outs])
             quality["plant"].update({"final_pose_mean": pose.mean(axis=0).tolist(), "final_pose_std": pose.std(axis=0).tolist()})
     from mpc_trajectory_generator_amd import _lib
+    if args.ensemble_stats is not None:
+        n, arrived, mean, cov = pooled([rh.ensemble_stats()[-1] for rh in loops])         # every sub-fleet's last step
+        std = np.sqrt(cov[:, [0, 2, 3]])
+        quality["ensemble"] = {"groups": ens_G, "copies": args.ensemble_stats or B, "members": n[:8].tolist(), "arrived": arrived[:8].tolist(),
+                               "mean": mean[:8].tolist(), "std": std[:8].tolist(),
+                               "device_bytes": int(sum(rh.max_steps * ens_G * _lib.ENSEMBLE_DTYPE.itemsize + 4 * (ens_G + 1 + rh.B) for rh in loops))}
+        if args.ensemble:
+            host_std = np.array(quality["plant"]["final_pose_std"])
+            quality["ensemble"]["std_rel_diff_from_host"] = float((np.abs(std[0] - host_std) / np.where(host_std > 0, host_std, 1.0)).max())
     if args.log:
         tot = [rh.step_totals() for rh in loops]
         summ = np.concatenate([rh.drive_summary() for rh in loops])
@@ -341,6 +387,7 @@ if not args.host:
                                + (f", clearance monitor in groups of {args.monitor}" if args.monitor else "")
                                + (f", map monitor on the scene's {args.map} polygons" if args.map else "")
                                + (", drive log" if args.log else "")
+                               + (f", ensemble statistics in {ens_G} group{'s' if ens_G > 1 else ''}" if args.ensemble_stats is not None else "")
                                + (f", at most {args.budget} PANOC iterations per solve (NotConvergedOutOfTime beyond)" if args.budget else "")
                                + (f", fleet split into {args.split} sub-fleets on {args.split} streams" if args.split > 1 else ""),
                    "kernel": solver.kernel_name},
