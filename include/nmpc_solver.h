@@ -650,6 +650,42 @@ int nmpc_loop_ensemble(nmpc_loop *l, nmpc_ensemble_stat *out, int max_steps);
 /* G, or 0 on a loop without the stage. */
 int nmpc_loop_ensemble_groups(nmpc_loop *l);
 
+/* ---- walls: the nearest points of the map's wall segments, as circles, on device --------------------
+ * The only static obstacles the assembly puts into p are circles on the vertices a route bends around; a wall between two corners, an
+ * obstacle the route merely passes and the boundary are not in p, and the map monitor can count wall hits but nothing prevents them.
+ * The walls are an opt-in stage of the loop (the rule: DESIGN.md section 5.9): every step, between the assembly of p and the solve --
+ * behind the crowd's and the peers' overlays, in front of the gather of a retiring loop -- each active robot's closest points on the E wall
+ * segments, measured against its predicted poses (X_k, Y_k), k = 0 .. N - 1 (those of the peers setters and of the crowd: with a plant
+ * that measures they start from the measured pose), become circles in the LAST M static-circle slots of its p.  Unfused f64 in the order
+ * written, `/` IEEE, no sqrt:
+ *   per edge e and stage k   the map monitor's wall distance: ex = x2 - x1, ey = y2 - y1, L2 = ex*ex + ey*ey; t = 0 unless L2 > 0, then
+ *                            t = ((X - x1)*ex + (Y - y1)*ey)/L2, `if (t < 0) t = 0; if (t > 1) t = 1`; cx = x1 + t*ex, cy = y1 + t*ey,
+ *                            dx = X - cx, dy = Y - cy, v = dx*dx + dy*dy
+ *   per edge                 D(e) from +inf takes v on the strict v < D, stages ascending (a NaN never lowers it, the first of equal stages
+ *                            stays); k*(e) is that stage and (cx, cy) of that stage the edge's centre; a candidate if D(e) < range*range
+ *   selection                the candidates in ascending (D, e) order; one is skipped if ddx*ddx + ddy*ddy < spacing*spacing against the
+ *                            centre of any candidate already taken (spacing = 0 skips nothing), otherwise taken; M taken at the most
+ *   placement                the m-th taken (m = 0, 1, ...) over circle slot Nobs - M + m of p as (cx, cy, radius); a slot that finds no
+ *                            candidate keeps what the assembly put there, zeros
+ *   record                   wall_edge [B][M] = the edge in that slot, wall_stage [B][M] = its k*, -1 for none
+ * The last M slots are free because the setter refuses a loop on which any of its R routes has n_vert + M > Nobs (under missions every
+ * route is a candidate for every robot): the assembly fills at most n_vert slots from the front and zeroes the rest every step.  A retired
+ * robot keeps its p and its record, a step with nobody active launches nothing for the stage.  The solver does not change: a circle is
+ * culled by its own radius.  The clearance monitor reads the circle slots of p as the solve read them, radius > 0, so its `circle`
+ * record sees the wall circles too: that is intended.
+ *   edge [n_edge][4]  x1 y1 x2 y2 per wall segment, every coordinate finite, 1 <= n_edge <= 1024; no polygon structure is needed
+ *   M                 circle slots given to the walls, 1 <= M <= Nobs and n_vert + M <= Nobs on every route
+ *   radius, range     finite and > 0;  spacing  finite and >= 0
+ * To be called once, before the loop's first step, in any order with the other setters; it makes the predicted poses exist as a crowd
+ * alone does.  NMPC_ERR_BAD_ARG with a message that names the function, and nothing changed or allocated, for a NULL edge (a NULL loop:
+ * NMPC_ERR_BAD_ARG), n_edge outside 1 .. 1024, a coordinate that is not finite, M < 1, M > Nobs, a route with n_vert + M > Nobs (the
+ * message names it), a radius or a range that is not finite and positive, a spacing that is negative or not finite, a call after a step,
+ * or a second call.  A loop without the stage enqueues what it enqueued before this function existed. */
+int nmpc_loop_set_walls(nmpc_loop *l, int n_edge, const double *edge, int M, double radius, double range, double spacing);
+/* Synchronises, then copies what is asked for (NULL = skip): wall_edge [B][M] and wall_stage [B][M] of each robot's last step, -1 for
+ * none.  NMPC_ERR_BAD_ARG on a loop without walls or before its first step. */
+int nmpc_loop_walls(nmpc_loop *l, int32_t *wall_edge, int32_t *wall_stage);
+
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);
 /* a/b and sqrt(a) as the device computes them: out_div/out_sqrt [n]. */

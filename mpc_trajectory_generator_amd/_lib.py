@@ -30,6 +30,7 @@ SYMBOLS = (
     "nmpc_loop_set_crowd", "nmpc_loop_crowd", "nmpc_loop_set_crowd_monitor", "nmpc_loop_crowd_clearance",
     "nmpc_loop_set_plant", "nmpc_loop_plant_applied", "nmpc_loop_plant_measured",
     "nmpc_loop_set_ensemble", "nmpc_loop_ensemble", "nmpc_loop_ensemble_groups",
+    "nmpc_loop_set_walls", "nmpc_loop_walls",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -369,6 +370,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_ensemble.restype = C.c_int
     lib.nmpc_loop_ensemble_groups.argtypes = [vp]
     lib.nmpc_loop_ensemble_groups.restype = C.c_int
+    lib.nmpc_loop_set_walls.argtypes = [vp, C.c_int, dp, C.c_int, C.c_double, C.c_double, C.c_double]
+    lib.nmpc_loop_set_walls.restype = C.c_int
+    lib.nmpc_loop_walls.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.nmpc_loop_walls.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]

@@ -751,6 +751,99 @@ __global__ __launch_bounds__(64) void nmpc_loop_crowd_monitor_kernel(LoopView L,
     }
 }
 
+// ---- walls: each robot's closest points on the map's wall segments as circles (nmpc_loop_set_walls; the rule is DESIGN.md section 5.9) ----
+// One kernel between the peers' and the solve: per active robot and edge the smallest wall distance (that of nmpc_loop_map_kernel) over its
+// predicted positions, the first M of the edges with D < range^2 in (D, e) order that keep `spacing` from the ones taken before them, each
+// one's closest point written over one of the LAST M circle slots of p.  The setter has made sure the assembly leaves those slots zero.
+constexpr int WALLS_MAX_EDGES = 1024;       // 16 edges per lane
+constexpr int WALLS_MAX_SLOTS = 64;         // M <= nobs <= 64 (nmpc_new)
+
+struct WallArgs {
+    int E, M;
+    double radius, range2, spacing2;
+    const double *edge;       // [E][4] x1 y1 x2 y2
+    const double *pred;       // [B][N][3]: the loop's predicted poses (nmpc_loop_predict_kernel)
+    int *wall_edge;           // [B][M]: the edge in circle slot nobs - M + m of p[b], -1 = none
+    int *wall_stage;          // [B][M]: the stage at which it came closest
+
+    static size_t lds_bytes(int E) { return (size_t)E * (3 * sizeof(double) + sizeof(int)) + WALLS_MAX_SLOTS * sizeof(int); }
+};
+
+// One wave per active robot, WallArgs::lds_bytes(E) of dynamic LDS: D | cx | cy [E] doubles, k* [E] and the taken edges [64] ints.  The
+// predicted positions go to LDS; lanes stride over the edges, each against all N stages in ascending order (a strict <: the first of equal
+// stages stays, a NaN lowers nothing), and park (D, cx, cy, k*) in LDS.  Then the walk: every round each lane offers the smallest (D, e) of
+// its candidates that lies behind the last one considered, wave_argmin names the next of the wave, and lanes 0 .. m - 1 test its centre
+// against the m taken before.  A round considers one candidate, so the walk ends after E rounds at the most, with M taken or with no
+// candidate left, whichever comes first: no loop's bounds depend on a pose.
+__global__ __launch_bounds__(64) void nmpc_loop_walls_kernel(LoopView L, WallArgs w)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    extern __shared__ double wall_lds[];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int N = L.N, E = w.E, M = w.M;
+    double *sD = wall_lds, *sx = sD + E, *sy = sx + E;
+    int *sk = (int *)(sy + E), *taken = sk + E;
+    for (int k = lane; k < N; k += 64) {
+        own[2 * k] = w.pred[((size_t)b * N + k) * 3];
+        own[2 * k + 1] = w.pred[((size_t)b * N + k) * 3 + 1];
+    }
+    __syncthreads();
+    for (int e = lane; e < E; e += 64) {
+        const double x1 = w.edge[4 * e], y1 = w.edge[4 * e + 1], x2 = w.edge[4 * e + 2], y2 = w.edge[4 * e + 3];
+        const double ex = x2 - x1, ey = y2 - y1;
+        const double L2 = ex * ex + ey * ey;
+        double D = __builtin_inf(), bx = 0.0, by = 0.0;
+        int bk = -1;
+        for (int k = 0; k < N; ++k) {
+            const double x = own[2 * k], y = own[2 * k + 1];
+            double t = 0.0;
+            if (L2 > 0.0) {
+                t = ((x - x1) * ex + (y - y1) * ey) / L2;
+                if (t < 0.0) t = 0.0;
+                if (t > 1.0) t = 1.0;
+            }
+            const double cx = x1 + t * ex, cy = y1 + t * ey;
+            const double dx = x - cx, dy = y - cy;
+            const double v = dx * dx + dy * dy;
+            if (v < D) { D = v; bx = cx; by = cy; bk = k; }
+        }
+        sD[e] = D; sx[e] = bx; sy[e] = by; sk[e] = bk;
+    }
+    __syncthreads();
+    double *pc = L.P + (size_t)b * L.n_p + L.p_circ() + 3 * (size_t)(L.nobs - M);
+    int *we = w.wall_edge + (size_t)b * M, *ws = w.wall_stage + (size_t)b * M;
+    double ld = -1.0;         // the last candidate considered: behind it comes every real one (D >= 0)
+    int le = -1;
+    int m = 0;
+    for (int round = 0; round < E && m < M; ++round) {
+        double d = __builtin_inf();
+        int j = LOOP_NONE;
+        for (int e = lane; e < E; e += 64) {
+            const double c = sD[e];
+            if (c < w.range2 && (c > ld || (c == ld && e > le)) && c < d) { d = c; j = e; }      // (a lane's edges ascend: of equal D the first stays)
+        }
+        wave_argmin(d, j);
+        if (j == LOOP_NONE) break;            // (wave-uniform) no candidate left: the remaining slots keep the assembly's zeros
+        ld = d; le = j;
+        const double cx = sx[j], cy = sy[j];
+        bool close = false;
+        if (lane < m) {
+            const int q = taken[lane];
+            const double ddx = cx - sx[q], ddy = cy - sy[q];
+            close = ddx * ddx + ddy * ddy < w.spacing2;
+        }
+        if (__any(close)) continue;           // (wave-uniform)
+        if (lane == 0) {
+            taken[m] = j;
+            pc[3 * m] = cx; pc[3 * m + 1] = cy; pc[3 * m + 2] = w.radius;
+            we[m] = j; ws[m] = sk[j];
+        }
+        ++m;
+        __syncthreads();                      // lane 0's store of taken[] before the next round's loads
+    }
+    for (int q = m + lane; q < M; q += 64) { we[q] = -1; ws[q] = -1; }
+}
+
 // ---- retirement: robots that reached their goal leave the loop (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9) ----
 struct RetireArgs {
     int *retired_at;          // [B]: -1 = active

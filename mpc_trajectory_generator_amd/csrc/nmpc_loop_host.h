@@ -3,7 +3,7 @@
 // after the handle, fail, HIP_TRY and solve_launch.
 //
 // A loop is its view (nmpc::LoopView: the shape, the per-robot arrays and the active list, the same for every kernel), its base
-// (assemble -> solve -> advance) and up to nine stages, each a sub-struct with its device buffers and the argument block of its own
+// (assemble -> solve -> advance) and up to ten stages, each a sub-struct with its device buffers and the argument block of its own
 // kernels.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop as it
 // was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the configuration
 // final.  The loop keeps ONE counter, `steps`: nmpc_loop_step derives everything that changes per step from it and the active count
@@ -107,6 +107,12 @@ struct LoopPlant {
     bool made() const { return on; }
     bool measures() const { return a.meas[0] > 0.0 || a.meas[1] > 0.0 || a.meas[2] > 0.0; }
 };
+struct LoopWalls {           // nmpc_loop_set_walls: one more kernel per step, between the peers' kernels and the solve
+    nmpc::WallArgs a{};
+    DevBuf<double> edge;             // [E][4]
+    DevBuf<int> wall_edge, wall_stage;   // [B][M] each
+    bool made() const { return edge != nullptr; }
+};
 struct LoopEnsemble {        // nmpc_loop_set_ensemble: one more kernel per step, the step's last
     nmpc::EnsembleArgs a{};
     DevBuf<int> goff, gmem;              // [G + 1], [B]: the groups' members, ascending inside a group
@@ -121,6 +127,7 @@ struct nmpc_loop {
     int steps = 0, max_steps = 0;        // steps taken: the loop's one counter (nmpc::LoopStep::after)
     int R = 1;
     std::vector<int> h_route_of;         // [B] as given at creation
+    std::vector<int> h_n_vert;           // [R]: every route's vertices, for the walls setter
     DevBuf<double> d_tab;        // every route's tables, one allocation
     DevBuf<nmpc::LoopRoute> d_routes;   // [R]
     DevBuf<int> d_route_of;      // [B]
@@ -128,7 +135,7 @@ struct nmpc_loop {
     DevBuf<int> d_idx;
     DevBuf<unsigned char> d_done;
     DevBuf<nmpc_status> d_st;
-    DevBuf<double> d_pred;       // [B][N][3]: every robot's predicted poses, made by the first of the peers and crowd setters
+    DevBuf<double> d_pred;       // [B][N][3]: every robot's predicted poses, made by the first of the peers, crowd and walls setters
     LoopPeers peers;
     LoopCrowd crowd;
     LoopRetire retire;
@@ -138,6 +145,7 @@ struct nmpc_loop {
     LoopLog log;
     LoopPlant plant;
     LoopEnsemble ensemble;
+    LoopWalls walls;
 };
 
 static bool route_ok(const nmpc_handle *h, const nmpc_route *r)
@@ -202,6 +210,7 @@ int nmpc_loop_new_routes(nmpc_handle *h, const nmpc_route *routes, int R, const 
         d.base = r->base_speed; d.radius = r->radius; d.pad = r->dyn_pad;
         for (int k = 0; k < 10; ++k) d.w[k] = r->weights[k];
     }
+    for (int i = 0; i < R; ++i) l->h_n_vert.push_back(routes[i].n_vert);
     l->h_route_of.assign(B, 0);
     if (route_of) l->h_route_of.assign(route_of, route_of + B);
     HIP_TRY(h, l->d_tab.upload(tab.data(), ntab));
@@ -556,6 +565,41 @@ int nmpc_loop_set_ensemble(nmpc_loop *l, const int32_t *group_of, int G)
     return NMPC_OK;
 }
 
+int nmpc_loop_set_walls(nmpc_loop *l, int n_edge, const double *edge, int M, double radius, double range, double spacing)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_walls", l->walls.made(), "the loop has its walls already")) return rc;
+    nmpc_handle *h = l->h;
+    const nmpc::LoopView &v = l->v;
+    const size_t B = (size_t)v.B;
+    if (!edge) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: edge is NULL");
+    if (n_edge < 1 || n_edge > nmpc::WALLS_MAX_EDGES) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: n_edge outside 1 .. 1024");
+    for (int i = 0; i < 4 * n_edge; ++i)
+        if (!(edge[i] >= -DBL_MAX && edge[i] <= DBL_MAX))
+            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_walls: a coordinate of edge " + std::to_string(i / 4) + " is not finite").c_str());
+    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: M < 1");
+    if (M > v.nobs || M > nmpc::WALLS_MAX_SLOTS) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: M > Nobs, no such circle slot");
+    for (int i = 0; i < l->R; ++i)
+        if (l->h_n_vert[i] + M > v.nobs)
+            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_walls: route " + std::to_string(i) + " has " + std::to_string(l->h_n_vert[i]) +
+                                              " vertices, n_vert + M > Nobs: its last M circle slots are not free").c_str());
+    for (const double x : {radius, range})
+        if (!(x > 0.0) || x > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: radius and range must be finite and positive");
+    if (!(spacing >= 0.0) || spacing > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: spacing must be finite and not negative");
+    LoopWalls st;
+    DevBuf<double> pred;           // the loop's, unless the peers or the crowd have made it
+    if (!l->d_pred) HIP_TRY(h, pred.alloc(B * v.N * 3));
+    HIP_TRY(h, st.edge.upload(edge, 4 * (size_t)n_edge));
+    HIP_TRY(h, st.wall_edge.alloc_fill(B * M, 0xFF));              // -1
+    HIP_TRY(h, st.wall_stage.alloc_fill(B * M, 0xFF));
+    nmpc::WallArgs &w = st.a;
+    w.E = n_edge; w.M = M; w.radius = radius; w.range2 = range * range; w.spacing2 = spacing * spacing;
+    w.edge = st.edge; w.pred = l->d_pred.p ? l->d_pred.p : pred.p; w.wall_edge = st.wall_edge; w.wall_stage = st.wall_stage;
+    l->walls = std::move(st);
+    if (pred) l->d_pred = std::move(pred);
+    return NMPC_OK;
+}
+
 // a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
 static int loop_nactive(nmpc_loop *l, int *n)
 {
@@ -612,6 +656,8 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
                 hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, v, p);
             }
         }
+        if (l->walls.made())
+            hipLaunchKernelGGL(nmpc::nmpc_loop_walls_kernel, dim3(n), dim3(64), nmpc::WallArgs::lds_bytes(l->walls.a.E), s, v, l->walls.a);
         if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, v, r.a);
         HIP_TRY(h, hipGetLastError());
         // warm start: previous controls and multipliers, penalty back to its initial value (the server's behaviour).  The solve runs on
@@ -746,6 +792,17 @@ int nmpc_loop_crowd(nmpc_loop *l, double *table, int32_t *seen)
     // step k (k = 0, 1, ...) wrote buffer (k & 1) ^ 1
     HIP_TRY(l->h, c.tab[((l->steps - 1) & 1) ^ 1].read(table, (size_t)c.a.D * l->v.N * 5));
     HIP_TRY(l->h, c.seen.read(seen, (size_t)l->v.B * c.a.M));
+    return NMPC_OK;
+}
+
+int nmpc_loop_walls(nmpc_loop *l, int32_t *wall_edge, int32_t *wall_stage)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    const LoopWalls &w = l->walls;
+    if (!w.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_walls: the loop has no walls (nmpc_loop_set_walls)");
+    if (l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_walls: before the loop's first step");
+    HIP_TRY(l->h, w.wall_edge.read(wall_edge, (size_t)l->v.B * w.a.M));
+    HIP_TRY(l->h, w.wall_stage.read(wall_stage, (size_t)l->v.B * w.a.M));
     return NMPC_OK;
 }
 

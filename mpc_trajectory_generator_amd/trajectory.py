@@ -515,6 +515,47 @@ class Crowd:
         return (p1, p2, freq, rx, ry, ang), sinus
 
 
+WALLS_MAX_EDGES = 1024       # E of a loop's walls at the most (nmpc_loop_set_walls)
+
+
+@dataclasses.dataclass(frozen=True)
+class Walls:
+    """How the robots of a loop see the map's walls, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon``
+    alike: every step, each active robot's closest points on the wall segments ``edges`` [E, 4] = (x1, y1, x2, y2), measured against its
+    predicted positions, closer than ``range`` and, among themselves, no closer than ``spacing``, take the LAST ``slots`` static-circle
+    slots of its parameter vector as circles of ``radius``.  No polygon structure is needed (``frontend.map_edges(...)[0]`` gives a
+    scene's edges, ``workloads.subdivided_map`` a finer cut).  Every route of the loop must leave the slots free: n_vert + slots <=
+    Nobs.  ``wall_edge`` and ``wall_stage`` [B, slots] name the edge in each slot and the stage at which it came closest (-1: none)."""
+    edges: object
+    slots: int
+    radius: float
+    range: float
+    spacing: float = 0.0
+
+    def checked(self, cfg, routes):
+        """-> edges [E, 4] float64, contiguous; ValueError for what ``nmpc_loop_set_walls`` refuses (``routes``: every route of the
+        loop, a mission's later legs included)."""
+        edges = np.ascontiguousarray(self.edges, dtype=np.float64)
+        if edges.ndim != 2 or edges.shape[1] != 4:
+            raise ValueError(f"walls: edges of shape {edges.shape}, not [E, 4]")
+        E = len(edges)
+        if E < 1 or E > WALLS_MAX_EDGES:
+            raise ValueError(f"walls: {E} edges, 1 to {WALLS_MAX_EDGES} are taken")
+        if not np.isfinite(edges).all():
+            raise ValueError("walls: a coordinate that is not finite")
+        if self.slots < 1 or self.slots > cfg.Nobs:
+            raise ValueError(f"walls: slots = {self.slots} with Nobs = {cfg.Nobs}")
+        for i, r in enumerate(routes):
+            if len(r.vertices) + self.slots > cfg.Nobs:
+                raise ValueError(f"walls: route {i} has {len(r.vertices)} vertices, slots = {self.slots} and Nobs = {cfg.Nobs}: no free circle slot")
+        for v in (self.radius, self.range):
+            if not (math.isfinite(v) and v > 0):
+                raise ValueError("walls: radius and range must be finite and positive")
+        if not (math.isfinite(self.spacing) and self.spacing >= 0):
+            raise ValueError("walls: spacing must be finite and not negative")
+        return edges
+
+
 PEER_GRID_CAP = 128          # cells per axis at the most (csrc/nmpc_loop.h)
 
 
@@ -993,7 +1034,7 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None, ensemble=None):
+                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None, ensemble=None, walls=None):
         self.routes = list(routes)
         cfg, B = self.routes[0].cfg, len(starts)
         route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
@@ -1055,6 +1096,11 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             g = np.zeros(B, dtype=np.int32) if g is None else g
             self._ens_members = [(int(v), np.nonzero(g == v)[0]) for v in np.unique(g)]      # members in ascending robot index
             self._ens = []                                                    # per step: [G] records
+        self.walls = walls
+        if walls is not None:
+            self._wall_edges = walls.checked(cfg, self.routes)
+            self.wall_edge = np.full((B, walls.slots), -1, dtype=np.int32)    # the edge in circle slot Nobs - slots + m of robot b's p (-1: none)
+            self.wall_stage = np.full((B, walls.slots), -1, dtype=np.int32)   # the stage at which it came closest
 
     def step(self, solve_fn):
         out = super().step(solve_fn)
@@ -1168,8 +1214,71 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._overlay_crowd(P)
         if self.peers is not None:
             self._overlay_peers(P)
+        if self.walls is not None:
+            self._overlay_walls(P)
         self._P_step = P                                                     # what this step's solve reads: the monitor's p
         return P
+
+    def _overlay_walls(self, P):
+        """The walls' rule on the parameter vectors of the active robots, in place.  Per edge and stage the map
+        monitor's wall distance (``MapMonitor.rows``) against the predicted positions; D(e) = the smallest over the stages, taken on a
+        strict ``<`` in ascending stage (a NaN never lowers it, the first of equal stages stays), with that stage and its closest point;
+        the candidates D < range^2 walked in (D, e) order, one skipped if its point lies closer than ``spacing`` to a point already
+        taken, until ``slots`` are taken; the m-th over circle slot Nobs - slots + m as (cx, cy, radius)."""
+        cfg, wl, edges = self.cfg, self.walls, self._wall_edges
+        N, M, E = cfg.N_hor, wl.slots, len(edges)
+        base = cfg.n_p - cfg.nx * N - cfg.Ndynobs * cfg.ndynobs * N - cfg.Nobs * cfg.nobs + (cfg.Nobs - M) * cfg.nobs
+        who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
+        if not len(who):
+            return
+        pred = self.predict()
+        r2, s2 = wl.range * wl.range, wl.spacing * wl.spacing
+        x1, y1, x2, y2 = (edges[:, k][None, :] for k in range(4))
+        self.wall_edge[who], self.wall_stage[who] = -1, -1
+        rows = max(1, (1 << 21) // E)                                        # robots per pass: bounds the [rows, E] tables
+        for r0 in range(0, len(who), rows):
+            me = who[r0:r0 + rows]
+            n, at = len(me), np.arange(len(me))
+            D, ks = np.full((n, E), np.inf), np.full((n, E), -1, dtype=np.int32)
+            CX, CY = np.zeros((n, E)), np.zeros((n, E))
+            with np.errstate(all="ignore"):
+                ex, ey = x2 - x1, y2 - y1
+                L2 = ex * ex + ey * ey
+                pos = L2 > 0
+                for k in range(N):                                           # min over the stages, in order
+                    X, Y = pred[me, k, 0][:, None], pred[me, k, 1][:, None]
+                    t = ((X - x1) * ex + (Y - y1) * ey) / np.where(pos, L2, 1.0)
+                    t = np.where(t < 0, 0.0, t)
+                    t = np.where(t > 1, 1.0, t)
+                    t = np.where(pos, t, 0.0)
+                    cx, cy = x1 + t * ex, y1 + t * ey
+                    dx, dy = X - cx, Y - cy
+                    v = dx * dx + dy * dy
+                    lower = v < D
+                    D, ks = np.where(lower, v, D), np.where(lower, np.int32(k), ks)
+                    CX, CY = np.where(lower, cx, CX), np.where(lower, cy, CY)
+                ok = D < r2
+            order = np.argsort(np.where(ok, D, np.inf), axis=1, kind="stable")       # (D, e)
+            ncand = ok.sum(axis=1)
+            taken = np.zeros(n, dtype=np.int64)
+            tx, ty = np.full((n, M), np.nan), np.full((n, M), np.nan)        # the centres taken (a NaN: not yet, nothing is close to it)
+            for r in range(int(ncand.max()) if n else 0):
+                live = (r < ncand) & (taken < M)
+                if not live.any():
+                    break
+                e = order[:, r]
+                cx, cy = CX[at, e], CY[at, e]
+                with np.errstate(invalid="ignore"):
+                    ddx, ddy = cx[:, None] - tx, cy[:, None] - ty
+                    close = (ddx * ddx + ddy * ddy < s2).any(axis=1)
+                take = live & ~close
+                i, m = at[take], taken[take]
+                b = me[i]
+                tx[i, m], ty[i, m] = cx[i], cy[i]
+                self.wall_edge[b, m], self.wall_stage[b, m] = e[i], ks[i, e[i]]
+                col = base + m * cfg.nobs
+                P[b, col], P[b, col + 1], P[b, col + 2] = cx[i], cy[i], wl.radius
+                taken[take] += 1
 
     def crowd_table(self):
         """-> [D, N, 5]: every obstacle of the crowd over the horizon as the last step wrote it (a step taken)."""
@@ -1606,11 +1715,16 @@ class DeviceRecedingHorizon:
     (``nmpc_loop_set_ensemble``): ``nmpc_loop_ensemble_kernel``, one workgroup per group, the step's last kernel.
     ``ensemble_stats()`` reads the table.  Its host mirror is ``FleetRecedingHorizon`` with the same ``ensemble``
     (tests/test_gpu_ensemble_loop.py).
+
+    ``walls`` (a ``Walls``): every step each active robot's closest points on the map's wall segments, measured against its predicted
+    poses, become circles in the last ``slots`` circle slots of its parameter vector (``nmpc_loop_set_walls``):
+    ``nmpc_loop_walls_kernel``, one wave per robot, between the peers' kernels and the solve.  ``walls()`` reads the edges and stages
+    chosen.  Its host mirror is ``FleetRecedingHorizon`` with the same ``walls`` (tests/test_gpu_walls_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
                  route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None,
-                 ensemble=None):
+                 ensemble=None, walls=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -1710,6 +1824,15 @@ class DeviceRecedingHorizon:
                 self.close()
                 raise
             self._set(self.lib.nmpc_loop_set_ensemble(h, _lib.as_i32p(g), G))
+        self._walls = walls
+        if walls is not None:
+            try:
+                edges = walls.checked(cfg, routes)
+            except ValueError:
+                self.close()
+                raise
+            self._set(self.lib.nmpc_loop_set_walls(h, len(edges), _lib.as_dp(edges), int(walls.slots), float(walls.radius), float(walls.range),
+                                                   float(walls.spacing)))
         self.missions = missions
         self._leg_off = None
         if missions is not None:
@@ -1811,6 +1934,14 @@ class DeviceRecedingHorizon:
         rec = np.empty(self.B, dtype=_lib.CROWD_CLEARANCE_DTYPE)
         self.solver._check(self.lib.nmpc_loop_crowd_clearance(self._l, rec.ctypes.data))
         return rec
+
+    def walls(self):
+        """-> (wall_edge, wall_stage) [B, slots] int32 after synchronising: the edge in circle slot Nobs - slots + m of each robot's
+        parameter vector at its last step and the stage at which it came closest, -1 for none.  Needs ``walls`` and a step taken."""
+        M = self._walls.slots if self._walls is not None else 0
+        edge, stage = np.empty((self.B, M), dtype=np.int32), np.empty((self.B, M), dtype=np.int32)
+        self.solver._check(self.lib.nmpc_loop_walls(self._l, _lib.as_i32p(edge), _lib.as_i32p(stage)))
+        return edge, stage
 
     def map_clearance(self):
         """-> the map monitor's records [B] (``_lib.MAP_CLEARANCE_DTYPE``: wall2, wall_row, wall_edge, hits, hit_row, hit_poly, reserved)

@@ -304,6 +304,30 @@ def ensemble_differing(dev, host):
     return [f for f in a.dtype.names if a[f].tobytes() != np.ascontiguousarray(b[f], dtype=a[f].dtype).tobytes()]
 
 
+def walls_differing(dev, host):
+    """What the walls keep (``dev``: a ``DeviceRecedingHorizon`` with walls, ``host``: its mirror) -> the names out of wall_edge and
+    wall_stage that are not equal (the circles themselves are part of P)."""
+    got = dict(zip(("wall_edge", "wall_stage"), dev.walls()))
+    return [n for n, a in got.items() if a.shape != getattr(host, n).shape or not np.array_equal(a, getattr(host, n))]
+
+
+def subdivided_map(edges, poly_off, pieces):
+    """-> (edges [E * pieces, 4], poly_off): every edge of a map (``frontend.map_edges``) cut into ``pieces`` collinear pieces, in the
+    edge's direction, polygon by polygon as before: piece i runs from a + (i / pieces) * (b - a) to the next piece's start, and the last
+    ends exactly at the original end point b.  ``pieces`` = 1 gives the map back.  For tests and benchmarks with many edges;
+    ``trajectory.MapMonitor`` and ``trajectory.Walls`` take the result."""
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1, 4)
+    pieces = int(pieces)
+    if pieces < 1:
+        raise ValueError("subdivided_map: pieces < 1")
+    a, b = edges[:, None, 0:2], edges[:, None, 2:4]
+    f = (np.arange(pieces + 1, dtype=np.float64) / float(pieces))[None, :, None]
+    pts = a + f * (b - a)                                                   # [E, pieces + 1, 2]
+    pts[:, 0], pts[:, -1] = edges[:, 0:2], edges[:, 2:4]
+    out = np.concatenate([pts[:, :-1], pts[:, 1:]], axis=2).reshape(-1, 4)
+    return np.ascontiguousarray(out), (np.asarray(poly_off, dtype=np.int64) * pieces).astype(np.int32)
+
+
 LOG_PRODUCTS = ("controls", "step_records", "drive_summary", "step_totals")
 LOG_CLOCK_FIELDS = ("solve_time_ms", "solve_ms_max")      # read from a clock: no two runs agree on them
 

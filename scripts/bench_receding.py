@@ -31,7 +31,12 @@ section 5.9): without M the whole fleet is one group (with --ensemble: the study
 gives is repeated M times (workloads.grouped_ensemble: --batch x M robots, the copies of a robot one group, interleaved) and, under the plant, each
 group is the Monte-Carlo study of one robot.  The result line gains ensemble: from the device's records of the last step, per group (the first 8)
 the members, the mean pose, the standard deviations of x, y and the heading and the arrived count -- the records of the --split sub-fleets pooled
-on the host -- and with --ensemble the largest relative difference of those standard deviations from the host-side spread beside them.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
+on the host -- and with --ensemble the largest relative difference of those standard deviations from the host-side spread beside them.
+--walls M: the walls stage (nmpc_loop_set_walls): every step each robot's closest points on the scene's true walls
+(frontend.map_edges, with --walls-pieces P every edge cut into P pieces by workloads.subdivided_map) within --walls-range metres of its predicted
+path, no closer to each other than --walls-spacing, become circles of --walls-radius (default vehicle_width / 2 + vehicle_margin) in the last M
+static-circle slots of its p; the result line gains walls: the edges and the share of those slots filled at the last step, and with --map the
+map_clearance beside it is the closest approach with the walls seen.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -96,6 +101,12 @@ ap.add_argument("--ensemble", action="store_true", help="--routes 1: B copies of
 ap.add_argument("--ensemble-stats", type=int, nargs="?", const=0, default=None, metavar="M",
                 help="device loop only: per-group pose statistics after every step, kept on the device; without M one group of everybody, with M "
                      "every robot of the fleet M times (--batch x M robots), the copies of a robot one group")
+ap.add_argument("--walls", type=int, default=0, metavar="M",
+                help="device loop only: M > 0 of the static-circle slots go to the closest points on the scene's walls (every route must leave them free)")
+ap.add_argument("--walls-range", type=float, default=2.0, metavar="R", help="with --walls: how far from its predicted path a robot sees a wall, in metres")
+ap.add_argument("--walls-spacing", type=float, default=0.0, metavar="S", help="with --walls: no two wall circles of a robot closer than this, in metres")
+ap.add_argument("--walls-radius", type=float, default=None, metavar="RC", help="with --walls: the circles' radius (default vehicle_width / 2 + vehicle_margin)")
+ap.add_argument("--walls-pieces", type=int, default=1, metavar="P", help="with --walls: every edge of the map cut into P pieces (26 P edges, 1024 at the most)")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
@@ -119,6 +130,8 @@ if args.crowd and (args.host or args.steps < 1):
     ap.error("--crowd is the device loop's: it needs the device loop (no --host) and --steps >= 1")
 if (args.crowd_watch or args.crowd < 0) and args.crowd < 1:
     ap.error("--crowd D: D >= 1, and --crowd-watch goes with it")
+if args.walls < 0 or (args.walls and (args.host or args.steps < 1)) or args.walls_pieces < 1:
+    ap.error("--walls M: M >= 1, on the device loop (no --host) with --steps >= 1; --walls-pieces P: P >= 1")
 planted = args.plant_act > 0 or args.plant_proc > 0 or args.plant_meas > 0
 if min(args.plant_act, args.plant_proc, args.plant_meas) < 0 or (planted and args.host):
     ap.error("--plant-act, --plant-proc, --plant-meas: >= 0, on the device loop (no --host)")
@@ -162,6 +175,14 @@ if args.crowd:
     from mpc_trajectory_generator_amd.trajectory import Crowd
     from mpc_trajectory_generator_amd.workloads import crowd_ellipses
     crowd = Crowd(crowd_ellipses(cfg, args.scene, args.crowd, 2), args.crowd_slots, args.crowd_range, watch=args.crowd_watch)
+
+walls = None
+if args.walls:
+    from mpc_trajectory_generator_amd.frontend import map_edges, scene_planner
+    from mpc_trajectory_generator_amd.trajectory import Walls
+    from mpc_trajectory_generator_amd.workloads import subdivided_map
+    walls = Walls(subdivided_map(*map_edges(scene_planner(cfg, args.scene)), args.walls_pieces)[0], args.walls,
+                  cfg.vehicle_width / 2 + cfg.vehicle_margin if args.walls_radius is None else args.walls_radius, args.walls_range, args.walls_spacing)
 
 planning = {}
 legs_of = None
@@ -223,6 +244,9 @@ if args.peers:
 if args.crowd:
     fleet += (f", a crowd of {args.crowd} moving obstacles (workloads.crowd_ellipses, seed 2), {args.crowd_slots} crowd slots per robot, "
               f"range {args.crowd_range} m" + (", crowd observer" if args.crowd_watch else "") + ("" if args.peers else f", {K} scripted ellipses"))
+if walls is not None:
+    fleet += (f", {args.walls} wall slots per robot over {len(walls.edges)} edges, range {args.walls_range} m, spacing {args.walls_spacing} m, "
+              f"radius {walls.radius} m")
 solver = BatchSolver(cfg, max_batch=B, **sopts)
 missions_of = lambda ids: None
 routes_of = lambda ids: (routes, None if route_of is None else route_of[ids])
@@ -275,7 +299,8 @@ if not args.host:
         return DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                      route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
                                      missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None, crowd=crowd,
-                                     plant=plant_of(ids), ensemble=None if ens_group_of is None else Ensemble(ens_group_of[ids], groups=ens_G))
+                                     plant=plant_of(ids), ensemble=None if ens_group_of is None else Ensemble(ens_group_of[ids], groups=ens_G),
+                                     walls=walls)
 
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
@@ -324,7 +349,13 @@ if not args.host:
     if args.map:
         rec = np.concatenate([rh.map_clearance() for rh in loops])
         quality["map_clearance"] = {"polygons": args.map, "edges": len(map_monitor.edges), "robots_hit_frac": float((rec["hits"] > 0).mean()),
-                                    "rows_hit": int(rec["hits"].sum()), "min_wall_m": float(np.sqrt(rec["wall2"].min()))}
+                                    "rows_hit": int(rec["hits"].sum()), "min_wall_m": float(np.sqrt(rec["wall2"].min())),
+                                    "median_wall_m": float(np.sqrt(np.median(rec["wall2"])))}
+    if walls is not None:
+        edge = np.concatenate([rh.walls()[0] for rh in loops])            # the last step's
+        quality["walls"] = {"edges": len(walls.edges), "slots": args.walls, "range_m": args.walls_range, "spacing_m": args.walls_spacing,
+                            "radius_m": walls.radius, "slots_filled_frac": float((edge >= 0).mean()),
+                            "robots_with_a_wall_frac": float((edge >= 0).any(axis=1).mean())}
     if args.crowd:
         seen = np.concatenate([rh.crowd_seen() for rh in loops])          # the last step's
         quality["crowd"] = {"obstacles": args.crowd, "slots": args.crowd_slots, "range_m": args.crowd_range,
