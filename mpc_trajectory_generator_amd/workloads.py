@@ -200,6 +200,19 @@ def tiled_fleet(routes, route_of, starts, idx0, copies):
         np.asarray(idx0)[rows].astype(np.int32)
 
 
+def placed_fleet(routes, route_of, starts, idx0, places):
+    """-> (routes, route_of, starts, idx0) of the same robots in another order: ``places`` = {position: robot} puts each named robot
+    at its position by swapping it with whoever stands there, in the order given (a robot named twice follows its swaps).  Without
+    peers and plant ids the robots of a loop do not depend on each other, so only the index a robot is known by changes: the way to
+    put a robot chosen on a dry run where a kernel's strides and chunks meet it."""
+    order = np.arange(len(starts))
+    for pos, robot in places.items():
+        at = int(np.nonzero(order == robot)[0][0])
+        order[[pos, at]] = order[[at, pos]]
+    return list(routes), np.asarray(route_of)[order].astype(np.int32), np.array(starts, dtype=np.float64)[order], \
+        np.asarray(idx0)[order].astype(np.int32)
+
+
 def ensemble_fleet(route, start, B, idx0=0):
     """-> (routes, route_of, starts, idx0): B copies of one robot on ``route``, at the pose ``start`` and reference sample ``idx0``.
     Without a plant every row of a loop over it is the same; under a ``trajectory.Plant`` robot b draws the disturbances of id b: the
