@@ -440,6 +440,44 @@ int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map);
 /* Synchronises, then copies the records out [B]; on a loop without the stage the initial record everywhere. */
 int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out);
 
+/* ---- track monitor: how closely each robot followed its route, on device --------------------------
+ * The controller's cost is built around the distance to the route (cte_penalty, q, qtheta), and the reference's users judge a tuning by
+ * laying the driven path over the planned one (src/eval_diff_configs.py, src/gen_res_diff_maps.py).  The track monitor is an opt-in
+ * stage of the loop that keeps that comparison on the device (the rule: DESIGN.md section 5.9).  It observes only: no p, u, y, state,
+ * status, trajectory or other record differs by a bit from the loop without it.  One more kernel per step, after the advance (or the
+ * plant) and the clearance, map and crowd monitors and before the log and the missions' dispatch, over the robots the step drove
+ * (those it retires at its end included).  With s = num_steps_taken, step n appends the trajectory rows r = n*s + 1 + i, i = 0 .. s - 1;
+ * (x, y, th) is the pose of row r (with a plant the true pose) and the route is routes[route_of[b]] as the step found it, so under
+ * missions a row is measured against the leg it was driven on.  Its polyline has the points Q_j = (x_ref[j], y_ref[j]), j = 0 ..
+ * n_ref - 1, and n_seg = max(n_ref - 1, 1) segments, segment j from Q_j to Q_e, e = min(j + 1, n_ref - 1) (n_ref = 1: one segment of
+ * zero length).  Unfused f64 in the order written, IEEE division, no sqrt; a comparison that is false (a NaN) has the literal consequence:
+ *   squared distance to segment j: ex = x2 - x1, ey = y2 - y1, L2 = ex*ex + ey*ey; t = 0 unless L2 > 0, then t = ((x - x1)*ex +
+ *     (y - y1)*ey)/L2; if (t < 0 && j > 0) t = 0; if (t > 1) t = 1; cx = x1 + t*ex, cy = y1 + t*ey, dx = x - cx, dy = y - cy,
+ *     v = dx*dx + dy*dy.  Segment 0 is NOT clamped below: the reference's table begins one sample after the start
+ *     (src/mpc/mpc_generator.py:17-57), and a robot still leaving its start, or the end of its previous leg, is on the line
+ *   per row: (v*, j*) from (+inf, -1), the segments ascending, taking v on the strict v < v* (the first minimal segment stays, a NaN is
+ *     passed over).  j* = -1 (a NaN pose): the row adds 1 to `rows` and nothing else.  Otherwise d = th - theta_ref[e*], e* = min(j* + 1,
+ *     n_ref - 1), a = d < 0 ? -d : d.  The heading error is NOT wrapped: the cost does not wrap either (cost_fn,
+ *     src/mpc/mpc_generator.py:59-63), so this is the error the controller itself sees
+ *   the record, in row order: rows += 1; cte2_sum = cte2_sum + v*; dth2_sum = dth2_sum + d*d; if v* > cte2_max: cte2_max = v*,
+ *     cte_row = r, cte_seg = j*; if a > dth_max: dth_max = a, dth_row = r; last_seg = j* (progress along the route: it drops when a new
+ *     leg begins); if v* > tol*tol: off_rows += 1, and off_row = r if it was -1.  Both maxima are strict: the earliest row stays, and
+ *     a robot exactly on its route keeps -1
+ * Initially 0, 0, 0, 0, 0, -1, -1, -1, -1, 0, -1, 0.  A robot retired earlier keeps its record, a step with nobody active launches
+ * nothing for this stage, records run across legs.  sizeof(nmpc_tracking) == 64.
+ * To be called once, before the loop's first step, in any order with the other setters, on a loop that records its trajectory.
+ * NMPC_ERR_BAD_ARG with a message that names the function, and nothing changed or allocated, for a tol that is negative or not finite
+ * (a NULL loop: NMPC_ERR_BAD_ARG), a call after a step, a second call or a loop with max_steps == 0.  A loop without the stage
+ * enqueues what it enqueued before this function existed. */
+typedef struct nmpc_tracking {           /* 64 bytes */
+    double cte2_max, cte2_sum, dth_max, dth2_sum;
+    int32_t rows, cte_row, cte_seg, dth_row, last_seg, off_rows, off_row, reserved;
+} nmpc_tracking;
+int nmpc_loop_set_track_monitor(nmpc_loop *l, double tol);
+/* Synchronises, then copies the records out [B] (before the first step: the initial records); NMPC_ERR_BAD_ARG on a loop without the
+ * stage. */
+int nmpc_loop_tracking(nmpc_loop *l, nmpc_tracking *out);
+
 /* ---- drive log: each robot's applied controls and solve outcomes, on device -----------------------
  * The reference's PathGenerator.run gives back the path, the controls that were applied and how long each solve took, and reports a
  * bad exit status at the step where it occurs (src/path_generator.py:385-394,431-437).  The drive log is an opt-in stage of the loop

@@ -31,6 +31,7 @@ SYMBOLS = (
     "nmpc_loop_set_plant", "nmpc_loop_plant_applied", "nmpc_loop_plant_measured",
     "nmpc_loop_set_ensemble", "nmpc_loop_ensemble", "nmpc_loop_ensemble_groups",
     "nmpc_loop_set_walls", "nmpc_loop_walls",
+    "nmpc_loop_set_track_monitor", "nmpc_loop_tracking",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
 
@@ -104,6 +105,12 @@ assert CLEARANCE_DTYPE.itemsize == 40
 MAP_CLEARANCE_DTYPE = np.dtype([("wall2", "<f8"), ("wall_row", "<i4"), ("wall_edge", "<i4"), ("hits", "<i4"),
                                 ("hit_row", "<i4"), ("hit_poly", "<i4"), ("reserved", "<i4")])
 assert MAP_CLEARANCE_DTYPE.itemsize == 32
+
+# nmpc_tracking: how far a robot was from its route, in position and heading, and the rows at which (nmpc_loop_set_track_monitor)
+TRACKING_DTYPE = np.dtype([("cte2_max", "<f8"), ("cte2_sum", "<f8"), ("dth_max", "<f8"), ("dth2_sum", "<f8"),
+                           ("rows", "<i4"), ("cte_row", "<i4"), ("cte_seg", "<i4"), ("dth_row", "<i4"), ("last_seg", "<i4"),
+                           ("off_rows", "<i4"), ("off_row", "<i4"), ("reserved", "<i4")])
+assert TRACKING_DTYPE.itemsize == 64
 
 # nmpc_peer_grid: the grid the peers of a step were found through (nmpc_loop_set_peers_grid)
 PEER_GRID_DTYPE = np.dtype([("origin", "<f8", 2), ("h", "<f8", 2), ("W", "<f8", 2), ("nx", "<i4"), ("ny", "<i4"), ("filed", "<i4"), ("reserved", "<i4")])
@@ -338,6 +345,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_map_monitor.restype = C.c_int
     lib.nmpc_loop_map_clearance.argtypes = [vp, vp]
     lib.nmpc_loop_map_clearance.restype = C.c_int
+    lib.nmpc_loop_set_track_monitor.argtypes = [vp, C.c_double]
+    lib.nmpc_loop_set_track_monitor.restype = C.c_int
+    lib.nmpc_loop_tracking.argtypes = [vp, vp]
+    lib.nmpc_loop_tracking.restype = C.c_int
     lib.nmpc_loop_set_missions.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.nmpc_loop_set_missions.restype = C.c_int
     lib.nmpc_loop_legs.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

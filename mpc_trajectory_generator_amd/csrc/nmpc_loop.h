@@ -1107,6 +1107,87 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(LoopView L, LoopStep 
     }
 }
 
+// ---- track monitor: how far each robot was from the route it was asked to follow (nmpc_loop_set_track_monitor; the rule is DESIGN.md
+// section 5.9).  It observes: the record is the only thing it writes.  The route is routes[route_of[b]] as the step found it (the dispatch
+// comes after), its polyline Q_j = (x_ref[j], y_ref[j]), n_seg = max(n_ref - 1, 1) segments, segment j from Q_j to Q_e, e = min(j + 1,
+// n_ref - 1).  For the pose (x, y, th) of row r, unfused f64 in the order written, no sqrt:
+//   segment j   ex = x2 - x1, ey = y2 - y1, L2 = ex*ex + ey*ey; t = 0 unless L2 > 0, then t = ((x - x1)*ex + (y - y1)*ey)/L2;
+//               `if (t < 0 && j > 0) t = 0; if (t > 1) t = 1` (segment 0 runs on backwards: the table begins one sample after the start);
+//               dx = x - (x1 + t*ex), dy = y - (y1 + t*ey), v = dx*dx + dy*dy
+//   row         (v*, j*) = the first smallest v over the segments, from (+inf, -1) by a strict <: a NaN is passed over.  j* = -1: the row
+//               counts in `rows` and nowhere else.  Otherwise d = th - theta_ref[e*], e* = min(j* + 1, n_ref - 1), a = |d|, not wrapped
+//               (the cost does not wrap either), and the record takes: rows += 1; cte2_sum += v*; dth2_sum += d*d; a strictly larger v*
+//               (cte2_max, cte_row, cte_seg); a strictly larger a (dth_max, dth_row); last_seg = j*; if v* > tol*tol: off_rows += 1 and
+//               off_row = r if it was -1
+struct TrackArgs {
+    double tol2;              // tol * tol
+    nmpc_tracking *rec;       // [B]
+};
+
+// One wave per robot the step drove, after the advance (or the plant: the true poses) and the other monitors, before the dispatch: the
+// robot's s new poses go to LDS.  Row by row, lanes stride over the segments (consecutive lanes read consecutive samples of x_ref and
+// y_ref through the cache), each lane keeps the first minimum of its own ascending segments, wave_argmin names the row's, and lane 0
+// folds the row into the record, which it holds in registers from before the first row to after the last.  Every loop is bounded by s
+// or n_seg.
+__global__ __launch_bounds__(64) void nmpc_loop_track_kernel(LoopView L, LoopStep stp, AssembleArgs g, TrackArgs k)
+{
+    __shared__ double own[3 * NMPC_MAX_HORIZON];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    // the robot's route: the same for the whole wave (read before any store, so that the loads can be scalar)
+    const LoopRoute &rt = g.routes[L.route_of[b]];
+    const double *xr = g.tab + rt.xr, *yr = g.tab + rt.yr, *thr = g.tab + rt.thr;
+    const int n = rt.n_ref, n_seg = n > 1 ? n - 1 : 1, s = L.s, row0 = stp.traj_row;
+    for (int i = lane; i < s; i += 64) {
+        const double *row = L.row(row0 + i, b);
+        own[3 * i] = row[0];
+        own[3 * i + 1] = row[1];
+        own[3 * i + 2] = row[2];
+    }
+    __syncthreads();
+    nmpc_tracking c = k.rec[b];
+    for (int i = 0; i < s; ++i) {
+        const double x = own[3 * i], y = own[3 * i + 1], th = own[3 * i + 2];
+        const int r = row0 + i;
+        double bv = __builtin_inf();
+        int bj = LOOP_NONE;
+        for (int j = lane; j < n_seg; j += 64) {
+            const int e = j + 1 < n ? j + 1 : n - 1;
+            const double x1 = xr[j], y1 = yr[j], x2 = xr[e], y2 = yr[e];
+            const double ex = x2 - x1, ey = y2 - y1;
+            const double L2 = ex * ex + ey * ey;
+            double t = 0.0;
+            if (L2 > 0.0) {
+                t = ((x - x1) * ex + (y - y1) * ey) / L2;
+                if (t < 0.0 && j > 0) t = 0.0;
+                if (t > 1.0) t = 1.0;
+            }
+            const double cx = x1 + t * ex, cy = y1 + t * ey;
+            const double dx = x - cx, dy = y - cy;
+            const double v = dx * dx + dy * dy;
+            if (v < bv) { bv = v; bj = j; }               // (a lane's segments ascend: among equal values the first stays)
+        }
+        wave_argmin(bv, bj);
+        if (lane == 0) {
+            c.rows += 1;
+            if (bj != LOOP_NONE) {
+                const int e = bj + 1 < n ? bj + 1 : n - 1;
+                const double d = th - thr[e];
+                const double a = d < 0.0 ? -d : d;
+                c.cte2_sum = c.cte2_sum + bv;
+                c.dth2_sum = c.dth2_sum + d * d;
+                if (bv > c.cte2_max) { c.cte2_max = bv; c.cte_row = r; c.cte_seg = bj; }
+                if (a > c.dth_max) { c.dth_max = a; c.dth_row = r; }
+                c.last_seg = bj;
+                if (bv > k.tol2) {
+                    c.off_rows += 1;
+                    if (c.off_row == -1) c.off_row = r;
+                }
+            }
+        }
+    }
+    if (lane == 0) k.rec[b] = c;
+}
+
 // ---- drive log: each robot's applied controls and solve outcomes (nmpc_loop_set_log; the rule is DESIGN.md section 5.9).  It observes:
 // its four tables are the only things it writes.
 struct LogArgs {

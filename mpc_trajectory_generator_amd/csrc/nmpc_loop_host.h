@@ -3,7 +3,7 @@
 // after the handle, fail, HIP_TRY and solve_launch.
 //
 // A loop is its view (nmpc::LoopView: the shape, the per-robot arrays and the active list, the same for every kernel), its base
-// (assemble -> solve -> advance) and up to ten stages, each a sub-struct with its device buffers and the argument block of its own
+// (assemble -> solve -> advance) and up to eleven stages, each a sub-struct with its device buffers and the argument block of its own
 // kernels.  A setter makes its stage whole in a local and moves it into the loop, so a refused or failed call leaves the loop as it
 // was, and a stage is on when it is made.  Setters come in any order but not after the first step, so step 0 finds the configuration
 // final.  The loop keeps ONE counter, `steps`: nmpc_loop_step derives everything that changes per step from it and the active count
@@ -81,6 +81,12 @@ struct LoopMap {             // nmpc_loop_set_map_monitor: one more kernel per s
     DevBuf<nmpc_map_clearance> rec;  // [B]
     bool made() const { return rec != nullptr; }
 };
+// nmpc_loop_set_track_monitor: one more kernel per step, after the advance and the other monitors and before the log and the dispatch
+struct LoopTrack {
+    nmpc::TrackArgs a{};
+    DevBuf<nmpc_tracking> rec;       // [B]
+    bool made() const { return rec != nullptr; }
+};
 // nmpc_loop_set_missions: a robot at its goal takes up the next route of its mission; one more kernel per step, before the compaction
 struct LoopMissions {
     nmpc::DispatchArgs a{};
@@ -141,6 +147,7 @@ struct nmpc_loop {
     LoopRetire retire;
     LoopMonitor monitor;
     LoopMap map;
+    LoopTrack track;
     LoopMissions missions;
     LoopLog log;
     LoopPlant plant;
@@ -454,6 +461,25 @@ int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map)
     return NMPC_OK;
 }
 
+static_assert(sizeof(nmpc_tracking) == 64, "nmpc_tracking is 64 bytes");
+static const nmpc_tracking TRACKING_NONE = {0.0, 0.0, 0.0, 0.0, 0, -1, -1, -1, -1, 0, -1, 0};
+
+int nmpc_loop_set_track_monitor(nmpc_loop *l, double tol)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, "nmpc_loop_set_track_monitor", l->track.made(), "the loop has its track monitor already")) return rc;
+    nmpc_handle *h = l->h;
+    const int B = l->v.B;
+    if (!(tol >= 0.0) || tol > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_track_monitor: tol must be finite and not negative");
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_track_monitor: the loop records no trajectory (max_steps == 0)");
+    LoopTrack st;
+    const std::vector<nmpc_tracking> none(B, TRACKING_NONE);
+    HIP_TRY(h, st.rec.upload(none.data(), B));
+    st.a.tol2 = tol * tol; st.a.rec = st.rec;
+    l->track = std::move(st);
+    return NMPC_OK;
+}
+
 int nmpc_loop_set_missions(nmpc_loop *l, const int32_t *leg_off, const int32_t *leg_route)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
@@ -678,6 +704,8 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
             hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, l->monitor.a, r.retired_at);
         if (l->map.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, v, stp, l->map.a);
         if (cr.watched()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a);
+        // the track monitor measures against the route the rows were driven on: the dispatch comes after
+        if (l->track.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_track_kernel, dim3(n), dim3(64), 0, s, v, stp, l->a, l->track.a);
         // the log sees the leg and the p the solve belonged to: the dispatch comes after (leg: the missions', NULL without them)
         if (l->log.made()) {
             hipLaunchKernelGGL(nmpc::nmpc_loop_log_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, l->log.a, l->missions.leg.p);
@@ -829,6 +857,15 @@ int nmpc_loop_map_clearance(nmpc_loop *l, nmpc_map_clearance *out)
         return NMPC_OK;
     }
     HIP_TRY(l->h, l->map.rec.read(out, B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_tracking(nmpc_loop *l, nmpc_tracking *out)
+{
+    if (!out) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_settle(l)) return rc;
+    if (!l->track.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_tracking: the loop has no track monitor (nmpc_loop_set_track_monitor)");
+    HIP_TRY(l->h, l->track.rec.read(out, l->v.B));
     return NMPC_OK;
 }
 

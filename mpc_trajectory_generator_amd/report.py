@@ -123,3 +123,37 @@ def ensemble_text(stats, group: int = 0) -> str:
         lines.append(f"{k + 1:>5}{float(r['mean'][0]):>10.4f}{float(r['mean'][1]):>10.4f}{a:>10.4f}{b:>10.4f}{np.sqrt(max(tt, 0.0)):>10.4f}"
                      f"{np.sqrt(max(float(r['far2']), 0.0)):>10.4f}{int(r['far_robot']):>7d}{int(r['arrived']) / n:>9.1%}")
     return "\n".join(lines) + "\n"
+
+
+def tracking_summary(records) -> dict:
+    """What a set of track-monitor records (``tracking()`` [n], ``_lib.TRACKING_DTYPE``) says as a whole, computed here on the host:
+    the largest and the RMS cross-track error in metres (sums over all rows that had a closest segment: ``rows`` counts NaN poses too,
+    which add nothing to the sums), the largest and the RMS heading error in radians (not wrapped, as the cost sees it), the share of
+    rows off the route and of robots that ever were."""
+    rec = np.asarray(records)
+    rows = int(rec["rows"].sum())
+    div = float(max(rows, 1))
+    return {"robots": int(len(rec)), "rows": rows,
+            "cte_max_m": float(np.sqrt(rec["cte2_max"].max(initial=0.0))), "cte_rms_m": float(np.sqrt(rec["cte2_sum"].sum() / div)),
+            "dth_max_rad": float(rec["dth_max"].max(initial=0.0)), "dth_rms_rad": float(np.sqrt(rec["dth2_sum"].sum() / div)),
+            "rows_off_frac": float(rec["off_rows"].sum() / div), "robots_off_frac": float((rec["off_rows"] > 0).mean()) if len(rec) else 0.0}
+
+
+def tracking_text(records, group_of=None) -> str:
+    """One line for the fleet and, with ``group_of`` [B], one per group (ascending group index) of a track monitor's records (``tracking()``
+    [B] of a ``DeviceRecedingHorizon`` or its host mirror): the largest and the RMS cross-track error in metres, the share of rows off
+    the route, the share of robots that ever were, and the largest heading error in radians (``tracking_summary``)."""
+    rec = np.asarray(records)
+    sets = [("fleet", np.ones(len(rec), dtype=bool))]
+    if group_of is not None:
+        g = np.asarray(group_of).reshape(-1)
+        if len(g) != len(rec):
+            raise ValueError(f"group_of of length {len(g)} for {len(rec)} records")
+        sets += [(f"group {int(v)}", g == v) for v in np.unique(g)]
+    lines = ["Route tracking", f"{'':<12}{'robots':>8}{'rows':>10}{'cte max m':>12}{'cte rms m':>12}{'rows off':>10}{'robots off':>12}{'dth max rad':>13}",
+             "-" * 89]
+    for name, sel in sets:
+        s = tracking_summary(rec[sel])
+        lines.append(f"{name:<12}{s['robots']:>8d}{s['rows']:>10d}{s['cte_max_m']:>12.4f}{s['cte_rms_m']:>12.4f}{s['rows_off_frac']:>10.1%}"
+                     f"{s['robots_off_frac']:>12.1%}{s['dth_max_rad']:>13.4f}")
+    return "\n".join(lines) + "\n"

@@ -813,6 +813,122 @@ class MapMonitor:
         return rec
 
 
+def no_tracking(B: int):
+    """-> the track monitor's initial records [B]: sums, maxima and counts 0, rows and segments -1."""
+    rec = np.zeros(B, dtype=_lib.TRACKING_DTYPE)
+    rec["cte_row"] = rec["cte_seg"] = rec["dth_row"] = rec["last_seg"] = rec["off_row"] = -1
+    return rec
+
+
+@dataclasses.dataclass(frozen=True)
+class TrackMonitor:
+    """The track monitor, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon`` alike: per robot, how far the
+    poses driven so far were from the route it was asked to follow -- the largest and the summed squared distance to the polyline through
+    the route's reference samples, the largest and the summed squared heading error against the sample at the end of the closest segment,
+    the rows at which the maxima occurred, the closest segment of the newest row (progress along the route) and the rows further than
+    ``tol`` metres from the route (``tracking()``, a ``_lib.TRACKING_DTYPE`` array [B]).  The heading error is NOT wrapped: the cost does
+    not wrap either (``cost_fn``, src/mpc/mpc_generator.py:59-63), so it is the error the controller itself sees.  It observes only."""
+    tol: float = 0.5
+
+    def checked(self):
+        """-> ``tol`` as a float; ValueError for what ``nmpc_loop_set_track_monitor`` refuses."""
+        try:
+            tol = float(self.tol)
+        except (TypeError, ValueError):
+            raise ValueError(f"track monitor: tol = {self.tol!r} is not a number") from None
+        if not (tol >= 0.0) or not math.isfinite(tol):
+            raise ValueError(f"track monitor: tol = {tol} must be finite and not negative")
+        return tol
+
+    @staticmethod
+    def table(routes):
+        """-> (ref [R, W, 3], n [R]): every route's reference samples (x, y, theta) side by side, W the longest route's, a row padded with
+        its last sample; each route's own length.  ``routes``: objects with ``x_ref``, ``y_ref`` and ``theta_ref`` (``harness.Route``)."""
+        rows = [np.stack([np.asarray(r.x_ref, dtype=np.float64), np.asarray(r.y_ref, dtype=np.float64),
+                          np.asarray(r.theta_ref, dtype=np.float64)], axis=1) for r in routes]
+        n = np.array([len(v) for v in rows], dtype=np.int64)
+        assert (n >= 1).all()
+        ref = np.empty((len(rows), int(n.max()), 3))
+        for r, v in enumerate(rows):
+            ref[r, :len(v)], ref[r, len(v):] = v, v[-1]
+        return ref, n
+
+    @staticmethod
+    def rows(table, route_of, x, y):
+        """The rule's distance for m poses (x, y) [m], pose i against route ``route_of[i]`` of ``table`` -> (v [m], j [m]): the smallest
+        squared distance to a segment that is not NaN and the first segment that has it; (+inf, -1) where there is none.  Unfused f64 in
+        the order DESIGN.md section 5.9 writes; segment 0 is not clamped below."""
+        ref, n = table
+        route_of = np.asarray(route_of, dtype=np.int64).reshape(-1)
+        x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
+        m, S = len(x), max(ref.shape[1] - 1, 1)
+        chunk = max(1, (1 << 20) // S)
+        if m > chunk:
+            parts = [TrackMonitor.rows(table, route_of[i:i + chunk], x[i:i + chunk], y[i:i + chunk]) for i in range(0, m, chunk)]
+            return tuple(np.concatenate(c) for c in zip(*parts))
+        nr = n[route_of][:, None]
+        j = np.arange(S)[None, :]
+        valid = j < np.maximum(nr - 1, 1)
+        rt = route_of[:, None]
+        a, e = np.minimum(j, nr - 1), np.minimum(j + 1, nr - 1)
+        x1, y1, x2, y2 = ref[rt, a, 0], ref[rt, a, 1], ref[rt, e, 0], ref[rt, e, 1]
+        X, Y = x[:, None], y[:, None]
+        with np.errstate(all="ignore"):
+            ex, ey = x2 - x1, y2 - y1
+            L2 = ex * ex + ey * ey
+            pos = L2 > 0
+            t = ((X - x1) * ex + (Y - y1) * ey) / np.where(pos, L2, 1.0)
+            t = np.where((t < 0) & (j > 0), 0.0, t)
+            t = np.where(t > 1, 1.0, t)
+            t = np.where(pos, t, 0.0)
+            cx, cy = x1 + t * ex, y1 + t * ey
+            dx, dy = X - cx, Y - cy
+            v = dx * dx + dy * dy
+        v = np.where(np.isnan(v) | ~valid, np.inf, v)
+        k = np.argmin(v, axis=1)                                            # the first segment with the smallest value
+        best = v[np.arange(m), k]
+        return best, np.where(best < np.inf, k, -1).astype(np.int32)
+
+    def fold(self, rec, who, r, table, route_of, pose):
+        """Trajectory row ``r`` of the robots ``who`` [m] (distinct), their poses ``pose`` [m, 3] against the routes ``route_of`` [m] of
+        ``table``, into the records ``rec`` [B], in place: the rule's update, both maxima strict."""
+        tol = self.checked()
+        ref, n = table
+        who, route_of = np.asarray(who, dtype=np.int64), np.asarray(route_of, dtype=np.int64).reshape(-1)
+        pose = np.asarray(pose, dtype=np.float64).reshape(-1, 3)
+        v, j = self.rows(table, route_of, pose[:, 0], pose[:, 1])
+        rec["rows"][who] += 1
+        ok = j >= 0
+        b, v, j, rt, th = who[ok], v[ok], j[ok], route_of[ok], pose[ok, 2]
+        e = np.minimum(j + 1, n[rt] - 1)
+        with np.errstate(all="ignore"):
+            d = th - ref[rt, e, 2]
+            a = np.where(d < 0, -d, d)
+            rec["cte2_sum"][b] = rec["cte2_sum"][b] + v
+            rec["dth2_sum"][b] = rec["dth2_sum"][b] + d * d
+            up = v > rec["cte2_max"][b]
+            rec["cte2_max"][b[up]], rec["cte_row"][b[up]], rec["cte_seg"][b[up]] = v[up], r, j[up]
+            up = a > rec["dth_max"][b]
+            rec["dth_max"][b[up]], rec["dth_row"][b[up]] = a[up], r
+            rec["last_seg"][b] = j
+            off = v > tol * tol
+        first = off & (rec["off_row"][b] == -1)
+        rec["off_row"][b[first]] = r
+        rec["off_rows"][b[off]] += 1
+
+    def scan(self, traj, routes, route_of=None):
+        """The rule over the rows >= 1 of a recorded trajectory table [rows, B, 3] (x, y, theta), robot b against the fixed route
+        ``routes[route_of[b]]`` (default: route 0) -> the records [B] a monitor would hold for robots driven over all those rows."""
+        T = np.asarray(traj, dtype=np.float64)
+        B = T.shape[1]
+        rec = no_tracking(B)
+        route_of = np.zeros(B, dtype=np.int64) if route_of is None else np.asarray(route_of, dtype=np.int64).reshape(B)
+        table, who = self.table(routes), np.arange(B)
+        for r in range(1, T.shape[0]):
+            self.fold(rec, who, r, table, route_of, T[r])
+        return rec
+
+
 @dataclasses.dataclass(frozen=True)
 class DriveLog:
     """The drive log, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon`` alike: the controls every robot
@@ -1031,10 +1147,14 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     ``ensemble`` (an ``Ensemble``): ``ensemble_stats()`` [steps, G] holds one ``_lib.ENSEMBLE_DTYPE`` record per group and step
     (DESIGN.md section 5.9), appended by ``step`` when everything else of the step is over -- behind ``advance`` and, on a retiring
     fleet, ``retire`` -- from the true poses of all members, ``retired_at`` (a retiring fleet) or ``done``.  Nothing else reads it.
+
+    ``track`` (a ``TrackMonitor``): ``tracking()`` [B] holds how far every robot was from its route, in position and heading
+    (DESIGN.md section 5.9), updated by ``advance`` -- before ``retire``, so a row is measured against the leg it was driven on --
+    from the rows it appends to ``traj`` (under a plant the true poses), for the robots the step drove.
     """
 
     def __init__(self, routes, route_of, starts, dyn_obs=None, sincos=None, sinus_object=False, idx0=None, peers=None, retire=False,
-                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None, ensemble=None, walls=None):
+                 monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None, ensemble=None, walls=None, track=None):
         self.routes = list(routes)
         cfg, B = self.routes[0].cfg, len(starts)
         route_of = np.asarray(route_of, dtype=np.int64).reshape(B)
@@ -1101,6 +1221,17 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._wall_edges = walls.checked(cfg, self.routes)
             self.wall_edge = np.full((B, walls.slots), -1, dtype=np.int32)    # the edge in circle slot Nobs - slots + m of robot b's p (-1: none)
             self.wall_stage = np.full((B, walls.slots), -1, dtype=np.int32)   # the stage at which it came closest
+        self.track = track
+        if track is not None:
+            track.checked()
+            self._track_tab = TrackMonitor.table(self.routes)
+            self._track_rec = no_tracking(B)
+
+    def tracking(self):
+        """-> the track monitor's records [B] (``_lib.TRACKING_DTYPE``), a copy; needs a ``track``."""
+        if self.track is None:
+            raise ValueError("the fleet has no track monitor (track=TrackMonitor(...))")
+        return self._track_rec.copy()
 
     def step(self, solve_fn):
         out = super().step(solve_fn)
@@ -1491,6 +1622,8 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._map_update()
         if self.crowd is not None and self.crowd.watch:
             self._crowd_update()
+        if self.track is not None:
+            self._track_update()
         if self.log is not None:
             self._log_update(U)
         self.steps += 1
@@ -1552,6 +1685,17 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         tot["inner_total"] = inner.astype(np.uint64).sum()
         ms = st["solve_time_ms"]
         tot["solve_ms_max"] = np.where(ms > 0, ms, 0.0).max()
+
+    def _track_update(self):
+        """The track monitor's rule on the s rows this step appended, for the robots the step drove, each against
+        its route as the step found it (``retire`` comes after): ``TrackMonitor.fold``, vectorised over robots and segments."""
+        s = self.cfg.num_steps_taken
+        who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
+        if not len(who):
+            return
+        for i in range(s):
+            pose = self.traj[len(self.traj) - s + i]
+            self.track.fold(self._track_rec, who, self.steps * s + 1 + i, self._track_tab, self.route_of[who], pose[who])
 
     def _map_update(self):
         """The map monitor's rule on the s rows this step appended, each against the row before it, for the robots
@@ -1720,11 +1864,17 @@ class DeviceRecedingHorizon:
     poses, become circles in the last ``slots`` circle slots of its parameter vector (``nmpc_loop_set_walls``):
     ``nmpc_loop_walls_kernel``, one wave per robot, between the peers' kernels and the solve.  ``walls()`` reads the edges and stages
     chosen.  Its host mirror is ``FleetRecedingHorizon`` with the same ``walls`` (tests/test_gpu_walls_loop.py).
+
+    ``track`` (a ``TrackMonitor``, needs ``max_steps`` > 0): how far every robot was from the route it was asked to follow, in position
+    and (unwrapped) heading, the rows of the largest errors, its progress along the route and the rows further than ``tol`` from it are
+    kept on the device (``nmpc_loop_set_track_monitor``): ``nmpc_loop_track_kernel``, one wave per robot, after the
+    advance and the other monitors and before the log and the dispatch.  ``tracking()`` reads the records.  Its host mirror is
+    ``FleetRecedingHorizon`` with the same ``track`` (tests/test_gpu_track_loop.py).
     """
 
     def __init__(self, solver, route, starts, dyn_obs=None, max_steps: int = 0, idx0=None, sinus_object=False,
                  route_of=None, peers=None, retire=False, monitor=None, missions=None, map_monitor=None, log=None, crowd=None, plant=None,
-                 ensemble=None, walls=None):
+                 ensemble=None, walls=None, track=None):
         single = isinstance(route, harness.Route)
         routes = [route] if single else list(route)
         cfg = self.cfg = routes[0].cfg
@@ -1833,6 +1983,14 @@ class DeviceRecedingHorizon:
                 raise
             self._set(self.lib.nmpc_loop_set_walls(h, len(edges), _lib.as_dp(edges), int(walls.slots), float(walls.radius), float(walls.range),
                                                    float(walls.spacing)))
+        self.track = track
+        if track is not None:
+            try:
+                tol = track.checked()
+            except ValueError:
+                self.close()
+                raise
+            self._set(self.lib.nmpc_loop_set_track_monitor(h, tol))
         self.missions = missions
         self._leg_off = None
         if missions is not None:
@@ -1948,6 +2106,13 @@ class DeviceRecedingHorizon:
         after synchronising; without a ``map_monitor`` the initial record everywhere."""
         rec = np.empty(self.B, dtype=_lib.MAP_CLEARANCE_DTYPE)
         self.solver._check(self.lib.nmpc_loop_map_clearance(self._l, rec.ctypes.data))
+        return rec
+
+    def tracking(self):
+        """-> the track monitor's records [B] (``_lib.TRACKING_DTYPE``: cte2_max, cte2_sum, dth_max, dth2_sum, rows, cte_row, cte_seg,
+        dth_row, last_seg, off_rows, off_row, reserved) after synchronising; the initial records before the first step.  Needs a ``track``."""
+        rec = np.empty(self.B, dtype=_lib.TRACKING_DTYPE)
+        self.solver._check(self.lib.nmpc_loop_tracking(self._l, rec.ctypes.data))
         return rec
 
     def _log(self, want_ctrl):

@@ -293,6 +293,14 @@ def map_clearance_differing(dev, host):
     return [f for f in a.dtype.names if a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes() or a[f].shape != b[f].shape]
 
 
+def tracking_differing(dev, host):
+    """``clearance_differing`` for the track monitor's records (``dev``: a ``DeviceRecedingHorizon`` with a track monitor or its
+    ``tracking()``, ``host``: its mirror or the mirror's ``tracking()``): the fields that are not bit-equal."""
+    a = dev.tracking() if callable(getattr(dev, "tracking", None)) else dev
+    b = host.tracking() if callable(getattr(host, "tracking", None)) else host
+    return [f for f in a.dtype.names if a[f].tobytes() != np.asarray(b[f], dtype=a[f].dtype).tobytes() or a[f].shape != b[f].shape]
+
+
 def plant_differing(dev, host):
     """What a plant keeps (``dev``: a ``DeviceRecedingHorizon``, ``host``: its mirror, both with ``applied()`` and ``measured()``) -> the
     names that are not bit-equal: a value compares by its bytes, so -0.0 is not 0.0 and a NaN equals itself."""

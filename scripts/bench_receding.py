@@ -16,6 +16,8 @@ from the goal of the one before; the routes are planned on the device (frontend.
 gains plan_ms (the planner kernels' time over all batches, redraws included) and routes_planned.  --map [inflated]: the map monitor
 (nmpc_loop_set_map_monitor) on the scene's original polygons, the true walls, or with "inflated" on the polygons the
 planner plans on; the result line then has map_clearance: the share of robots with a hit, the rows hit and the fleet's smallest wall distance.
+--track [TOL]: the track monitor (nmpc_loop_set_track_monitor): the result line then has tracking: the fleet's largest
+and RMS cross-track error in metres, its largest and RMS heading error and the share of rows and of robots further than TOL (0.5 m) from the route.
 --log: the drive log (nmpc_loop_set_log): the result line then has drive_log: the share of non-converged solves per exit
 status, the worst step's slowest solve and the fleet's largest acceleration.  --crowd D: a crowd of D moving obstacles shared by the whole fleet
 (nmpc_loop_set_crowd; workloads.crowd_ellipses, seed 2): --crowd-slots of the Ndynobs ellipse slots go to the closest
@@ -48,7 +50,7 @@ sys.path.insert(0, ".")
 from mpc_trajectory_generator_amd import named_config                            # noqa: E402
 from mpc_trajectory_generator_amd import harness                                 # noqa: E402
 from mpc_trajectory_generator_amd.solver import BatchSolver                      # noqa: E402
-from mpc_trajectory_generator_amd.trajectory import DriveLog, Ensemble, FleetRecedingHorizon, MapMonitor, Monitor, Peers, VectorizedRecedingHorizon    # noqa: E402
+from mpc_trajectory_generator_amd.trajectory import DriveLog, Ensemble, FleetRecedingHorizon, MapMonitor, Monitor, Peers, TrackMonitor, VectorizedRecedingHorizon   # noqa: E402
 from mpc_trajectory_generator_amd.workloads import moving_ellipses, route_fleet   # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -85,6 +87,8 @@ ap.add_argument("--monitor", type=int, nargs="?", const=0, default=None, metavar
 ap.add_argument("--map", nargs="?", const="original", default=None, choices=("original", "inflated"), metavar="inflated",
                 help="device loop only: keep every robot's closest approach to the scene's walls and its rows inside an obstacle, outside the "
                      "boundary or through an edge on the device, and report them; 'inflated': against the polygons the planner plans on")
+ap.add_argument("--track", type=float, nargs="?", const=0.5, default=None, metavar="TOL",
+                help="device loop only: the track monitor, rows further than TOL metres (default 0.5) from the route count as off it")
 ap.add_argument("--log", action="store_true",
                 help="device loop only: keep every robot's applied controls, a record of every solve, a summary per robot and the fleet's "
                      "totals per step on the device, and report from them")
@@ -120,6 +124,8 @@ if args.peer_cell is not None and not args.peers:
     ap.error("--peer-cell goes with --peers G")
 if args.map and (args.host or args.steps < 1):
     ap.error("--map reads the trajectory the device loop records: it needs the device loop (no --host) and --steps >= 1")
+if args.track is not None and (args.host or args.steps < 1 or not 0 <= args.track < float("inf")):
+    ap.error("--track [TOL]: TOL >= 0 and finite, on the device loop (no --host) with --steps >= 1")
 if args.log and (args.host or args.steps < 1):
     ap.error("--log is the device loop's, and its length is --steps: it needs the device loop (no --host) and --steps >= 1")
 if args.legs < 1 or (args.legs > 1 and (not args.retire or args.host)):
@@ -300,7 +306,7 @@ if not args.host:
                                      route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
                                      missions=missions_of(ids), map_monitor=map_monitor, log=DriveLog() if args.log else None, crowd=crowd,
                                      plant=plant_of(ids), ensemble=None if ens_group_of is None else Ensemble(ens_group_of[ids], groups=ens_G),
-                                     walls=walls)
+                                     walls=walls, track=None if args.track is None else TrackMonitor(args.track))
 
     for ids in parts:
         sv = solver if not loops else BatchSolver(cfg, max_batch=len(ids), **sopts)
@@ -351,6 +357,9 @@ if not args.host:
         quality["map_clearance"] = {"polygons": args.map, "edges": len(map_monitor.edges), "robots_hit_frac": float((rec["hits"] > 0).mean()),
                                     "rows_hit": int(rec["hits"].sum()), "min_wall_m": float(np.sqrt(rec["wall2"].min())),
                                     "median_wall_m": float(np.sqrt(np.median(rec["wall2"])))}
+    if args.track is not None:
+        from mpc_trajectory_generator_amd.report import tracking_summary
+        quality["tracking"] = {"tol_m": args.track, **tracking_summary(np.concatenate([rh.tracking() for rh in loops]))}
     if walls is not None:
         edge = np.concatenate([rh.walls()[0] for rh in loops])            # the last step's
         quality["walls"] = {"edges": len(walls.edges), "slots": args.walls, "range_m": args.walls_range, "spacing_m": args.walls_spacing,
@@ -417,6 +426,7 @@ if not args.host:
                                + (", robots retire at their goals" if args.retire else "")
                                + (f", clearance monitor in groups of {args.monitor}" if args.monitor else "")
                                + (f", map monitor on the scene's {args.map} polygons" if args.map else "")
+                               + (f", track monitor with tol {args.track} m" if args.track is not None else "")
                                + (", drive log" if args.log else "")
                                + (f", ensemble statistics in {ens_G} group{'s' if ens_G > 1 else ''}" if args.ensemble_stats is not None else "")
                                + (f", at most {args.budget} PANOC iterations per solve (NotConvergedOutOfTime beyond)" if args.budget else "")
