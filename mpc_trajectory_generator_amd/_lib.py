@@ -282,6 +282,10 @@ def load_library(experiments: bool = False) -> C.CDLL:
                 raise RuntimeError(f"{variant_path(EXPERIMENTS)} REFUSED by the code-generation check: " + json.dumps(check)[:2000])
             _lib_experiments = _bind(C.CDLL(variant_path(EXPERIMENTS)), variant_path(EXPERIMENTS))
             assert _lib_experiments.nmpc_experiments_build() == 1
+            # the readers of the launch order: this variant's alone, declared nowhere in include/nmpc_solver.h
+            u8p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+            _lib_experiments.nmpc_debug_launch_order.argtypes = [C.c_void_p, i32p, i32p, u8p, i32p]
+            _lib_experiments.nmpc_debug_order_of.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), u8p, i32p]
         return _lib_experiments
     if _lib is not None:
         return _lib

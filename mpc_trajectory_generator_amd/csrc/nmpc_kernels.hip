@@ -120,6 +120,8 @@ struct nmpc_handle {
     DevBuf<int> d_order;           // launch order (hard-looking instances first)
     bool use_order = true;
     DevBuf<unsigned char> d_cls;
+    int order_n = 0;               // the last solve launch: instances it ordered (its B), 0 = it fetched in index order
+    bool order_from_prev = false;  // ... and whether their levels came from the previous statuses
     Staging stg;
     SmallArena small;
     // wall-clock limits (nmpc_set_time_limits): as given, in ms, and in ticks of the 100 MHz constant clock (0 = off); any limit set -> the Timed<> kernels
@@ -358,8 +360,10 @@ static int solve_launch(nmpc_handle *h, int B, const double *d_p, double *d_u, c
     HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, sizeof(unsigned int), s));
     // one instance per wave, three query points per pass: N_hor <= 20 with one stage per lane (hybrid / tri layouts), 20 < N_hor <= 40 with two
     const int grid = B < h->grid_cap ? B : h->grid_cap;          // waves that take instances
+    h->order_n = 0; h->order_from_prev = false;
     if (B > grid) {        // more instances than resident waves: hand the hard-looking ones out first
         if (h->use_order) {
+            h->order_n = B; h->order_from_prev = prev != nullptr;
             if (prev) hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, prev, h->d_cls.p);
             else hipLaunchKernelGGL(nmpc::nmpc_classify_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a, h->d_cls.p);
             hipLaunchKernelGGL(nmpc::nmpc_order_kernel, dim3(1), dim3(1024), 0, s, B, h->d_cls.p, h->d_order.p);
@@ -644,5 +648,47 @@ int nmpc_test_divsqrt_host(nmpc_handle *h, int n, const double *a, const double 
     if (!b) return NMPC_ERR_BAD_ARG;
     return run_unary_test(h, n, a, b, out_div, out_sqrt, 1);
 }
+
+// ---- the launch order, readable in the experiments build only (tests/test_gpu_launch_order.py); include/nmpc_solver.h declares neither and
+// the product exports neither ----
+#ifdef NMPC_EXPERIMENTS
+// what the handle's last solve launch used, after the device has finished it: *n = its B, or 0 if it fetched in index order (B within the
+// resident waves, or NMPC_ORDER=0); *from_prev = the levels came from statuses; cls[0..n), order[0..n) (either may be NULL)
+int nmpc_debug_launch_order(nmpc_handle *h, int32_t *n, int32_t *from_prev, uint8_t *cls, int32_t *order)
+{
+    if (!h || !n || !from_prev) return NMPC_ERR_BAD_ARG;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    *n = h->order_n; *from_prev = h->order_from_prev ? 1 : 0;
+    HIP_TRY(h, h->d_cls.read(cls, (size_t)h->order_n));
+    HIP_TRY(h, h->d_order.read(order, (size_t)h->order_n));
+    return NMPC_OK;
+}
+
+// the order of B instances whose previous solves took passes[b] evaluation passes: the two kernels solve_launch enqueues for a launch with
+// statuses, on the handle's own buffers (so the record of the last launch is cleared), without a solve behind them
+int nmpc_debug_order_of(nmpc_handle *h, int B, const uint32_t *passes, uint8_t *cls, int32_t *order)
+{
+    if (!h || !passes) return NMPC_ERR_BAD_ARG;
+    if (!h->alive) return NMPC_ERR_DEAD_HANDLE;
+    if (B < 1 || B > h->max_batch) return fail(h, NMPC_ERR_BAD_ARG, "bad batch arguments");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    std::vector<nmpc_status> st((size_t)B);
+    std::memset(st.data(), 0, st.size() * sizeof(nmpc_status));
+    for (int b = 0; b < B; ++b) st[b].reserved = passes[b];
+    DevBuf<nmpc_status> prev;
+    HIP_TRY(h, prev.upload(st.data(), st.size()));
+    h->order_n = 0; h->order_from_prev = false;
+    hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, nullptr, B, prev.p, h->d_cls.p);
+    hipLaunchKernelGGL(nmpc::nmpc_order_kernel, dim3(1), dim3(1024), 0, nullptr, B, h->d_cls.p, h->d_order.p);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, h->d_cls.read(cls, (size_t)B));
+    HIP_TRY(h, h->d_order.read(order, (size_t)B));
+    return NMPC_OK;
+}
+#endif
 
 }  // extern "C"

@@ -33,6 +33,7 @@ class BatchSolver:
     def __init__(self, cfg: Config, max_batch: int = 8192, device: int = 0, experiments: bool = False,
                  max_duration_ms: float = 0.0, batch_budget_ms: float = 0.0, **opts):
         self.cfg = cfg
+        self.experiments = bool(experiments)
         # raises if the HIP library cannot be had.  (experiments: tests / scripts only -- the variant that reads the NMPC_* environment knobs)
         self.lib = _lib.load_library(experiments=experiments)
         self.pb = problem_from_config(cfg)
@@ -182,6 +183,33 @@ class BatchSolver:
         self._check(self.lib.nmpc_test_divsqrt_host(self._h, a.size, _lib.as_dp(a), _lib.as_dp(b),
                                                     _lib.as_dp(q), _lib.as_dp(r)))
         return q, r
+
+    # ------------------------------------------------------------------ the launch order (tests; experiments build only)
+    def _order_readers(self):
+        if not self.experiments:
+            raise SolverError(-3, "the launch order can be read in the experiments build only (BatchSolver(..., experiments=True))")
+
+    def launch_order(self):
+        """What this handle's last solve launch used, after the device has finished it: (n, from_prev, levels [n],
+        order [n]).  n = the launch's batch size, or 0 if it fetched its instances in index order; from_prev: the levels came from the
+        previous solves' pass counts (the on-device loop) instead of the inputs."""
+        self._order_readers()
+        n, prev = C.c_int32(0), C.c_int32(0)
+        cls, order = np.zeros(self.max_batch, dtype=np.uint8), np.zeros(self.max_batch, dtype=np.int32)
+        self._check(self.lib.nmpc_debug_launch_order(self._h, C.byref(n), C.byref(prev), cls.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                     _lib.as_i32p(order)))
+        return n.value, prev.value, cls[:n.value].copy(), order[:n.value].copy()
+
+    def order_of(self, passes):
+        """(levels, order) the order kernels give instances whose previous solves took ``passes`` evaluation passes (uint32 [B], B <=
+        max_batch): the kernels a launch with previous statuses enqueues, without a solve behind them."""
+        self._order_readers()
+        passes = np.ascontiguousarray(passes, dtype=np.uint32)
+        B = passes.size
+        cls, order = np.zeros(B, dtype=np.uint8), np.zeros(B, dtype=np.int32)
+        self._check(self.lib.nmpc_debug_order_of(self._h, B, passes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 cls.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.as_i32p(order)))
+        return cls, order
 
 
 def status_from_bytes(t):

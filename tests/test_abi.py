@@ -65,6 +65,9 @@ def test_shipped_library_reads_no_environment():
     assert b"getenv" not in blob
     lib = _lib.load_library()
     assert lib.nmpc_experiments_build() == 0
+    # ... and none of the readers of the launch order (tests/test_gpu_launch_order.py): they are the experiments variant's alone
+    for name in ("nmpc_debug_launch_order", "nmpc_debug_order_of"):
+        assert name.encode() not in blob and not hasattr(lib, name) and name not in _lib.SYMBOLS
 
 
 def test_product_does_not_import_oracle():
