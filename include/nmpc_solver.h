@@ -163,9 +163,30 @@ const char *nmpc_kernel_name(const nmpc_handle *h);
 /* Diagnostic: the radius in metres of the circle culling this handle's solves use, 1.1 * N * ts * max(|vmin|, |vmax|): what the
  * bounds let a robot travel in a horizon, plus a margin.  Any value gives the same results; 0 for a NULL handle. */
 double nmpc_cull_radius(const nmpc_handle *h);
+/* Diagnostic: how this handle would launch a solve of B instances (0 <= B <= max_batch), and two constants of the handle.  Launches
+ * nothing.  With W = resident_waves -- the waves the chip holds at once, CUs x 8 for N_hor <= 20 (x 4 if two teams' LDS do not fit a
+ * CU) and CUs x 4 for 20 < N_hor <= 40 -- and G = W / 4, the workgroups of four waves that fit:
+ *   grid        waves that take instances, min(B, W)
+ *   owners      waves per workgroup that take instances: ceil(B / G), at least 1 and at most 4; the other waves help
+ *   workgroups  ceil(grid / owners), at most G
+ *   ordered     1 if B > W: the instances are handed out hard-looking ones first (two more kernels ahead of the solve)
+ *   pools       1 if B > W: instances may leave their wave at outer-iteration boundaries (the pools and their counters are cleared)
+ *               (the experiments build's knobs can switch either off)
+ *   pool_cap    slots of a pool's ring in this launch, B
+ *   staging_chunk_bytes   the size of each of the host path's two pinned bounce buffers: arrays travel in chunks of it
+ * NMPC_ERR_BAD_ARG for a NULL argument or a B outside the range. */
+typedef struct nmpc_launch_info {        /* 40 bytes */
+    int32_t grid, owners, workgroups, ordered, pools, pool_cap, resident_waves, reserved;
+    int64_t staging_chunk_bytes;
+} nmpc_launch_info;
+int nmpc_launch_geometry(const nmpc_handle *h, int B, nmpc_launch_info *out);
 
 /* Device path: every pointer is device memory on the handle's device; the launch is enqueued on
  * `stream` (a hipStream_t, NULL = default stream) and the call returns without synchronising.
+ * Everything a launch enqueues -- the clearing of the work queue, of the pools and of their counters, the kernels that order the
+ * instances, the solve -- goes to `stream`.  The handle owns those queue, order and pool buffers, one set for all of its launches:
+ * launches of one handle are ordered only when they are enqueued on one stream, and two launches of one handle in flight on different
+ * streams are undefined.  Two batches in flight take two handles.
  *   d_u      [B][n_u]  in: initial guess, out: solution
  *   d_y0     [B][n1]   initial multipliers, or NULL (zeros)
  *   d_c0     [B]       initial penalties, or NULL (opts.initial_penalty)

@@ -19,7 +19,7 @@ BUILD_INFO = os.path.join(_CSRC, "build_info.json")      # written by build_libr
 # every symbol include/nmpc_solver.h declares
 SYMBOLS = (
     "nmpc_default_opts", "nmpc_n_u", "nmpc_n_p", "nmpc_n1", "nmpc_n2", "nmpc_new", "nmpc_free",
-    "nmpc_ping", "nmpc_last_error", "nmpc_abi_version", "nmpc_experiments_build", "nmpc_kernel_name", "nmpc_cull_radius", "nmpc_solve_batch_device",
+    "nmpc_ping", "nmpc_last_error", "nmpc_abi_version", "nmpc_experiments_build", "nmpc_kernel_name", "nmpc_cull_radius", "nmpc_launch_geometry", "nmpc_solve_batch_device",
     "nmpc_solve_batch_host", "nmpc_last_batch_ms", "nmpc_set_time_limits", "nmpc_eval_batch_device", "nmpc_eval_batch_host",
     "nmpc_test_sincos_host", "nmpc_test_divsqrt_host",
     "nmpc_loop_new", "nmpc_loop_new_routes", "nmpc_loop_set_peers", "nmpc_loop_free", "nmpc_loop_step", "nmpc_loop_read", "nmpc_loop_params",
@@ -87,6 +87,14 @@ class NmpcPlant(C.Structure):
 
 
 assert C.sizeof(NmpcPlant) == 96
+
+
+class NmpcLaunchInfo(C.Structure):
+    _fields_ = [("grid", C.c_int32), ("owners", C.c_int32), ("workgroups", C.c_int32), ("ordered", C.c_int32), ("pools", C.c_int32),
+                ("pool_cap", C.c_int32), ("resident_waves", C.c_int32), ("reserved", C.c_int32), ("staging_chunk_bytes", C.c_int64)]
+
+
+assert C.sizeof(NmpcLaunchInfo) == 40
 
 STATUS_DTYPE = np.dtype([("exit_status", "<i4"), ("num_outer_iterations", "<u4"),
                          ("num_inner_iterations", "<u4"), ("num_cost_evals", "<u4"),
@@ -315,6 +323,8 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_kernel_name.restype = C.c_char_p
     lib.nmpc_cull_radius.argtypes = [vp]
     lib.nmpc_cull_radius.restype = C.c_double
+    lib.nmpc_launch_geometry.argtypes = [vp, C.c_int, C.POINTER(NmpcLaunchInfo)]
+    lib.nmpc_launch_geometry.restype = C.c_int
     lib.nmpc_last_batch_ms.argtypes = [vp]
     lib.nmpc_last_batch_ms.restype = C.c_double
     lib.nmpc_solve_batch_device.argtypes = [vp, C.c_int] + [vp] * 7

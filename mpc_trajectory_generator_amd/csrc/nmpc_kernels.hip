@@ -29,6 +29,8 @@
 #include "nmpc_plan.h"
 #include "nmpc_order.h"
 #include "nmpc_host.h"
+#include "nmpc_launch.h"
+static_assert(nmpc::LAUNCH_TEAM_WAVES == nmpc::TEAM_WAVES, "nmpc_launch.h: the waves of a team");
 
 // =================================================================================================
 // C ABI (include/nmpc_solver.h)
@@ -297,6 +299,19 @@ static bool timed(const nmpc_handle *h) { return h->tl_dur > 0 || h->tl_budget >
 const char *nmpc_kernel_name(const nmpc_handle *h) { return h ? h->kernel[timed(h)]->name : ""; }
 double nmpc_cull_radius(const nmpc_handle *h) { return h ? h->cull_radius : 0.0; }
 
+static constexpr size_t PIN_CHUNK = 4u << 20;      // bytes of each pinned bounce buffer of the host path (h2d_staged / d2h_staged)
+static nmpc::LaunchGeometry geometry_of(const nmpc_handle *h, int B)
+{
+    return nmpc::launch_geometry(B, h->grid_cap, h->P, h->use_order, h->park_min, h->sched_mode, h->team_owners_forced);
+}
+int nmpc_launch_geometry(const nmpc_handle *h, int B, nmpc_launch_info *out)
+{
+    if (!h || !out || B < 0 || B > h->max_batch) return NMPC_ERR_BAD_ARG;
+    const nmpc::LaunchGeometry g = geometry_of(h, B);
+    *out = nmpc_launch_info{g.grid, g.owners, g.workgroups, g.ordered, g.pools, g.pool_cap, h->grid_cap, 0, (int64_t)PIN_CHUNK};
+    return NMPC_OK;
+}
+
 // a limit in ms -> ticks of the 100 MHz clock: 0 stays 0 (off), anything above it is at least one tick, and at most 2^52 ticks (16 months)
 static long long ms_to_ticks(double ms)
 {
@@ -359,50 +374,40 @@ static int solve_launch(nmpc_handle *h, int B, const double *d_p, double *d_u, c
     if (h->tl_budget > 0) hipLaunchKernelGGL(nmpc_stamp_kernel, dim3(1), dim3(64), 0, s, h->d_t0.p);
     HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, sizeof(unsigned int), s));
     // one instance per wave, three query points per pass: N_hor <= 20 with one stage per lane (hybrid / tri layouts), 20 < N_hor <= 40 with two
-    const int grid = B < h->grid_cap ? B : h->grid_cap;          // waves that take instances
+    const nmpc::LaunchGeometry geo = geometry_of(h, B);          // (nmpc_launch.h: the rule; nmpc_launch_geometry reports it)
     h->order_n = 0; h->order_from_prev = false;
-    if (B > grid) {        // more instances than resident waves: hand the hard-looking ones out first
-        if (h->use_order) {
-            h->order_n = B; h->order_from_prev = prev != nullptr;
-            if (prev) hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, prev, h->d_cls.p);
-            else hipLaunchKernelGGL(nmpc::nmpc_classify_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a, h->d_cls.p);
-            hipLaunchKernelGGL(nmpc::nmpc_order_kernel, dim3(1), dim3(1024), 0, s, B, h->d_cls.p, h->d_order.p);
-            a.order = h->d_order;
+    if (geo.ordered) {     // more instances than resident waves: hand the hard-looking ones out first
+        h->order_n = B; h->order_from_prev = prev != nullptr;
+        if (prev) hipLaunchKernelGGL(nmpc::nmpc_classify_prev_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, prev, h->d_cls.p);
+        else hipLaunchKernelGGL(nmpc::nmpc_classify_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a, h->d_cls.p);
+        hipLaunchKernelGGL(nmpc::nmpc_order_kernel, dim3(1), dim3(1024), 0, s, B, h->d_cls.p, h->d_order.p);
+        a.order = h->d_order;
+    }
+    if (geo.pools) {       // ... and instances may leave their wave at outer-iteration boundaries
+        const size_t cap = (size_t)geo.pool_cap;      // ring buffers of this launch: an instance waits in at most one slot at a time
+        const size_t cap_max = (size_t)h->max_batch;
+        Pools &pl = h->pools;
+        if (!pl.made()) {      // (all three or none: a half-made set is released and made again)
+            pl.release();
+            HIP_TRY(h, pl.park.alloc(cap_max * nmpc::park_stride(h->pb.N)));
+            HIP_TRY(h, pl.pool.alloc(nmpc::NPOOLS * cap_max));
+            HIP_TRY(h, pl.ctr.alloc(4 * nmpc::NPOOLS + 2));
         }
-        if ((h->P == 20 && (h->park_min > 0 || h->sched_mode > 0)) || (h->P == 40 && h->sched_mode > 0)) {      // instances may leave their wave at outer-iteration boundaries
-            const size_t cap = (size_t)B;                 // ring buffers of this launch: an instance waits in at most one slot at a time
-            const size_t cap_max = (size_t)h->max_batch;
-            Pools &pl = h->pools;
-            if (!pl.made()) {      // (all three or none: a half-made set is released and made again)
-                pl.release();
-                HIP_TRY(h, pl.park.alloc(cap_max * nmpc::park_stride(h->pb.N)));
-                HIP_TRY(h, pl.pool.alloc(nmpc::NPOOLS * cap_max));
-                HIP_TRY(h, pl.ctr.alloc(4 * nmpc::NPOOLS + 2));
-            }
-            HIP_TRY(h, hipMemsetAsync(pl.pool, 0xFF, nmpc::NPOOLS * cap * sizeof(int), s));
-            HIP_TRY(h, hipMemsetAsync(pl.ctr, 0, (4 * nmpc::NPOOLS + 2) * sizeof(unsigned int), s));
-            a.park_min = h->P == 20 ? h->park_min : 0; a.park_depth = h->park_depth;      // (the slot migration is the one-stage kernel's: two waves per SIMD)
-            a.park = pl.park; a.pool = pl.pool; a.pool_ctr = pl.ctr; a.pool_cap = (int)cap;
-            a.sched_mode = h->sched_mode;
-        }
+        HIP_TRY(h, hipMemsetAsync(pl.pool, 0xFF, nmpc::NPOOLS * cap * sizeof(int), s));
+        HIP_TRY(h, hipMemsetAsync(pl.ctr, 0, (4 * nmpc::NPOOLS + 2) * sizeof(unsigned int), s));
+        a.park_min = h->P == 20 ? h->park_min : 0; a.park_depth = h->park_depth;      // (the slot migration is the one-stage kernel's: two waves per SIMD)
+        a.park = pl.park; a.pool = pl.pool; a.pool_ctr = pl.ctr; a.pool_cap = (int)cap;
+        a.sched_mode = h->sched_mode;
     }
     {
-        // teams of four waves.  With fewer instances than workgroups fit on the chip every instance gets a workgroup of its
-        // own (one wave solves, three help from the first iteration on: the small-batch / latency mode); otherwise as many
-        // waves per workgroup take instances as it needs for all of them to start at once, up to all four.
-        const int max_wgs = h->grid_cap / nmpc::TEAM_WAVES;
-        int owners = (B + max_wgs - 1) / max_wgs;
-        if (owners > nmpc::TEAM_WAVES) owners = nmpc::TEAM_WAVES;
-        if (h->team_owners_forced > 0) owners = h->team_owners_forced;
-        int wgs = (grid + owners - 1) / owners;
-        if (wgs > max_wgs) wgs = max_wgs;
-        a.team_owners = owners;
-        a.sched_long_cap = (int)(h->sched_theta * (double)(wgs * owners));
-        a.sched_cold_cap = (int)(h->sched_cold * (double)(wgs * owners));
+        // teams of four waves, geo.owners of them taking instances (nmpc_launch.h)
+        a.team_owners = geo.owners;
+        a.sched_long_cap = (int)(h->sched_theta * (double)(geo.workgroups * geo.owners));
+        a.sched_cold_cap = (int)(h->sched_cold * (double)(geo.workgroups * geo.owners));
         a.team_help = h->team_help;
         a.cull_radius = h->cull_radius;
         // (with a limit set: the same kernel with the wall-clock test compiled in, nmpc_set_time_limits)
-        hipLaunchKernelGGL(h->kernel[timed(h)]->fn, dim3(wgs), dim3(64 * nmpc::TEAM_WAVES), h->team_lds, s, a);
+        hipLaunchKernelGGL(h->kernel[timed(h)]->fn, dim3(geo.workgroups), dim3(64 * nmpc::TEAM_WAVES), h->team_lds, s, a);
     }
     HIP_TRY(h, hipGetLastError());
     return NMPC_OK;
@@ -433,7 +438,6 @@ int nmpc_eval_batch_device(nmpc_handle *h, int B, const double *d_p, const doubl
 }
 
 // ---- host path: staging buffers sized for max_batch, allocated on first use ----
-static constexpr size_t PIN_CHUNK = 4u << 20;
 static int ensure_staging(nmpc_handle *h)
 {
     Staging &g = h->stg;

@@ -107,6 +107,14 @@ class BatchSolver:
         """The circle-culling radius in metres this handle's solves use (diagnostic; any value gives the same results)."""
         return float(self.lib.nmpc_cull_radius(self._h))
 
+    def launch_geometry(self, B: int) -> dict:
+        """How this handle would launch a solve of ``B`` instances (nmpc_launch_geometry; diagnostic, launches nothing): ``grid``,
+        ``owners``, ``workgroups``, ``ordered``, ``pools``, ``pool_cap``, and the handle's ``resident_waves`` and
+        ``staging_chunk_bytes``."""
+        info = _lib.NmpcLaunchInfo()
+        self._check(self.lib.nmpc_launch_geometry(self._h, int(B), C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in info._fields_ if name != "reserved"}
+
     @property
     def last_batch_ms(self) -> float:
         """Kernel time (HIP events) of the last host-path ``solve`` on this handle; per-instance times are in
