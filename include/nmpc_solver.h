@@ -745,6 +745,41 @@ int nmpc_loop_set_walls(nmpc_loop *l, int n_edge, const double *edge, int M, dou
  * none.  NMPC_ERR_BAD_ARG on a loop without walls or before its first step. */
 int nmpc_loop_walls(nmpc_loop *l, int32_t *wall_edge, int32_t *wall_stage);
 
+/* ---- walls of large maps: the edges a robot measures are found through a grid ---------------------
+ * nmpc_loop_set_walls measures every edge against every robot and takes 1024 edges at the most.  nmpc_loop_set_walls_grid is the same
+ * stage with the same rule -- its result IS nmpc_loop_set_walls' rule over all n_edge edges, for any n_edge it accepts: D(e), k*(e), the
+ * (D, e) selection with spacing, the placement and the record are the ones above -- but a robot forms D(e) only for the edges filed near
+ * it in a uniform grid.  The edges never move: the setter builds the grid once, on the host, and uploads it (DESIGN.md section 5.9 has
+ * the rule and the argument that no edge with D(e) < range*range is ever hidden).
+ *   grid      origin = the minimum over all edge end points, per axis; per axis n = floor(extent/cell) + 1 cells of edge h = cell, or, where
+ *             that would be more than 512 (the cap), n = 512 cells of edge h = extent/512; nx, ny >= 1
+ *   cellof    cellof(v) = clamp(floor((v - origin)/h), 0, n - 1) per axis, clamped in double before the conversion: monotone in v
+ *   filing    edge e in every cell of cellof(min(x1, x2)) .. cellof(max(x1, x2)) x cellof(min(y1, y2)) .. cellof(max(y1, y2))
+ *   storage   CSR, cells row-major (y*nx + x): cell c holds cell_edge[cell_off[c] .. cell_off[c + 1]), edge indices ascending
+ *   window    lo, hi = the minimum and maximum of the robot's predicted positions over the stages at which both coordinates are finite (a
+ *             robot without such a stage looks at nothing and gets no wall); per axis the cells cellof((lo - range) - m(lo)) ..
+ *             cellof((hi + range) + m(hi)) with the margin m(v) = slack + 2^-40*|v|, slack = 2^-40*(range + A) + 2^-500, A the largest
+ *             |coordinate| of an edge
+ *   looked    [B]: the distinct edges of the window's cells, each measured once however many cells it is filed in
+ * One kernel per step, one wave per active robot, in nmpc_loop_walls_kernel's place.  Candidates go to a list of 256 in LDS; a robot with
+ * more takes exact rounds that measure the window again for "the smallest (D, e) behind the last one considered": no bound on candidates.
+ *   n_edge            1 .. 1048576
+ *   cell              finite and > 0, metres
+ *   filings           8388608 (2^23) at the most over all edges
+ * Everything else as nmpc_loop_set_walls, refusals included; in addition NMPC_ERR_BAD_ARG, with a message that names the function and
+ * nothing changed or allocated on the device, for a cell that is not finite and positive and for a map with more filings than the limit
+ * (the message says to use a larger cell or shorter edges).  It is the loop's walls call: a second call, a call after a step and a call
+ * after nmpc_loop_set_walls are refused, and nmpc_loop_set_walls after it.  nmpc_loop_walls reads the record of either setter. */
+int nmpc_loop_set_walls_grid(nmpc_loop *l, int n_edge, const double *edge, int M, double radius, double range, double spacing, double cell);
+typedef struct nmpc_wall_grid {
+    double origin[2], h[2];
+    int32_t nx, ny, entries, reserved;
+} nmpc_wall_grid;
+/* Synchronises, then copies what is asked for (NULL = skip): the grid's header, cell_off [nx*ny + 1], cell_edge [entries] (read the
+ * header first for the sizes) and looked [B] of the last step (a retired robot keeps its last).  NMPC_ERR_BAD_ARG on a loop without
+ * nmpc_loop_set_walls_grid, and when looked is asked for before the loop's first step. */
+int nmpc_loop_wall_grid(nmpc_loop *l, nmpc_wall_grid *out, int32_t *cell_off, int32_t *cell_edge, int32_t *looked);
+
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);
 /* a/b and sqrt(a) as the device computes them: out_div/out_sqrt [n]. */

@@ -30,7 +30,7 @@ SYMBOLS = (
     "nmpc_loop_set_crowd", "nmpc_loop_crowd", "nmpc_loop_set_crowd_monitor", "nmpc_loop_crowd_clearance",
     "nmpc_loop_set_plant", "nmpc_loop_plant_applied", "nmpc_loop_plant_measured",
     "nmpc_loop_set_ensemble", "nmpc_loop_ensemble", "nmpc_loop_ensemble_groups",
-    "nmpc_loop_set_walls", "nmpc_loop_walls",
+    "nmpc_loop_set_walls", "nmpc_loop_walls", "nmpc_loop_set_walls_grid", "nmpc_loop_wall_grid",
     "nmpc_loop_set_track_monitor", "nmpc_loop_tracking",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
@@ -123,6 +123,10 @@ assert TRACKING_DTYPE.itemsize == 64
 # nmpc_peer_grid: the grid the peers of a step were found through (nmpc_loop_set_peers_grid)
 PEER_GRID_DTYPE = np.dtype([("origin", "<f8", 2), ("h", "<f8", 2), ("W", "<f8", 2), ("nx", "<i4"), ("ny", "<i4"), ("filed", "<i4"), ("reserved", "<i4")])
 assert PEER_GRID_DTYPE.itemsize == 64
+
+# nmpc_wall_grid: the grid the walls' edges are found through (nmpc_loop_set_walls_grid)
+WALL_GRID_DTYPE = np.dtype([("origin", "<f8", 2), ("h", "<f8", 2), ("nx", "<i4"), ("ny", "<i4"), ("entries", "<i4"), ("reserved", "<i4")])
+assert WALL_GRID_DTYPE.itemsize == 48
 
 # the drive log (nmpc_loop_set_log): nmpc_step_record, one per robot and step; nmpc_drive_summary, one per robot; nmpc_step_totals, one per step
 STEP_RECORD_DTYPE = np.dtype([("exit_status", "<i4"), ("leg", "<i4"), ("num_inner_iterations", "<u4"), ("num_outer_iterations", "<u4"),
@@ -399,6 +403,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_walls.restype = C.c_int
     lib.nmpc_loop_walls.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.nmpc_loop_walls.restype = C.c_int
+    lib.nmpc_loop_set_walls_grid.argtypes = [vp, C.c_int, dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]
+    lib.nmpc_loop_set_walls_grid.restype = C.c_int
+    lib.nmpc_loop_wall_grid.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.nmpc_loop_wall_grid.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]

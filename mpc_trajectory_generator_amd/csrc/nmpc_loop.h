@@ -844,6 +844,216 @@ __global__ __launch_bounds__(64) void nmpc_loop_walls_kernel(LoopView L, WallArg
     for (int q = m + lane; q < M; q += 64) { we[q] = -1; ws[q] = -1; }
 }
 
+// ---- walls through a grid (nmpc_loop_set_walls_grid; the rule, and why it hides no edge: DESIGN.md section 5.9) ----
+// The same rule over fewer edges.  The edges never move, so the setter builds the grid once, on the host: every edge is filed in every
+// cell of the rectangle of cells its box covers (CSR: cell_off, cell_edge, the edges ascending inside a cell), and a robot measures the
+// edges filed in the cells its predicted positions can reach.  Every D is formed by the expression of nmpc_loop_walls_kernel and tested
+// against the same range2, so a window wider than needed changes no result.
+constexpr int WALL_GRID_CAP = 512;                  // cells per axis at the most
+constexpr int WALL_GRID_MAX_EDGES = 1 << 20;
+constexpr int WALL_GRID_MAX_ENTRIES = 1 << 23;      // filings at the most (cell_edge and cell_tag: 32 MB each)
+constexpr int WALL_GRID_LIST = 256;                 // candidates the LDS list holds; more take the exact rounds
+
+struct WallGridArgs {
+    double origin[2], h[2];
+    int nx, ny;
+    double range, slack;      // the window's margin: slack = 2^-40 (range + the largest |coordinate| of an edge) + 2^-500
+    const int *cell_off;      // [nx * ny + 1]: cell c (row-major, y * nx + x) holds cell_edge[cell_off[c] .. cell_off[c + 1])
+    const int *cell_edge;     // [entries]
+    const int *cell_tag;      // [entries]: di | dj << 9 | col0 << 18, the filing's place in its edge's rectangle and the rectangle's first column
+    int *looked;              // [B]: the distinct edges the last step measured
+};
+
+// the cell of coordinate v on an axis of n cells of edge h from o: monotone non-decreasing in v (every operation is; t is a NaN only
+// with h = inf, where every v answers 0), clamped in double before the conversion.  The setter's filing uses the same function.
+__host__ __device__ __forceinline__ int wall_cellof(double v, double o, double h, int n)
+{
+    const double t = (v - o) / h;
+    if (!(t > 0.0)) return 0;
+    if (t >= (double)n) return n - 1;
+    return (int)t;
+}
+
+// D(e), its centre and k* against the positions in LDS: the expression of nmpc_loop_walls_kernel, operation for operation
+__device__ __forceinline__ void wall_closest(const double *own, int N, const double *ed, double &D, double &bx, double &by, int &bk)
+{
+    const double x1 = ed[0], y1 = ed[1], x2 = ed[2], y2 = ed[3];
+    const double ex = x2 - x1, ey = y2 - y1;
+    const double L2 = ex * ex + ey * ey;
+    D = __builtin_inf(); bx = 0.0; by = 0.0; bk = -1;
+    for (int k = 0; k < N; ++k) {
+        const double x = own[2 * k], y = own[2 * k + 1];
+        double t = 0.0;
+        if (L2 > 0.0) {
+            t = ((x - x1) * ex + (y - y1) * ey) / L2;
+            if (t < 0.0) t = 0.0;
+            if (t > 1.0) t = 1.0;
+        }
+        const double cx = x1 + t * ex, cy = y1 + t * ey;
+        const double dx = x - cx, dy = y - cy;
+        const double v = dx * dx + dy * dy;
+        if (v < D) { D = v; bx = cx; by = cy; bk = k; }
+    }
+}
+
+// One wave per active robot.  The predicted positions go to LDS and their box over the finite stages (a wave reduction of minima and
+// maxima) gives the window cx0 .. cx1 x cy0 .. cy1; a robot without a finite stage looks at nothing.  A row of the window is one run of
+// cell_edge; the rows' runs are laid end to end and the lanes stride over them in steps of 64, all lanes together.  An edge filed in
+// several cells of the window is measured in one of them only, the first of its rectangle that lies in the window (di == max(0, cx0 -
+// col0), the same in j), so `looked` counts distinct edges.  A candidate (D < range2) is appended to an LDS list at the place a ballot gives it.  The walk is that of
+// nmpc_loop_walls_kernel: every round each lane offers the smallest (D, e) of its candidates that lies behind the last one considered,
+// wave_argmin names the wave's, the lane that offered it hands over its centre and stage, and lanes 0 .. m - 1 test the centre against the
+// m taken before.  With WALL_GRID_LIST candidates or fewer a lane's candidates are its entries of the list; with more the list is
+// dropped and every round measures the window again, which needs no memory and gives the same (D, e) sequence.  A round considers one
+// candidate: the walk ends after `seen` rounds at the most, seen <= E the window's distinct edges.  No loop's bounds depend on a pose
+// other than through the window, which is clamped to the grid.
+__global__ __launch_bounds__(64) void nmpc_loop_walls_grid_kernel(LoopView L, WallArgs w, WallGridArgs g)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    __shared__ double lD[WALL_GRID_LIST], lx[WALL_GRID_LIST], ly[WALL_GRID_LIST];
+    __shared__ int lE[WALL_GRID_LIST], lk[WALL_GRID_LIST];
+    __shared__ double tx[WALLS_MAX_SLOTS], ty[WALLS_MAX_SLOTS];
+    __shared__ int rbeg[WALL_GRID_CAP], rpre[WALL_GRID_CAP + 1];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int N = L.N, M = w.M;
+    const double inf = __builtin_inf();
+    double lox = inf, loy = inf, hix = -inf, hiy = -inf;
+    for (int k = lane; k < N; k += 64) {
+        const double x = w.pred[((size_t)b * N + k) * 3], y = w.pred[((size_t)b * N + k) * 3 + 1];
+        own[2 * k] = x;
+        own[2 * k + 1] = y;
+        if (fabs(x) < inf && fabs(y) < inf) {          // a stage with a NaN or an infinity lowers nobody's D
+            lox = x < lox ? x : lox; loy = y < loy ? y : loy;
+            hix = x > hix ? x : hix; hiy = y > hiy ? y : hiy;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        double o = __shfl_xor(lox, off); lox = o < lox ? o : lox;
+        o = __shfl_xor(loy, off); loy = o < loy ? o : loy;
+        o = __shfl_xor(hix, off); hix = o > hix ? o : hix;
+        o = __shfl_xor(hiy, off); hiy = o > hiy ? o : hiy;
+    }
+    __syncthreads();
+    // the window: the same in every lane; cy1 < cy0 for a robot that looks at nothing
+    const int nx = g.nx;
+    int cx0 = 0, cx1 = 0, cy0 = 0, cy1 = -1;
+    if (lox <= hix) {
+        const double tm = 0x1p-40;
+        cx0 = wall_cellof((lox - g.range) - (g.slack + tm * fabs(lox)), g.origin[0], g.h[0], nx);
+        cx1 = wall_cellof((hix + g.range) + (g.slack + tm * fabs(hix)), g.origin[0], g.h[0], nx);
+        cy0 = wall_cellof((loy - g.range) - (g.slack + tm * fabs(loy)), g.origin[1], g.h[1], g.ny);
+        cy1 = wall_cellof((hiy + g.range) + (g.slack + tm * fabs(hiy)), g.origin[1], g.h[1], g.ny);
+    }
+    // the window's rows: row r is the run cell_edge[rbeg[r] .. ) of rpre[r + 1] - rpre[r] filings, rpre the exclusive prefix sums (a wave scan
+    // per 64 rows).  The filings of all rows then count as ONE list of `total`, over which the lanes stride: a window of several short rows
+    // costs one pass, not one per row.
+    const int R = cy1 - cy0 + 1;
+    int total = 0;
+    for (int r0 = 0; r0 < R; r0 += 64) {
+        const int r = r0 + lane;
+        int i0 = 0, len = 0;
+        if (r < R) {
+            i0 = g.cell_off[(cy0 + r) * nx + cx0];
+            len = g.cell_off[(cy0 + r) * nx + cx1 + 1] - i0;
+        }
+        int sum = len;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(sum, off);
+            if (lane >= off) sum += o;
+        }
+        if (r < R) { rbeg[r] = i0; rpre[r] = total + sum - len; }
+        total += __shfl(sum, 63);
+    }
+    if (lane == 0) rpre[R > 0 ? R : 0] = total;
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // place idx < total of that list: its filing's place i in cell_edge and, from the filing's tag, whether this is the cell at which its
+    // edge is measured (at most nine halvings over the rows; the last row r with rpre[r] <= idx holds idx, rows without filings are passed)
+    auto mine = [&](int idx, int &i) {
+        int lo = 0, hi = R - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (rpre[mid] <= idx) lo = mid; else hi = mid - 1;
+        }
+        i = rbeg[lo] + (idx - rpre[lo]);
+        const int tag = g.cell_tag[i];
+        const int di = tag & 511, dj = (tag >> 9) & 511, col0 = tag >> 18, row0 = cy0 + lo - dj;
+        return di == (cx0 > col0 ? cx0 - col0 : 0) && dj == (cy0 > row0 ? cy0 - row0 : 0);
+    };
+    int seen = 0, cnt = 0;
+    for (int base = 0; base < total; base += 64) {
+        const int idx = base + lane;
+        bool cand = false;
+        double D = inf, bx = 0.0, by = 0.0;
+        int bk = -1, e = LOOP_NONE, i = 0;
+        const bool meas = idx < total && mine(idx, i);
+        if (meas) {
+            e = g.cell_edge[i];
+            wall_closest(own, N, w.edge + 4 * (size_t)e, D, bx, by, bk);
+            cand = D < w.range2;
+        }
+        seen += __popcll(__ballot(meas));
+        const unsigned long long cm = __ballot(cand);
+        const int at = cnt + __popcll(cm & below);
+        if (cand && at < WALL_GRID_LIST) { lD[at] = D; lx[at] = bx; ly[at] = by; lE[at] = e; lk[at] = bk; }
+        cnt += __popcll(cm);
+    }
+    __syncthreads();
+    const bool listed = cnt <= WALL_GRID_LIST;        // (wave-uniform)
+    double *pc = L.P + (size_t)b * L.n_p + L.p_circ() + 3 * (size_t)(L.nobs - M);
+    int *we = w.wall_edge + (size_t)b * M, *ws = w.wall_stage + (size_t)b * M;
+    double ld = -1.0;         // the last candidate considered: behind it comes every real one (D >= 0)
+    int le = -1;
+    int m = 0;
+    for (int round = 0; round < seen && m < M; ++round) {
+        // this lane's offer: (d, j) with its centre and stage.  Among equal D the smaller edge index is kept.
+        double d = inf, ox = 0.0, oy = 0.0;
+        int j = LOOP_NONE, ok = -1;
+        if (listed) {
+            for (int q = lane; q < cnt; q += 64) {
+                const double c = lD[q];
+                const int e = lE[q];
+                if ((c > ld || (c == ld && e > le)) && (c < d || (c == d && e < j))) { d = c; j = e; ox = lx[q]; oy = ly[q]; ok = lk[q]; }
+            }
+        } else {
+            for (int idx = lane; idx < total; idx += 64) {
+                int i;
+                if (!mine(idx, i)) continue;
+                const int e = g.cell_edge[i];
+                double c, bx, by;
+                int bk;
+                wall_closest(own, N, w.edge + 4 * (size_t)e, c, bx, by, bk);
+                if (c < w.range2 && (c > ld || (c == ld && e > le)) && (c < d || (c == d && e < j))) { d = c; j = e; ox = bx; oy = by; ok = bk; }
+            }
+        }
+        double dd = d;
+        int jj = j;
+        wave_argmin(dd, jj);
+        if (jj == LOOP_NONE) break;           // (wave-uniform) no candidate left: the remaining slots keep the assembly's zeros
+        ld = dd; le = jj;
+        const int src = __ffsll((long long)__ballot(j == jj)) - 1;      // the one lane that measured edge jj
+        const double cx = __shfl(ox, src), cy = __shfl(oy, src);
+        const int ck = __shfl(ok, src);
+        bool close = false;
+        if (lane < m) {
+            const double ddx = cx - tx[lane], ddy = cy - ty[lane];
+            close = ddx * ddx + ddy * ddy < w.spacing2;
+        }
+        if (__any(close)) continue;           // (wave-uniform)
+        if (lane == 0) {
+            tx[m] = cx; ty[m] = cy;
+            pc[3 * m] = cx; pc[3 * m + 1] = cy; pc[3 * m + 2] = w.radius;
+            we[m] = jj; ws[m] = ck;
+        }
+        ++m;
+        __syncthreads();                      // lane 0's stores of tx, ty before the next round's loads
+    }
+    for (int q = m + lane; q < M; q += 64) { we[q] = -1; ws[q] = -1; }
+    if (lane == 0) g.looked[b] = seen;
+}
+
 // ---- retirement: robots that reached their goal leave the loop (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9) ----
 struct RetireArgs {
     int *retired_at;          // [B]: -1 = active

@@ -117,7 +117,13 @@ struct LoopWalls {           // nmpc_loop_set_walls: one more kernel per step, b
     nmpc::WallArgs a{};
     DevBuf<double> edge;             // [E][4]
     DevBuf<int> wall_edge, wall_stage;   // [B][M] each
+    // nmpc_loop_set_walls_grid: the edges a robot measures come from a grid built by the setter, nmpc_loop_walls_grid_kernel in the place
+    // of nmpc_loop_walls_kernel
+    nmpc::WallGridArgs g{};
+    nmpc_wall_grid hdr{};
+    DevBuf<int> cell_off, cell_edge, cell_tag, looked;     // [nx * ny + 1], [entries], [entries], [B]
     bool made() const { return edge != nullptr; }
+    bool grid() const { return cell_off != nullptr; }
 };
 struct LoopEnsemble {        // nmpc_loop_set_ensemble: one more kernel per step, the step's last
     nmpc::EnsembleArgs a{};
@@ -591,27 +597,98 @@ int nmpc_loop_set_ensemble(nmpc_loop *l, const int32_t *group_of, int G)
     return NMPC_OK;
 }
 
-int nmpc_loop_set_walls(nmpc_loop *l, int n_edge, const double *edge, int M, double radius, double range, double spacing)
+// The grid of nmpc_loop_set_walls_grid, built once on the host (the rule: DESIGN.md section 5.9; trajectory.wall_grid is its NumPy
+// statement): the header, the CSR arrays and per filing its tag for nmpc_loop_walls_grid_kernel.  -> false if the filings exceed
+// WALL_GRID_MAX_ENTRIES, with nothing allocated beyond the per-edge rectangles.
+struct WallGridHost {
+    nmpc_wall_grid hdr{};
+    double amax = 0.0;
+    std::vector<int> cell_off, cell_edge, cell_tag;
+    bool build(int E, const double *edge, double cell)
+    {
+        double lo[2] = {edge[0], edge[1]}, hi[2] = {edge[0], edge[1]};
+        for (int i = 0; i < 4 * E; ++i) {
+            const double v = edge[i];
+            lo[i & 1] = v < lo[i & 1] ? v : lo[i & 1];
+            hi[i & 1] = v > hi[i & 1] ? v : hi[i & 1];
+            amax = std::fabs(v) > amax ? std::fabs(v) : amax;
+        }
+        int n[2];
+        for (int ax = 0; ax < 2; ++ax) {
+            const double ext = hi[ax] - lo[ax], q = ext / cell;
+            hdr.origin[ax] = lo[ax];
+            if (q < (double)nmpc::WALL_GRID_CAP) { n[ax] = (int)q + 1; hdr.h[ax] = cell; }
+            else { n[ax] = nmpc::WALL_GRID_CAP; hdr.h[ax] = ext / (double)nmpc::WALL_GRID_CAP; }
+        }
+        hdr.nx = n[0]; hdr.ny = n[1];
+        // every edge's rectangle of cells: c0, c1, r0, r1
+        std::vector<int> rect(4 * (size_t)E);
+        long long entries = 0;
+        for (int e = 0; e < E; ++e) {
+            const double *d = edge + 4 * (size_t)e;
+            int *r = rect.data() + 4 * (size_t)e;
+            r[0] = nmpc::wall_cellof(d[0] < d[2] ? d[0] : d[2], lo[0], hdr.h[0], n[0]);
+            r[1] = nmpc::wall_cellof(d[0] < d[2] ? d[2] : d[0], lo[0], hdr.h[0], n[0]);
+            r[2] = nmpc::wall_cellof(d[1] < d[3] ? d[1] : d[3], lo[1], hdr.h[1], n[1]);
+            r[3] = nmpc::wall_cellof(d[1] < d[3] ? d[3] : d[1], lo[1], hdr.h[1], n[1]);
+            entries += (long long)(r[1] - r[0] + 1) * (r[3] - r[2] + 1);
+        }
+        if (entries > nmpc::WALL_GRID_MAX_ENTRIES) return false;
+        hdr.entries = (int)entries;
+        const size_t cells = (size_t)n[0] * n[1];
+        cell_off.assign(cells + 1, 0);
+        for (int e = 0; e < E; ++e) {
+            const int *r = rect.data() + 4 * (size_t)e;
+            for (int j = r[2]; j <= r[3]; ++j)
+                for (int i = r[0]; i <= r[1]; ++i) cell_off[(size_t)j * n[0] + i + 1]++;
+        }
+        for (size_t c = 0; c < cells; ++c) cell_off[c + 1] += cell_off[c];
+        cell_edge.resize(entries); cell_tag.resize(entries);
+        std::vector<int> at(cell_off.begin(), cell_off.end() - 1);
+        for (int e = 0; e < E; ++e) {          // edges in ascending index: they ascend inside every cell
+            const int *r = rect.data() + 4 * (size_t)e;
+            for (int j = r[2]; j <= r[3]; ++j)
+                for (int i = r[0]; i <= r[1]; ++i) {
+                    const int k = at[(size_t)j * n[0] + i]++;
+                    cell_edge[k] = e;
+                    cell_tag[k] = (i - r[0]) | (j - r[2]) << 9 | r[0] << 18;
+                }
+        }
+        return true;
+    }
+};
+
+// both walls setters: `cell` NULL = every edge against every robot (nmpc_loop_set_walls), else the grid's cell
+static int loop_set_walls(nmpc_loop *l, const char *name, int max_edge, int n_edge, const double *edge, int M, double radius, double range,
+                          double spacing, const double *cell)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
-    if (const int rc = loop_setter(l, "nmpc_loop_set_walls", l->walls.made(), "the loop has its walls already")) return rc;
+    if (const int rc = loop_setter(l, name, l->walls.made(), "the loop has its walls already")) return rc;
     nmpc_handle *h = l->h;
     const nmpc::LoopView &v = l->v;
     const size_t B = (size_t)v.B;
-    if (!edge) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: edge is NULL");
-    if (n_edge < 1 || n_edge > nmpc::WALLS_MAX_EDGES) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: n_edge outside 1 .. 1024");
+    const std::string fn = std::string(name) + ": ";
+    if (!edge) return fail(h, NMPC_ERR_BAD_ARG, (fn + "edge is NULL").c_str());
+    if (n_edge < 1 || n_edge > max_edge) return fail(h, NMPC_ERR_BAD_ARG, (fn + "n_edge outside 1 .. " + std::to_string(max_edge)).c_str());
     for (int i = 0; i < 4 * n_edge; ++i)
         if (!(edge[i] >= -DBL_MAX && edge[i] <= DBL_MAX))
-            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_walls: a coordinate of edge " + std::to_string(i / 4) + " is not finite").c_str());
-    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: M < 1");
-    if (M > v.nobs || M > nmpc::WALLS_MAX_SLOTS) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: M > Nobs, no such circle slot");
+            return fail(h, NMPC_ERR_BAD_ARG, (fn + "a coordinate of edge " + std::to_string(i / 4) + " is not finite").c_str());
+    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, (fn + "M < 1").c_str());
+    if (M > v.nobs || M > nmpc::WALLS_MAX_SLOTS) return fail(h, NMPC_ERR_BAD_ARG, (fn + "M > Nobs, no such circle slot").c_str());
     for (int i = 0; i < l->R; ++i)
         if (l->h_n_vert[i] + M > v.nobs)
-            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_walls: route " + std::to_string(i) + " has " + std::to_string(l->h_n_vert[i]) +
+            return fail(h, NMPC_ERR_BAD_ARG, (fn + "route " + std::to_string(i) + " has " + std::to_string(l->h_n_vert[i]) +
                                               " vertices, n_vert + M > Nobs: its last M circle slots are not free").c_str());
     for (const double x : {radius, range})
-        if (!(x > 0.0) || x > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: radius and range must be finite and positive");
-    if (!(spacing >= 0.0) || spacing > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_walls: spacing must be finite and not negative");
+        if (!(x > 0.0) || x > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (fn + "radius and range must be finite and positive").c_str());
+    if (!(spacing >= 0.0) || spacing > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (fn + "spacing must be finite and not negative").c_str());
+    WallGridHost gh;
+    if (cell) {
+        if (!(*cell > 0.0) || *cell > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (fn + "cell must be finite and positive").c_str());
+        if (!gh.build(n_edge, edge, *cell))
+            return fail(h, NMPC_ERR_BAD_ARG, (fn + "the edges are filed in more than " + std::to_string(nmpc::WALL_GRID_MAX_ENTRIES) +
+                                              " cells in all: use a larger cell or shorter edges").c_str());
+    }
     LoopWalls st;
     DevBuf<double> pred;           // the loop's, unless the peers or the crowd have made it
     if (!l->d_pred) HIP_TRY(h, pred.alloc(B * v.N * 3));
@@ -621,9 +698,31 @@ int nmpc_loop_set_walls(nmpc_loop *l, int n_edge, const double *edge, int M, dou
     nmpc::WallArgs &w = st.a;
     w.E = n_edge; w.M = M; w.radius = radius; w.range2 = range * range; w.spacing2 = spacing * spacing;
     w.edge = st.edge; w.pred = l->d_pred.p ? l->d_pred.p : pred.p; w.wall_edge = st.wall_edge; w.wall_stage = st.wall_stage;
+    if (cell) {
+        HIP_TRY(h, st.cell_off.upload(gh.cell_off.data(), gh.cell_off.size()));
+        HIP_TRY(h, st.cell_edge.upload(gh.cell_edge.data(), gh.cell_edge.size()));
+        HIP_TRY(h, st.cell_tag.upload(gh.cell_tag.data(), gh.cell_tag.size()));
+        HIP_TRY(h, st.looked.alloc_fill(B, 0));
+        st.hdr = gh.hdr;
+        nmpc::WallGridArgs &g = st.g;
+        for (int ax = 0; ax < 2; ++ax) { g.origin[ax] = gh.hdr.origin[ax]; g.h[ax] = gh.hdr.h[ax]; }
+        g.nx = gh.hdr.nx; g.ny = gh.hdr.ny;
+        g.range = range; g.slack = 0x1p-40 * (range + gh.amax) + 0x1p-500;
+        g.cell_off = st.cell_off; g.cell_edge = st.cell_edge; g.cell_tag = st.cell_tag; g.looked = st.looked;
+    }
     l->walls = std::move(st);
     if (pred) l->d_pred = std::move(pred);
     return NMPC_OK;
+}
+
+int nmpc_loop_set_walls(nmpc_loop *l, int n_edge, const double *edge, int M, double radius, double range, double spacing)
+{
+    return loop_set_walls(l, "nmpc_loop_set_walls", nmpc::WALLS_MAX_EDGES, n_edge, edge, M, radius, range, spacing, nullptr);
+}
+
+int nmpc_loop_set_walls_grid(nmpc_loop *l, int n_edge, const double *edge, int M, double radius, double range, double spacing, double cell)
+{
+    return loop_set_walls(l, "nmpc_loop_set_walls_grid", nmpc::WALL_GRID_MAX_EDGES, n_edge, edge, M, radius, range, spacing, &cell);
 }
 
 // a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
@@ -682,7 +781,9 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
                 hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, v, p);
             }
         }
-        if (l->walls.made())
+        if (l->walls.grid())
+            hipLaunchKernelGGL(nmpc::nmpc_loop_walls_grid_kernel, dim3(n), dim3(64), 0, s, v, l->walls.a, l->walls.g);
+        else if (l->walls.made())
             hipLaunchKernelGGL(nmpc::nmpc_loop_walls_kernel, dim3(n), dim3(64), nmpc::WallArgs::lds_bytes(l->walls.a.E), s, v, l->walls.a);
         if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, v, r.a);
         HIP_TRY(h, hipGetLastError());
@@ -827,10 +928,23 @@ int nmpc_loop_walls(nmpc_loop *l, int32_t *wall_edge, int32_t *wall_stage)
 {
     if (const int rc = loop_settle(l)) return rc;
     const LoopWalls &w = l->walls;
-    if (!w.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_walls: the loop has no walls (nmpc_loop_set_walls)");
+    if (!w.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_walls: the loop has no walls (nmpc_loop_set_walls, nmpc_loop_set_walls_grid)");
     if (l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_walls: before the loop's first step");
     HIP_TRY(l->h, w.wall_edge.read(wall_edge, (size_t)l->v.B * w.a.M));
     HIP_TRY(l->h, w.wall_stage.read(wall_stage, (size_t)l->v.B * w.a.M));
+    return NMPC_OK;
+}
+
+int nmpc_loop_wall_grid(nmpc_loop *l, nmpc_wall_grid *out, int32_t *cell_off, int32_t *cell_edge, int32_t *looked)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    const LoopWalls &w = l->walls;
+    if (!w.grid()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_wall_grid: the loop has no walls grid (nmpc_loop_set_walls_grid)");
+    if (looked && l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_wall_grid: looked before the loop's first step");
+    if (out) *out = w.hdr;
+    HIP_TRY(l->h, w.cell_off.read(cell_off, (size_t)w.hdr.nx * w.hdr.ny + 1));
+    HIP_TRY(l->h, w.cell_edge.read(cell_edge, (size_t)w.hdr.entries));
+    HIP_TRY(l->h, w.looked.read(looked, (size_t)l->v.B));
     return NMPC_OK;
 }
 

@@ -516,6 +516,9 @@ class Crowd:
 
 
 WALLS_MAX_EDGES = 1024       # E of a loop's walls at the most (nmpc_loop_set_walls)
+WALL_GRID_MAX_EDGES = 1 << 20        # ... with a ``cell`` (nmpc_loop_set_walls_grid)
+WALL_GRID_MAX_ENTRIES = 1 << 23      # filings of all edges at the most
+WALL_GRID_CAP = 512                  # cells per axis at the most (csrc/nmpc_loop.h)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -525,12 +528,17 @@ class Walls:
     predicted positions, closer than ``range`` and, among themselves, no closer than ``spacing``, take the LAST ``slots`` static-circle
     slots of its parameter vector as circles of ``radius``.  No polygon structure is needed (``frontend.map_edges(...)[0]`` gives a
     scene's edges, ``workloads.subdivided_map`` a finer cut).  Every route of the loop must leave the slots free: n_vert + slots <=
-    Nobs.  ``wall_edge`` and ``wall_stage`` [B, slots] name the edge in each slot and the stage at which it came closest (-1: none)."""
+    Nobs.  ``wall_edge`` and ``wall_stage`` [B, slots] name the edge in each slot and the stage at which it came closest (-1: none).
+
+    ``cell`` (metres; ``None``: every edge against every robot, 1024 edges at the most) finds the edges a robot measures through a
+    static grid (``wall_grid``, ``nmpc_loop_set_walls_grid``): up to 1048576 edges, at a cost that grows with what is near a robot, not
+    with the map.  No result depends on it; ``wall_looked`` [B] counts the distinct edges each robot measured at its last step."""
     edges: object
     slots: int
     radius: float
     range: float
     spacing: float = 0.0
+    cell: float = None
 
     def checked(self, cfg, routes):
         """-> edges [E, 4] float64, contiguous; ValueError for what ``nmpc_loop_set_walls`` refuses (``routes``: every route of the
@@ -539,8 +547,11 @@ class Walls:
         if edges.ndim != 2 or edges.shape[1] != 4:
             raise ValueError(f"walls: edges of shape {edges.shape}, not [E, 4]")
         E = len(edges)
-        if E < 1 or E > WALLS_MAX_EDGES:
-            raise ValueError(f"walls: {E} edges, 1 to {WALLS_MAX_EDGES} are taken")
+        most = WALLS_MAX_EDGES if self.cell is None else WALL_GRID_MAX_EDGES
+        if E < 1 or E > most:
+            raise ValueError(f"walls: {E} edges, 1 to {most} are taken")
+        if self.cell is not None and not (math.isfinite(self.cell) and self.cell > 0):
+            raise ValueError("walls: cell must be finite and positive")
         if not np.isfinite(edges).all():
             raise ValueError("walls: a coordinate that is not finite")
         if self.slots < 1 or self.slots > cfg.Nobs:
@@ -554,6 +565,105 @@ class Walls:
         if not (math.isfinite(self.spacing) and self.spacing >= 0):
             raise ValueError("walls: spacing must be finite and not negative")
         return edges
+
+
+class WallGrid:
+    """The static grid of a map's wall segments (``wall_grid``): ``origin`` [2], ``h`` [2] the cells' edges, ``nx``, ``ny``, ``entries``
+    (what ``nmpc_loop_wall_grid`` returns as its header), the CSR arrays ``cell_off`` [nx * ny + 1] and ``cell_edge`` [entries] int32
+    (cells row-major, y * nx + x; edge indices ascending inside a cell), every edge's rectangle of cells ``rect`` [E, 4] = (first column,
+    last column, first row, last row), ``window(pred_b, range)`` and ``looks_at(pred_b, range)``."""
+
+    def header(self):
+        """-> the header as one ``_lib.WALL_GRID_DTYPE`` record, as the device reports it."""
+        rec = np.zeros((), dtype=_lib.WALL_GRID_DTYPE)
+        rec["origin"], rec["h"] = self.origin, self.h
+        rec["nx"], rec["ny"], rec["entries"] = self.nx, self.ny, self.entries
+        return rec
+
+    def _cellof(self, v, axis):
+        """The cell of coordinate ``v`` on ``axis``: monotone non-decreasing in ``v``, clamped before the conversion (wall_cellof of
+        csrc/nmpc_loop.h).  Filing and looking up use this one function."""
+        n = (self.nx, self.ny)[axis]
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = (np.float64(v) - self.origin[axis]) / self.h[axis]
+        if not t > 0.0:
+            return 0
+        if t >= float(n):
+            return n - 1
+        return int(t)
+
+    def window(self, pred_b, range):
+        """-> (cx0, cx1, cy0, cy1), inclusive: the cells a robot with the predicted positions ``pred_b`` [N, >= 2] looks at; None for
+        a robot without a stage at which both coordinates are finite."""
+        xy = np.asarray(pred_b, dtype=np.float64)[:, :2]
+        xy = xy[np.isfinite(xy).all(axis=1)]
+        if not len(xy):
+            return None
+        lo, hi, r, tm = xy.min(axis=0), xy.max(axis=0), np.float64(range), np.float64(2.0 ** -40)
+        slack = tm * (r + self.amax) + np.float64(2.0 ** -500)
+        with np.errstate(over="ignore"):
+            a = [(lo[ax] - r) - (slack + tm * abs(lo[ax])) for ax in (0, 1)]
+            z = [(hi[ax] + r) + (slack + tm * abs(hi[ax])) for ax in (0, 1)]
+        return self._cellof(a[0], 0), self._cellof(z[0], 0), self._cellof(a[1], 1), self._cellof(z[1], 1)
+
+    def looks_at(self, pred_b, range):
+        """-> the distinct edges filed in the cells of the robot's window, ascending (none for a robot without a window)."""
+        w = self.window(pred_b, range)
+        if w is None:
+            return np.zeros(0, dtype=np.int32)
+        cx0, cx1, cy0, cy1 = w
+        r = self.rect
+        return np.nonzero((r[:, 0] <= cx1) & (r[:, 1] >= cx0) & (r[:, 2] <= cy1) & (r[:, 3] >= cy0))[0].astype(np.int32)
+
+
+def wall_grid(edges, cell):
+    """The static grid of the walls rule with a ``cell`` over ``edges`` [E, 4], in the setter's arithmetic: -> a
+    ``WallGrid``.
+
+    ``origin`` is the minimum over all end points per axis; an axis has floor(extent / cell) + 1 cells of edge ``cell``, or
+    ``WALL_GRID_CAP`` cells of edge extent / ``WALL_GRID_CAP`` where that would be more.  Edge e is filed in every cell of the rectangle
+    cellof(min(x1, x2)) .. cellof(max(x1, x2)) x cellof(min(y1, y2)) .. cellof(max(y1, y2)).  A robot looks at the cells from that of
+    ``(lo - range) - m(lo)`` to that of ``(hi + range) + m(hi)`` per axis, lo and hi the extremes of its finite predicted positions and
+    m(v) = slack + 2^-40 |v|, slack = 2^-40 (range + the largest |coordinate| of an edge) + 2^-500: every edge with D < range^2 is filed
+    there.  ValueError if the filings exceed ``WALL_GRID_MAX_ENTRIES``."""
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    E = len(edges)
+    g = WallGrid()
+    g.cell = float(cell)
+    xs, ys = edges[:, [0, 2]], edges[:, [1, 3]]
+    g.origin = np.array([xs.min(), ys.min()])
+    g.amax = np.float64(np.abs(edges).max())
+    g.h = np.array([g.cell, g.cell])
+    n = [1, 1]
+    with np.errstate(over="ignore"):
+        ext = np.array([xs.max(), ys.max()]) - g.origin
+    for ax in (0, 1):
+        q = ext[ax] / g.cell
+        if q < float(WALL_GRID_CAP):
+            n[ax] = int(q) + 1
+        else:
+            n[ax], g.h[ax] = WALL_GRID_CAP, ext[ax] / float(WALL_GRID_CAP)
+    g.nx, g.ny = n
+
+    def cells(v, ax):                                                       # _cellof over an array
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = (v - g.origin[ax]) / g.h[ax]
+        t = np.where(t > 0.0, t, 0.0)                                       # (a NaN goes to 0)
+        return np.where(t >= float(n[ax]), n[ax] - 1, np.minimum(t, float(n[ax])).astype(np.int64)).astype(np.int64)
+    g.rect = np.stack([cells(xs.min(axis=1), 0), cells(xs.max(axis=1), 0), cells(ys.min(axis=1), 1), cells(ys.max(axis=1), 1)], axis=1)
+    w, hgt = g.rect[:, 1] - g.rect[:, 0] + 1, g.rect[:, 3] - g.rect[:, 2] + 1
+    g.entries = int((w * hgt).sum())
+    if g.entries > WALL_GRID_MAX_ENTRIES:
+        raise ValueError(f"walls: the edges are filed in {g.entries} cells in all, more than {WALL_GRID_MAX_ENTRIES}: use a larger cell or shorter edges")
+    # every filing (e, cell), edge after edge; a stable sort by cell keeps the edges ascending inside a cell
+    e_of = np.repeat(np.arange(E, dtype=np.int64), w * hgt)
+    k = np.arange(g.entries, dtype=np.int64) - np.repeat(np.cumsum(w * hgt) - w * hgt, w * hgt)      # the filing's number inside its edge
+    we = w[e_of]
+    c_of = (g.rect[e_of, 2] + k // we) * g.nx + g.rect[e_of, 0] + k % we
+    order = np.argsort(c_of, kind="stable")
+    g.cell_edge = e_of[order].astype(np.int32)
+    g.cell_off = np.concatenate([[0], np.cumsum(np.bincount(c_of, minlength=g.nx * g.ny))]).astype(np.int32)
+    return g
 
 
 PEER_GRID_CAP = 128          # cells per axis at the most (csrc/nmpc_loop.h)
@@ -1221,6 +1331,9 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._wall_edges = walls.checked(cfg, self.routes)
             self.wall_edge = np.full((B, walls.slots), -1, dtype=np.int32)    # the edge in circle slot Nobs - slots + m of robot b's p (-1: none)
             self.wall_stage = np.full((B, walls.slots), -1, dtype=np.int32)   # the stage at which it came closest
+            if walls.cell is not None:
+                self.wall_grid = wall_grid(self._wall_edges, walls.cell)
+                self.wall_looked = np.zeros(B, dtype=np.int32)                # the distinct edges each robot measured at its last step
         self.track = track
         if track is not None:
             track.checked()
@@ -1363,6 +1476,8 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         if not len(who):
             return
         pred = self.predict()
+        if wl.cell is not None:                                              # the results below are the all-edges rule's: the grid only counts
+            self.wall_looked[who] = [len(self.wall_grid.looks_at(pred[b], wl.range)) for b in who]
         r2, s2 = wl.range * wl.range, wl.spacing * wl.spacing
         x1, y1, x2, y2 = (edges[:, k][None, :] for k in range(4))
         self.wall_edge[who], self.wall_stage[who] = -1, -1
@@ -1863,7 +1978,9 @@ class DeviceRecedingHorizon:
     ``walls`` (a ``Walls``): every step each active robot's closest points on the map's wall segments, measured against its predicted
     poses, become circles in the last ``slots`` circle slots of its parameter vector (``nmpc_loop_set_walls``):
     ``nmpc_loop_walls_kernel``, one wave per robot, between the peers' kernels and the solve.  ``walls()`` reads the edges and stages
-    chosen.  Its host mirror is ``FleetRecedingHorizon`` with the same ``walls`` (tests/test_gpu_walls_loop.py).
+    chosen.  Its host mirror is ``FleetRecedingHorizon`` with the same ``walls`` (tests/test_gpu_walls_loop.py).  With ``walls.cell`` the
+    edges a robot measures come from a static grid built by the setter (``nmpc_loop_set_walls_grid``, ``nmpc_loop_walls_grid_kernel``): the
+    same results on up to 1048576 edges, ``wall_grid()`` reads the grid and the edges each robot looked at (tests/test_gpu_walls_grid_loop.py).
 
     ``track`` (a ``TrackMonitor``, needs ``max_steps`` > 0): how far every robot was from the route it was asked to follow, in position
     and (unwrapped) heading, the rows of the largest errors, its progress along the route and the rows further than ``tol`` from it are
@@ -1981,8 +2098,12 @@ class DeviceRecedingHorizon:
             except ValueError:
                 self.close()
                 raise
-            self._set(self.lib.nmpc_loop_set_walls(h, len(edges), _lib.as_dp(edges), int(walls.slots), float(walls.radius), float(walls.range),
-                                                   float(walls.spacing)))
+            if walls.cell is None:
+                self._set(self.lib.nmpc_loop_set_walls(h, len(edges), _lib.as_dp(edges), int(walls.slots), float(walls.radius), float(walls.range),
+                                                       float(walls.spacing)))
+            else:
+                self._set(self.lib.nmpc_loop_set_walls_grid(h, len(edges), _lib.as_dp(edges), int(walls.slots), float(walls.radius),
+                                                            float(walls.range), float(walls.spacing), float(walls.cell)))
         self.track = track
         if track is not None:
             try:
@@ -2100,6 +2221,17 @@ class DeviceRecedingHorizon:
         edge, stage = np.empty((self.B, M), dtype=np.int32), np.empty((self.B, M), dtype=np.int32)
         self.solver._check(self.lib.nmpc_loop_walls(self._l, _lib.as_i32p(edge), _lib.as_i32p(stage)))
         return edge, stage
+
+    def wall_grid(self):
+        """-> (header, cell_off [nx * ny + 1], cell_edge [entries], looked [B]) after synchronising: the grid the walls' edges are found
+        through (one ``_lib.WALL_GRID_DTYPE`` record: origin, h, nx, ny, entries), its CSR arrays (int32) and the distinct edges each robot
+        measured at its last step.  Needs ``walls`` with a ``cell`` and a step taken."""
+        hdr = np.zeros((), dtype=_lib.WALL_GRID_DTYPE)
+        self.solver._check(self.lib.nmpc_loop_wall_grid(self._l, hdr.ctypes.data, None, None, None))
+        off, edge = np.empty(int(hdr["nx"]) * int(hdr["ny"]) + 1, dtype=np.int32), np.empty(int(hdr["entries"]), dtype=np.int32)
+        looked = np.empty(self.B, dtype=np.int32)
+        self.solver._check(self.lib.nmpc_loop_wall_grid(self._l, None, _lib.as_i32p(off), _lib.as_i32p(edge), _lib.as_i32p(looked)))
+        return hdr, off, edge, looked
 
     def map_clearance(self):
         """-> the map monitor's records [B] (``_lib.MAP_CLEARANCE_DTYPE``: wall2, wall_row, wall_edge, hits, hit_row, hit_poly, reserved)

@@ -332,6 +332,17 @@ def walls_differing(dev, host):
     return [n for n, a in got.items() if a.shape != getattr(host, n).shape or not np.array_equal(a, getattr(host, n))]
 
 
+def wall_grid_differing(dev, host):
+    """What walls with a ``cell`` keep beside ``walls_differing`` (``dev``: a ``DeviceRecedingHorizon`` with such walls and a step
+    taken, ``host``: its mirror) -> the names out of the grid's header fields, cell_off, cell_edge and looked that differ from the
+    mirror's ``wall_grid`` and ``wall_looked``."""
+    hdr, off, edge, looked = dev.wall_grid()
+    g, want = host.wall_grid, host.wall_grid.header()
+    bad = [f for f in ("origin", "h", "nx", "ny", "entries") if hdr[f].tobytes() != want[f].tobytes()]
+    pairs = (("cell_off", off, g.cell_off), ("cell_edge", edge, g.cell_edge), ("looked", looked, host.wall_looked))
+    return bad + [n for n, a, b in pairs if a.shape != b.shape or not np.array_equal(a, b)]
+
+
 def subdivided_map(edges, poly_off, pieces):
     """-> (edges [E * pieces, 4], poly_off): every edge of a map (``frontend.map_edges``) cut into ``pieces`` collinear pieces, in the
     edge's direction, polygon by polygon as before: piece i runs from a + (i / pieces) * (b - a) to the next piece's start, and the last

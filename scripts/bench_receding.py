@@ -37,7 +37,9 @@ on the host -- and with --ensemble the largest relative difference of those stan
 --walls M: the walls stage (nmpc_loop_set_walls): every step each robot's closest points on the scene's true walls
 (frontend.map_edges, with --walls-pieces P every edge cut into P pieces by workloads.subdivided_map) within --walls-range metres of its predicted
 path, no closer to each other than --walls-spacing, become circles of --walls-radius (default vehicle_width / 2 + vehicle_margin) in the last M
-static-circle slots of its p; the result line gains walls: the edges and the share of those slots filled at the last step, and with --map the
+static-circle slots of its p (--walls-cell H: the edges a robot measures are found through a grid of H-metre cells, nmpc_loop_set_walls_grid, which
+lifts the limit of 1024 edges; the result line then has the edges looked at and, from whole runs of the same fleet timed in this run, the time per step
+under the grid's setter, under the all-edges one up to 1024 edges, and their difference: the two solve the same problems, so it is the stages'); the result line gains walls: the edges and the share of those slots filled at the last step, and with --map the
 map_clearance beside it is the closest approach with the walls seen.  --host: parameter assembly on the host (NumPy-vectorised) around BatchSolver.solve.  Prints one JSON line."""
 import argparse
 import json
@@ -110,7 +112,11 @@ ap.add_argument("--walls", type=int, default=0, metavar="M",
 ap.add_argument("--walls-range", type=float, default=2.0, metavar="R", help="with --walls: how far from its predicted path a robot sees a wall, in metres")
 ap.add_argument("--walls-spacing", type=float, default=0.0, metavar="S", help="with --walls: no two wall circles of a robot closer than this, in metres")
 ap.add_argument("--walls-radius", type=float, default=None, metavar="RC", help="with --walls: the circles' radius (default vehicle_width / 2 + vehicle_margin)")
-ap.add_argument("--walls-pieces", type=int, default=1, metavar="P", help="with --walls: every edge of the map cut into P pieces (26 P edges, 1024 at the most)")
+ap.add_argument("--walls-pieces", type=int, default=1, metavar="P",
+                help="with --walls: every edge of the map cut into P pieces (26 P edges; 1024 at the most without --walls-cell, 1048576 with it)")
+ap.add_argument("--walls-cell", type=float, default=None, metavar="H",
+                help="with --walls: find the edges a robot measures through a static grid of H-metre cells (nmpc_loop_set_walls_grid): the same "
+                     "circles; the result line gains the edges looked at and, up to 1024 edges, the time per step under either setter and their difference")
 ap.add_argument("--back", type=int, default=60, help="--routes 1: no robot starts within this many samples of the route's end")
 ap.add_argument("--experiments", action="store_true", help="the experiments build of the library (reads the NMPC_* knobs: A/B runs only)")
 args = ap.parse_args()
@@ -138,6 +144,8 @@ if (args.crowd_watch or args.crowd < 0) and args.crowd < 1:
     ap.error("--crowd D: D >= 1, and --crowd-watch goes with it")
 if args.walls < 0 or (args.walls and (args.host or args.steps < 1)) or args.walls_pieces < 1:
     ap.error("--walls M: M >= 1, on the device loop (no --host) with --steps >= 1; --walls-pieces P: P >= 1")
+if args.walls_cell is not None and not (args.walls and 0 < args.walls_cell < float("inf")):
+    ap.error("--walls-cell H: goes with --walls, H finite and positive")
 planted = args.plant_act > 0 or args.plant_proc > 0 or args.plant_meas > 0
 if min(args.plant_act, args.plant_proc, args.plant_meas) < 0 or (planted and args.host):
     ap.error("--plant-act, --plant-proc, --plant-meas: >= 0, on the device loop (no --host)")
@@ -188,7 +196,8 @@ if args.walls:
     from mpc_trajectory_generator_amd.trajectory import Walls
     from mpc_trajectory_generator_amd.workloads import subdivided_map
     walls = Walls(subdivided_map(*map_edges(scene_planner(cfg, args.scene)), args.walls_pieces)[0], args.walls,
-                  cfg.vehicle_width / 2 + cfg.vehicle_margin if args.walls_radius is None else args.walls_radius, args.walls_range, args.walls_spacing)
+                  cfg.vehicle_width / 2 + cfg.vehicle_margin if args.walls_radius is None else args.walls_radius, args.walls_range, args.walls_spacing,
+                  cell=args.walls_cell)
 
 planning = {}
 legs_of = None
@@ -252,7 +261,7 @@ if args.crowd:
               f"range {args.crowd_range} m" + (", crowd observer" if args.crowd_watch else "") + ("" if args.peers else f", {K} scripted ellipses"))
 if walls is not None:
     fleet += (f", {args.walls} wall slots per robot over {len(walls.edges)} edges, range {args.walls_range} m, spacing {args.walls_spacing} m, "
-              f"radius {walls.radius} m")
+              f"radius {walls.radius} m" + (f", found through a grid of {args.walls_cell} m" if args.walls_cell is not None else ""))
 solver = BatchSolver(cfg, max_batch=B, **sopts)
 missions_of = lambda ids: None
 routes_of = lambda ids: (routes, None if route_of is None else route_of[ids])
@@ -300,7 +309,7 @@ if not args.host:
             cov = cov + wi[:, None] * (r["cov"] + np.stack([d[:, 0] * d[:, 0], d[:, 0] * d[:, 1], d[:, 1] * d[:, 1], d[:, 2] * d[:, 2]], axis=1))
         return n, arrived, mean, cov
 
-    def make_loop(sv, ids):
+    def make_loop(sv, ids, walls=walls):
         sub_routes, sub_route_of = routes_of(ids)
         return DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                      route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
@@ -365,6 +374,39 @@ if not args.host:
         quality["walls"] = {"edges": len(walls.edges), "slots": args.walls, "range_m": args.walls_range, "spacing_m": args.walls_spacing,
                             "radius_m": walls.radius, "slots_filled_frac": float((edge >= 0).mean()),
                             "robots_with_a_wall_frac": float((edge >= 0).any(axis=1).mean())}
+        if args.walls_cell is not None:
+            grids = [rh.wall_grid() for rh in loops]                      # the same grid in every sub-fleet; looked is the last step's
+            looked = np.concatenate([g[3] for g in grids])
+            hdr = grids[0][0]
+            quality["walls"].update({"cell_m": args.walls_cell, "cells": [int(hdr["nx"]), int(hdr["ny"])], "filings": int(hdr["entries"]),
+                                     "looked_mean": float(looked.mean()), "looked_max": int(looked.max())})
+            # the stage's cost per step under either setter: whole runs of the same fleet on one stream, timed behind the first step, with
+            # the grid's setter and (up to 1024 edges) the all-edges one.  The two solve the same problems bit for bit, so the difference of
+            # their times is the difference of the two stages, nothing else.  The run without walls is there for scale only: it solves other
+            # problems (no wall circles).  A kernel's own time needs a trace (rocprofv3 --kernel-trace --stats).
+            import dataclasses
+
+            def ms_per_step(w):
+                rhs = [make_loop(rh.solver, ids, w) for rh, ids in zip(loops, parts)]
+                for rh in rhs:
+                    rh.step()
+                    rh.read()
+                t = time.perf_counter()
+                for k in range(1, args.steps):
+                    for rh in rhs:
+                        rh.step()
+                for rh in rhs:
+                    rh.read()
+                t = time.perf_counter() - t
+                for rh in rhs:
+                    rh.close()
+                return 1e3 * t / max(args.steps - 1, 1)
+            if not args.retire:
+                stage = {"ms_per_step_without_walls": ms_per_step(None), "ms_per_step_grid": ms_per_step(walls)}
+                if len(walls.edges) <= 1024:
+                    stage["ms_per_step_all_edges"] = ms_per_step(dataclasses.replace(walls, cell=None))
+                    stage["all_edges_minus_grid_ms_per_step"] = stage["ms_per_step_all_edges"] - stage["ms_per_step_grid"]
+                quality["walls"]["stage"] = stage
     if args.crowd:
         seen = np.concatenate([rh.crowd_seen() for rh in loops])          # the last step's
         quality["crowd"] = {"obstacles": args.crowd, "slots": args.crowd_slots, "range_m": args.crowd_range,
