@@ -25,6 +25,7 @@
 #include "nmpc_solve_hyb.h"
 #include "nmpc_solve_hyb2.h"
 #include "nmpc_rng.h"
+#include "nmpc_geom.h"
 #include "nmpc_loop.h"
 #include "nmpc_plan.h"
 #include "nmpc_order.h"

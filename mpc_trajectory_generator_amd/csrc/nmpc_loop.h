@@ -13,7 +13,8 @@
 //
 // Arithmetic: index selections (window arg-min, vertex window, braking-table filter) use the same
 // unfused IEEE operations as the host mirror (`trajectory.VectorizedRecedingHorizon`), so they are
-// bit-identical to it; sin / cos are the kernels' own sincos_cw (the mirror takes it as a hook).
+// bit-identical to it; sin / cos are the kernels' own sincos_cw (the mirror takes it as a hook).  What several kernels must compute
+// operation for operation is one function: the geometry that the host shares in nmpc_geom.h (included before this file), the rest here.
 //
 // Retirement (nmpc_loop_set_retire; the rule is DESIGN.md section 5.9): a robot whose terminal test holds after an advance leaves the
 // loop for good, as the reference's `while not terminal` ends.  The kernels of a step then run over the list of the robots still
@@ -130,6 +131,80 @@ __device__ __forceinline__ void wave_argmin3(double &d, int &r, int &j)
         const int oj = __shfl_xor(j, off);
         if (od < d || (od == d && (orow < r || (orow == r && oj < j)))) { d = od; r = orow; j = oj; }
     }
+}
+
+// minimum / maximum over the wave, result in every lane (the order of the reduction does not show)
+template <class T>
+__device__ __forceinline__ T wave_min(T v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const T o = __shfl_xor(v, off);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+template <class T>
+__device__ __forceinline__ T wave_max(T v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const T o = __shfl_xor(v, off);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// What the one-wave-per-robot kernels stage in `own` (LDS), barrier included.
+// Robot b's N predicted positions, own[2 k] = x, own[2 k + 1] = y of stage k; each(x, y) sees every position its lane loads.
+template <class Each>
+__device__ __forceinline__ void stage_pred(double *own, const double *pred, int b, int N, Each each)
+{
+    for (int k = threadIdx.x; k < N; k += 64) {
+        const double x = pred[((size_t)b * N + k) * 3], y = pred[((size_t)b * N + k) * 3 + 1];
+        own[2 * k] = x;
+        own[2 * k + 1] = y;
+        each(x, y);
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ void stage_pred(double *own, const double *pred, int b, int N)
+{
+    stage_pred(own, pred, b, N, [](double, double) {});
+}
+
+// the first C components of robot b's trajectory rows row0 .. row0 + n - 1, own[C i + c] = component c of row row0 + i
+template <int C>
+__device__ __forceinline__ void stage_rows(double *own, const LoopView &L, int b, int row0, int n)
+{
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const double *row = L.row(row0 + i, b);
+#pragma unroll
+        for (int c = 0; c < C; ++c) own[C * i + c] = row[c];
+    }
+    __syncthreads();
+}
+
+// One Euler step of the unicycle under the control (v, w) (mpc_generator.py:225-235): the advance's, the predictions' and the plant's.
+__device__ __forceinline__ void unicycle_step(double &x, double &y, double &th, double v, double w, double ts)
+{
+    double sn, cs;
+    sincos_cw(th, sn, cs);
+    x = x + ts * (v * cs);
+    y = y + ts * (v * sn);
+    th = th + ts * w;
+}
+
+// the level of the ellipse q = (x, y, rx, ry, theta) at the position (x, y): the cost's (a/rx)^2 + (c/ry)^2, below 1 inside
+__device__ __forceinline__ double ellipse_level(double x, double y, const double *q)
+{
+    const double dx = x - q[0], dy = y - q[1];
+    double sn, cs;
+    sincos_cw(q[4], sn, cs);
+    const double al = dx * cs + dy * sn, ac = dx * sn - dy * cs;
+    return (al * al) / (q[2] * q[2]) + (ac * ac) / (q[3] * q[3]);
 }
 
 // times = numpy.linspace(t0, t0 + H * ts, H)[i]   (visibility.py:204)
@@ -301,6 +376,28 @@ __global__ __launch_bounds__(64) void nmpc_loop_assemble_kernel(LoopView L, Loop
     }
 }
 
+// the terminal test (path_generator.py:397): within GOAL_POS_TOL of the goal on both axes, the last commanded speed below GOAL_VEL_TOL
+constexpr double GOAL_POS_TOL = 0.05, GOAL_VEL_TOL = 0.005;
+
+// the pose after a control into the robot's trajectory row r, if the loop keeps a trajectory
+__device__ __forceinline__ void drive_row(const LoopView &L, int r, int b, double x, double y, double th)
+{
+    if (L.traj) {
+        double *row = L.row(r, b);
+        row[0] = x; row[1] = y; row[2] = th;
+    }
+}
+
+// the end of a drive over the controls u: the true pose into `state`, the last COMMANDED control into last_u, the terminal test on both
+__device__ __forceinline__ void drive_end(const LoopView &L, const AssembleArgs &g, int b, const double *u, double x, double y, double th)
+{
+    L.state[3 * b] = x; L.state[3 * b + 1] = y; L.state[3 * b + 2] = th;
+    const double lv = u[2 * (L.s - 1)], lw = u[2 * (L.s - 1) + 1];
+    L.last_u[2 * b] = lv; L.last_u[2 * b + 1] = lw;
+    const double *end = g.routes[L.route_of[b]].end;
+    L.done[b] = (fabs(x - end[0]) <= GOAL_POS_TOL && fabs(y - end[1]) <= GOAL_POS_TOL && fabs(lv) < GOAL_VEL_TOL) ? 1 : 0;
+}
+
 // one thread per robot: Euler advance over the steps taken (mpc_generator.py:225-235), terminal test (:397)
 __global__ void nmpc_loop_advance_kernel(LoopView L, LoopStep stp, AssembleArgs g)
 {
@@ -310,22 +407,10 @@ __global__ void nmpc_loop_advance_kernel(LoopView L, LoopStep stp, AssembleArgs 
     const double *u = L.U + (size_t)b * L.n_u;
     double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
     for (int i = 0; i < L.s; ++i) {
-        const double v = u[2 * i], w = u[2 * i + 1];
-        double sn, cs;
-        sincos_cw(th, sn, cs);
-        x = x + L.ts * (v * cs);
-        y = y + L.ts * (v * sn);
-        th = th + L.ts * w;
-        if (L.traj) {
-            double *row = L.row(stp.traj_row + i, b);
-            row[0] = x; row[1] = y; row[2] = th;
-        }
+        unicycle_step(x, y, th, u[2 * i], u[2 * i + 1], L.ts);
+        drive_row(L, stp.traj_row + i, b, x, y, th);
     }
-    L.state[3 * b] = x; L.state[3 * b + 1] = y; L.state[3 * b + 2] = th;
-    const double lv = u[2 * (L.s - 1)], lw = u[2 * (L.s - 1) + 1];
-    L.last_u[2 * b] = lv; L.last_u[2 * b + 1] = lw;
-    const double *end = g.routes[L.route_of[b]].end;
-    L.done[b] = (fabs(x - end[0]) <= 0.05 && fabs(y - end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
+    drive_end(L, g, b, u, x, y, th);
 }
 
 // ---- peers: the robots of a group see each other (nmpc_loop_set_peers; the rule is DESIGN.md section 5.9) ----
@@ -345,7 +430,7 @@ struct PeerArgs {
     GroupLists grp;
 };
 
-// one thread per robot: pred[b][k] = the pose after k + 1 Euler steps (the expression of nmpc_loop_advance_kernel) under the
+// one thread per robot: pred[b][k] = the pose after k + 1 Euler steps (unicycle_step, as nmpc_loop_advance_kernel takes them) under the
 // previous plan shifted by the s controls already applied, its last control held beyond the plan's end
 // (a retired robot's row is not computed here: nmpc_loop_compact_kernel parked it)
 __global__ void nmpc_loop_predict_kernel(LoopView L, LoopStep stp, double *pred)
@@ -358,12 +443,7 @@ __global__ void nmpc_loop_predict_kernel(LoopView L, LoopStep stp, double *pred)
     double x = L.state[3 * b], y = L.state[3 * b + 1], th = L.state[3 * b + 2];
     for (int k = 0; k < L.N; ++k) {
         const int c = L.s + k < L.N ? L.s + k : L.N - 1;
-        const double v = u[2 * c], w = u[2 * c + 1];
-        double sn, cs;
-        sincos_cw(th, sn, cs);
-        x = x + L.ts * (v * cs);
-        y = y + L.ts * (v * sn);
-        th = th + L.ts * w;
+        unicycle_step(x, y, th, u[2 * c], u[2 * c + 1], L.ts);
         out[3 * k] = x; out[3 * k + 1] = y; out[3 * k + 2] = th;
     }
 }
@@ -382,6 +462,13 @@ __device__ __forceinline__ double peer_closeness(const double *own, const double
         if (d < D) D = d;
     }
     return D;
+}
+
+// the list without a candidate
+__device__ __forceinline__ void peer_none(double (&bd)[NDYN_MAX], int (&bj)[NDYN_MAX])
+{
+#pragma unroll
+    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
 }
 
 // candidate (cd, cj) into the lane's sorted list
@@ -445,15 +532,10 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_kernel(LoopView L, PeerArg
     // the group's member range: the same for the whole wave
     const int g = a.grp.group_of[b];
     const int lo = a.grp.goff[g], hi = a.grp.goff[g + 1];
-    for (int k = lane; k < N; k += 64) {
-        own[2 * k] = a.pred[((size_t)b * N + k) * 3];
-        own[2 * k + 1] = a.pred[((size_t)b * N + k) * 3 + 1];
-    }
-    __syncthreads();
+    stage_pred(own, a.pred, b, N);
     double bd[NDYN_MAX];
     int bj[NDYN_MAX];
-#pragma unroll
-    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
+    peer_none(bd, bj);
     for (int i = lo + lane; i < hi; i += 64) {
         const int j = a.grp.gmem[i];
         const double D = peer_closeness(own, a.pred + (size_t)j * N * 3, N, 3);
@@ -478,23 +560,7 @@ struct PeerGridArgs {
     int *cell_mem;            // [B]
 };
 
-// the cell of coordinate v on an axis of n cells of edge h from o: monotone non-decreasing in v (every operation is; t is a NaN
-// only with h = inf, where every v answers 0)
-__device__ __forceinline__ int peer_cellof(double v, double o, double h, int n)
-{
-    const double t = (v - o) / h;
-    if (!(t > 0.0)) return 0;
-    if (t >= (double)n) return n - 1;
-    return (int)t;
-}
-
-// an axis of the grid: cells of edge `cell` over the extent ex >= 0 of the lower corners, or CAP cells of edge ex / CAP
-__device__ __forceinline__ void peer_grid_axis(double ex, double cell, int &n, double &h)
-{
-    const double q = ex / cell;
-    if (q < (double)PEER_GRID_CAP) { n = (int)q + 1; h = cell; }
-    else { n = PEER_GRID_CAP; h = ex / (double)PEER_GRID_CAP; }
-}
+// (the cell of a coordinate and the rule for an axis, over the extent of the lower corners: cellof and grid_axis of nmpc_geom.h)
 
 // a box's extent rounded up: never below the real hi - lo
 __device__ __forceinline__ double peer_extent_up(double hi, double lo)
@@ -511,13 +577,7 @@ __global__ void nmpc_loop_peer_box_kernel(LoopView L, PeerArgs a, PeerGridArgs g
     const double *p = a.pred + (size_t)b * L.N * 3;
     const double inf = __builtin_inf();
     double lx = inf, ly = inf, hx = -inf, hy = -inf;
-    for (int k = 0; k < L.N; ++k) {
-        const double x = p[3 * k], y = p[3 * k + 1];
-        if (fabs(x) < inf && fabs(y) < inf) {      // a stage with a NaN or an infinity is in nobody's D
-            lx = x < lx ? x : lx; ly = y < ly ? y : ly;
-            hx = x > hx ? x : hx; hy = y > hy ? y : hy;
-        }
-    }
+    for (int k = 0; k < L.N; ++k) box_fold(p[3 * k], p[3 * k + 1], lx, ly, hx, hy);
     double *out = g.box + 4 * (size_t)b;
     out[0] = lx; out[1] = ly; out[2] = hx; out[3] = hy;
 }
@@ -549,14 +609,9 @@ __global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(LoopView L, P
         }
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
+    for (int q = 0; q < 6; ++q) v[q] = q < 2 ? wave_min(v[q]) : wave_max(v[q]);
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            const double o = __shfl_xor(v[q], off);
-            v[q] = q < 2 ? (o < v[q] ? o : v[q]) : (o > v[q] ? o : v[q]);
-        }
-        nf += __shfl_xor(nf, off);
-    }
+    for (int off = 32; off >= 1; off >>= 1) nf += __shfl_xor(nf, off);
     if ((t & 63) == 0) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) red[t >> 6][q] = v[q];
@@ -579,8 +634,8 @@ __global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(LoopView L, P
     double hx = g.cell, hy = g.cell;
     if (nf == 0) { v[0] = 0.0; v[1] = 0.0; }
     else {
-        peer_grid_axis(v[2] - v[0], g.cell, nx, hx);
-        peer_grid_axis(v[3] - v[1], g.cell, ny, hy);
+        grid_axis(v[2] - v[0], g.cell, PEER_GRID_CAP, nx, hx);
+        grid_axis(v[3] - v[1], g.cell, PEER_GRID_CAP, ny, hy);
     }
     const int cells = nx * ny;
     if (t == 0) {
@@ -595,7 +650,7 @@ __global__ __launch_bounds__(1024) void nmpc_loop_peer_grid_kernel(LoopView L, P
         const double *bx = g.box + 4 * (size_t)b;
         int c = -1;
         if (bx[0] <= bx[2]) {
-            c = peer_cellof(bx[1], v[1], hy, ny) * nx + peer_cellof(bx[0], v[0], hx, nx);
+            c = cellof(bx[1], v[1], hy, ny) * nx + cellof(bx[0], v[0], hx, nx);
             atomicAdd(g.cell_off + c, 1);
         }
         g.cell_of[b] = c;
@@ -629,24 +684,19 @@ __global__ __launch_bounds__(64) void nmpc_loop_peers_grid_kernel(LoopView L, Pe
     __shared__ double own[2 * NMPC_MAX_HORIZON];
     const int b = L.robot(blockIdx.x), lane = threadIdx.x;
     const int N = L.N;
-    for (int k = lane; k < N; k += 64) {
-        own[2 * k] = a.pred[((size_t)b * N + k) * 3];
-        own[2 * k + 1] = a.pred[((size_t)b * N + k) * 3 + 1];
-    }
-    __syncthreads();
+    stage_pred(own, a.pred, b, N);
     double bd[NDYN_MAX];
     int bj[NDYN_MAX];
-#pragma unroll
-    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
+    peer_none(bd, bj);
     // the box, the grid and the window: the same for the whole wave
     const double *bx = g.box + 4 * (size_t)b;
     const nmpc_peer_grid *h = g.hdr;
     if (bx[0] <= bx[2]) {                               // an unfiled robot finds nobody
         const int nx = h->nx, ny = h->ny, grp = a.grp.group_of[b];
-        const int cx0 = peer_cellof((bx[0] - g.range) - h->W[0], h->origin[0], h->h[0], nx);
-        const int cy0 = peer_cellof((bx[1] - g.range) - h->W[1], h->origin[1], h->h[1], ny);
-        const int cx1 = peer_cellof(bx[2] + g.range, h->origin[0], h->h[0], nx);
-        const int cy1 = peer_cellof(bx[3] + g.range, h->origin[1], h->h[1], ny);
+        const int cx0 = cellof((bx[0] - g.range) - h->W[0], h->origin[0], h->h[0], nx);
+        const int cy0 = cellof((bx[1] - g.range) - h->W[1], h->origin[1], h->h[1], ny);
+        const int cx1 = cellof(bx[2] + g.range, h->origin[0], h->h[0], nx);
+        const int cy1 = cellof(bx[3] + g.range, h->origin[1], h->h[1], ny);
         for (int row = cy0; row <= cy1; ++row) {
             const int i0 = g.cell_off[row * nx + cx0], i1 = g.cell_off[row * nx + cx1 + 1];
             for (int i = i0 + lane; i < i1; i += 64) {
@@ -697,15 +747,10 @@ __global__ __launch_bounds__(64) void nmpc_loop_crowd_kernel(LoopView L, LoopSte
     const int b = L.robot(blockIdx.x), lane = threadIdx.x;
     const int N = L.N, per = 5 * N;
     const double *tab = c.tab[stp.cur ^ 1];
-    for (int k = lane; k < N; k += 64) {
-        own[2 * k] = c.pred[((size_t)b * N + k) * 3];
-        own[2 * k + 1] = c.pred[((size_t)b * N + k) * 3 + 1];
-    }
-    __syncthreads();
+    stage_pred(own, c.pred, b, N);
     double bd[NDYN_MAX];
     int bj[NDYN_MAX];
-#pragma unroll
-    for (int q = 0; q < NDYN_MAX; ++q) { bd[q] = __builtin_inf(); bj[q] = LOOP_NONE; }
+    peer_none(bd, bj);
     for (int d = lane; d < c.D; d += 64) {
         const double C = peer_closeness(own, tab + (size_t)d * per, N, 5);
         if (C < c.range2) peer_keep(bd, bj, C, d);
@@ -723,23 +768,13 @@ __global__ __launch_bounds__(64) void nmpc_loop_crowd_monitor_kernel(LoopView L,
     const int b = L.robot(blockIdx.x), lane = threadIdx.x;
     const int s = L.s, N = L.N, row0 = stp.traj_row;
     const double *tab = c.tab[stp.cur ^ 1];
-    for (int i = lane; i < s; i += 64) {
-        const double *row = L.row(row0 + i, b);
-        own[2 * i] = row[0];
-        own[2 * i + 1] = row[1];
-    }
-    __syncthreads();
+    stage_rows<2>(own, L, b, row0, s);
     double bv = __builtin_inf();
     int br = LOOP_NONE, bo = LOOP_NONE;
     for (int i = 0; i < s; ++i) {
         const double x = own[2 * i], y = own[2 * i + 1];
         for (int d = lane; d < c.D; d += 64) {
-            const double *q = tab + ((size_t)d * N + i) * 5;
-            const double dx = x - q[0], dy = y - q[1];
-            double sn, cs;
-            sincos_cw(q[4], sn, cs);
-            const double al = dx * cs + dy * sn, ac = dx * sn - dy * cs;
-            const double v = (al * al) / (q[2] * q[2]) + (ac * ac) / (q[3] * q[3]);
+            const double v = ellipse_level(x, y, tab + ((size_t)d * N + i) * 5);
             if (v < bv) { bv = v; br = row0 + i; bo = d; }
         }
     }
@@ -766,88 +801,100 @@ struct WallArgs {
     int *wall_edge;           // [B][M]: the edge in circle slot nobs - M + m of p[b], -1 = none
     int *wall_stage;          // [B][M]: the stage at which it came closest
 
-    static size_t lds_bytes(int E) { return (size_t)E * (3 * sizeof(double) + sizeof(int)) + WALLS_MAX_SLOTS * sizeof(int); }
+    static size_t lds_bytes(int E) { return (size_t)E * (3 * sizeof(double) + sizeof(int)); }
 };
 
-// One wave per active robot, WallArgs::lds_bytes(E) of dynamic LDS: D | cx | cy [E] doubles, k* [E] and the taken edges [64] ints.  The
-// predicted positions go to LDS; lanes stride over the edges, each against all N stages in ascending order (a strict <: the first of equal
-// stages stays, a NaN lowers nothing), and park (D, cx, cy, k*) in LDS.  Then the walk: every round each lane offers the smallest (D, e) of
-// its candidates that lies behind the last one considered, wave_argmin names the next of the wave, and lanes 0 .. m - 1 test its centre
-// against the m taken before.  A round considers one candidate, so the walk ends after E rounds at the most, with M taken or with no
-// candidate left, whichever comes first: no loop's bounds depend on a pose.
-__global__ __launch_bounds__(64) void nmpc_loop_walls_kernel(LoopView L, WallArgs w)
+// D(e) of the edge ed = (x1, y1, x2, y2) against the N positions in `own` (LDS): the smallest wall distance (segment_closest, that of
+// nmpc_loop_map_kernel) over the stages in ascending order, with its closest point and stage k*.  A strict <: the first of equal
+// stages stays, a NaN lowers nothing (D = inf, k* = -1 if every stage is one).
+__device__ __forceinline__ void wall_closest(const double *own, int N, const double *ed, double &D, double &bx, double &by, int &bk)
 {
-    __shared__ double own[2 * NMPC_MAX_HORIZON];
-    extern __shared__ double wall_lds[];
-    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
-    const int N = L.N, E = w.E, M = w.M;
-    double *sD = wall_lds, *sx = sD + E, *sy = sx + E;
-    int *sk = (int *)(sy + E), *taken = sk + E;
-    for (int k = lane; k < N; k += 64) {
-        own[2 * k] = w.pred[((size_t)b * N + k) * 3];
-        own[2 * k + 1] = w.pred[((size_t)b * N + k) * 3 + 1];
+    const double x1 = ed[0], y1 = ed[1], x2 = ed[2], y2 = ed[3];
+    D = __builtin_inf(); bx = 0.0; by = 0.0; bk = -1;
+    for (int k = 0; k < N; ++k) {
+        double cx, cy;
+        const double v = segment_closest(own[2 * k], own[2 * k + 1], x1, y1, x2, y2, true, cx, cy);
+        if (v < D) { D = v; bx = cx; by = cy; bk = k; }
     }
-    __syncthreads();
-    for (int e = lane; e < E; e += 64) {
-        const double x1 = w.edge[4 * e], y1 = w.edge[4 * e + 1], x2 = w.edge[4 * e + 2], y2 = w.edge[4 * e + 3];
-        const double ex = x2 - x1, ey = y2 - y1;
-        const double L2 = ex * ex + ey * ey;
-        double D = __builtin_inf(), bx = 0.0, by = 0.0;
-        int bk = -1;
-        for (int k = 0; k < N; ++k) {
-            const double x = own[2 * k], y = own[2 * k + 1];
-            double t = 0.0;
-            if (L2 > 0.0) {
-                t = ((x - x1) * ex + (y - y1) * ey) / L2;
-                if (t < 0.0) t = 0.0;
-                if (t > 1.0) t = 1.0;
-            }
-            const double cx = x1 + t * ex, cy = y1 + t * ey;
-            const double dx = x - cx, dy = y - cy;
-            const double v = dx * dx + dy * dy;
-            if (v < D) { D = v; bx = cx; by = cy; bk = k; }
-        }
-        sD[e] = D; sx[e] = bx; sy[e] = by; sk[e] = bk;
-    }
-    __syncthreads();
+}
+
+// The walk of the walls rule, for both walls kernels.  Every round each lane offers the smallest (D, e) of its candidates that lies
+// behind the last one considered, (ld, le), with its centre and stage: offer(ld, le, d, j, ox, oy, ok), which leaves (inf, LOOP_NONE)
+// where the lane has none.  wave_argmin names the wave's, the one lane that offered it hands over its centre and stage, and lanes
+// 0 .. m - 1 test the centre against the m taken before; a centre that keeps `spacing` from all of them takes circle slot nobs - M + m
+// of p[b].  A round considers one candidate, so the walk ends after `rounds` rounds at the most (the caller's count of the edges it
+// measured), with M taken or with no candidate left, whichever comes first: no loop's bounds depend on a pose.
+template <class Offer>
+__device__ __forceinline__ void walls_walk(const LoopView &L, const WallArgs &w, int b, int rounds, Offer offer)
+{
+    __shared__ double tx[WALLS_MAX_SLOTS], ty[WALLS_MAX_SLOTS];      // the centres taken
+    const int lane = threadIdx.x, M = w.M;
     double *pc = L.P + (size_t)b * L.n_p + L.p_circ() + 3 * (size_t)(L.nobs - M);
     int *we = w.wall_edge + (size_t)b * M, *ws = w.wall_stage + (size_t)b * M;
     double ld = -1.0;         // the last candidate considered: behind it comes every real one (D >= 0)
     int le = -1;
     int m = 0;
-    for (int round = 0; round < E && m < M; ++round) {
-        double d = __builtin_inf();
-        int j = LOOP_NONE;
-        for (int e = lane; e < E; e += 64) {
-            const double c = sD[e];
-            if (c < w.range2 && (c > ld || (c == ld && e > le)) && c < d) { d = c; j = e; }      // (a lane's edges ascend: of equal D the first stays)
-        }
-        wave_argmin(d, j);
-        if (j == LOOP_NONE) break;            // (wave-uniform) no candidate left: the remaining slots keep the assembly's zeros
-        ld = d; le = j;
-        const double cx = sx[j], cy = sy[j];
+    for (int round = 0; round < rounds && m < M; ++round) {
+        double d = __builtin_inf(), ox = 0.0, oy = 0.0;
+        int j = LOOP_NONE, ok = -1;
+        offer(ld, le, d, j, ox, oy, ok);
+        double dd = d;
+        int jj = j;
+        wave_argmin(dd, jj);
+        if (jj == LOOP_NONE) break;           // (wave-uniform) no candidate left: the remaining slots keep the assembly's zeros
+        ld = dd; le = jj;
+        const int src = __ffsll((long long)__ballot(j == jj)) - 1;      // the one lane that measured edge jj
+        const double cx = __shfl(ox, src), cy = __shfl(oy, src);
+        const int ck = __shfl(ok, src);
         bool close = false;
         if (lane < m) {
-            const int q = taken[lane];
-            const double ddx = cx - sx[q], ddy = cy - sy[q];
+            const double ddx = cx - tx[lane], ddy = cy - ty[lane];
             close = ddx * ddx + ddy * ddy < w.spacing2;
         }
         if (__any(close)) continue;           // (wave-uniform)
         if (lane == 0) {
-            taken[m] = j;
+            tx[m] = cx; ty[m] = cy;
             pc[3 * m] = cx; pc[3 * m + 1] = cy; pc[3 * m + 2] = w.radius;
-            we[m] = j; ws[m] = sk[j];
+            we[m] = jj; ws[m] = ck;
         }
         ++m;
-        __syncthreads();                      // lane 0's store of taken[] before the next round's loads
+        __syncthreads();                      // lane 0's stores of tx, ty before the next round's loads
     }
     for (int q = m + lane; q < M; q += 64) { we[q] = -1; ws[q] = -1; }
+}
+
+// One wave per active robot, WallArgs::lds_bytes(E) of dynamic LDS: D | cx | cy [E] doubles and k* [E] ints.  The predicted positions
+// go to LDS; lanes stride over the edges (wall_closest) and park (D, cx, cy, k*) in LDS.  Then the walk, a lane's candidates being its
+// edges of the table with D < range2: E rounds at the most.
+__global__ __launch_bounds__(64) void nmpc_loop_walls_kernel(LoopView L, WallArgs w)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    extern __shared__ double wall_lds[];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int N = L.N, E = w.E;
+    double *sD = wall_lds, *sx = sD + E, *sy = sx + E;
+    int *sk = (int *)(sy + E);
+    stage_pred(own, w.pred, b, N);
+    for (int e = lane; e < E; e += 64) {
+        double D, bx, by;
+        int bk;
+        wall_closest(own, N, w.edge + 4 * (size_t)e, D, bx, by, bk);
+        sD[e] = D; sx[e] = bx; sy[e] = by; sk[e] = bk;
+    }
+    __syncthreads();
+    walls_walk(L, w, b, E, [&](double ld, int le, double &d, int &j, double &ox, double &oy, int &ok) {
+        for (int e = lane; e < E; e += 64) {
+            const double c = sD[e];
+            if (c < w.range2 && (c > ld || (c == ld && e > le)) && c < d) { d = c; j = e; }      // (a lane's edges ascend: of equal D the first stays)
+        }
+        if (j != LOOP_NONE) { ox = sx[j]; oy = sy[j]; ok = sk[j]; }
+    });
 }
 
 // ---- walls through a grid (nmpc_loop_set_walls_grid; the rule, and why it hides no edge: DESIGN.md section 5.9) ----
 // The same rule over fewer edges.  The edges never move, so the setter builds the grid once, on the host: every edge is filed in every
 // cell of the rectangle of cells its box covers (CSR: cell_off, cell_edge, the edges ascending inside a cell), and a robot measures the
-// edges filed in the cells its predicted positions can reach.  Every D is formed by the expression of nmpc_loop_walls_kernel and tested
+// edges filed in the cells its predicted positions can reach.  Every D is formed by wall_closest, as in nmpc_loop_walls_kernel, and tested
 // against the same range2, so a window wider than needed changes no result.
 constexpr int WALL_GRID_CAP = 512;                  // cells per axis at the most
 constexpr int WALL_GRID_MAX_EDGES = 1 << 20;
@@ -864,86 +911,37 @@ struct WallGridArgs {
     int *looked;              // [B]: the distinct edges the last step measured
 };
 
-// the cell of coordinate v on an axis of n cells of edge h from o: monotone non-decreasing in v (every operation is; t is a NaN only
-// with h = inf, where every v answers 0), clamped in double before the conversion.  The setter's filing uses the same function.
-__host__ __device__ __forceinline__ int wall_cellof(double v, double o, double h, int n)
-{
-    const double t = (v - o) / h;
-    if (!(t > 0.0)) return 0;
-    if (t >= (double)n) return n - 1;
-    return (int)t;
-}
-
-// D(e), its centre and k* against the positions in LDS: the expression of nmpc_loop_walls_kernel, operation for operation
-__device__ __forceinline__ void wall_closest(const double *own, int N, const double *ed, double &D, double &bx, double &by, int &bk)
-{
-    const double x1 = ed[0], y1 = ed[1], x2 = ed[2], y2 = ed[3];
-    const double ex = x2 - x1, ey = y2 - y1;
-    const double L2 = ex * ex + ey * ey;
-    D = __builtin_inf(); bx = 0.0; by = 0.0; bk = -1;
-    for (int k = 0; k < N; ++k) {
-        const double x = own[2 * k], y = own[2 * k + 1];
-        double t = 0.0;
-        if (L2 > 0.0) {
-            t = ((x - x1) * ex + (y - y1) * ey) / L2;
-            if (t < 0.0) t = 0.0;
-            if (t > 1.0) t = 1.0;
-        }
-        const double cx = x1 + t * ex, cy = y1 + t * ey;
-        const double dx = x - cx, dy = y - cy;
-        const double v = dx * dx + dy * dy;
-        if (v < D) { D = v; bx = cx; by = cy; bk = k; }
-    }
-}
-
 // One wave per active robot.  The predicted positions go to LDS and their box over the finite stages (a wave reduction of minima and
-// maxima) gives the window cx0 .. cx1 x cy0 .. cy1; a robot without a finite stage looks at nothing.  A row of the window is one run of
-// cell_edge; the rows' runs are laid end to end and the lanes stride over them in steps of 64, all lanes together.  An edge filed in
+// maxima) gives the window cx0 .. cx1 x cy0 .. cy1 (cellof of nmpc_geom.h, the function of the setter's filing); a robot without a
+// finite stage looks at nothing.  A row of the window is one run of cell_edge; the rows' runs are laid end to end and the lanes
+// stride over them in steps of 64, all lanes together.  An edge filed in
 // several cells of the window is measured in one of them only, the first of its rectangle that lies in the window (di == max(0, cx0 -
-// col0), the same in j), so `looked` counts distinct edges.  A candidate (D < range2) is appended to an LDS list at the place a ballot gives it.  The walk is that of
-// nmpc_loop_walls_kernel: every round each lane offers the smallest (D, e) of its candidates that lies behind the last one considered,
-// wave_argmin names the wave's, the lane that offered it hands over its centre and stage, and lanes 0 .. m - 1 test the centre against the
-// m taken before.  With WALL_GRID_LIST candidates or fewer a lane's candidates are its entries of the list; with more the list is
-// dropped and every round measures the window again, which needs no memory and gives the same (D, e) sequence.  A round considers one
-// candidate: the walk ends after `seen` rounds at the most, seen <= E the window's distinct edges.  No loop's bounds depend on a pose
-// other than through the window, which is clamped to the grid.
+// col0), the same in j), so `looked` counts distinct edges.  A candidate (D < range2) is appended to an LDS list at the place a ballot
+// gives it.  Then the walk (walls_walk).  With WALL_GRID_LIST candidates or fewer a lane's candidates are its entries of the list; with
+// more the list is dropped and every round measures the window again, which needs no memory and gives the same (D, e) sequence.  The
+// walk ends after `seen` rounds at the most, seen <= E the window's distinct edges.  No loop's bounds depend on a pose other than
+// through the window, which is clamped to the grid.
 __global__ __launch_bounds__(64) void nmpc_loop_walls_grid_kernel(LoopView L, WallArgs w, WallGridArgs g)
 {
     __shared__ double own[2 * NMPC_MAX_HORIZON];
     __shared__ double lD[WALL_GRID_LIST], lx[WALL_GRID_LIST], ly[WALL_GRID_LIST];
     __shared__ int lE[WALL_GRID_LIST], lk[WALL_GRID_LIST];
-    __shared__ double tx[WALLS_MAX_SLOTS], ty[WALLS_MAX_SLOTS];
     __shared__ int rbeg[WALL_GRID_CAP], rpre[WALL_GRID_CAP + 1];
     const int b = L.robot(blockIdx.x), lane = threadIdx.x;
-    const int N = L.N, M = w.M;
+    const int N = L.N;
     const double inf = __builtin_inf();
     double lox = inf, loy = inf, hix = -inf, hiy = -inf;
-    for (int k = lane; k < N; k += 64) {
-        const double x = w.pred[((size_t)b * N + k) * 3], y = w.pred[((size_t)b * N + k) * 3 + 1];
-        own[2 * k] = x;
-        own[2 * k + 1] = y;
-        if (fabs(x) < inf && fabs(y) < inf) {          // a stage with a NaN or an infinity lowers nobody's D
-            lox = x < lox ? x : lox; loy = y < loy ? y : loy;
-            hix = x > hix ? x : hix; hiy = y > hiy ? y : hiy;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        double o = __shfl_xor(lox, off); lox = o < lox ? o : lox;
-        o = __shfl_xor(loy, off); loy = o < loy ? o : loy;
-        o = __shfl_xor(hix, off); hix = o > hix ? o : hix;
-        o = __shfl_xor(hiy, off); hiy = o > hiy ? o : hiy;
-    }
-    __syncthreads();
+    stage_pred(own, w.pred, b, N, [&](double x, double y) { box_fold(x, y, lox, loy, hix, hiy); });
+    lox = wave_min(lox); loy = wave_min(loy); hix = wave_max(hix); hiy = wave_max(hiy);
     // the window: the same in every lane; cy1 < cy0 for a robot that looks at nothing
     const int nx = g.nx;
     int cx0 = 0, cx1 = 0, cy0 = 0, cy1 = -1;
     if (lox <= hix) {
         const double tm = 0x1p-40;
-        cx0 = wall_cellof((lox - g.range) - (g.slack + tm * fabs(lox)), g.origin[0], g.h[0], nx);
-        cx1 = wall_cellof((hix + g.range) + (g.slack + tm * fabs(hix)), g.origin[0], g.h[0], nx);
-        cy0 = wall_cellof((loy - g.range) - (g.slack + tm * fabs(loy)), g.origin[1], g.h[1], g.ny);
-        cy1 = wall_cellof((hiy + g.range) + (g.slack + tm * fabs(hiy)), g.origin[1], g.h[1], g.ny);
+        cx0 = cellof((lox - g.range) - (g.slack + tm * fabs(lox)), g.origin[0], g.h[0], nx);
+        cx1 = cellof((hix + g.range) + (g.slack + tm * fabs(hix)), g.origin[0], g.h[0], nx);
+        cy0 = cellof((loy - g.range) - (g.slack + tm * fabs(loy)), g.origin[1], g.h[1], g.ny);
+        cy1 = cellof((hiy + g.range) + (g.slack + tm * fabs(hiy)), g.origin[1], g.h[1], g.ny);
     }
     // the window's rows: row r is the run cell_edge[rbeg[r] .. ) of rpre[r + 1] - rpre[r] filings, rpre the exclusive prefix sums (a wave scan
     // per 64 rows).  The filings of all rows then count as ONE list of `total`, over which the lanes stride: a window of several short rows
@@ -1002,15 +1000,8 @@ __global__ __launch_bounds__(64) void nmpc_loop_walls_grid_kernel(LoopView L, Wa
     }
     __syncthreads();
     const bool listed = cnt <= WALL_GRID_LIST;        // (wave-uniform)
-    double *pc = L.P + (size_t)b * L.n_p + L.p_circ() + 3 * (size_t)(L.nobs - M);
-    int *we = w.wall_edge + (size_t)b * M, *ws = w.wall_stage + (size_t)b * M;
-    double ld = -1.0;         // the last candidate considered: behind it comes every real one (D >= 0)
-    int le = -1;
-    int m = 0;
-    for (int round = 0; round < seen && m < M; ++round) {
-        // this lane's offer: (d, j) with its centre and stage.  Among equal D the smaller edge index is kept.
-        double d = inf, ox = 0.0, oy = 0.0;
-        int j = LOOP_NONE, ok = -1;
+    // a lane's offer: among equal D the smaller edge index is kept
+    walls_walk(L, w, b, seen, [&](double ld, int le, double &d, int &j, double &ox, double &oy, int &ok) {
         if (listed) {
             for (int q = lane; q < cnt; q += 64) {
                 const double c = lD[q];
@@ -1028,29 +1019,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_walls_grid_kernel(LoopView L, Wa
                 if (c < w.range2 && (c > ld || (c == ld && e > le)) && (c < d || (c == d && e < j))) { d = c; j = e; ox = bx; oy = by; ok = bk; }
             }
         }
-        double dd = d;
-        int jj = j;
-        wave_argmin(dd, jj);
-        if (jj == LOOP_NONE) break;           // (wave-uniform) no candidate left: the remaining slots keep the assembly's zeros
-        ld = dd; le = jj;
-        const int src = __ffsll((long long)__ballot(j == jj)) - 1;      // the one lane that measured edge jj
-        const double cx = __shfl(ox, src), cy = __shfl(oy, src);
-        const int ck = __shfl(ok, src);
-        bool close = false;
-        if (lane < m) {
-            const double ddx = cx - tx[lane], ddy = cy - ty[lane];
-            close = ddx * ddx + ddy * ddy < w.spacing2;
-        }
-        if (__any(close)) continue;           // (wave-uniform)
-        if (lane == 0) {
-            tx[m] = cx; ty[m] = cy;
-            pc[3 * m] = cx; pc[3 * m + 1] = cy; pc[3 * m + 2] = w.radius;
-            we[m] = jj; ws[m] = ck;
-        }
-        ++m;
-        __syncthreads();                      // lane 0's stores of tx, ty before the next round's loads
-    }
-    for (int q = m + lane; q < M; q += 64) { we[q] = -1; ws[q] = -1; }
+    });
     if (lane == 0) g.looked[b] = seen;
 }
 
@@ -1142,12 +1111,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(LoopView L, LoopS
     const int s = L.s, N = L.N, nobs = L.nobs, K = L.K, row0 = stp.traj_row;
     const int g = m.grp.group_of[b];
     const int lo = m.grp.goff[g], hi = m.grp.goff[g + 1];
-    for (int i = lane; i < s; i += 64) {
-        const double *row = L.row(row0 + i, b);
-        own[2 * i] = row[0];
-        own[2 * i + 1] = row[1];
-    }
-    __syncthreads();
+    stage_rows<2>(own, L, b, row0, s);
     const double *p = L.P + (size_t)b * L.n_p;
     // ---- static circles: sqrt(dx^2 + dy^2) - r over the slots with r > 0
     double cv = __builtin_inf();
@@ -1175,12 +1139,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_monitor_kernel(LoopView L, LoopS
         const int tot = s * K;
         for (int e = lane; e < tot; e += 64) {
             const int i = e / K, k = e - i * K;
-            const double *q = pd + ((size_t)k * N + i) * 5;
-            const double dx = own[2 * i] - q[0], dy = own[2 * i + 1] - q[1];
-            double sn, cs;
-            sincos_cw(q[4], sn, cs);
-            const double al = dx * cs + dy * sn, ac = dx * sn - dy * cs;
-            const double v = (al * al) / (q[2] * q[2]) + (ac * ac) / (q[3] * q[3]);
+            const double v = ellipse_level(own[2 * i], own[2 * i + 1], pd + ((size_t)k * N + i) * 5);
             const int r = row0 + i;
             if (v < ev || (v == ev && r < er)) { ev = v; er = r; }
         }
@@ -1242,12 +1201,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(LoopView L, LoopStep 
     __shared__ double own[2 * (NMPC_MAX_HORIZON + 1)];
     const int b = L.robot(blockIdx.x), lane = threadIdx.x;
     const int s = L.s, E = m.E, n_poly = m.n_poly, row0 = stp.traj_row;      // (row0 >= 1: the row before it is there)
-    for (int i = lane; i <= s; i += 64) {
-        const double *row = L.row(row0 - 1 + i, b);
-        own[2 * i] = row[0];
-        own[2 * i + 1] = row[1];
-    }
-    __syncthreads();
+    stage_rows<2>(own, L, b, row0 - 1, s + 1);
     double wv = __builtin_inf();
     int wr = LOOP_NONE, we = LOOP_NONE;
     int hits = 0, hit_row = LOOP_NONE, hit_poly = LOOP_NONE;        // the same in every lane
@@ -1258,18 +1212,10 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(LoopView L, LoopStep 
         int fail = LOOP_NONE;
         for (int e = lane; e < E; e += 64) {
             const double x1 = m.edge[4 * e], y1 = m.edge[4 * e + 1], x2 = m.edge[4 * e + 2], y2 = m.edge[4 * e + 3];
-            const double ex = x2 - x1, ey = y2 - y1;
-            const double L2 = ex * ex + ey * ey;
-            double t = 0.0;
-            if (L2 > 0.0) {
-                t = ((x - x1) * ex + (y - y1) * ey) / L2;
-                if (t < 0.0) t = 0.0;
-                if (t > 1.0) t = 1.0;
-            }
-            const double cx = x1 + t * ex, cy = y1 + t * ey;
-            const double dx = x - cx, dy = y - cy;
-            const double v = dx * dx + dy * dy;
+            double cx, cy;
+            const double v = segment_closest(x, y, x1, y1, x2, y2, true, cx, cy);
             if (v < wv) { wv = v; wr = r; we = e; }       // (rows and a lane's edges ascend: among equal values the first stays)
+            const double ex = x2 - x1, ey = y2 - y1;
             const double o1 = ux * (y1 - ay) - uy * (x1 - ax);
             const double o2 = ux * (y2 - ay) - uy * (x2 - ax);
             const double o3 = ex * (ay - y1) - ey * (ax - x1);
@@ -1293,11 +1239,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(LoopView L, LoopStep 
             const bool bad = k == n_poly - 1 ? !odd : odd;
             if (bad && k < fail) fail = k;
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int o = __shfl_xor(fail, off);
-            if (o < fail) fail = o;
-        }
+        fail = wave_min(fail);
         if (fail != LOOP_NONE) {
             if (hits == 0) { hit_row = r; hit_poly = fail; }
             ++hits;
@@ -1347,13 +1289,7 @@ __global__ __launch_bounds__(64) void nmpc_loop_track_kernel(LoopView L, LoopSte
     const LoopRoute &rt = g.routes[L.route_of[b]];
     const double *xr = g.tab + rt.xr, *yr = g.tab + rt.yr, *thr = g.tab + rt.thr;
     const int n = rt.n_ref, n_seg = n > 1 ? n - 1 : 1, s = L.s, row0 = stp.traj_row;
-    for (int i = lane; i < s; i += 64) {
-        const double *row = L.row(row0 + i, b);
-        own[3 * i] = row[0];
-        own[3 * i + 1] = row[1];
-        own[3 * i + 2] = row[2];
-    }
-    __syncthreads();
+    stage_rows<3>(own, L, b, row0, s);
     nmpc_tracking c = k.rec[b];
     for (int i = 0; i < s; ++i) {
         const double x = own[3 * i], y = own[3 * i + 1], th = own[3 * i + 2];
@@ -1362,18 +1298,8 @@ __global__ __launch_bounds__(64) void nmpc_loop_track_kernel(LoopView L, LoopSte
         int bj = LOOP_NONE;
         for (int j = lane; j < n_seg; j += 64) {
             const int e = j + 1 < n ? j + 1 : n - 1;
-            const double x1 = xr[j], y1 = yr[j], x2 = xr[e], y2 = yr[e];
-            const double ex = x2 - x1, ey = y2 - y1;
-            const double L2 = ex * ex + ey * ey;
-            double t = 0.0;
-            if (L2 > 0.0) {
-                t = ((x - x1) * ex + (y - y1) * ey) / L2;
-                if (t < 0.0 && j > 0) t = 0.0;
-                if (t > 1.0) t = 1.0;
-            }
-            const double cx = x1 + t * ex, cy = y1 + t * ey;
-            const double dx = x - cx, dy = y - cy;
-            const double v = dx * dx + dy * dy;
+            double cx, cy;
+            const double v = segment_closest(x, y, xr[j], yr[j], xr[e], yr[e], j > 0, cx, cy);      // (segment 0 runs on backwards)
             if (v < bv) { bv = v; bj = j; }               // (a lane's segments ascend: among equal values the first stays)
         }
         wave_argmin(bv, bj);
@@ -1596,28 +1522,18 @@ __global__ __launch_bounds__(256) void nmpc_loop_plant_kernel(LoopView L, LoopSt
             t = t + p.act_add[1];
             wa = w + t * plant_xi(p.seed, id, r, 1u);
         }
-        double sn, cs;
-        sincos_cw(th, sn, cs);
-        x = x + L.ts * (va * cs);
+        // (a draw goes to its own coordinate only, and the step has read th already: after the three updates is between them)
+        unicycle_step(x, y, th, va, wa, L.ts);
         x = plant_add(x, p.proc[0], p, id, r, 2u);
-        y = y + L.ts * (va * sn);
         y = plant_add(y, p.proc[1], p, id, r, 3u);
-        th = th + L.ts * wa;
         th = plant_add(th, p.proc[2], p, id, r, 4u);
-        if (L.traj) {
-            double *row = L.row(stp.traj_row + i, b);
-            row[0] = x; row[1] = y; row[2] = th;
-        }
+        drive_row(L, stp.traj_row + i, b, x, y, th);
         if (p.applied) {
             double *out = p.applied + ((size_t)(stp.t + i) * L.B + b) * 2;
             out[0] = va; out[1] = wa;
         }
     }
-    L.state[3 * b] = x; L.state[3 * b + 1] = y; L.state[3 * b + 2] = th;
-    const double lv = u[2 * (L.s - 1)], lw = u[2 * (L.s - 1) + 1];
-    L.last_u[2 * b] = lv; L.last_u[2 * b + 1] = lw;
-    const double *end = g.routes[L.route_of[b]].end;
-    L.done[b] = (fabs(x - end[0]) <= 0.05 && fabs(y - end[1]) <= 0.05 && fabs(lv) < 0.005) ? 1 : 0;
+    drive_end(L, g, b, u, x, y, th);
 }
 
 // ---- missions: a robot at its goal takes up its next route (nmpc_loop_set_missions; the rule is DESIGN.md section 5.9) ----

@@ -615,10 +615,8 @@ struct WallGridHost {
         }
         int n[2];
         for (int ax = 0; ax < 2; ++ax) {
-            const double ext = hi[ax] - lo[ax], q = ext / cell;
             hdr.origin[ax] = lo[ax];
-            if (q < (double)nmpc::WALL_GRID_CAP) { n[ax] = (int)q + 1; hdr.h[ax] = cell; }
-            else { n[ax] = nmpc::WALL_GRID_CAP; hdr.h[ax] = ext / (double)nmpc::WALL_GRID_CAP; }
+            nmpc::grid_axis(hi[ax] - lo[ax], cell, nmpc::WALL_GRID_CAP, n[ax], hdr.h[ax]);
         }
         hdr.nx = n[0]; hdr.ny = n[1];
         // every edge's rectangle of cells: c0, c1, r0, r1
@@ -627,10 +625,10 @@ struct WallGridHost {
         for (int e = 0; e < E; ++e) {
             const double *d = edge + 4 * (size_t)e;
             int *r = rect.data() + 4 * (size_t)e;
-            r[0] = nmpc::wall_cellof(d[0] < d[2] ? d[0] : d[2], lo[0], hdr.h[0], n[0]);
-            r[1] = nmpc::wall_cellof(d[0] < d[2] ? d[2] : d[0], lo[0], hdr.h[0], n[0]);
-            r[2] = nmpc::wall_cellof(d[1] < d[3] ? d[1] : d[3], lo[1], hdr.h[1], n[1]);
-            r[3] = nmpc::wall_cellof(d[1] < d[3] ? d[3] : d[1], lo[1], hdr.h[1], n[1]);
+            r[0] = nmpc::cellof(d[0] < d[2] ? d[0] : d[2], lo[0], hdr.h[0], n[0]);
+            r[1] = nmpc::cellof(d[0] < d[2] ? d[2] : d[0], lo[0], hdr.h[0], n[0]);
+            r[2] = nmpc::cellof(d[1] < d[3] ? d[1] : d[3], lo[1], hdr.h[1], n[1]);
+            r[3] = nmpc::cellof(d[1] < d[3] ? d[3] : d[1], lo[1], hdr.h[1], n[1]);
             entries += (long long)(r[1] - r[0] + 1) * (r[3] - r[2] + 1);
         }
         if (entries > nmpc::WALL_GRID_MAX_ENTRIES) return false;

@@ -521,6 +521,49 @@ WALL_GRID_MAX_ENTRIES = 1 << 23      # filings of all edges at the most
 WALL_GRID_CAP = 512                  # cells per axis at the most (csrc/nmpc_loop.h)
 
 
+# ---- the loop's geometry (csrc/nmpc_geom.h): unfused f64, the same operations in the same order as the header's functions ----
+def segment_closest(x, y, x1, y1, x2, y2, clamp_below=True):
+    """The points of the segments (x1, y1) -> (x2, y2) closest to the positions (x, y), all broadcast against each other -> (v, cx, cy):
+    the squared distance and the point (segment_closest of csrc/nmpc_geom.h).  A segment without length is its first end; a NaN clamps
+    nothing.  ``clamp_below`` (a flag, or an array of them) False lets a segment run on backwards beyond its first end."""
+    with np.errstate(all="ignore"):
+        ex, ey = x2 - x1, y2 - y1
+        L2 = ex * ex + ey * ey
+        pos = L2 > 0
+        t = ((x - x1) * ex + (y - y1) * ey) / np.where(pos, L2, 1.0)
+        t = np.where((t < 0) & clamp_below, 0.0, t)
+        t = np.where(t > 1, 1.0, t)
+        t = np.where(pos, t, 0.0)
+        cx, cy = x1 + t * ex, y1 + t * ey
+        dx, dy = x - cx, y - cy
+        return dx * dx + dy * dy, cx, cy
+
+
+def grid_cellof(v, o, h, n):
+    """The cells (int64) of the coordinates ``v`` on an axis of ``n`` cells of edge ``h`` from ``o``: monotone non-decreasing in ``v``,
+    clamped before the conversion (cellof of csrc/nmpc_geom.h).  Filing and looking up, in both grids, use this one function."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (np.asarray(v, dtype=np.float64) - o) / h
+    t = np.where(t > 0.0, t, 0.0)                                           # (a NaN goes to 0)
+    return np.where(t >= float(n), n - 1, np.minimum(t, float(n)).astype(np.int64)).astype(np.int64)
+
+
+def grid_axis(extent, cell, cap):
+    """An axis of a grid -> (n, h): floor(extent / cell) + 1 cells of edge ``cell``, or ``cap`` cells of edge extent / ``cap`` where that
+    would be more (grid_axis of csrc/nmpc_geom.h)."""
+    with np.errstate(all="ignore"):
+        q = np.float64(extent) / np.float64(cell)
+        return (int(q) + 1, np.float64(cell)) if q < float(cap) else (cap, np.float64(extent) / float(cap))
+
+
+class _Grid:
+    """What ``WallGrid`` and ``PeerGrid`` share: ``origin`` [2], ``h`` [2], ``nx``, ``ny`` and the cell of a coordinate."""
+
+    def _cellof(self, v, axis):
+        """The cell of coordinate ``v`` on ``axis`` (``grid_cellof``)."""
+        return int(grid_cellof(v, self.origin[axis], self.h[axis], (self.nx, self.ny)[axis]))
+
+
 @dataclasses.dataclass(frozen=True)
 class Walls:
     """How the robots of a loop see the map's walls, for ``FleetRecedingHorizon`` and ``DeviceRecedingHorizon``
@@ -567,7 +610,7 @@ class Walls:
         return edges
 
 
-class WallGrid:
+class WallGrid(_Grid):
     """The static grid of a map's wall segments (``wall_grid``): ``origin`` [2], ``h`` [2] the cells' edges, ``nx``, ``ny``, ``entries``
     (what ``nmpc_loop_wall_grid`` returns as its header), the CSR arrays ``cell_off`` [nx * ny + 1] and ``cell_edge`` [entries] int32
     (cells row-major, y * nx + x; edge indices ascending inside a cell), every edge's rectangle of cells ``rect`` [E, 4] = (first column,
@@ -579,18 +622,6 @@ class WallGrid:
         rec["origin"], rec["h"] = self.origin, self.h
         rec["nx"], rec["ny"], rec["entries"] = self.nx, self.ny, self.entries
         return rec
-
-    def _cellof(self, v, axis):
-        """The cell of coordinate ``v`` on ``axis``: monotone non-decreasing in ``v``, clamped before the conversion (wall_cellof of
-        csrc/nmpc_loop.h).  Filing and looking up use this one function."""
-        n = (self.nx, self.ny)[axis]
-        with np.errstate(invalid="ignore", over="ignore"):
-            t = (np.float64(v) - self.origin[axis]) / self.h[axis]
-        if not t > 0.0:
-            return 0
-        if t >= float(n):
-            return n - 1
-        return int(t)
 
     def window(self, pred_b, range):
         """-> (cx0, cx1, cy0, cy1), inclusive: the cells a robot with the predicted positions ``pred_b`` [N, >= 2] looks at; None for
@@ -633,23 +664,13 @@ def wall_grid(edges, cell):
     xs, ys = edges[:, [0, 2]], edges[:, [1, 3]]
     g.origin = np.array([xs.min(), ys.min()])
     g.amax = np.float64(np.abs(edges).max())
-    g.h = np.array([g.cell, g.cell])
-    n = [1, 1]
     with np.errstate(over="ignore"):
         ext = np.array([xs.max(), ys.max()]) - g.origin
-    for ax in (0, 1):
-        q = ext[ax] / g.cell
-        if q < float(WALL_GRID_CAP):
-            n[ax] = int(q) + 1
-        else:
-            n[ax], g.h[ax] = WALL_GRID_CAP, ext[ax] / float(WALL_GRID_CAP)
-    g.nx, g.ny = n
+    (g.nx, hx), (g.ny, hy) = (grid_axis(ext[ax], g.cell, WALL_GRID_CAP) for ax in (0, 1))
+    g.h = np.array([hx, hy])
 
-    def cells(v, ax):                                                       # _cellof over an array
-        with np.errstate(invalid="ignore", over="ignore"):
-            t = (v - g.origin[ax]) / g.h[ax]
-        t = np.where(t > 0.0, t, 0.0)                                       # (a NaN goes to 0)
-        return np.where(t >= float(n[ax]), n[ax] - 1, np.minimum(t, float(n[ax])).astype(np.int64)).astype(np.int64)
+    def cells(v, ax):
+        return grid_cellof(v, g.origin[ax], g.h[ax], (g.nx, g.ny)[ax])
     g.rect = np.stack([cells(xs.min(axis=1), 0), cells(xs.max(axis=1), 0), cells(ys.min(axis=1), 1), cells(ys.max(axis=1), 1)], axis=1)
     w, hgt = g.rect[:, 1] - g.rect[:, 0] + 1, g.rect[:, 3] - g.rect[:, 2] + 1
     g.entries = int((w * hgt).sum())
@@ -669,7 +690,7 @@ def wall_grid(edges, cell):
 PEER_GRID_CAP = 128          # cells per axis at the most (csrc/nmpc_loop.h)
 
 
-class PeerGrid:
+class PeerGrid(_Grid):
     """The grid of one step (``peer_grid``): ``origin`` [2], ``h`` [2] the cells' edges, ``W`` [2] the largest box extent, ``nx``,
     ``ny``, ``filed`` (what ``nmpc_loop_peer_grid`` returns as its header), ``cell_of`` [B] int32 (row-major, y * nx + x; -1 =
     unfiled), the boxes ``lo``, ``hi`` [B, 2] and ``candidates(b)``."""
@@ -680,17 +701,6 @@ class PeerGrid:
         rec["origin"], rec["h"], rec["W"] = self.origin, self.h, self.W
         rec["nx"], rec["ny"], rec["filed"] = self.nx, self.ny, self.filed
         return rec
-
-    def _cellof(self, v, axis):
-        """The cell of coordinate ``v`` on ``axis``: monotone non-decreasing in ``v`` (peer_cellof of csrc/nmpc_loop.h)."""
-        n = (self.nx, self.ny)[axis]
-        with np.errstate(invalid="ignore", over="ignore"):
-            t = (np.float64(v) - self.origin[axis]) / self.h[axis]
-        if not t > 0.0:
-            return 0
-        if t >= float(n):
-            return n - 1
-        return int(t)
 
     def window(self, b):
         """-> (cx0, cx1, cy0, cy1), inclusive: the cells robot b looks at; None for an unfiled robot."""
@@ -746,14 +756,8 @@ def peer_grid(pred, range, cell):
         up = (w.view(np.int64) + 1).view(np.float64)                       # the next double above: never below the real hi - lo
         g.W = np.where(w < np.inf, up, w).max(axis=0)
         g.origin = lo.min(axis=0)
-        n = [1, 1]
-        for ax in (0, 1):
-            q = ex[ax] / g.cell
-            if q < float(PEER_GRID_CAP):
-                n[ax] = int(q) + 1
-            else:
-                n[ax], g.h[ax] = PEER_GRID_CAP, ex[ax] / float(PEER_GRID_CAP)
-        g.nx, g.ny = n
+        (g.nx, hx), (g.ny, hy) = (grid_axis(ex[ax], g.cell, PEER_GRID_CAP) for ax in (0, 1))
+        g.h = np.array([hx, hy])
         for b in np.nonzero(filed)[0]:
             g.cell_of[b] = g._cellof(g.lo[b, 1], 1) * g.nx + g._cellof(g.lo[b, 0], 0)
     cells = g.nx * g.ny
@@ -870,20 +874,12 @@ class MapMonitor:
         x1, y1, x2, y2 = (edges[:, k][None, :] for k in range(4))
         X, Y, AX, AY = x[:, None], y[:, None], ax[:, None], ay[:, None]
         at = np.arange(n)
+        v = segment_closest(X, Y, x1, y1, x2, y2)[0]
+        v = np.where(np.isnan(v), np.inf, v)
+        e = np.argmin(v, axis=1)
         with np.errstate(all="ignore"):
-            ex, ey = x2 - x1, y2 - y1
-            L2 = ex * ex + ey * ey
-            pos = L2 > 0
-            t = ((X - x1) * ex + (Y - y1) * ey) / np.where(pos, L2, 1.0)
-            t = np.where(t < 0, 0.0, t)
-            t = np.where(t > 1, 1.0, t)
-            t = np.where(pos, t, 0.0)
-            cx, cy = x1 + t * ex, y1 + t * ey
-            dx, dy = X - cx, Y - cy
-            v = dx * dx + dy * dy
-            v = np.where(np.isnan(v), np.inf, v)
-            e = np.argmin(v, axis=1)
             # crossing between the two rows (frontend._seg_intersect_strict)
+            ex, ey = x2 - x1, y2 - y1
             ux, uy = X - AX, Y - AY
             o1 = ux * (y1 - AY) - uy * (x1 - AX)
             o2 = ux * (y2 - AY) - uy * (x2 - AX)
@@ -983,17 +979,7 @@ class TrackMonitor:
         a, e = np.minimum(j, nr - 1), np.minimum(j + 1, nr - 1)
         x1, y1, x2, y2 = ref[rt, a, 0], ref[rt, a, 1], ref[rt, e, 0], ref[rt, e, 1]
         X, Y = x[:, None], y[:, None]
-        with np.errstate(all="ignore"):
-            ex, ey = x2 - x1, y2 - y1
-            L2 = ex * ex + ey * ey
-            pos = L2 > 0
-            t = ((X - x1) * ex + (Y - y1) * ey) / np.where(pos, L2, 1.0)
-            t = np.where((t < 0) & (j > 0), 0.0, t)
-            t = np.where(t > 1, 1.0, t)
-            t = np.where(pos, t, 0.0)
-            cx, cy = x1 + t * ex, y1 + t * ey
-            dx, dy = X - cx, Y - cy
-            v = dx * dx + dy * dy
+        v = segment_closest(X, Y, x1, y1, x2, y2, clamp_below=j > 0)[0]
         v = np.where(np.isnan(v) | ~valid, np.inf, v)
         k = np.argmin(v, axis=1)                                            # the first segment with the smallest value
         best = v[np.arange(m), k]
@@ -1487,19 +1473,9 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             n, at = len(me), np.arange(len(me))
             D, ks = np.full((n, E), np.inf), np.full((n, E), -1, dtype=np.int32)
             CX, CY = np.zeros((n, E)), np.zeros((n, E))
-            with np.errstate(all="ignore"):
-                ex, ey = x2 - x1, y2 - y1
-                L2 = ex * ex + ey * ey
-                pos = L2 > 0
+            with np.errstate(invalid="ignore"):
                 for k in range(N):                                           # min over the stages, in order
-                    X, Y = pred[me, k, 0][:, None], pred[me, k, 1][:, None]
-                    t = ((X - x1) * ex + (Y - y1) * ey) / np.where(pos, L2, 1.0)
-                    t = np.where(t < 0, 0.0, t)
-                    t = np.where(t > 1, 1.0, t)
-                    t = np.where(pos, t, 0.0)
-                    cx, cy = x1 + t * ex, y1 + t * ey
-                    dx, dy = X - cx, Y - cy
-                    v = dx * dx + dy * dy
+                    v, cx, cy = segment_closest(pred[me, k, 0][:, None], pred[me, k, 1][:, None], x1, y1, x2, y2)
                     lower = v < D
                     D, ks = np.where(lower, v, D), np.where(lower, np.int32(k), ks)
                     CX, CY = np.where(lower, cx, CX), np.where(lower, cy, CY)

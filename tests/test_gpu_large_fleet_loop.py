@@ -11,8 +11,8 @@ What each case makes a kernel do that no smaller case does:
 * grid peers at B = 1100 and 2100: ``block_chunk`` hands a thread of ``nmpc_loop_peer_grid_kernel`` two and three robots and leaves
   the threads behind them empty; 53 x 52 cells (1 m) give the scan's ``block_chunk(cells + 1)`` three entries per thread (as the
   160 robots of tests/test_gpu_peers_grid_loop.py::test_more_than_a_wave do, one robot per thread), 128 x 128 (0.25 m) seventeen,
-  and the ``cell_off`` zeroing loop further strides; at 0.25 m ``peer_grid_axis`` takes the clamp branch, so ``h`` and every
-  ``peer_cellof`` with it (the grid kernel's and the window of ``nmpc_loop_peers_grid_kernel``) are the device's division.
+  and the ``cell_off`` zeroing loop further strides; at 0.25 m ``grid_axis`` takes the clamp branch, so ``h`` and every
+  ``cellof`` with it (the grid kernel's and the window of ``nmpc_loop_peers_grid_kernel``) are the device's division.
 * the drive log at B = 1100 and 2100: the stride loop of ``nmpc_loop_log_totals_kernel`` runs twice and three times, all sixteen
   waves feed the LDS combine, and thread 1 meets the step's ``inner_max`` in two strides (robots 1 and 1025).
 * the retiring fleet: ``nmpc_loop_log_kernel``, ``nmpc_loop_measure_kernel`` and ``nmpc_loop_plant_kernel`` over five workgroups with
