@@ -595,6 +595,37 @@ int nmpc_loop_set_crowd(nmpc_loop *l, int D, const double *obst, double pad, int
 /* Synchronises, then copies what is asked for (NULL = skip): table [D][N][5] as the last step wrote it, and seen [B][M], the obstacle in
  * slot K + m of each robot's p at its last step, -1 for none.  NMPC_ERR_BAD_ARG on a loop without a crowd or before its first step. */
 int nmpc_loop_crowd(nmpc_loop *l, double *table, int32_t *seen);
+/* The crowd through a grid in space and stage: nmpc_loop_set_crowd with the same rule, table, slots, seen and observer, bit for bit, for
+ * up to 131072 obstacles, at a cost that grows with what is near a robot and not with the world (the rule, and why it misses nobody and
+ * keeps nobody twice: DESIGN.md section 5.9).  The setter fixes the geometry on the host: origin = the minimum per axis over the end
+ * points p1, p2 of obst whose two coordinates are finite, per axis floor(extent / cell) + 1 cells of edge `cell`, or 128 cells of edge
+ * extent / 128 where that would be more (one cell at (0, 0) without a finite end point), and N layers, one per stage.  Every step with an
+ * active robot, behind the table's advance, entry (d, k) of the table is filed under the cell of its position in layer k (unfiled if a
+ * coordinate is not finite; a position outside the extent goes to the edge cell), by a counting sort of five kernels; a robot then
+ * looks, per stage k at which its predicted position is finite, at the entries filed in the cells from that of (x - range) to that of
+ * (x + range) per axis in layer k, and entry (d, k) makes d a candidate, with the C(b, d) of nmpc_loop_set_crowd, if its d_k < range^2
+ * and no stage j < k has d_j < range^2.  One kernel takes the place of the all-obstacles selection.  The observer
+ * (nmpc_loop_set_crowd_monitor) stays all obstacles: its level has no cut-off a grid could use.
+ * This is the loop's crowd call: either setter after the other, a second call or a call after a step is refused.  NMPC_ERR_BAD_ARG with
+ * a message, nothing changed and nothing allocated, for everything nmpc_loop_set_crowd refuses (but D up to 131072 is taken) and for a
+ * cell that is not finite and positive.  nmpc_loop_crowd, nmpc_loop_set_crowd_monitor and nmpc_loop_crowd_clearance work on either kind. */
+int nmpc_loop_set_crowd_grid(nmpc_loop *l, int D, const double *obst, double pad, int M, double range, double cell);
+/* The crowd's grid, for tests and reports: the origin, the cells' edges and the cells per axis, the layers (N), and the entries filed at
+ * the last build (0 before any build). */
+typedef struct nmpc_crowd_grid {     /* 48 bytes */
+    double  origin[2], h[2];
+    int32_t nx, ny, layers, filed;
+} nmpc_crowd_grid;
+#ifdef __cplusplus
+static_assert(sizeof(nmpc_crowd_grid) == 48, "nmpc_crowd_grid layout");
+#else
+_Static_assert(sizeof(nmpc_crowd_grid) == 48, "nmpc_crowd_grid layout");
+#endif
+/* Synchronises, then copies what is asked for (NULL = skip): the header (available right after the setter), cell_of [D][N], the cell
+ * (layer * nx * ny + y * nx + x) each entry of the last step's table was filed under, -1 for an unfiled one, and looked [B], the filed
+ * entries in each robot's windows at its last step (a retired robot keeps its last; the all-obstacles selection looks at D * N).
+ * NMPC_ERR_BAD_ARG on a loop without nmpc_loop_set_crowd_grid, and for cell_of or looked before the loop's first step. */
+int nmpc_loop_crowd_grid(nmpc_loop *l, nmpc_crowd_grid *out, int32_t *cell_of, int32_t *looked);
 /* Crowd observer: each robot's closest approach to ANY obstacle of the crowd, in a slot of its p or not.  One more kernel per step, after the
  * advance, over the robots the step drove: for each of the step's s trajectory rows r = first + i and every d < D, the cost's level
  * (a*a)/(rx*rx) + (c*c)/(ry*ry) of the pose of row r against entry i of obstacle d's row of this step's table ((a, c) as nmpc_clearance's

@@ -28,6 +28,7 @@ SYMBOLS = (
     "nmpc_loop_set_peers_grid", "nmpc_loop_peer_grid",
     "nmpc_loop_set_log", "nmpc_loop_log", "nmpc_loop_drive_summary", "nmpc_loop_step_totals",
     "nmpc_loop_set_crowd", "nmpc_loop_crowd", "nmpc_loop_set_crowd_monitor", "nmpc_loop_crowd_clearance",
+    "nmpc_loop_set_crowd_grid", "nmpc_loop_crowd_grid",
     "nmpc_loop_set_plant", "nmpc_loop_plant_applied", "nmpc_loop_plant_measured",
     "nmpc_loop_set_ensemble", "nmpc_loop_ensemble", "nmpc_loop_ensemble_groups",
     "nmpc_loop_set_walls", "nmpc_loop_walls", "nmpc_loop_set_walls_grid", "nmpc_loop_wall_grid",
@@ -127,6 +128,10 @@ assert PEER_GRID_DTYPE.itemsize == 64
 # nmpc_wall_grid: the grid the walls' edges are found through (nmpc_loop_set_walls_grid)
 WALL_GRID_DTYPE = np.dtype([("origin", "<f8", 2), ("h", "<f8", 2), ("nx", "<i4"), ("ny", "<i4"), ("entries", "<i4"), ("reserved", "<i4")])
 assert WALL_GRID_DTYPE.itemsize == 48
+
+# nmpc_crowd_grid: the grid in space and stage the crowd's obstacles are found through (nmpc_loop_set_crowd_grid)
+CROWD_GRID_DTYPE = np.dtype([("origin", "<f8", 2), ("h", "<f8", 2), ("nx", "<i4"), ("ny", "<i4"), ("layers", "<i4"), ("filed", "<i4")])
+assert CROWD_GRID_DTYPE.itemsize == 48
 
 # the drive log (nmpc_loop_set_log): nmpc_step_record, one per robot and step; nmpc_drive_summary, one per robot; nmpc_step_totals, one per step
 STEP_RECORD_DTYPE = np.dtype([("exit_status", "<i4"), ("leg", "<i4"), ("num_inner_iterations", "<u4"), ("num_outer_iterations", "<u4"),
@@ -383,6 +388,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_crowd.restype = C.c_int
     lib.nmpc_loop_crowd.argtypes = [vp, dp, C.POINTER(C.c_int32)]
     lib.nmpc_loop_crowd.restype = C.c_int
+    lib.nmpc_loop_set_crowd_grid.argtypes = [vp, C.c_int, dp, C.c_double, C.c_int, C.c_double, C.c_double]
+    lib.nmpc_loop_set_crowd_grid.restype = C.c_int
+    lib.nmpc_loop_crowd_grid.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.nmpc_loop_crowd_grid.restype = C.c_int
     lib.nmpc_loop_set_crowd_monitor.argtypes = [vp]
     lib.nmpc_loop_set_crowd_monitor.restype = C.c_int
     lib.nmpc_loop_crowd_clearance.argtypes = [vp, vp]

@@ -786,6 +786,202 @@ __global__ __launch_bounds__(64) void nmpc_loop_crowd_monitor_kernel(LoopView L,
     }
 }
 
+// ---- the crowd through a grid in space and stage (nmpc_loop_set_crowd_grid; the rule, and why it misses nobody: DESIGN.md section 5.9) ----
+// The same selection over fewer obstacles.  The closeness rule pairs robot and obstacle stage by stage, so entry (d, k) of the table is
+// filed under the cell of its position in layer k of a grid the setter fixed (host, nmpc_geom.h), every step anew: a counting sort over
+// five kernels (zero, count, tile sums, scan, scatter), whose boundaries order its phases.  A robot then looks, per stage, only at the
+// entries filed within `range` of its own position at that stage, and an obstacle is kept at the first stage that finds it in range.
+constexpr int CROWD_GRID_CAP = 128;                 // cells per axis at the most
+constexpr int CROWD_GRID_MAX = 131072;              // D at the most: 5.2 M entries at N = 40
+
+struct CrowdGridArgs {
+    double origin[2], h[2];
+    int nx, ny, cells;        // cells = N * nx * ny: layer k holds the cells k * nx * ny + y * nx + x
+    double range;
+    int *cell_of;             // [D][N]: the entry's cell, -1 = unfiled (a coordinate that is not finite)
+    int *cell_off;            // [cells + 1]: cell c holds cell_mem[cell_off[c] .. cell_off[c + 1]); cell_off[cells] = the entries filed
+    int *tile_sum;            // [tiles]: the scan's sums per CROWD_GRID_TILE cells
+    int *cell_cur;            // [cells]: the scatter's cursors
+    int *cell_mem;            // [D * N]: the obstacle d of each filed entry (its stage is its cell's layer)
+    int *looked;              // [B]: the filed entries in the robot's windows at its last step
+};
+
+// one thread per cell, the one behind the last included: the populations start at zero
+__global__ __launch_bounds__(256) void nmpc_loop_crowd_grid_zero_kernel(CrowdGridArgs g)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c <= g.cells) g.cell_off[c] = 0;
+}
+
+// one thread per entry (d, k) of this step's table: its cell into cell_of, and the cell's population counted (integer atomics)
+__global__ __launch_bounds__(256) void nmpc_loop_crowd_grid_count_kernel(LoopView L, LoopStep stp, CrowdArgs c, CrowdGridArgs g)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= c.D * L.N) return;
+    const int k = e % L.N;
+    const double *q = c.tab[stp.cur ^ 1] + (size_t)e * 5;
+    const double x = q[0], y = q[1], inf = __builtin_inf();
+    int key = -1;
+    if (fabs(x) < inf && fabs(y) < inf) {
+        key = (k * g.ny + cellof(y, g.origin[1], g.h[1], g.ny)) * g.nx + cellof(x, g.origin[0], g.h[0], g.nx);
+        atomicAdd(g.cell_off + key, 1);
+    }
+    g.cell_of[e] = key;
+}
+
+// The exclusive scan of the populations, the entry behind the last cell included, over tiles of CROWD_GRID_TILE cells, one workgroup
+// per tile and four consecutive cells per thread (block_scan over the threads' sums).  First every tile's sum; then each tile adds up
+// the sums of the tiles in front of it and scans its own cells in place, and sets the scatter's cursors.  (One workgroup over all
+// cells in chunks, as nmpc_loop_peer_grid_kernel scans its 16 384, took 135 us for the 64 980 cells of a 57 x 57 x 20 grid.)
+constexpr int CROWD_GRID_TILE = 1024;
+
+__global__ __launch_bounds__(256) void nmpc_loop_crowd_grid_sum_kernel(CrowdGridArgs g)
+{
+    __shared__ int cnt[256];
+    const int c0 = blockIdx.x * CROWD_GRID_TILE + 4 * threadIdx.x;
+    int sum = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sum += c0 + q <= g.cells ? g.cell_off[c0 + q] : 0;
+    const int all = block_scan(cnt, sum);
+    if (threadIdx.x == 255) g.tile_sum[blockIdx.x] = all;
+}
+
+__global__ __launch_bounds__(256) void nmpc_loop_crowd_grid_scan_kernel(CrowdGridArgs g)
+{
+    __shared__ int cnt[256];
+    __shared__ int before;
+    const int t = threadIdx.x, tile = blockIdx.x;
+    int sum = 0;
+    for (int i = t; i < tile; i += 256) sum += g.tile_sum[i];
+    const int all = block_scan(cnt, sum);
+    if (t == 255) before = all;
+    __syncthreads();
+    const int c0 = tile * CROWD_GRID_TILE + 4 * t;
+    int n[4];
+    sum = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { n[q] = c0 + q <= g.cells ? g.cell_off[c0 + q] : 0; sum += n[q]; }
+    int run = before + block_scan(cnt, sum) - sum;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = c0 + q;
+        if (c <= g.cells) g.cell_off[c] = run;
+        if (c < g.cells) g.cell_cur[c] = run;
+        run += n[q];
+    }
+}
+
+// one thread per entry: a filed entry's obstacle into its cell's next place.  The order inside a cell is the atomics' and differs from
+// run to run; no result depends on it.
+__global__ __launch_bounds__(256) void nmpc_loop_crowd_grid_scatter_kernel(LoopView L, CrowdArgs c, CrowdGridArgs g)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= c.D * L.N) return;
+    const int key = g.cell_of[e];
+    if (key >= 0) g.cell_mem[atomicAdd(g.cell_cur + key, 1)] = e / L.N;
+}
+
+// One wave per active robot: the rule of nmpc_loop_crowd_kernel over the entries filed in the robot's windows.  Lane k forms the window
+// of stage k (none at a stage that is not finite: its d_k is never < range^2); the windows' rows, stage after stage, count as one list,
+// and each row of it is one run of cell_mem.  The list is taken 64 rows at a time: the lanes read the rows' bounds, a wave scan lays
+// the runs end to end, and the lanes stride over the entries of all 64 rows together (six halvings name an entry's row).  Entry (d, k)
+// keeps d if d_k < range^2 and no earlier stage has d_j < range^2 (ascending, four at a time, left at the first four with one): its
+// first stage in range alone, so one lane keeps d once, with the C of peer_closeness.  Every loop's bounds are read before it starts,
+// and no buffer's size depends on a population: a window of any number of rows and a row of any length take more rounds.
+__global__ __launch_bounds__(64) void nmpc_loop_crowd_grid_kernel(LoopView L, LoopStep stp, CrowdArgs c, CrowdGridArgs g)
+{
+    __shared__ double own[2 * NMPC_MAX_HORIZON];
+    __shared__ int wx0[NMPC_MAX_HORIZON], wx1[NMPC_MAX_HORIZON], wy0[NMPC_MAX_HORIZON], wpre[NMPC_MAX_HORIZON];
+    __shared__ int rbeg[64], rstage[64], rpre[64];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int N = L.N, per = 5 * N, nx = g.nx, ny = g.ny;
+    const double *tab = c.tab[stp.cur ^ 1];
+    const double inf = __builtin_inf();
+    stage_pred(own, c.pred, b, N);
+    // the windows: wpre = the exclusive prefix sums of the stages' rows
+    int rows = 0;
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        const int k = k0 + lane;
+        int n = 0;
+        if (k < N) {
+            const double x = own[2 * k], y = own[2 * k + 1];
+            int cx0 = 0, cx1 = 0, cy0 = 0;
+            if (fabs(x) < inf && fabs(y) < inf) {
+                cx0 = cellof(x - g.range, g.origin[0], g.h[0], nx);
+                cx1 = cellof(x + g.range, g.origin[0], g.h[0], nx);
+                cy0 = cellof(y - g.range, g.origin[1], g.h[1], ny);
+                n = cellof(y + g.range, g.origin[1], g.h[1], ny) - cy0 + 1;
+            }
+            wx0[k] = cx0; wx1[k] = cx1; wy0[k] = cy0;
+        }
+        int sum = n;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(sum, off);
+            if (lane >= off) sum += o;
+        }
+        if (k < N) wpre[k] = rows + sum - n;
+        rows += __shfl(sum, 63);
+    }
+    __syncthreads();
+    double bd[NDYN_MAX];
+    int bj[NDYN_MAX];
+    peer_none(bd, bj);
+    int looked = 0;
+    for (int q0 = 0; q0 < rows; q0 += 64) {
+        // row q of the list: the last stage k with wpre[k] <= q holds it (stages without a window are passed)
+        const int q = q0 + lane;
+        int i0 = 0, len = 0, k = 0;
+        if (q < rows) {
+            int lo = 0, hi = N - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (wpre[mid] <= q) lo = mid; else hi = mid - 1;
+            }
+            k = lo;
+            const int at = (k * ny + wy0[k] + (q - wpre[k])) * nx;
+            i0 = g.cell_off[at + wx0[k]];
+            len = g.cell_off[at + wx1[k] + 1] - i0;
+        }
+        int sum = len;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(sum, off);
+            if (lane >= off) sum += o;
+        }
+        const int total = __shfl(sum, 63);
+        rbeg[lane] = i0; rstage[lane] = k; rpre[lane] = sum - len;
+        __syncthreads();
+        for (int idx = lane; idx < total; idx += 64) {
+            int lo = 0, hi = 63;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (rpre[mid] <= idx) lo = mid; else hi = mid - 1;
+            }
+            const int kk = rstage[lo], d = g.cell_mem[rbeg[lo] + (idx - rpre[lo])];
+            const double *pj = tab + (size_t)d * per;
+            const double dx = own[2 * kk] - pj[5 * kk], dy = own[2 * kk + 1] - pj[5 * kk + 1];
+            if (dx * dx + dy * dy < c.range2) {
+                bool first = true;
+                for (int j0 = 0; j0 < kk && first; j0 += 4) {         // four stages at a time: their loads are in flight together
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const bool in = j0 + u < kk;
+                        const int j = in ? j0 + u : 0;
+                        const double ex = own[2 * j] - pj[5 * j], ey = own[2 * j + 1] - pj[5 * j + 1];
+                        if (in && ex * ex + ey * ey < c.range2) first = false;
+                    }
+                }
+                if (first) peer_keep(bd, bj, peer_closeness(own, pj, N, 5), d);
+            }
+        }
+        looked += total;
+        __syncthreads();                      // the rows' bounds are read before the next 64 take their place
+    }
+    peer_overlay(L, b, lane, bd, bj, L.K, c.M, c.seen + (size_t)b * c.M, [&](int d, int e) { return tab[(size_t)d * per + e]; });
+    if (lane == 0) g.looked[b] = looked;
+}
+
 // ---- walls: each robot's closest points on the map's wall segments as circles (nmpc_loop_set_walls; the rule is DESIGN.md section 5.9) ----
 // One kernel between the peers' and the solve: per active robot and edge the smallest wall distance (that of nmpc_loop_map_kernel) over its
 // predicted positions, the first M of the edges with D < range^2 in (D, e) order that keep `spacing` from the ones taken before them, each

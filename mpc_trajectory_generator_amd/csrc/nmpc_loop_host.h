@@ -52,8 +52,14 @@ struct LoopCrowd {
     DevBuf<double> obst, tab[2];     // [D][10], [D][N][5] twice
     DevBuf<int> seen;                // [B][M]
     DevBuf<nmpc_crowd_clearance> rec;    // [B]: the observer's
+    // nmpc_loop_set_crowd_grid: the obstacles a robot measures come from a grid in space and stage, filed anew every step: five kernels
+    // behind the table's advance, and nmpc_loop_crowd_grid_kernel in the place of nmpc_loop_crowd_kernel
+    nmpc::CrowdGridArgs g{};
+    nmpc_crowd_grid hdr{};               // (filed: read from the device when asked for)
+    DevBuf<int> cell_of, cell_off, tile_sum, cell_cur, cell_mem, looked;      // [D][N], [cells + 1], [tiles], [cells], [D * N], [B]
     bool made() const { return obst != nullptr; }
     bool watched() const { return rec != nullptr; }
+    bool grid() const { return cell_off != nullptr; }
 };
 // nmpc_loop_set_retire: robots at their goal leave the loop.  A step runs over the active list, the solve over gathered rows, and
 // the host learns the list's length one step late (nmpc_loop.h)
@@ -320,21 +326,45 @@ static int loop_set_peers(nmpc_loop *l, const char *fn, const int32_t *group_of,
 static constexpr int CROWD_MAX = 16384;
 static const nmpc_crowd_clearance CROWD_CLEARANCE_NONE = {__builtin_inf(), -1, -1};
 
-int nmpc_loop_set_crowd(nmpc_loop *l, int D, const double *obst, double pad, int M, double range)
+// The geometry of nmpc_loop_set_crowd_grid, fixed by the setter (the rule: DESIGN.md section 5.9; trajectory.crowd_grid is its NumPy
+// statement): over the end points of obst [D][10] whose two coordinates are finite, with the functions of nmpc_geom.h only.
+static nmpc_crowd_grid crowd_grid_geometry(int D, const double *obst, double cell, int N)
+{
+    const double inf = __builtin_inf();
+    double lx = inf, ly = inf, hx = -inf, hy = -inf;
+    for (int d = 0; d < D; ++d) {
+        const double *q = obst + 10 * (size_t)d;
+        nmpc::box_fold(q[0], q[1], lx, ly, hx, hy);
+        nmpc::box_fold(q[2], q[3], lx, ly, hx, hy);
+    }
+    nmpc_crowd_grid g{};
+    g.nx = g.ny = 1; g.h[0] = g.h[1] = cell; g.layers = N;
+    if (lx <= hx) {
+        g.origin[0] = lx; g.origin[1] = ly;
+        nmpc::grid_axis(hx - lx, cell, nmpc::CROWD_GRID_CAP, g.nx, g.h[0]);
+        nmpc::grid_axis(hy - ly, cell, nmpc::CROWD_GRID_CAP, g.ny, g.h[1]);
+    }
+    return g;
+}
+
+// both crowd setters: `cell` NULL = every obstacle against every robot (nmpc_loop_set_crowd), else the grid's cell
+static int loop_set_crowd(nmpc_loop *l, const char *name, int max_D, int D, const double *obst, double pad, int M, double range, const double *cell)
 {
     if (!l) return NMPC_ERR_BAD_ARG;
-    if (const int rc = loop_setter(l, "nmpc_loop_set_crowd", l->crowd.made(), "the loop has its crowd already")) return rc;
+    if (const int rc = loop_setter(l, name, l->crowd.made(), "the loop has its crowd already")) return rc;
     nmpc_handle *h = l->h;
     const nmpc::LoopView &v = l->v;
     const size_t B = (size_t)v.B;
-    if (D < 1 || D > CROWD_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: D outside 1 .. 16384");
-    if (!obst) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: obst is NULL");
-    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: M < 1");
+    const std::string fn = std::string(name) + ": ";
+    if (D < 1 || D > max_D) return fail(h, NMPC_ERR_BAD_ARG, (fn + "D outside 1 .. " + std::to_string(max_D)).c_str());
+    if (!obst) return fail(h, NMPC_ERR_BAD_ARG, (fn + "obst is NULL").c_str());
+    if (M < 1) return fail(h, NMPC_ERR_BAD_ARG, (fn + "M < 1").c_str());
     const int Mp = l->peers.made() ? l->peers.a.M : 0;
     if (v.K + M + Mp > v.ndyn)
-        return fail(h, NMPC_ERR_BAD_ARG, Mp ? "nmpc_loop_set_crowd: K + M + the peers' M > Ndynobs, no free ellipse slot" : "nmpc_loop_set_crowd: K + M > Ndynobs, no free ellipse slot");
-    if (!(pad >= -DBL_MAX && pad <= DBL_MAX)) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: pad must be finite");
-    if (!(range > 0.0) || range > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_crowd: range must be finite and positive");
+        return fail(h, NMPC_ERR_BAD_ARG, (fn + (Mp ? "K + M + the peers' M > Ndynobs, no free ellipse slot" : "K + M > Ndynobs, no free ellipse slot")).c_str());
+    if (!(pad >= -DBL_MAX && pad <= DBL_MAX)) return fail(h, NMPC_ERR_BAD_ARG, (fn + "pad must be finite").c_str());
+    if (!(range > 0.0) || range > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (fn + "range must be finite and positive").c_str());
+    if (cell && (!(*cell > 0.0) || *cell > DBL_MAX)) return fail(h, NMPC_ERR_BAD_ARG, (fn + "cell must be finite and positive").c_str());
     LoopCrowd st;
     DevBuf<double> pred;           // the loop's, unless the peers have made it
     if (!l->d_pred) HIP_TRY(h, pred.alloc(B * v.N * 3));
@@ -347,10 +377,34 @@ int nmpc_loop_set_crowd(nmpc_loop *l, int D, const double *obst, double pad, int
     c.D = D; c.M = M; c.pad = pad; c.range2 = range * range;
     c.obst = st.obst; c.tab[0] = st.tab[0]; c.tab[1] = st.tab[1];
     c.pred = l->d_pred.p ? l->d_pred.p : pred.p; c.seen = st.seen; c.rec = nullptr;
+    if (cell) {
+        st.hdr = crowd_grid_geometry(D, obst, *cell, v.N);
+        const size_t cells = (size_t)v.N * st.hdr.nx * st.hdr.ny, entries = (size_t)D * v.N;
+        HIP_TRY(h, st.cell_of.alloc_fill(entries, 0xFF));          // -1
+        HIP_TRY(h, st.cell_off.alloc_fill(cells + 1, 0));
+        HIP_TRY(h, st.cell_cur.alloc_fill(cells, 0));
+        HIP_TRY(h, st.tile_sum.alloc_fill((cells + nmpc::CROWD_GRID_TILE) / nmpc::CROWD_GRID_TILE, 0));
+        HIP_TRY(h, st.cell_mem.alloc_fill(entries, 0));
+        HIP_TRY(h, st.looked.alloc_fill(B, 0));
+        nmpc::CrowdGridArgs &g = st.g;
+        for (int ax = 0; ax < 2; ++ax) { g.origin[ax] = st.hdr.origin[ax]; g.h[ax] = st.hdr.h[ax]; }
+        g.nx = st.hdr.nx; g.ny = st.hdr.ny; g.cells = (int)cells; g.range = range;
+        g.cell_of = st.cell_of; g.cell_off = st.cell_off; g.tile_sum = st.tile_sum; g.cell_cur = st.cell_cur; g.cell_mem = st.cell_mem; g.looked = st.looked;
+    }
     l->crowd = std::move(st);
     if (pred) l->d_pred = std::move(pred);
     if (l->peers.made()) l->peers.a.first = v.K + M;       // the peers' slots follow the crowd's
     return NMPC_OK;
+}
+
+int nmpc_loop_set_crowd(nmpc_loop *l, int D, const double *obst, double pad, int M, double range)
+{
+    return loop_set_crowd(l, "nmpc_loop_set_crowd", CROWD_MAX, D, obst, pad, M, range, nullptr);
+}
+
+int nmpc_loop_set_crowd_grid(nmpc_loop *l, int D, const double *obst, double pad, int M, double range, double cell)
+{
+    return loop_set_crowd(l, "nmpc_loop_set_crowd_grid", nmpc::CROWD_GRID_MAX, D, obst, pad, M, range, &cell);
 }
 
 int nmpc_loop_set_crowd_monitor(nmpc_loop *l)
@@ -764,10 +818,20 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
     if (cr.made())
         hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_advance_kernel, dim3((cr.a.D * v.N * 5 + 255) / 256), dim3(256), 0, s, v, stp, cr.a);
     if (n > 0) {
+        if (cr.grid()) {           // this step's table filed: zero, count, tile sums, scan, scatter
+            const int entries = (cr.a.D * v.N + 255) / 256;
+            hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_grid_zero_kernel, dim3((cr.g.cells + 256) / 256), dim3(256), 0, s, cr.g);
+            hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_grid_count_kernel, dim3(entries), dim3(256), 0, s, v, stp, cr.a, cr.g);
+            const int tiles = (cr.g.cells + nmpc::CROWD_GRID_TILE) / nmpc::CROWD_GRID_TILE;        // cells + 1 entries
+            hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_grid_sum_kernel, dim3(tiles), dim3(256), 0, s, cr.g);
+            hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_grid_scan_kernel, dim3(tiles), dim3(256), 0, s, cr.g);
+            hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_grid_scatter_kernel, dim3(entries), dim3(256), 0, s, v, cr.a, cr.g);
+        }
         if (pl.made() && pl.measures()) hipLaunchKernelGGL(nmpc::nmpc_loop_measure_kernel, dim3((n + 255) / 256), dim3(256), 0, s, v, stp, pl.a);
         hipLaunchKernelGGL(nmpc::nmpc_loop_assemble_kernel, dim3(n), dim3(64), 0, s, told, stp, l->a);
         if (l->d_pred) hipLaunchKernelGGL(nmpc::nmpc_loop_predict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, told, stp, l->d_pred.p);
-        if (cr.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a);
+        if (cr.grid()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_grid_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a, cr.g);
+        else if (cr.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a);
         if (l->peers.made()) {
             const nmpc::PeerArgs &p = l->peers.a;
             if (l->peers.grid()) {     // the boxes and the grid over all B: a retired robot stays filed
@@ -914,11 +978,26 @@ int nmpc_loop_crowd(nmpc_loop *l, double *table, int32_t *seen)
 {
     if (const int rc = loop_settle(l)) return rc;
     const LoopCrowd &c = l->crowd;
-    if (!c.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_crowd: the loop has no crowd (nmpc_loop_set_crowd)");
+    if (!c.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_crowd: the loop has no crowd (nmpc_loop_set_crowd, nmpc_loop_set_crowd_grid)");
     if (l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_crowd: before the loop's first step");
     // step k (k = 0, 1, ...) wrote buffer (k & 1) ^ 1
     HIP_TRY(l->h, c.tab[((l->steps - 1) & 1) ^ 1].read(table, (size_t)c.a.D * l->v.N * 5));
     HIP_TRY(l->h, c.seen.read(seen, (size_t)l->v.B * c.a.M));
+    return NMPC_OK;
+}
+
+int nmpc_loop_crowd_grid(nmpc_loop *l, nmpc_crowd_grid *out, int32_t *cell_of, int32_t *looked)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    const LoopCrowd &c = l->crowd;
+    if (!c.grid()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_crowd_grid: the loop has no crowd grid (nmpc_loop_set_crowd_grid)");
+    if ((cell_of || looked) && l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_crowd_grid: cell_of and looked before the loop's first step");
+    if (out) {
+        *out = c.hdr;          // filed: the entry behind the last cell, as the last build's scan left it (0 before any build)
+        HIP_TRY(l->h, hipMemcpy(&out->filed, c.cell_off.p + c.g.cells, sizeof(int), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(l->h, c.cell_of.read(cell_of, (size_t)c.a.D * l->v.N));
+    HIP_TRY(l->h, c.looked.read(looked, (size_t)l->v.B));
     return NMPC_OK;
 }
 

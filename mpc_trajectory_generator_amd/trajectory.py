@@ -476,6 +476,8 @@ class Peers:
 
 
 CROWD_MAX = 16384            # D of a crowd at the most (nmpc_loop_set_crowd)
+CROWD_GRID_MAX = 131072      # ... with a ``cell`` (nmpc_loop_set_crowd_grid)
+CROWD_GRID_CAP = 128         # cells per axis at the most (csrc/nmpc_loop.h)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -487,12 +489,18 @@ class Crowd:
     ``obstacles`` = ``(p1 [D, 2], p2 [D, 2], freq [D], rx [D], ry [D], angle [D])`` as one robot's ``dyn_obs``; ``sinus`` [D] bool =
     who follows the sinusoidal law (``None``: nobody).  The values are not checked: an obstacle with a NaN is never chosen.
     ``watch=True`` (the device needs ``max_steps`` > 0): ``crowd_clearance`` [B] keeps every robot's closest approach to ANY obstacle
-    of the crowd, chosen or not (a ``_lib.CROWD_CLEARANCE_DTYPE`` array).  It observes only."""
+    of the crowd, chosen or not (a ``_lib.CROWD_CLEARANCE_DTYPE`` array).  It observes only.
+
+    ``cell`` (metres; ``None``: every obstacle against every robot, 16384 obstacles at the most) finds the same obstacles through a
+    grid in space and stage (``crowd_grid``, ``nmpc_loop_set_crowd_grid``): up to 131072 obstacles, at a cost that grows with what is
+    near a robot, not with the world.  No result depends on it; ``crowd_looked`` [B] counts the table's entries each robot looked at
+    at its last step (all obstacles: D * N).  The observer stays all obstacles."""
     obstacles: object
     slots: int
     range: float
     sinus: object = None
     watch: bool = False
+    cell: float = None
 
     def checked(self, B: int, K: int, Ndynobs: int, Mp: int = 0):
         """-> (obstacles as six contiguous float64 arrays, sinus [D] bool); ValueError for what ``nmpc_loop_set_crowd`` refuses
@@ -501,8 +509,11 @@ class Crowd:
             raise ValueError("crowd: obstacles = (p1, p2, freq, rx, ry, angle)")
         p1, p2, freq, rx, ry, ang = (np.ascontiguousarray(a, dtype=np.float64) for a in self.obstacles)
         D = len(freq)
-        if D < 1 or D > CROWD_MAX:
-            raise ValueError(f"crowd: {D} obstacles, 1 to {CROWD_MAX} are taken")
+        most = CROWD_MAX if self.cell is None else CROWD_GRID_MAX
+        if D < 1 or D > most:
+            raise ValueError(f"crowd: {D} obstacles, 1 to {most} are taken")
+        if self.cell is not None and not (math.isfinite(self.cell) and self.cell > 0):
+            raise ValueError("crowd: cell must be finite and positive")
         if p1.shape != (D, 2) or p2.shape != (D, 2) or any(a.shape != (D,) for a in (freq, rx, ry, ang)):
             raise ValueError("crowd: obstacles of shapes other than [D, 2], [D, 2], [D], [D], [D], [D]")
         if self.slots < 1 or K + self.slots + Mp > Ndynobs:
@@ -557,7 +568,7 @@ def grid_axis(extent, cell, cap):
 
 
 class _Grid:
-    """What ``WallGrid`` and ``PeerGrid`` share: ``origin`` [2], ``h`` [2], ``nx``, ``ny`` and the cell of a coordinate."""
+    """What ``WallGrid``, ``PeerGrid`` and ``CrowdGrid`` share: ``origin`` [2], ``h`` [2], ``nx``, ``ny`` and the cell of a coordinate."""
 
     def _cellof(self, v, axis):
         """The cell of coordinate ``v`` on ``axis`` (``grid_cellof``)."""
@@ -765,6 +776,98 @@ def peer_grid(pred, range, cell):
     order = who[np.argsort(g.cell_of[who], kind="stable")]                  # ascending robot index inside a cell
     g.cell_mem = order.astype(np.int64)
     g.cell_off = np.concatenate([[0], np.cumsum(np.bincount(g.cell_of[who], minlength=cells))]).astype(np.int64)
+    return g
+
+
+class CrowdGrid(_Grid):
+    """The crowd's grid in space and stage (``crowd_grid``): ``origin`` [2], ``h`` [2] the cells' edges, ``nx``, ``ny``, ``layers`` (N)
+    and ``filed`` (what ``nmpc_loop_crowd_grid`` returns as its header), fixed by the obstacles' end points; ``file(table)`` files one
+    step's table: ``cell_of`` [D, N] int32 (layer * nx * ny + y * nx + x; -1 = unfiled), ``cell_off`` [layers * nx * ny + 1] and
+    ``cell_mem`` [filed] (the obstacle of each filed entry, ascending inside a cell); ``window(x, y, range)``,
+    ``candidates(pred_b, range)`` and ``looked(pred_b, range)``."""
+
+    def header(self):
+        """-> the header as one ``_lib.CROWD_GRID_DTYPE`` record, as the device reports it (``filed``: of the last ``file``, 0 before)."""
+        rec = np.zeros((), dtype=_lib.CROWD_GRID_DTYPE)
+        rec["origin"], rec["h"] = self.origin, self.h
+        rec["nx"], rec["ny"], rec["layers"], rec["filed"] = self.nx, self.ny, self.layers, self.filed
+        return rec
+
+    def file(self, table):
+        """File the entries of ``table`` [D, layers, >= 2]: entry (d, k) under the cell of its position in layer k, unfiled if a
+        coordinate is not finite -> ``cell_of`` [D, layers] int32."""
+        table = np.asarray(table, dtype=np.float64)
+        D, N = table.shape[:2]
+        assert N == self.layers
+        x, y = table[:, :, 0], table[:, :, 1]
+        ok = np.isfinite(x) & np.isfinite(y)
+        key = (np.arange(N, dtype=np.int64)[None, :] * self.ny + grid_cellof(y, self.origin[1], self.h[1], self.ny)) * self.nx \
+            + grid_cellof(x, self.origin[0], self.h[0], self.nx)
+        self.cell_of = np.where(ok, key, -1).astype(np.int32)
+        flat = self.cell_of.reshape(-1)
+        who = np.nonzero(flat >= 0)[0]                                      # entries e = d * layers + k, ascending
+        self.filed = len(who)
+        order = who[np.argsort(flat[who], kind="stable")]                   # ascending d inside a cell (its k is the layer's)
+        self.cell_mem = (order // N).astype(np.int64)
+        self.cell_off = np.concatenate([[0], np.cumsum(np.bincount(flat[who], minlength=self.layers * self.nx * self.ny))]).astype(np.int64)
+        return self.cell_of
+
+    def window(self, x, y, range):
+        """-> (cx0, cx1, cy0, cy1), inclusive: the cells of a layer that a robot at (x, y) looks at; None unless both are finite."""
+        x, y, r = np.float64(x), np.float64(y), np.float64(range)
+        if not (np.isfinite(x) and np.isfinite(y)):
+            return None
+        with np.errstate(over="ignore"):
+            return self._cellof(x - r, 0), self._cellof(x + r, 0), self._cellof(y - r, 1), self._cellof(y + r, 1)
+
+    def row_ranges(self, pred_b, range):
+        """-> [(k, i0, i1)] per row of the robot's windows, stage after stage: the row's entries are ``cell_mem[i0:i1]`` at stage k."""
+        out = []
+        for k in np.arange(self.layers):
+            w = self.window(pred_b[k][0], pred_b[k][1], range)
+            if w is None:
+                continue
+            cx0, cx1, cy0, cy1 = w
+            for row in np.arange(cy0, cy1 + 1):
+                at = (k * self.ny + row) * self.nx
+                out.append((k, int(self.cell_off[at + cx0]), int(self.cell_off[at + cx1 + 1])))
+        return out
+
+    def candidates(self, pred_b, range):
+        """-> (d, k): the filed entries in the windows of a robot with the predicted positions ``pred_b`` [layers, >= 2], row after
+        row and stage after stage, as two int64 arrays."""
+        rr = self.row_ranges(pred_b, range)
+        if not rr:
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        return (np.concatenate([self.cell_mem[i0:i1] for _, i0, i1 in rr]),
+                np.concatenate([np.full(i1 - i0, k, dtype=np.int64) for k, i0, i1 in rr]))
+
+    def looked(self, pred_b, range):
+        """-> the number of filed entries in the robot's windows (what the device reports as ``looked``)."""
+        return sum(i1 - i0 for _, i0, i1 in self.row_ranges(pred_b, range))
+
+
+def crowd_grid(obstacles, N, cell):
+    """The geometry of the crowd's rule with a ``cell`` for ``obstacles`` = (p1 [D, 2], p2 [D, 2], ...) and a
+    horizon of ``N`` stages, in the setter's arithmetic: -> a ``CrowdGrid``, nothing filed yet.
+
+    ``origin`` is the minimum per axis over the end points p1, p2 whose two coordinates are finite; an axis has floor(extent / cell) + 1
+    cells of edge ``cell``, or ``CROWD_GRID_CAP`` cells of edge extent / ``CROWD_GRID_CAP`` where that would be more; without a finite
+    end point the grid is one cell at (0, 0).  There are N layers.  Entry (d, k) of a step's table is filed under the cell of its
+    position in layer k; a robot looks, at stage k, at the cells from that of ``x - range`` to that of ``x + range`` per axis: every
+    entry with d_k < range^2 is filed there, inside the extent or not, because the cell of a coordinate is clamped and monotone."""
+    ends = np.concatenate([np.asarray(obstacles[0], dtype=np.float64).reshape(-1, 2), np.asarray(obstacles[1], dtype=np.float64).reshape(-1, 2)])
+    ends = ends[np.isfinite(ends).all(axis=1)]
+    g = CrowdGrid()
+    g.cell, g.layers, g.filed = float(cell), int(N), 0
+    g.nx = g.ny = 1
+    g.origin, g.h = np.zeros(2), np.array([g.cell, g.cell])
+    if len(ends):
+        g.origin = ends.min(axis=0)
+        with np.errstate(over="ignore"):
+            ext = ends.max(axis=0) - g.origin
+        (g.nx, hx), (g.ny, hy) = (grid_axis(ext[ax], g.cell, CROWD_GRID_CAP) for ax in (0, 1))
+        g.h = np.array([hx, hy])
     return g
 
 
@@ -1233,7 +1336,10 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     ``crowd`` (a ``Crowd``): D moving obstacles of the world.  ``assemble`` advances their table
     (``crowd_table()`` [D, N, 5]), every step and whoever is active, and overlays each active robot's closest ones on the parameter
     vectors it returns, in front of the peers and never on the carried dynamic blocks; ``crowd_seen`` [B, slots] names them (a retired
-    robot keeps its last).  With ``crowd.watch``, ``advance`` updates ``crowd_clearance()`` [B] for the robots the step drove.
+    robot keeps its last); ``crowd_who`` and ``crowd_pred`` [B, N, 3] keep the robots the last selection ran for and the predictions
+    it read.  With ``crowd.watch``, ``advance`` updates ``crowd_clearance()`` [B] for the robots the step drove.  With
+    ``crowd.cell`` C is formed through ``crowd_grid`` only (the ``CrowdGrid``, filed anew every step with an active robot): the same
+    obstacles, and ``crowd_looked`` [B] counts the entries each robot looked at; without it this class stays the all-obstacles yardstick.
 
     ``plant`` (a ``Plant``): seeded actuation, process and measurement noise.  ``assemble`` and ``predict``
     start from the measured poses (``measured()`` [B, 3]) and nothing else does; ``advance`` applies the disturbed controls and adds
@@ -1274,6 +1380,9 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
             self._crowd_tab = None                                            # [D, N, 5] as the last step wrote it
             self.crowd_seen = np.full((B, crowd.slots), -1, dtype=np.int32)   # the obstacle in slot K + m of robot b's p (-1: none)
             self._crowd_rec = no_crowd_clearance(B)
+            if crowd.cell is not None:
+                self.crowd_grid = crowd_grid(self._crowd_obs, cfg.N_hor, crowd.cell)      # filed anew every step with an active robot
+                self.crowd_looked = np.zeros(B, dtype=np.int32)               # the filed entries in each robot's windows at its last step
         self.peers = peers
         if peers is not None:
             g = peers.checked(B, self.K + self._Mc, cfg.Ndynobs)
@@ -1531,12 +1640,16 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         per = cfg.ndynobs * N
         base = cfg.n_p - cfg.nx * N - cfg.Ndynobs * per + self.K * per       # slot K of the dynamic block
         who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
+        self.crowd_who = who                                                 # whom this step's selection ran for
         if not len(who):
             return
-        pred = self.predict()
+        self.crowd_pred = pred = self.predict()                              # what it read
         r2 = cr.range * cr.range
         self.crowd_seen[who] = -1
-        rows = max(1, (1 << 22) // D)                                        # robots per pass: bounds the [rows, D] tables
+        if cr.cell is not None:
+            self._overlay_crowd_grid(P, pred, who, base, per, r2)
+            return
+        rows = max(1, (1 << 22) // D)                                       # robots per pass: bounds the [rows, D] tables
         for r0 in range(0, len(who), rows):
             me = who[r0:r0 + rows]
             C = np.full((len(me), D), np.inf)
@@ -1553,6 +1666,30 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
                 b, src = me[got], j[got]
                 self.crowd_seen[b, m] = src
                 P[b, base + m * per:base + (m + 1) * per] = tab[src].reshape(len(b), per)
+
+    def _overlay_crowd_grid(self, P, pred, who, base, per, r2):
+        """``_overlay_crowd`` with C formed through ``crowd_grid`` only: this step's table is filed, and robot
+        by robot an entry (d, k) of its windows makes d a candidate if d_k < range^2 and no earlier stage has d_j < range^2, with C
+        over all stages as the all-obstacles rule forms it; the same (C, d) order and overlay."""
+        cr, tab, grid = self.crowd, self._crowd_tab, self.crowd_grid
+        grid.file(tab)
+        for b in who:
+            d, k = grid.candidates(pred[b], cr.range)
+            self.crowd_looked[b] = len(d)
+            if not len(d):
+                continue
+            with np.errstate(invalid="ignore", over="ignore"):
+                dx, dy = pred[b, k, 0] - tab[d, k, 0], pred[b, k, 1] - tab[d, k, 1]
+                near = dx * dx + dy * dy < r2
+                d, k = d[near], k[near]
+                dx, dy = pred[b][None, :, 0] - tab[d, :, 0], pred[b][None, :, 1] - tab[d, :, 1]
+                dd = dx * dx + dy * dy                                        # [n, N]
+                first = np.argmax(dd < r2, axis=1) == k                       # the entry's stage is d's first in range
+            d, dd = d[first], dd[first]
+            C = np.where(np.isnan(dd), np.inf, dd).min(axis=1)                # min over the stages, a NaN passed over
+            for m, src in enumerate(d[np.lexsort((d, C))][:cr.slots]):        # (C, d)
+                self.crowd_seen[b, m] = src
+                P[b, base + m * per:base + (m + 1) * per] = tab[src].reshape(per)
 
     def _crowd_update(self):
         """The crowd observer's rule on the s rows this step appended, for the robots it drove: row
@@ -1938,7 +2075,10 @@ class DeviceRecedingHorizon:
     ``crowd`` (a ``Crowd``): D moving obstacles of the world, one table on the device advanced once per step, and every step each
     active robot's closest ones in ellipse slots of its own (``nmpc_loop_set_crowd``): two more kernels per step,
     three with ``crowd.watch`` (needs ``max_steps`` > 0).  ``crowd_table()``, ``crowd_seen()`` and ``crowd_clearance()`` read the
-    results.  Its host mirror is ``FleetRecedingHorizon`` with the same ``crowd`` (tests/test_gpu_crowd_loop.py).
+    results.  Its host mirror is ``FleetRecedingHorizon`` with the same ``crowd`` (tests/test_gpu_crowd_loop.py).  With ``crowd.cell``
+    the obstacles are found through a grid in space and stage (``nmpc_loop_set_crowd_grid``: up to 131072 obstacles, five more kernels
+    per step that file the table): the same results, ``crowd_grid()`` reads the grid and what each robot looked at
+    (tests/test_gpu_crowd_grid_loop.py).
 
     ``plant`` (a ``Plant``): seeded actuation, process and measurement noise drawn on the device (``nmpc_loop_set_plant``, DESIGN.md
     section 5.9): ``nmpc_loop_plant_kernel`` in the place of the advance and, with a ``meas`` > 0, ``nmpc_loop_measure_kernel`` in front of
@@ -2018,8 +2158,12 @@ class DeviceRecedingHorizon:
             obst = np.ascontiguousarray(np.concatenate([p1, p2, freq[:, None], rx[:, None], ry[:, None], ang[:, None],
                                                         sinus.astype(np.float64)[:, None], direction[:, None]], axis=1))
             self._crowd_D = len(obst)
-            self._set(self.lib.nmpc_loop_set_crowd(h, self._crowd_D, _lib.as_dp(obst), cfg.vehicle_width / 2 + cfg.vehicle_margin,
-                                                   int(crowd.slots), float(crowd.range)))
+            pad = cfg.vehicle_width / 2 + cfg.vehicle_margin
+            if crowd.cell is None:
+                self._set(self.lib.nmpc_loop_set_crowd(h, self._crowd_D, _lib.as_dp(obst), pad, int(crowd.slots), float(crowd.range)))
+            else:
+                self._set(self.lib.nmpc_loop_set_crowd_grid(h, self._crowd_D, _lib.as_dp(obst), pad, int(crowd.slots), float(crowd.range),
+                                                            float(crowd.cell)))
             if crowd.watch:
                 self._set(self.lib.nmpc_loop_set_crowd_monitor(h))
         self.peers = peers
@@ -2182,6 +2326,17 @@ class DeviceRecedingHorizon:
         seen = np.empty((self.B, self.crowd.slots), dtype=np.int32)
         self.solver._check(self.lib.nmpc_loop_crowd(self._l, None, _lib.as_i32p(seen)))
         return seen
+
+    def crowd_grid(self):
+        """-> (header, cell_of [D, N] int32, looked [B] int32) after synchronising: the grid the crowd's obstacles are found through
+        (one ``_lib.CROWD_GRID_DTYPE`` record: origin, h, nx, ny, layers, filed), the cell each entry of the last step's table was
+        filed under (-1: unfiled) and the filed entries in each robot's windows at its last step.  Needs a ``crowd`` with a ``cell``
+        and a step taken."""
+        hdr = np.zeros((), dtype=_lib.CROWD_GRID_DTYPE)
+        D = self._crowd_D if self.crowd is not None else 0                   # (without a crowd the library says so)
+        cell_of, looked = np.empty((D, self.cfg.N_hor), dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        self.solver._check(self.lib.nmpc_loop_crowd_grid(self._l, hdr.ctypes.data, _lib.as_i32p(cell_of), _lib.as_i32p(looked)))
+        return hdr, cell_of, looked
 
     def crowd_clearance(self):
         """-> the crowd observer's records [B] (``_lib.CROWD_CLEARANCE_DTYPE``: level, row, obstacle) after synchronising; without

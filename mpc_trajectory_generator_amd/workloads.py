@@ -343,6 +343,18 @@ def wall_grid_differing(dev, host):
     return bad + [n for n, a, b in pairs if a.shape != b.shape or not np.array_equal(a, b)]
 
 
+def crowd_grid_differing(dev, grid, looked=None):
+    """What a crowd with a ``cell`` keeps beside its table and ``seen`` (``dev``: a ``DeviceRecedingHorizon`` with such a crowd and a
+    step taken, ``grid``: a ``trajectory.CrowdGrid`` in which the same step's table is filed, ``looked`` [B]: what it counts for each
+    robot's last step, or None) -> the names out of the header's fields, cell_of and looked that differ.  The order inside a cell is
+    not the device's to keep, so ``cell_mem`` is not compared: ``cell_of`` fixes every cell's members."""
+    hdr, cell_of, looked_dev = dev.crowd_grid()
+    want = grid.header()
+    bad = [f for f in want.dtype.names if hdr[f].tobytes() != want[f].tobytes()]
+    pairs = [("cell_of", cell_of, grid.cell_of)] + ([] if looked is None else [("looked", looked_dev, np.asarray(looked))])
+    return bad + [n for n, a, b in pairs if a.shape != b.shape or not np.array_equal(a, b)]
+
+
 def subdivided_map(edges, poly_off, pieces):
     """-> (edges [E * pieces, 4], poly_off): every edge of a map (``frontend.map_edges``) cut into ``pieces`` collinear pieces, in the
     edge's direction, polygon by polygon as before: piece i runs from a + (i / pieces) * (b - a) to the next piece's start, and the last

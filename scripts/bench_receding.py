@@ -21,7 +21,10 @@ and RMS cross-track error in metres, its largest and RMS heading error and the s
 --log: the drive log (nmpc_loop_set_log): the result line then has drive_log: the share of non-converged solves per exit
 status, the worst step's slowest solve and the fleet's largest acceleration.  --crowd D: a crowd of D moving obstacles shared by the whole fleet
 (nmpc_loop_set_crowd; workloads.crowd_ellipses, seed 2): --crowd-slots of the Ndynobs ellipse slots go to the closest
-ones within --crowd-range metres, the result line gains crowd: the share of those slots filled at the last step; with --crowd-watch also the
+ones within --crowd-range metres, the result line gains crowd: the share of those slots filled at the last step (--crowd-cell H: the obstacles a
+robot measures are found through a grid in space and stage of H-metre cells, nmpc_loop_set_crowd_grid, which lifts the limit of 16384 obstacles to
+131072; crowd then also has the grid's cells, the entries filed, and the mean and the largest number of the table's entries a robot looked at at
+the last step beside the D * N the all-obstacles selection looks at); with --crowd-watch also the
 observer (nmpc_loop_set_crowd_monitor): the robots whose level against some obstacle fell below 1, and how many of those closest approaches
 were to an obstacle the robot did not have in a slot at that step (found by an untimed second run that reads the slots after every step).
 --plant-act G, --plant-proc P, --plant-meas M, --plant-seed S: a disturbed plant (nmpc_loop_set_plant): actuation noise of
@@ -98,6 +101,9 @@ ap.add_argument("--crowd", type=int, default=0, metavar="D",
                 help="device loop only: D > 0 moving obstacles of the scene, shared by the whole fleet (every sub-fleet sees the same crowd)")
 ap.add_argument("--crowd-slots", type=int, default=2, help="with --crowd: ellipse slots given to the crowd (the others stay scripted, or go to peers)")
 ap.add_argument("--crowd-range", type=float, default=10.0, help="with --crowd: how far a robot sees an obstacle of the crowd, in metres")
+ap.add_argument("--crowd-cell", type=float, default=None, metavar="H",
+                help="with --crowd: the obstacles a robot measures are found through a grid in space and stage of H-metre cells "
+                     "(nmpc_loop_set_crowd_grid: the same obstacles, D up to 131072 instead of 16384)")
 ap.add_argument("--crowd-watch", action="store_true", help="with --crowd: keep every robot's closest approach to any obstacle of the crowd on the device")
 ap.add_argument("--plant-act", type=float, default=0.0, metavar="G", help="device loop only: actuation noise, sigma = G * |control| on v and omega")
 ap.add_argument("--plant-proc", type=float, default=0.0, metavar="P", help="device loop only: process noise on x, y (metres) and theta (radians) per applied control")
@@ -142,6 +148,8 @@ if args.crowd and (args.host or args.steps < 1):
     ap.error("--crowd is the device loop's: it needs the device loop (no --host) and --steps >= 1")
 if (args.crowd_watch or args.crowd < 0) and args.crowd < 1:
     ap.error("--crowd D: D >= 1, and --crowd-watch goes with it")
+if args.crowd_cell is not None and not (args.crowd and 0 < args.crowd_cell < float("inf")):
+    ap.error("--crowd-cell H: goes with --crowd, H finite and positive")
 if args.walls < 0 or (args.walls and (args.host or args.steps < 1)) or args.walls_pieces < 1:
     ap.error("--walls M: M >= 1, on the device loop (no --host) with --steps >= 1; --walls-pieces P: P >= 1")
 if args.walls_cell is not None and not (args.walls and 0 < args.walls_cell < float("inf")):
@@ -188,7 +196,7 @@ crowd = None
 if args.crowd:
     from mpc_trajectory_generator_amd.trajectory import Crowd
     from mpc_trajectory_generator_amd.workloads import crowd_ellipses
-    crowd = Crowd(crowd_ellipses(cfg, args.scene, args.crowd, 2), args.crowd_slots, args.crowd_range, watch=args.crowd_watch)
+    crowd = Crowd(crowd_ellipses(cfg, args.scene, args.crowd, 2), args.crowd_slots, args.crowd_range, watch=args.crowd_watch, cell=args.crowd_cell)
 
 walls = None
 if args.walls:
@@ -258,7 +266,8 @@ if args.peers:
               + (f", found through a grid of {args.peer_cell} m" if args.peer_cell is not None else ""))
 if args.crowd:
     fleet += (f", a crowd of {args.crowd} moving obstacles (workloads.crowd_ellipses, seed 2), {args.crowd_slots} crowd slots per robot, "
-              f"range {args.crowd_range} m" + (", crowd observer" if args.crowd_watch else "") + ("" if args.peers else f", {K} scripted ellipses"))
+              f"range {args.crowd_range} m" + (f", found through a grid of {args.crowd_cell} m" if args.crowd_cell is not None else "") +
+              (", crowd observer" if args.crowd_watch else "") + ("" if args.peers else f", {K} scripted ellipses"))
 if walls is not None:
     fleet += (f", {args.walls} wall slots per robot over {len(walls.edges)} edges, range {args.walls_range} m, spacing {args.walls_spacing} m, "
               f"radius {walls.radius} m" + (f", found through a grid of {args.walls_cell} m" if args.walls_cell is not None else ""))
@@ -411,6 +420,12 @@ if not args.host:
         seen = np.concatenate([rh.crowd_seen() for rh in loops])          # the last step's
         quality["crowd"] = {"obstacles": args.crowd, "slots": args.crowd_slots, "range_m": args.crowd_range,
                             "slots_filled_frac": float((seen >= 0).mean())}
+        if args.crowd_cell is not None:                                   # what each robot looked at at its last step, beside all obstacles' D * N
+            grids = [rh.crowd_grid() for rh in loops]
+            hdr, looked = grids[0][0], np.concatenate([g[2] for g in grids])
+            quality["crowd"].update({"cell_m": args.crowd_cell, "cells": [int(hdr["nx"]), int(hdr["ny"]), int(hdr["layers"])],
+                                     "filed": int(hdr["filed"]), "looked_mean": float(looked.mean()), "looked_max": int(looked.max()),
+                                     "all_obstacles_look_at": args.crowd * cfg.N_hor})
         if args.crowd_watch:
             # a second, untimed run of the same loops (bit for bit the same) that reads the slots after every step
             recs = [rh.crowd_clearance() for rh in loops]
