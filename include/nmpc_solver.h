@@ -811,6 +811,42 @@ typedef struct nmpc_wall_grid {
  * nmpc_loop_set_walls_grid, and when looked is asked for before the loop's first step. */
 int nmpc_loop_wall_grid(nmpc_loop *l, nmpc_wall_grid *out, int32_t *cell_off, int32_t *cell_edge, int32_t *looked);
 
+/* ---- map monitor of large maps: the edges a row is judged against are found through the walls grid --
+ * nmpc_loop_set_map_monitor measures every pose against every edge and takes 1024 edges at the most.  nmpc_loop_set_map_monitor_grid is
+ * the same stage with the same record over a map of up to 1048576 edges: a row is judged against the edges filed near it in THE WALLS
+ * GRID above (origin, the cap of 512 cells per axis, cellof, the filing of an edge in the rectangle of its end points' cells, CSR with
+ * ascending edge indices, 2^23 filings at the most, m(v) = slack + 2^-40*|v| with slack = 2^-40*(range + A) + 2^-500 and A the largest
+ * |coordinate| of an edge), built once by the setter over the map's edges.  Everything is unfused f64 in the order written, as the
+ * all-edges rule above, whose v, containment predicate and crossing test are used word for word.  For the pose P = (x, y) of row r and
+ * A = (ax, ay) of row r - 1:
+ *   window W(r)   per axis the cells cellof((lo - range) - m(lo)) .. cellof((hi + range) + m(hi)), lo and hi the smaller and larger of the
+ *                 two rows' coordinates on that axis; every distinct edge filed in W(r) is taken once, however many cells hold it
+ *   wall distance for those edges, v against P; only v < range*range is a candidate; the record keeps the lexicographic minimum of
+ *                 (v, r, e) as above
+ *   crossing      for those edges, o1*o2 < -1e-9 && o3*o4 < -1e-9; the polygon that owns a crossed edge fails
+ *   containment   the cells of grid row cellof_y(y) from column cellof_x(x - m(x)) to the last; every distinct edge filed there is taken
+ *                 once: (y1 > y) != (y2 > y) and x1 + ((y - y1)*(x2 - x1))/(y2 - y1) > x is a crossing of the edge's polygon; parity per
+ *                 polygon, an obstacle fails on an odd count, the boundary on an even one
+ *   non-finite    if x, y, ax or ay is not finite the row takes the whole grid for all three tests, every edge once: the all-edges rule
+ *   verdict       as above: the smallest failing polygon index, hits, hit_row, hit_poly; the record, its initial values, retired robots
+ *                 and legs as above
+ * Wall distance (restricted to v < range*range) and containment are the all-edges rule's for every input, and an edge the all-edges
+ * rule finds crossed lies in W(r) under the bound of DESIGN.md section 5.9, which has the arguments.  Nothing bounds the candidates or
+ * the ray's hits: a pose whose ray meets more obstacle edges than the kernel's list holds (512) is judged in exact rounds.
+ *   n_edge            3 .. 1048576, n_poly >= 1
+ *   range, cell       finite and > 0, metres
+ *   filings           8388608 (2^23) at the most over all edges
+ * Everything nmpc_loop_set_map_monitor refuses is refused here, and a range or a cell that is not finite and positive and a map with
+ * more filings than the limit: NMPC_ERR_BAD_ARG with a message that names the function, nothing changed or allocated on the device.  It
+ * is the loop's map-monitor call: a second call, a call after a step and a call after nmpc_loop_set_map_monitor are refused, and
+ * nmpc_loop_set_map_monitor after it.  nmpc_loop_map_clearance reads the record of either setter. */
+int nmpc_loop_set_map_monitor_grid(nmpc_loop *l, const nmpc_scene *map, double range, double cell);
+/* Synchronises, then copies what is asked for (NULL = skip): the grid's header, cell_off [nx*ny + 1], cell_edge [entries] (read the
+ * header first for the sizes) and looked [B]: the distinct edges of W(r) summed over the rows of each robot's last step (a retired
+ * robot keeps its last).  NMPC_ERR_BAD_ARG on a loop without nmpc_loop_set_map_monitor_grid, and when looked is asked for before the
+ * loop's first step. */
+int nmpc_loop_map_grid(nmpc_loop *l, nmpc_wall_grid *out, int32_t *cell_off, int32_t *cell_edge, int32_t *looked);
+
 /* Arithmetic primitives of the kernels, exported for bit-level checks: out_s/out_c [n]. */
 int nmpc_test_sincos_host(nmpc_handle *h, int n, const double *x, double *out_s, double *out_c);
 /* a/b and sqrt(a) as the device computes them: out_div/out_sqrt [n]. */

@@ -32,6 +32,7 @@ SYMBOLS = (
     "nmpc_loop_set_plant", "nmpc_loop_plant_applied", "nmpc_loop_plant_measured",
     "nmpc_loop_set_ensemble", "nmpc_loop_ensemble", "nmpc_loop_ensemble_groups",
     "nmpc_loop_set_walls", "nmpc_loop_walls", "nmpc_loop_set_walls_grid", "nmpc_loop_wall_grid",
+    "nmpc_loop_set_map_monitor_grid", "nmpc_loop_map_grid",
     "nmpc_loop_set_track_monitor", "nmpc_loop_tracking",
     "nmpc_planner_new", "nmpc_planner_free", "nmpc_planner_visibility", "nmpc_plan_batch_device", "nmpc_plan_batch_host", "nmpc_planner_last_ms",
 )
@@ -416,6 +417,10 @@ def _bind(lib: C.CDLL, path: str) -> C.CDLL:
     lib.nmpc_loop_set_walls_grid.restype = C.c_int
     lib.nmpc_loop_wall_grid.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.nmpc_loop_wall_grid.restype = C.c_int
+    lib.nmpc_loop_set_map_monitor_grid.argtypes = [vp, C.POINTER(NmpcScene), C.c_double, C.c_double]
+    lib.nmpc_loop_set_map_monitor_grid.restype = C.c_int
+    lib.nmpc_loop_map_grid.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.nmpc_loop_map_grid.restype = C.c_int
     lib.nmpc_loop_free.argtypes = [vp]
     lib.nmpc_loop_free.restype = None
     lib.nmpc_planner_new.argtypes = [C.POINTER(NmpcScene), C.c_int, C.c_int, C.POINTER(vp)]

@@ -1455,6 +1455,214 @@ __global__ __launch_bounds__(64) void nmpc_loop_map_kernel(LoopView L, LoopStep 
     }
 }
 
+// ---- map monitor through a grid (nmpc_loop_set_map_monitor_grid; the rule, and why it is the all-edges rule's result: DESIGN.md
+// section 5.9) ----
+// The same three tests over fewer edges.  The grid is the walls grid (WallGridArgs, built by the setter's WallGridHost::build): a row
+// measures the distinct edges filed in the window of its two poses padded by `range` for the wall distance (only v < range^2 is a
+// candidate) and the crossing, and the distinct edges filed in the grid row of y, from the column of x - m(x) to the last, for the
+// containment.  A row with a coordinate that is not finite is judged against every edge, as nmpc_loop_map_kernel judges it.
+constexpr int MAP_GRID_HITS = 512;          // ray hits on obstacle edges the LDS list holds; a pose with more takes the exact rounds
+
+// the sum over the wave, result in every lane
+__device__ __forceinline__ int wave_sum(int v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// The two steps below are nmpc_loop_walls_grid_kernel's, statement for statement; that kernel keeps them in its body, as built and measured.
+// The rows cy0 .. cy0 + R - 1 of a window over the columns cx0 .. cx1, for a wave: row r is the run cell_edge[rbeg[r] .. ) of rpre[r + 1] -
+// rpre[r] filings, rpre the exclusive prefix sums (a wave scan per 64 rows), -> their total.  The filings of all rows then count as ONE
+// list, over which the lanes stride: a window of several short rows costs one pass, not one per row.  Barrier included.
+__device__ __forceinline__ int window_rows(const WallGridArgs &g, int cx0, int cx1, int cy0, int R, int *rbeg, int *rpre)
+{
+    const int lane = threadIdx.x, nx = g.nx;
+    int total = 0;
+    for (int r0 = 0; r0 < R; r0 += 64) {
+        const int r = r0 + lane;
+        int i0 = 0, len = 0;
+        if (r < R) {
+            i0 = g.cell_off[(cy0 + r) * nx + cx0];
+            len = g.cell_off[(cy0 + r) * nx + cx1 + 1] - i0;
+        }
+        int sum = len;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(sum, off);
+            if (lane >= off) sum += o;
+        }
+        if (r < R) { rbeg[r] = i0; rpre[r] = total + sum - len; }
+        total += __shfl(sum, 63);
+    }
+    if (lane == 0) rpre[R > 0 ? R : 0] = total;
+    __syncthreads();
+    return total;
+}
+
+// place idx < total of that list: its filing's place i in cell_edge and, from the filing's tag, whether this is the cell at which its
+// edge is measured (at most nine halvings over the rows; the last row r with rpre[r] <= idx holds idx, rows without filings are passed)
+__device__ __forceinline__ bool window_filing(const WallGridArgs &g, int cx0, int cy0, int R, const int *rbeg, const int *rpre, int idx, int &i)
+{
+    int lo = 0, hi = R - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rpre[mid] <= idx) lo = mid; else hi = mid - 1;
+    }
+    i = rbeg[lo] + (idx - rpre[lo]);
+    const int tag = g.cell_tag[i];
+    const int di = tag & 511, dj = (tag >> 9) & 511, col0 = tag >> 18, row0 = cy0 + lo - dj;
+    return di == (cx0 > col0 ? cx0 - col0 : 0) && dj == (cy0 > row0 ? cy0 - row0 : 0);
+}
+
+// One wave per robot the step drove, in nmpc_loop_map_kernel's place: the robot's s + 1 poses go to LDS.  Row by row:
+//   window       its rows are runs of cell_edge laid end to end (window_rows, window_filing: nmpc_loop_walls_grid_kernel's); the lanes stride
+//                over the filings, an edge filed in several cells of the window is taken in the first cell of its rectangle that lies in
+//                the window (the filing's tag), so `looked` counts distinct edges.  Wall distance and crossing test per edge, as in nmpc_loop_map_kernel.
+//   containment  one run of cell_edge; an edge is taken in the first column of its rectangle at or behind the ray's first.  A hit on the
+//                boundary is counted, a hit on an obstacle appends its polygon to an LDS list at the place a ballot gives it.  Then rounds:
+//                each names the smallest polygon behind the last one named and counts its hits (a lane keeps the smallest of its
+//                entries and how often it saw it; a wave minimum and a wave sum follow); an odd count fails it and ends the rounds, as
+//                does a polygon that is not below what has failed already.  With more hits than the list holds a round walks the run
+//                again, which needs no memory and names the same polygons.  There are no more rounds than hits.
+// Every loop is bounded by s, E, n_poly or the grid's size: the window and the ray are clamped to the grid.
+__global__ __launch_bounds__(64) void nmpc_loop_map_grid_kernel(LoopView L, LoopStep stp, MapArgs m, WallGridArgs g)
+{
+    __shared__ double own[2 * (NMPC_MAX_HORIZON + 1)];
+    __shared__ int rbeg[WALL_GRID_CAP], rpre[WALL_GRID_CAP + 1];
+    __shared__ int hk[MAP_GRID_HITS];
+    const int b = L.robot(blockIdx.x), lane = threadIdx.x;
+    const int s = L.s, E = m.E, n_poly = m.n_poly, row0 = stp.traj_row, nx = g.nx;
+    const double inf = __builtin_inf(), tm = 0x1p-40, range2 = g.range * g.range;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    stage_rows<2>(own, L, b, row0 - 1, s + 1);
+    double wv = inf;
+    int wr = LOOP_NONE, we = LOOP_NONE;
+    int hits = 0, hit_row = LOOP_NONE, hit_poly = LOOP_NONE, looked = 0;      // the same in every lane
+    // wall distance and crossing test of edge e for the row's poses
+    auto measure = [&](int e, int r, double ax, double ay, double x, double y, int &fail) {
+        const double x1 = m.edge[4 * (size_t)e], y1 = m.edge[4 * (size_t)e + 1], x2 = m.edge[4 * (size_t)e + 2], y2 = m.edge[4 * (size_t)e + 3];
+        double cx, cy;
+        const double v = segment_closest(x, y, x1, y1, x2, y2, true, cx, cy);
+        if (v < range2 && (v < wv || (v == wv && (r < wr || (r == wr && e < we))))) { wv = v; wr = r; we = e; }
+        const double ux = x - ax, uy = y - ay, ex = x2 - x1, ey = y2 - y1;
+        const double o1 = ux * (y1 - ay) - uy * (x1 - ax);
+        const double o2 = ux * (y2 - ay) - uy * (x2 - ax);
+        const double o3 = ex * (ay - y1) - ey * (ax - x1);
+        const double o4 = ex * (y - y1) - ey * (x - x1);
+        if (o1 * o2 < -1e-9 && o3 * o4 < -1e-9) {
+            const int k = m.edge_poly[e];
+            if (k < fail) fail = k;
+        }
+    };
+    // whether the ray from (x, y) to the right meets edge e by the containment's predicate
+    auto meets = [&](int e, double x, double y) {
+        const double y1 = m.edge[4 * (size_t)e + 1], y2 = m.edge[4 * (size_t)e + 3];
+        if ((y1 > y) == (y2 > y)) return false;
+        const double x1 = m.edge[4 * (size_t)e], x2 = m.edge[4 * (size_t)e + 2];
+        return x1 + ((y - y1) * (x2 - x1)) / (y2 - y1) > x;
+    };
+    for (int i = 0; i < s; ++i) {
+        const double ax = own[2 * i], ay = own[2 * i + 1], x = own[2 * i + 2], y = own[2 * i + 3];
+        const int r = row0 + i;
+        int fail = LOOP_NONE;
+        if (!(fabs(x) < inf && fabs(y) < inf && fabs(ax) < inf && fabs(ay) < inf)) {      // (wave-uniform) every edge, polygon by polygon
+            for (int e = lane; e < E; e += 64) measure(e, r, ax, ay, x, y, fail);
+            for (int k = lane; k < n_poly; k += 64) {
+                bool odd = false;
+                for (int e = m.poly_off[k]; e < m.poly_off[k + 1]; ++e)
+                    if (meets(e, x, y)) odd = !odd;
+                if ((k == n_poly - 1 ? !odd : odd) && k < fail) fail = k;
+            }
+            fail = wave_min(fail);
+            looked += E;
+        } else {
+            // ---- the window of the two poses
+            const double lox = x < ax ? x : ax, hix = x < ax ? ax : x, loy = y < ay ? y : ay, hiy = y < ay ? ay : y;
+            const int cx0 = cellof((lox - g.range) - (g.slack + tm * fabs(lox)), g.origin[0], g.h[0], nx);
+            const int cx1 = cellof((hix + g.range) + (g.slack + tm * fabs(hix)), g.origin[0], g.h[0], nx);
+            const int cy0 = cellof((loy - g.range) - (g.slack + tm * fabs(loy)), g.origin[1], g.h[1], g.ny);
+            const int cy1 = cellof((hiy + g.range) + (g.slack + tm * fabs(hiy)), g.origin[1], g.h[1], g.ny);
+            const int R = cy1 - cy0 + 1;          // >= 1: cellof is monotone
+            const int total = window_rows(g, cx0, cx1, cy0, R, rbeg, rpre);
+            for (int base = 0; base < total; base += 64) {
+                const int idx = base + lane;
+                int at;
+                const bool meas = idx < total && window_filing(g, cx0, cy0, R, rbeg, rpre, idx, at);
+                if (meas) measure(g.cell_edge[at], r, ax, ay, x, y, fail);
+                looked += __popcll(__ballot(meas));
+            }
+            fail = wave_min(fail);
+            // ---- the ray: grid row cellof(y), from the column of x - m(x) to the last
+            const int c0 = cellof(x - (g.slack + tm * fabs(x)), g.origin[0], g.h[0], nx);
+            const int cy = cellof(y, g.origin[1], g.h[1], g.ny);
+            const int i0 = g.cell_off[cy * nx + c0], i1 = g.cell_off[cy * nx + nx];
+            // the edge a filing of the run stands for, LOOP_NONE where another filing of the run does
+            auto taken = [&](int at) {
+                const int tag = g.cell_tag[at];
+                const int col0 = tag >> 18;
+                return (tag & 511) == (c0 > col0 ? c0 - col0 : 0) ? g.cell_edge[at] : LOOP_NONE;
+            };
+            int nb = 0, cnt = 0;
+            for (int base = i0; base < i1; base += 64) {
+                const int at = base + lane;
+                int k = LOOP_NONE;
+                if (at < i1) {
+                    const int e = taken(at);
+                    if (e != LOOP_NONE && meets(e, x, y)) k = m.edge_poly[e];
+                }
+                if (k == n_poly - 1) { ++nb; k = LOOP_NONE; }
+                const unsigned long long hm = __ballot(k != LOOP_NONE);
+                const int to = cnt + __popcll(hm & below);
+                if (k != LOOP_NONE && to < MAP_GRID_HITS) hk[to] = k;
+                cnt += __popcll(hm);
+            }
+            __syncthreads();
+            const bool listed = cnt <= MAP_GRID_HITS;       // (wave-uniform)
+            int last = -1;
+            for (int round = 0; round < cnt; ++round) {
+                int km = LOOP_NONE, c = 0;
+                auto offer = [&](int k) {
+                    if (k > last && k <= km) { c = k < km ? 1 : c + 1; km = k; }
+                };
+                if (listed) {
+                    for (int q = lane; q < cnt; q += 64) offer(hk[q]);
+                } else {
+                    for (int at = i0 + lane; at < i1; at += 64) {
+                        const int e = taken(at);
+                        if (e == LOOP_NONE || !meets(e, x, y)) continue;
+                        const int k = m.edge_poly[e];
+                        if (k != n_poly - 1) offer(k);
+                    }
+                }
+                const int kk = wave_min(km);
+                if (kk >= fail) break;            // (wave-uniform) nothing left below what has failed
+                if (wave_sum(km == kk ? c : 0) & 1) { fail = kk; break; }
+                last = kk;
+            }
+            if (!(wave_sum(nb) & 1) && n_poly - 1 < fail) fail = n_poly - 1;
+            __syncthreads();                      // this row's loads of rbeg, rpre and hk before the next row's stores
+        }
+        if (fail != LOOP_NONE) {
+            if (hits == 0) { hit_row = r; hit_poly = fail; }
+            ++hits;
+        }
+    }
+    wave_argmin3(wv, wr, we);
+    if (lane == 0) {
+        nmpc_map_clearance c = m.rec[b];
+        if (wv < c.wall2 || (wv == c.wall2 && (wr < c.wall_row || (wr == c.wall_row && we < c.wall_edge)))) {
+            c.wall2 = wv; c.wall_row = wr; c.wall_edge = we;
+        }
+        if (hits > 0) {
+            if (c.hits == 0) { c.hit_row = hit_row; c.hit_poly = hit_poly; }
+            c.hits += hits;
+        }
+        m.rec[b] = c;
+        g.looked[b] = looked;
+    }
+}
+
 // ---- track monitor: how far each robot was from the route it was asked to follow (nmpc_loop_set_track_monitor; the rule is DESIGN.md
 // section 5.9).  It observes: the record is the only thing it writes.  The route is routes[route_of[b]] as the step found it (the dispatch
 // comes after), its polyline Q_j = (x_ref[j], y_ref[j]), n_seg = max(n_ref - 1, 1) segments, segment j from Q_j to Q_e, e = min(j + 1,

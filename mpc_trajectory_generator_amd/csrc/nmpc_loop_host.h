@@ -80,11 +80,31 @@ struct LoopMonitor {         // nmpc_loop_set_monitor: one more kernel per step,
     DevBuf<nmpc_clearance> rec;      // [B]
     bool made() const { return rec != nullptr; }
 };
+// The walls grid on the device, for the two stages that find edges through it (nmpc_loop_set_walls_grid, nmpc_loop_set_map_monitor_grid):
+// what WallGridHost::build made, uploaded, and the kernels' argument block
+struct WallGridHost;
+struct LoopWallGrid {
+    nmpc::WallGridArgs g{};
+    nmpc_wall_grid hdr{};
+    DevBuf<int> cell_off, cell_edge, cell_tag, looked;     // [nx * ny + 1], [entries], [entries], [B]
+    bool made() const { return cell_off != nullptr; }
+    hipError_t upload(const WallGridHost &gh, double range, size_t B);
+    // what nmpc_loop_wall_grid and nmpc_loop_map_grid copy out (NULL = skip)
+    hipError_t read(nmpc_wall_grid *out, int32_t *off, int32_t *edge, int32_t *seen, size_t B) const
+    {
+        if (out) *out = hdr;
+        hipError_t e = cell_off.read(off, (size_t)hdr.nx * hdr.ny + 1);
+        if (e == hipSuccess) e = cell_edge.read(edge, (size_t)hdr.entries);
+        if (e == hipSuccess) e = looked.read(seen, B);
+        return e;
+    }
+};
 struct LoopMap {             // nmpc_loop_set_map_monitor: one more kernel per step, after the advance and the clearance monitor
     nmpc::MapArgs a{};
     DevBuf<double> edge;             // [E][4]
     DevBuf<int> poly_off, edge_poly; // [n_poly + 1], [E]
     DevBuf<nmpc_map_clearance> rec;  // [B]
+    LoopWallGrid grid;               // nmpc_loop_set_map_monitor_grid: nmpc_loop_map_grid_kernel in the place of nmpc_loop_map_kernel
     bool made() const { return rec != nullptr; }
 };
 // nmpc_loop_set_track_monitor: one more kernel per step, after the advance and the other monitors and before the log and the dispatch
@@ -125,11 +145,8 @@ struct LoopWalls {           // nmpc_loop_set_walls: one more kernel per step, b
     DevBuf<int> wall_edge, wall_stage;   // [B][M] each
     // nmpc_loop_set_walls_grid: the edges a robot measures come from a grid built by the setter, nmpc_loop_walls_grid_kernel in the place
     // of nmpc_loop_walls_kernel
-    nmpc::WallGridArgs g{};
-    nmpc_wall_grid hdr{};
-    DevBuf<int> cell_off, cell_edge, cell_tag, looked;     // [nx * ny + 1], [entries], [entries], [B]
+    LoopWallGrid grid;
     bool made() const { return edge != nullptr; }
-    bool grid() const { return cell_off != nullptr; }
 };
 struct LoopEnsemble {        // nmpc_loop_set_ensemble: one more kernel per step, the step's last
     nmpc::EnsembleArgs a{};
@@ -482,44 +499,7 @@ int nmpc_loop_set_monitor(nmpc_loop *l, const int32_t *group_of)
     return NMPC_OK;
 }
 
-static const nmpc_map_clearance MAP_CLEARANCE_NONE = {__builtin_inf(), -1, -1, 0, -1, -1, 0};
-static constexpr int MAP_MAX_EDGES = 1024;
-
-int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map)
-{
-    if (!l) return NMPC_ERR_BAD_ARG;
-    if (const int rc = loop_setter(l, "nmpc_loop_set_map_monitor", l->map.made(), "the loop has its map monitor already")) return rc;
-    nmpc_handle *h = l->h;
-    const int B = l->v.B;
-    if (!map) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: map is NULL");
-    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: the loop records no trajectory (max_steps == 0)");
-    const int E = map->n_edge, np = map->n_poly;
-    if (E < 3 || E > MAP_MAX_EDGES) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: n_edge outside 3 .. 1024");
-    if (np < 1 || np > E / 3) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: n_poly outside 1 .. n_edge / 3");
-    if (!map->edge || !map->poly_off) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: edge or poly_off is NULL");
-    if (map->poly_off[0] != 0 || map->poly_off[np] != E) return fail(h, NMPC_ERR_BAD_ARG, "nmpc_loop_set_map_monitor: poly_off does not run from 0 to n_edge");
-    for (int k = 0; k < np; ++k)
-        if (map->poly_off[k + 1] > E || map->poly_off[k] < 0 || map->poly_off[k + 1] - map->poly_off[k] < 3)
-            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_map_monitor: poly_off gives polygon " + std::to_string(k) + " fewer than three edges").c_str());
-    for (int i = 0; i < 4 * E; ++i)
-        if (!(map->edge[i] >= -DBL_MAX && map->edge[i] <= DBL_MAX))
-            return fail(h, NMPC_ERR_BAD_ARG, ("nmpc_loop_set_map_monitor: a coordinate of edge " + std::to_string(i / 4) + " is not finite").c_str());
-    std::vector<int> owner(E);
-    for (int k = 0; k < np; ++k)
-        for (int e = map->poly_off[k]; e < map->poly_off[k + 1]; ++e) owner[e] = k;
-    LoopMap st;
-    const std::vector<nmpc_map_clearance> none(B, MAP_CLEARANCE_NONE);
-    HIP_TRY(h, st.rec.upload(none.data(), B));
-    HIP_TRY(h, st.edge.upload(map->edge, 4 * (size_t)E));
-    HIP_TRY(h, st.poly_off.upload(map->poly_off, (size_t)np + 1));
-    HIP_TRY(h, st.edge_poly.upload(owner.data(), E));
-    nmpc::MapArgs &m = st.a;
-    m.E = E; m.n_poly = np;
-    m.edge = st.edge; m.poly_off = st.poly_off; m.edge_poly = st.edge_poly;
-    m.rec = st.rec;
-    l->map = std::move(st);
-    return NMPC_OK;
-}
+// (the map monitor's setters stand behind the walls': they share the walls grid)
 
 static_assert(sizeof(nmpc_tracking) == 64, "nmpc_tracking is 64 bytes");
 static const nmpc_tracking TRACKING_NONE = {0.0, 0.0, 0.0, 0.0, 0, -1, -1, -1, -1, 0, -1, 0};
@@ -710,6 +690,21 @@ struct WallGridHost {
     }
 };
 
+hipError_t LoopWallGrid::upload(const WallGridHost &gh, double range, size_t B)
+{
+    hipError_t e = cell_off.upload(gh.cell_off.data(), gh.cell_off.size());
+    if (e == hipSuccess) e = cell_edge.upload(gh.cell_edge.data(), gh.cell_edge.size());
+    if (e == hipSuccess) e = cell_tag.upload(gh.cell_tag.data(), gh.cell_tag.size());
+    if (e == hipSuccess) e = looked.alloc_fill(B, 0);
+    if (e != hipSuccess) return e;
+    hdr = gh.hdr;
+    for (int ax = 0; ax < 2; ++ax) { g.origin[ax] = gh.hdr.origin[ax]; g.h[ax] = gh.hdr.h[ax]; }
+    g.nx = gh.hdr.nx; g.ny = gh.hdr.ny;
+    g.range = range; g.slack = 0x1p-40 * (range + gh.amax) + 0x1p-500;
+    g.cell_off = cell_off; g.cell_edge = cell_edge; g.cell_tag = cell_tag; g.looked = looked;
+    return hipSuccess;
+}
+
 // both walls setters: `cell` NULL = every edge against every robot (nmpc_loop_set_walls), else the grid's cell
 static int loop_set_walls(nmpc_loop *l, const char *name, int max_edge, int n_edge, const double *edge, int M, double radius, double range,
                           double spacing, const double *cell)
@@ -750,18 +745,7 @@ static int loop_set_walls(nmpc_loop *l, const char *name, int max_edge, int n_ed
     nmpc::WallArgs &w = st.a;
     w.E = n_edge; w.M = M; w.radius = radius; w.range2 = range * range; w.spacing2 = spacing * spacing;
     w.edge = st.edge; w.pred = l->d_pred.p ? l->d_pred.p : pred.p; w.wall_edge = st.wall_edge; w.wall_stage = st.wall_stage;
-    if (cell) {
-        HIP_TRY(h, st.cell_off.upload(gh.cell_off.data(), gh.cell_off.size()));
-        HIP_TRY(h, st.cell_edge.upload(gh.cell_edge.data(), gh.cell_edge.size()));
-        HIP_TRY(h, st.cell_tag.upload(gh.cell_tag.data(), gh.cell_tag.size()));
-        HIP_TRY(h, st.looked.alloc_fill(B, 0));
-        st.hdr = gh.hdr;
-        nmpc::WallGridArgs &g = st.g;
-        for (int ax = 0; ax < 2; ++ax) { g.origin[ax] = gh.hdr.origin[ax]; g.h[ax] = gh.hdr.h[ax]; }
-        g.nx = gh.hdr.nx; g.ny = gh.hdr.ny;
-        g.range = range; g.slack = 0x1p-40 * (range + gh.amax) + 0x1p-500;
-        g.cell_off = st.cell_off; g.cell_edge = st.cell_edge; g.cell_tag = st.cell_tag; g.looked = st.looked;
-    }
+    if (cell) HIP_TRY(h, st.grid.upload(gh, range, B));
     l->walls = std::move(st);
     if (pred) l->d_pred = std::move(pred);
     return NMPC_OK;
@@ -775,6 +759,68 @@ int nmpc_loop_set_walls(nmpc_loop *l, int n_edge, const double *edge, int M, dou
 int nmpc_loop_set_walls_grid(nmpc_loop *l, int n_edge, const double *edge, int M, double radius, double range, double spacing, double cell)
 {
     return loop_set_walls(l, "nmpc_loop_set_walls_grid", nmpc::WALL_GRID_MAX_EDGES, n_edge, edge, M, radius, range, spacing, &cell);
+}
+
+static const nmpc_map_clearance MAP_CLEARANCE_NONE = {__builtin_inf(), -1, -1, 0, -1, -1, 0};
+static constexpr int MAP_MAX_EDGES = 1024;
+
+// both map monitor setters: `grid` NULL = every edge against every robot (nmpc_loop_set_map_monitor), else {range, cell} of the walls
+// grid the edges are found through
+static int loop_set_map(nmpc_loop *l, const char *name, int max_edge, const nmpc_scene *map, const double *grid)
+{
+    if (!l) return NMPC_ERR_BAD_ARG;
+    if (const int rc = loop_setter(l, name, l->map.made(), "the loop has its map monitor already")) return rc;
+    nmpc_handle *h = l->h;
+    const int B = l->v.B;
+    const std::string fn = std::string(name) + ": ";
+    if (!map) return fail(h, NMPC_ERR_BAD_ARG, (fn + "map is NULL").c_str());
+    if (!l->d_traj) return fail(h, NMPC_ERR_BAD_ARG, (fn + "the loop records no trajectory (max_steps == 0)").c_str());
+    const int E = map->n_edge, np = map->n_poly;
+    if (E < 3 || E > max_edge) return fail(h, NMPC_ERR_BAD_ARG, (fn + "n_edge outside 3 .. " + std::to_string(max_edge)).c_str());
+    if (np < 1 || np > E / 3) return fail(h, NMPC_ERR_BAD_ARG, (fn + "n_poly outside 1 .. n_edge / 3").c_str());
+    if (!map->edge || !map->poly_off) return fail(h, NMPC_ERR_BAD_ARG, (fn + "edge or poly_off is NULL").c_str());
+    if (map->poly_off[0] != 0 || map->poly_off[np] != E) return fail(h, NMPC_ERR_BAD_ARG, (fn + "poly_off does not run from 0 to n_edge").c_str());
+    for (int k = 0; k < np; ++k)
+        if (map->poly_off[k + 1] > E || map->poly_off[k] < 0 || map->poly_off[k + 1] - map->poly_off[k] < 3)
+            return fail(h, NMPC_ERR_BAD_ARG, (fn + "poly_off gives polygon " + std::to_string(k) + " fewer than three edges").c_str());
+    for (int i = 0; i < 4 * E; ++i)
+        if (!(map->edge[i] >= -DBL_MAX && map->edge[i] <= DBL_MAX))
+            return fail(h, NMPC_ERR_BAD_ARG, (fn + "a coordinate of edge " + std::to_string(i / 4) + " is not finite").c_str());
+    WallGridHost gh;
+    if (grid) {
+        for (int i = 0; i < 2; ++i)
+            if (!(grid[i] > 0.0) || grid[i] > DBL_MAX) return fail(h, NMPC_ERR_BAD_ARG, (fn + "range and cell must be finite and positive").c_str());
+        if (!gh.build(E, map->edge, grid[1]))
+            return fail(h, NMPC_ERR_BAD_ARG, (fn + "the edges are filed in more than " + std::to_string(nmpc::WALL_GRID_MAX_ENTRIES) +
+                                              " cells in all: use a larger cell or shorter edges").c_str());
+    }
+    std::vector<int> owner(E);
+    for (int k = 0; k < np; ++k)
+        for (int e = map->poly_off[k]; e < map->poly_off[k + 1]; ++e) owner[e] = k;
+    LoopMap st;
+    const std::vector<nmpc_map_clearance> none(B, MAP_CLEARANCE_NONE);
+    HIP_TRY(h, st.rec.upload(none.data(), B));
+    HIP_TRY(h, st.edge.upload(map->edge, 4 * (size_t)E));
+    HIP_TRY(h, st.poly_off.upload(map->poly_off, (size_t)np + 1));
+    HIP_TRY(h, st.edge_poly.upload(owner.data(), E));
+    if (grid) HIP_TRY(h, st.grid.upload(gh, grid[0], B));
+    nmpc::MapArgs &m = st.a;
+    m.E = E; m.n_poly = np;
+    m.edge = st.edge; m.poly_off = st.poly_off; m.edge_poly = st.edge_poly;
+    m.rec = st.rec;
+    l->map = std::move(st);
+    return NMPC_OK;
+}
+
+int nmpc_loop_set_map_monitor(nmpc_loop *l, const nmpc_scene *map)
+{
+    return loop_set_map(l, "nmpc_loop_set_map_monitor", MAP_MAX_EDGES, map, nullptr);
+}
+
+int nmpc_loop_set_map_monitor_grid(nmpc_loop *l, const nmpc_scene *map, double range, double cell)
+{
+    const double grid[2] = {range, cell};
+    return loop_set_map(l, "nmpc_loop_set_map_monitor_grid", nmpc::WALL_GRID_MAX_EDGES, map, grid);
 }
 
 // a retiring loop's active robots as the last step enqueued leaves them: waits for that step's count to arrive, not for the device
@@ -843,8 +889,8 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
                 hipLaunchKernelGGL(nmpc::nmpc_loop_peers_kernel, dim3(n), dim3(64), 0, s, v, p);
             }
         }
-        if (l->walls.grid())
-            hipLaunchKernelGGL(nmpc::nmpc_loop_walls_grid_kernel, dim3(n), dim3(64), 0, s, v, l->walls.a, l->walls.g);
+        if (l->walls.grid.made())
+            hipLaunchKernelGGL(nmpc::nmpc_loop_walls_grid_kernel, dim3(n), dim3(64), 0, s, v, l->walls.a, l->walls.grid.g);
         else if (l->walls.made())
             hipLaunchKernelGGL(nmpc::nmpc_loop_walls_kernel, dim3(n), dim3(64), nmpc::WallArgs::lds_bytes(l->walls.a.E), s, v, l->walls.a);
         if (retiring) hipLaunchKernelGGL(nmpc::nmpc_loop_gather_kernel, dim3(n), dim3(256), 0, s, v, r.a);
@@ -865,7 +911,8 @@ int nmpc_loop_step(nmpc_loop *l, void *stream)
         // retired_at as the step found it (NULL without retirement)
         if (l->monitor.made())
             hipLaunchKernelGGL(nmpc::nmpc_loop_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, l->monitor.a, r.retired_at);
-        if (l->map.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, v, stp, l->map.a);
+        if (l->map.grid.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_map_grid_kernel, dim3(n), dim3(64), 0, s, v, stp, l->map.a, l->map.grid.g);
+        else if (l->map.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_map_kernel, dim3(n), dim3(64), 0, s, v, stp, l->map.a);
         if (cr.watched()) hipLaunchKernelGGL(nmpc::nmpc_loop_crowd_monitor_kernel, dim3(n), dim3(64), 0, s, v, stp, cr.a);
         // the track monitor measures against the route the rows were driven on: the dispatch comes after
         if (l->track.made()) hipLaunchKernelGGL(nmpc::nmpc_loop_track_kernel, dim3(n), dim3(64), 0, s, v, stp, l->a, l->track.a);
@@ -1016,12 +1063,19 @@ int nmpc_loop_wall_grid(nmpc_loop *l, nmpc_wall_grid *out, int32_t *cell_off, in
 {
     if (const int rc = loop_settle(l)) return rc;
     const LoopWalls &w = l->walls;
-    if (!w.grid()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_wall_grid: the loop has no walls grid (nmpc_loop_set_walls_grid)");
+    if (!w.grid.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_wall_grid: the loop has no walls grid (nmpc_loop_set_walls_grid)");
     if (looked && l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_wall_grid: looked before the loop's first step");
-    if (out) *out = w.hdr;
-    HIP_TRY(l->h, w.cell_off.read(cell_off, (size_t)w.hdr.nx * w.hdr.ny + 1));
-    HIP_TRY(l->h, w.cell_edge.read(cell_edge, (size_t)w.hdr.entries));
-    HIP_TRY(l->h, w.looked.read(looked, (size_t)l->v.B));
+    HIP_TRY(l->h, w.grid.read(out, cell_off, cell_edge, looked, (size_t)l->v.B));
+    return NMPC_OK;
+}
+
+int nmpc_loop_map_grid(nmpc_loop *l, nmpc_wall_grid *out, int32_t *cell_off, int32_t *cell_edge, int32_t *looked)
+{
+    if (const int rc = loop_settle(l)) return rc;
+    const LoopMap &m = l->map;
+    if (!m.grid.made()) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_map_grid: the loop has no map monitor grid (nmpc_loop_set_map_monitor_grid)");
+    if (looked && l->steps == 0) return fail(l->h, NMPC_ERR_BAD_ARG, "nmpc_loop_map_grid: looked before the loop's first step");
+    HIP_TRY(l->h, m.grid.read(out, cell_off, cell_edge, looked, (size_t)l->v.B));
     return NMPC_OK;
 }
 

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import functools
 import math
 import time
 
@@ -943,31 +944,119 @@ class MapMonitor:
     approach to the walls of a polygon map over the poses driven so far, and the rows at which it stood inside an obstacle, outside the
     boundary or went through an edge between two rows (``map_clearance``, a ``_lib.MAP_CLEARANCE_DTYPE`` array [B]).  It observes only.
     ``edges`` [E, 4] = (x1, y1, x2, y2) polygon by polygon, the obstacles first and the boundary last; ``poly_off`` [n_poly + 1]: polygon
-    k owns the edges poly_off[k] .. poly_off[k + 1] (``frontend.map_edges`` gives both for a planner's scene)."""
+    k owns the edges poly_off[k] .. poly_off[k + 1] (``frontend.map_edges`` gives both for a planner's scene).
+
+    ``cell`` and ``range`` (metres, both or neither; ``None``: every pose against every edge, 1024 edges at the most) find the edges a
+    row is judged against through the walls grid (``wall_grid``, ``nmpc_loop_set_map_monitor_grid``): up to 1048576 edges.  Hits are the
+    all-edges rule's; the wall record keeps only distances below ``range`` (``rows_grid``)."""
     edges: object
     poly_off: object
+    cell: float = None
+    range: float = None
 
     def checked(self):
-        """-> (edges [E, 4] float64, poly_off [n_poly + 1] int32), contiguous; ValueError for what ``nmpc_loop_set_map_monitor`` refuses."""
+        """-> (edges [E, 4] float64, poly_off [n_poly + 1] int32), contiguous; ValueError for what ``nmpc_loop_set_map_monitor``, or with
+        a ``cell`` ``nmpc_loop_set_map_monitor_grid``, refuses."""
         edges = np.ascontiguousarray(self.edges, dtype=np.float64)
         off = np.ascontiguousarray(self.poly_off, dtype=np.int32).reshape(-1)
         if edges.ndim != 2 or edges.shape[1] != 4:
             raise ValueError(f"map monitor: edges of shape {edges.shape}, not [E, 4]")
         E, n_poly = len(edges), len(off) - 1
-        if E < 3 or E > MAP_MAX_EDGES:
-            raise ValueError(f"map monitor: {E} edges, 3 to {MAP_MAX_EDGES} are taken")
+        most = MAP_MAX_EDGES if self.cell is None else WALL_GRID_MAX_EDGES
+        if E < 3 or E > most:
+            raise ValueError(f"map monitor: {E} edges, 3 to {most} are taken")
         if n_poly < 1 or n_poly > E // 3:
             raise ValueError(f"map monitor: {n_poly} polygons for {E} edges")
         if off[0] != 0 or off[-1] != E or (np.diff(off) < 3).any():
             raise ValueError("map monitor: poly_off must ascend from 0 to E in steps of three edges at least")
         if not np.isfinite(edges).all():
             raise ValueError("map monitor: a coordinate that is not finite")
+        if (self.cell is None) != (self.range is None):
+            raise ValueError("map monitor: cell and range go together")
+        if self.cell is not None:
+            for v in (self.cell, self.range):
+                if not (math.isfinite(v) and v > 0):
+                    raise ValueError("map monitor: cell and range must be finite and positive")
+            self.grid                                                       # (ValueError for more filings than the grid takes)
         return edges, off
+
+    @functools.cached_property
+    def grid(self):
+        """The walls grid over the map's edges (``wall_grid(edges, cell)``), built at the first use."""
+        return wall_grid(self.edges, self.cell)
+
+    @functools.cached_property
+    def _edge_poly(self):
+        off = np.asarray(self.poly_off, dtype=np.int64).reshape(-1)
+        return np.repeat(np.arange(len(off) - 1, dtype=np.int32), np.diff(off))
+
+    def rows_grid(self, ax, ay, x, y):
+        """The rule with a ``cell`` for n poses, one at a time over the edges its cells hold -> (v, e, poly, looked)
+        [n]: as ``rows``, but v is +inf (and e -1) unless a wall of the window is closer than ``range``; ``looked`` counts the distinct
+        edges of each row's window W(r), all E for a row with a coordinate that is not finite."""
+        edges, off = self.checked()
+        g, owner, n_poly = self.grid, self._edge_poly, len(off) - 1
+        ax, ay, x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (ax, ay, x, y))
+        n, E = len(x), len(edges)
+        rng, tm = np.float64(self.range), np.float64(2.0 ** -40)
+        slack = tm * (rng + g.amax) + np.float64(2.0 ** -500)
+        r2 = rng * rng
+        v_out, e_out = np.full(n, np.inf), np.full(n, -1, dtype=np.int32)
+        poly_out, looked = np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.int32)
+
+        def filed(cx0, cx1, cy0, cy1):
+            """the distinct edges filed in the cells cx0 .. cx1 x cy0 .. cy1, ascending"""
+            at = np.arange(cy0, cy1 + 1) * g.nx
+            lo, hi = g.cell_off[at + cx0], g.cell_off[at + cx1 + 1]
+            if (hi - lo).sum() > E:                                         # cheaper by the edges' rectangles: the same set
+                r = g.rect
+                return np.nonzero((r[:, 0] <= cx1) & (r[:, 1] >= cx0) & (r[:, 2] <= cy1) & (r[:, 3] >= cy0))[0]
+            return np.unique(np.concatenate([g.cell_edge[a:b] for a, b in zip(lo, hi)]))
+
+        def m(v):
+            return slack + tm * abs(v)
+        with np.errstate(all="ignore"):
+            for i in range(n):
+                X, Y, AX, AY = x[i], y[i], ax[i], ay[i]
+                if np.isfinite([X, Y, AX, AY]).all():
+                    lo, hi = (min(X, AX), min(Y, AY)), (max(X, AX), max(Y, AY))
+                    win = filed(g._cellof((lo[0] - rng) - m(lo[0]), 0), g._cellof((hi[0] + rng) + m(hi[0]), 0),
+                                g._cellof((lo[1] - rng) - m(lo[1]), 1), g._cellof((hi[1] + rng) + m(hi[1]), 1))
+                    cy = g._cellof(Y, 1)
+                    ray = filed(g._cellof(X - m(X), 0), g.nx - 1, cy, cy)
+                else:
+                    win = ray = np.arange(E)
+                looked[i] = len(win)
+                x1, y1, x2, y2 = (edges[win, k] for k in range(4))
+                v = segment_closest(X, Y, x1, y1, x2, y2)[0]
+                v = np.where(v < r2, v, np.inf)                             # (a NaN is no candidate)
+                if len(v) and v.min() < np.inf:
+                    k = int(np.argmin(v))                                   # the first of equal values: the edges ascend
+                    v_out[i], e_out[i] = v[k], win[k]
+                ex, ey = x2 - x1, y2 - y1
+                ux, uy = X - AX, Y - AY
+                o1 = ux * (y1 - AY) - uy * (x1 - AX)
+                o2 = ux * (y2 - AY) - uy * (x2 - AX)
+                o3 = ex * (AY - y1) - ey * (AX - x1)
+                o4 = ex * (Y - y1) - ey * (X - x1)
+                fails = np.zeros(n_poly, dtype=bool)
+                fails[owner[win[(o1 * o2 < -1e-9) & (o3 * o4 < -1e-9)]]] = True
+                x1, y1, x2, y2 = (edges[ray, k] for k in range(4))
+                straddle = (y1 > Y) != (y2 > Y)
+                xi = x1 + ((Y - y1) * (x2 - x1)) / np.where(straddle, y2 - y1, 1.0)
+                odd = (np.bincount(owner[ray[straddle & (xi > X)]], minlength=n_poly) & 1).astype(bool)
+                odd[-1] = ~odd[-1]                                          # the boundary fails on an even count
+                fails |= odd
+                if fails.any():
+                    poly_out[i] = np.argmax(fails)
+        return v_out, e_out, poly_out, looked
 
     def rows(self, ax, ay, x, y):
         """The rule for n poses (x, y) [n], each with the pose (ax, ay) of the row before -> (v [n], e [n], poly [n]): the smallest squared
         wall distance that is not NaN (+inf without any) and the first edge that has it, and the smallest failing polygon index, -1
-        if none fails.  Unfused f64 in the order DESIGN.md section 5.9 writes."""
+        if none fails.  Unfused f64 in the order DESIGN.md section 5.9 writes.  With a ``cell``: ``rows_grid`` without its count."""
+        if self.cell is not None:
+            return self.rows_grid(ax, ay, x, y)[:3]
         edges, off = self.checked()
         ax, ay, x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (ax, ay, x, y))
         n, chunk = len(x), max(1, (1 << 20) // len(edges))
@@ -1321,7 +1410,9 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
     the step drove.  Nothing else reads it.
 
     ``map_monitor`` (a ``MapMonitor``): ``map_clearance`` [B] holds every robot's closest approach to the map's walls and its hits
-    (DESIGN.md section 5.9), updated by ``advance`` from the rows it appends to ``traj``, for the robots the step drove.
+    (DESIGN.md section 5.9), updated by ``advance`` from the rows it appends to ``traj``, for the robots the step drove.  With a ``cell``
+    the rule is the grid's (``MapMonitor.rows_grid``) and ``map_looked`` [B] counts the distinct edges of the windows of each robot's
+    last step.
 
     ``missions`` (a ``Missions``, needs ``retire=True``): ``retire`` re-dispatches an active robot that is done and has another leg
     instead of retiring it: ``leg`` [B] and ``route_of`` [B] move on, ``leg_at`` [B, Lmax] takes the step count
@@ -1405,6 +1496,8 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         if map_monitor is not None:
             map_monitor.checked()
             self.map_clearance = no_map_clearance(B)
+            if map_monitor.cell is not None:
+                self.map_looked = np.zeros(B, dtype=np.int32)                 # the distinct edges of W(r) over the rows of each robot's last step
         self.log = log
         if log is not None:
             self._ctrl, self._rec, self._tot = [], [], []                     # per step: [s, B, 2], [B], one record
@@ -1932,11 +2025,18 @@ class FleetRecedingHorizon(VectorizedRecedingHorizon):
         who = np.arange(self.B) if self.active is None else np.nonzero(self.active)[0]
         if not len(who):
             return
+        grid = self.map_monitor.cell is not None
+        if grid:
+            self.map_looked[who] = 0
         for i in range(s):
             r = self.steps * s + 1 + i
             at = len(self.traj) - s + i
             pose, prev = self.traj[at], self.traj[at - 1]
-            v, e, poly = self.map_monitor.rows(prev[who, 0], prev[who, 1], pose[who, 0], pose[who, 1])
+            if grid:
+                v, e, poly, looked = self.map_monitor.rows_grid(prev[who, 0], prev[who, 1], pose[who, 0], pose[who, 1])
+                self.map_looked[who] += looked
+            else:
+                v, e, poly = self.map_monitor.rows(prev[who, 0], prev[who, 1], pose[who, 0], pose[who, 1])
             b, better = who, v < rec["wall2"][who]
             rec["wall2"][b[better]], rec["wall_row"][b[better]], rec["wall_edge"][b[better]] = v[better], r, e[better]
             hit = poly >= 0
@@ -2060,7 +2160,10 @@ class DeviceRecedingHorizon:
     ``map_monitor`` (a ``MapMonitor``, needs ``max_steps`` > 0): every robot's closest approach to the walls of a polygon map, and the rows
     at which it was inside an obstacle, outside the boundary or went through an edge, are kept on the device
     (``nmpc_loop_set_map_monitor``), one more kernel per step after the advance; ``map_clearance()`` reads the
-    records.  Its host mirror is ``FleetRecedingHorizon`` with the same ``map_monitor`` (tests/test_gpu_map_monitor_loop.py).
+    records.  Its host mirror is ``FleetRecedingHorizon`` with the same ``map_monitor`` (tests/test_gpu_map_monitor_loop.py).  A
+    ``MapMonitor`` with a ``cell`` finds the edges through the walls grid (``nmpc_loop_set_map_monitor_grid``,
+    ``nmpc_loop_map_grid_kernel``): up to 1048576 edges, ``map_grid()`` reads the grid and the edges each robot looked at
+    (tests/test_gpu_map_grid_loop.py).
 
     ``missions`` (a ``Missions``, needs ``retire=True``): every robot drives the routes of its mission leg after leg and retires after
     the last (``nmpc_loop_set_missions``); one more kernel per step, before the active list is rebuilt.
@@ -2189,7 +2292,10 @@ class DeviceRecedingHorizon:
                 self.close()
                 raise
             sc = _lib.NmpcScene(0, len(edges), len(off) - 1, 0, None, _lib.as_dp(edges), _lib.as_i32p(off))
-            self._set(self.lib.nmpc_loop_set_map_monitor(h, C.byref(sc)))
+            if map_monitor.cell is None:
+                self._set(self.lib.nmpc_loop_set_map_monitor(h, C.byref(sc)))
+            else:
+                self._set(self.lib.nmpc_loop_set_map_monitor_grid(h, C.byref(sc), float(map_monitor.range), float(map_monitor.cell)))
         self.log = log
         if log is not None:
             self._set(self.lib.nmpc_loop_set_log(h))
@@ -2357,11 +2463,21 @@ class DeviceRecedingHorizon:
         """-> (header, cell_off [nx * ny + 1], cell_edge [entries], looked [B]) after synchronising: the grid the walls' edges are found
         through (one ``_lib.WALL_GRID_DTYPE`` record: origin, h, nx, ny, entries), its CSR arrays (int32) and the distinct edges each robot
         measured at its last step.  Needs ``walls`` with a ``cell`` and a step taken."""
+        return self._read_grid(self.lib.nmpc_loop_wall_grid)
+
+    def map_grid(self):
+        """-> (header, cell_off, cell_edge, looked [B]) after synchronising, as ``wall_grid``: the grid the map monitor's edges are found
+        through and the distinct edges of W(r) summed over the rows of each robot's last step.  Needs a ``map_monitor`` with a ``cell``
+        and a step taken."""
+        return self._read_grid(self.lib.nmpc_loop_map_grid)
+
+    def _read_grid(self, read):
+        """``read``: nmpc_loop_wall_grid or nmpc_loop_map_grid, called for the header and then for the arrays it sizes"""
         hdr = np.zeros((), dtype=_lib.WALL_GRID_DTYPE)
-        self.solver._check(self.lib.nmpc_loop_wall_grid(self._l, hdr.ctypes.data, None, None, None))
+        self.solver._check(read(self._l, hdr.ctypes.data, None, None, None))
         off, edge = np.empty(int(hdr["nx"]) * int(hdr["ny"]) + 1, dtype=np.int32), np.empty(int(hdr["entries"]), dtype=np.int32)
         looked = np.empty(self.B, dtype=np.int32)
-        self.solver._check(self.lib.nmpc_loop_wall_grid(self._l, None, _lib.as_i32p(off), _lib.as_i32p(edge), _lib.as_i32p(looked)))
+        self.solver._check(read(self._l, None, _lib.as_i32p(off), _lib.as_i32p(edge), _lib.as_i32p(looked)))
         return hdr, off, edge, looked
 
     def map_clearance(self):

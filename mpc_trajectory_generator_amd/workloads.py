@@ -343,6 +343,18 @@ def wall_grid_differing(dev, host):
     return bad + [n for n, a, b in pairs if a.shape != b.shape or not np.array_equal(a, b)]
 
 
+def map_grid_differing(dev, host):
+    """``wall_grid_differing`` for a map monitor with a ``cell`` (``dev``: a ``DeviceRecedingHorizon`` with one and a step taken, ``host``:
+    its mirror) -> the names out of the grid's header fields, cell_off, cell_edge and looked that differ from the mirror's
+    ``map_monitor.grid`` and ``map_looked``."""
+    hdr, off, edge, looked = dev.map_grid()
+    g = host.map_monitor.grid
+    want = g.header()
+    bad = [f for f in ("origin", "h", "nx", "ny", "entries") if hdr[f].tobytes() != want[f].tobytes()]
+    pairs = (("cell_off", off, g.cell_off), ("cell_edge", edge, g.cell_edge), ("looked", looked, host.map_looked))
+    return bad + [n for n, a, b in pairs if a.shape != b.shape or not np.array_equal(a, b)]
+
+
 def crowd_grid_differing(dev, grid, looked=None):
     """What a crowd with a ``cell`` keeps beside its table and ``seen`` (``dev``: a ``DeviceRecedingHorizon`` with such a crowd and a
     step taken, ``grid``: a ``trajectory.CrowdGrid`` in which the same step's table is filed, ``looked`` [B]: what it counts for each

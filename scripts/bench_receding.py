@@ -15,7 +15,10 @@ of robots that were inside a circle, inside a padded ellipse and closer to a gro
 from the goal of the one before; the routes are planned on the device (frontend.DevicePlanner), and the result line
 gains plan_ms (the planner kernels' time over all batches, redraws included) and routes_planned.  --map [inflated]: the map monitor
 (nmpc_loop_set_map_monitor) on the scene's original polygons, the true walls, or with "inflated" on the polygons the
-planner plans on; the result line then has map_clearance: the share of robots with a hit, the rows hit and the fleet's smallest wall distance.
+planner plans on; the result line then has map_clearance: the share of robots with a hit, the rows hit and the fleet's smallest wall distance,
+and (without --retire) the stage's time per step, from whole runs of the same fleet with and without it.  --map-pieces P cuts every edge into P
+pieces (workloads.subdivided_map); --map-cell H [--map-range R] finds the edges through the walls grid (nmpc_loop_set_map_monitor_grid), which
+lifts the limit of 1024 edges; map_clearance then has the grid and the edges looked at.
 --track [TOL]: the track monitor (nmpc_loop_set_track_monitor): the result line then has tracking: the fleet's largest
 and RMS cross-track error in metres, its largest and RMS heading error and the share of rows and of robots further than TOL (0.5 m) from the route.
 --log: the drive log (nmpc_loop_set_log): the result line then has drive_log: the share of non-converged solves per exit
@@ -92,6 +95,12 @@ ap.add_argument("--monitor", type=int, nargs="?", const=0, default=None, metavar
 ap.add_argument("--map", nargs="?", const="original", default=None, choices=("original", "inflated"), metavar="inflated",
                 help="device loop only: keep every robot's closest approach to the scene's walls and its rows inside an obstacle, outside the "
                      "boundary or through an edge on the device, and report them; 'inflated': against the polygons the planner plans on")
+ap.add_argument("--map-cell", type=float, default=None, metavar="H",
+                help="with --map: find the edges a row is judged against through the walls grid of H-metre cells (nmpc_loop_set_map_monitor_grid), "
+                     "which lifts the limit of 1024 edges; the result line gains the edges looked at and the stage's time per step")
+ap.add_argument("--map-range", type=float, default=2.0, metavar="R", help="with --map-cell: walls further than R metres are not recorded")
+ap.add_argument("--map-pieces", type=int, default=1, metavar="P",
+                help="with --map: every edge of the map cut into P pieces (1024 edges at the most without --map-cell, 1048576 with it)")
 ap.add_argument("--track", type=float, nargs="?", const=0.5, default=None, metavar="TOL",
                 help="device loop only: the track monitor, rows further than TOL metres (default 0.5) from the route count as off it")
 ap.add_argument("--log", action="store_true",
@@ -136,6 +145,10 @@ if args.peer_cell is not None and not args.peers:
     ap.error("--peer-cell goes with --peers G")
 if args.map and (args.host or args.steps < 1):
     ap.error("--map reads the trajectory the device loop records: it needs the device loop (no --host) and --steps >= 1")
+if args.map_pieces < 1 or ((args.map_cell is not None or args.map_pieces > 1) and not args.map):
+    ap.error("--map-cell H, --map-pieces P: go with --map, P >= 1")
+if args.map_cell is not None and not (0 < args.map_cell < float("inf") and 0 < args.map_range < float("inf")):
+    ap.error("--map-cell H, --map-range R: finite and positive")
 if args.track is not None and (args.host or args.steps < 1 or not 0 <= args.track < float("inf")):
     ap.error("--track [TOL]: TOL >= 0 and finite, on the device loop (no --host) with --steps >= 1")
 if args.log and (args.host or args.steps < 1):
@@ -190,7 +203,9 @@ def monitor_of(n):
 map_monitor = None
 if args.map:
     from mpc_trajectory_generator_amd.frontend import map_edges, scene_planner
-    map_monitor = MapMonitor(*map_edges(scene_planner(cfg, args.scene), inflated=args.map == "inflated"))
+    from mpc_trajectory_generator_amd.workloads import subdivided_map
+    map_monitor = MapMonitor(*subdivided_map(*map_edges(scene_planner(cfg, args.scene), inflated=args.map == "inflated"), args.map_pieces),
+                             cell=args.map_cell, range=None if args.map_cell is None else args.map_range)
 
 crowd = None
 if args.crowd:
@@ -318,7 +333,7 @@ if not args.host:
             cov = cov + wi[:, None] * (r["cov"] + np.stack([d[:, 0] * d[:, 0], d[:, 0] * d[:, 1], d[:, 1] * d[:, 1], d[:, 2] * d[:, 2]], axis=1))
         return n, arrived, mean, cov
 
-    def make_loop(sv, ids, walls=walls):
+    def make_loop(sv, ids, walls=walls, map_monitor=map_monitor):
         sub_routes, sub_route_of = routes_of(ids)
         return DeviceRecedingHorizon(sv, sub_routes, starts[ids], dyn and tuple(a[ids] for a in dyn), max_steps=args.steps, idx0=i0[ids],
                                      route_of=sub_route_of, peers=peers_of(len(ids)), retire=args.retire, monitor=monitor_of(len(ids)),
@@ -375,6 +390,37 @@ if not args.host:
         quality["map_clearance"] = {"polygons": args.map, "edges": len(map_monitor.edges), "robots_hit_frac": float((rec["hits"] > 0).mean()),
                                     "rows_hit": int(rec["hits"].sum()), "min_wall_m": float(np.sqrt(rec["wall2"].min())),
                                     "median_wall_m": float(np.sqrt(np.median(rec["wall2"])))}
+        if args.map_cell is not None:
+            grids = [rh.map_grid() for rh in loops]                       # the same grid in every sub-fleet; looked is the last step's
+            looked = np.concatenate([g[3] for g in grids])
+            hdr = grids[0][0]
+            near = rec["wall2"][np.isfinite(rec["wall2"])]                # (walls beyond the range are not recorded)
+            quality["map_clearance"].update({"robots_with_a_wall_frac": float(len(near) / len(rec)),
+                                             "median_wall_m": float(np.sqrt(np.median(near))) if len(near) else None})
+            quality["map_clearance"].update({"cell_m": args.map_cell, "range_m": args.map_range, "cells": [int(hdr["nx"]), int(hdr["ny"])],
+                                             "filings": int(hdr["entries"]), "looked_mean": float(looked.mean()), "looked_max": int(looked.max())})
+        if not args.retire:
+            # the stage's time per step: whole runs of the same fleet, timed behind the first step, with the map monitor and without it.
+            # The stage observes only, so the two solve the same problems bit for bit and the difference of their times is the stage's.
+            # A kernel's own time needs a trace (rocprofv3 --kernel-trace --stats).
+            def map_ms_per_step(mm):
+                rhs = [make_loop(rh.solver, ids, map_monitor=mm) for rh, ids in zip(loops, parts)]
+                for rh in rhs:
+                    rh.step()
+                    rh.read()
+                t = time.perf_counter()
+                for k in range(1, args.steps):
+                    for rh in rhs:
+                        rh.step()
+                for rh in rhs:
+                    rh.read()
+                t = time.perf_counter() - t
+                for rh in rhs:
+                    rh.close()
+                return 1e3 * t / max(args.steps - 1, 1)
+            with_it, without = map_ms_per_step(map_monitor), map_ms_per_step(None)
+            quality["map_clearance"]["stage"] = {"ms_per_step_with_map": with_it, "ms_per_step_without_map": without,
+                                                 "map_stage_ms_per_step": with_it - without}
     if args.track is not None:
         from mpc_trajectory_generator_amd.report import tracking_summary
         quality["tracking"] = {"tol_m": args.track, **tracking_summary(np.concatenate([rh.tracking() for rh in loops]))}
@@ -483,6 +529,8 @@ if not args.host:
                                + (", robots retire at their goals" if args.retire else "")
                                + (f", clearance monitor in groups of {args.monitor}" if args.monitor else "")
                                + (f", map monitor on the scene's {args.map} polygons" if args.map else "")
+                               + (f" cut into {len(map_monitor.edges)} edges" if args.map and args.map_pieces > 1 else "")
+                               + (f", found through a grid of {args.map_cell} m" if args.map_cell is not None else "")
                                + (f", track monitor with tol {args.track} m" if args.track is not None else "")
                                + (", drive log" if args.log else "")
                                + (f", ensemble statistics in {ens_G} group{'s' if ens_G > 1 else ''}" if args.ensemble_stats is not None else "")
